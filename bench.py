@@ -1,14 +1,18 @@
 #!/usr/bin/env python3
 """bench.py — sliding-window solves/sec of the MI355X Estimator::optimization() hot path.
 
-    python bench.py --gpus N --steps K --warmup W [--workload ...]
+    python bench.py --gpus N --steps K --warmup W [--workload ...] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the headline; --full adds the roofline and kernel timings, the
+secondary figures named below and the CPU baseline.  --dump-outputs DIR writes what the last timed step returned (solution
+and prior) as .npy files, so that two builds can be compared output for output on identical inputs.
 
 One "step" = one whole optimization(): trust-region solve (Ceres DENSE_SCHUR + DOGLEG semantics, <= 8 iterations, no
 wall-clock cap), the gauge fix of double2vector(), and MARGIN_OLD marginalization — inputs already resident in HBM when the
 timed region starts.  Workloads (--workload; default window300 at every N — one window stream per GPU, the SAME window on every
-rank, no data-path collective: weak scaling, so the values of N = 1, 2, 4, 8 are one curve — and at N > 1 the line also
-carries the strong-scaling figure of configs[3] as `window100k_sharded` (with the same window's one-GPU time and the speed-up)
+rank, no data-path collective: weak scaling, so the values of N = 1, 2, 4, 8 are one curve — and at N > 1 with --full the
+line also carries the strong-scaling figure of configs[3] as `window100k_sharded` (with the same window's one-GPU time and the speed-up)
 and configs[4] as `batch512_weak`):
   window300          BASELINE.json configs[1]: one 10-keyframe / 300-landmark window per rank, prior from a warm-up
                      MARGIN_OLD step; latency-bound (sequential solves of the resident window, synchronous call)
@@ -420,6 +424,49 @@ def stream_record(device, flag, n_stream=33, ahead=True):
         e.close()
 
 
+DUMP_MAX_WINDOWS = 64  # 64 priors of 172 x 172 doubles: 15 MB, well inside the 64 MB a dump may take
+
+
+def dump_sample(batch):
+    """The slots whose outputs --dump-outputs writes: all of a small batch, a fixed seeded sample of a large one."""
+    if batch <= DUMP_MAX_WINDOWS:
+        return list(range(batch))
+    return sorted(int(s) for s in np.random.default_rng(0).choice(batch, DUMP_MAX_WINDOWS, replace=False))
+
+
+def dump_outputs(out_dir, results):
+    """What a caller of the timed path receives, as DIR/<name>.npy (float64, one row per window, NaN where a window has
+    fewer landmarks, iterations or prior blocks than the widest): results = [(slot, Solution, Prior), ...]."""
+    from lfvio import abi
+
+    os.makedirs(out_dir, exist_ok=True)
+    B = len(results)
+    n_lm = max(s.N for _, s, _ in results)
+    n_it = max(min(s.c.num_iterations, abi.MAX_TRACE) for _, s, _ in results)
+    n_pr = max(p.n for _, _, p in results)
+    n_bl = max(p.num_blocks for _, _, p in results)
+    a = dict(windows=np.array([slot for slot, _, _ in results], dtype=np.float64),
+             pose=np.empty((B, abi.NUM_FRAMES, 7)), speed_bias=np.empty((B, abi.NUM_FRAMES, 9)), ex_pose=np.empty((B, 7)),
+             td=np.empty(B), inv_depth=np.full((B, n_lm), np.nan), summary=np.empty((B, 6)), trace=np.full((B, n_it, 8), np.nan),
+             prior_shape=np.empty((B, 4)), prior_blocks=np.full((B, n_bl, 3), np.nan), prior_x0=np.full((B, n_bl, 9), np.nan),
+             prior_J=np.full((B, n_pr, n_pr), np.nan), prior_r=np.full((B, n_pr), np.nan))
+    for i, (_, s, p) in enumerate(results):
+        a["pose"][i], a["speed_bias"][i], a["ex_pose"][i], a["td"][i] = s.pose, s.speed_bias, s.ex_pose, s.td
+        a["inv_depth"][i, :s.N] = s.lam
+        c = s.c
+        a["summary"][i] = (c.num_iterations, c.num_successful_steps, c.num_unsuccessful_steps, c.termination, c.initial_cost, c.final_cost)
+        for k, t in enumerate(s.trace()):
+            a["trace"][i, k] = (t["cost"], t["cost_change"], t["gradient_max_norm"], t["step_norm"], t["relative_decrease"],
+                                t["radius"], t["valid"], t["successful"])
+        a["prior_shape"][i] = (p.valid, p.m, p.n, p.num_blocks)
+        if p.num_blocks:
+            a["prior_blocks"][i, :p.num_blocks] = p.block_list()
+            a["prior_x0"][i, :p.num_blocks] = [p.x0(b) for b in range(p.num_blocks)]
+        a["prior_J"][i, :p.n, :p.n], a["prior_r"][i, :p.n] = p.J(), p.r()
+    for name, v in a.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(v, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -436,7 +483,19 @@ def main():
                     help="also time 512 resident windows per GPU (no collective) and add it to the line as 'batch512_weak' "
                          "(on by default next to the sharded workload on more than one GPU)")
     ap.add_argument("--lib", default=None, help="A/B runs: another build of the product library (default: lf-vio_amd/liblfvio_hip.so)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the roofline and kernel timings (runs of their own), the secondary "
+                         "figures (window300: default-cap and split calls, batch512, window100k, stream, replay; batch512: the "
+                         "two-stream form; N > 1: window100k_sharded and batch512_weak) and the single-thread CPU baseline; "
+                         "--no-secondary / --no-cpu-baseline trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned to its caller as DIR/<name>.npy (float64, a "
+                         "leading window axis; a batch larger than 64 windows by a fixed seeded sample of 64; windows.npy: their slots, "
+                         "or the index of the stream's window)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    full = args.full
 
     # stdout carries ONE JSON line.  Libraries below (RCCL prints a version banner through C stdio when a communicator is
     # created, flushed at exit) must not add to it: file descriptor 1 is pointed at stderr for the run, the line is written to
@@ -607,52 +666,61 @@ def main():
         lat = dict(mean_ms=float(l.mean()), p50_ms=float(np.median(l)), p95_ms=float(np.percentile(l, 95)), max_ms=float(l.max()),
                    passes_histogram={str(k): v for k, v in sorted(passes_hist.items())})
 
-    # ---- roofline of the residual/Jacobian sweep kernel (k_lin), measured live with HIP events on the
-    #      library's own stream; algorithmic bytes per launch = 68 (M - N) + 88 N over what the launch sweeps
-    reps = 200 if n_lm <= 1000 else 20
-    tk = grp if sharded else eng  # (the sharded window lives in the group's context)
-    # (a resident batch is linearized window by window — k_linw, which also holds what k_sum did; everything else by k_lin)
-    # (... and a large single window group by group — k_linb, the same strip sweep)
-    # (the library says which one the launch takes; a failure of the timing call itself is a failure of the bench)
-    sweep = tk.sweep_kernel(batch)
-    linw, linb = sweep == 1, sweep == 2
-    lin_ms = tk.time_kernel({0: 0, 1: 12, 2: 15}[sweep], batch, reps)
-    bytes_per_launch = sum(algorithmic_bytes(w.N, w.M) for w in wins[:batch]) if not sharded else algorithmic_bytes(local_N, local_M)
-    achieved = bytes_per_launch / (lin_ms * 1e-3) / 1e9
-    rows = ["k_linw<false>"] if linw else ["k_linb<false>"] if linb else (["k_lin<1, false>", "k_lin<2, false>", "k_lin<8, false>"] if batch >= 64 else ["k_lin<7, false>"])
-    traffic, traffic_src = pmc_traffic(workload if not stream_mode else "window300", rows)
-    kernel_name = ("k_linw (window-resident sweep: IMU + prior factors, every observation once — residual, Jacobian basis, Gram SYRK —, "
-                   "LDS accumulators of H_pp, Schur SYRK; one workgroup per window)") if linw else \
-        ("k_linb (the strip sweep of k_linw over one large window: a workgroup per group of strips of one start frame — every observation once, "
-         "Gram SYRK into LDS accumulators, Schur SYRK over the group —, partial sums added by k_sumb)") if linb else \
-        "k_lin (visual residual/Jacobian sweep: landmark rows + Schur SYRK, Gram chunks, IMU, prior)"
-    roofline = dict(bound="hbm", kernel=kernel_name,
-                    achieved=achieved, peak=HBM_PEAK_GBS, unit="GB/s", frac=achieved / HBM_PEAK_GBS, traffic=traffic,
-                    traffic_source=traffic_src,
-                    algorithmic_bytes_per_launch=bytes_per_launch, avg_launch_us=lin_ms * 1e3,
-                    note=("latency-bound at N=300 (0.1 MB per sweep); see DESIGN.md for the FP64-VALU roofline and the 100k-landmark sweep" if n_lm <= 1000 else
-                          "FP64-issue-bound, not HBM-bound (26 FLOP/B against a ridge of 9.8): VALU issue share and counter traffic in profiles/, DESIGN.md section 5"))
-    if linw or linb:
-        flops = sum(2.0e3 * (w.M - w.N) + 1.6e3 * w.N for w in wins[:batch])  # ~2.0 k per residual block + 1.6 k per landmark
-        roofline.update(note="FP64-bound (SURVEY section 8(d): 26 FLOP/B against a ridge of 9.8): see fp64_*; the HBM figures are kept because the metric's "
-                             "contract prices this kernel in bytes", fp64_tflops=flops / (lin_ms * 1e-3) / 1e12,
-                        fp64_frac=flops / (lin_ms * 1e-3) / 1e12 / FP64_PEAK_TFLOPS, flops_per_launch=flops)
-        extra = dict(k_solve_us=tk.time_kernel(13 if linw else 3, batch, max(reps // 4, 5)) * 1e3)
-        if linb:
-            extra.update(k_sumb_us=tk.time_kernel(16, batch, reps) * 1e3, k_backsub_wt_us=tk.time_kernel(17, batch, reps) * 1e3)
-    else:
-        extra = dict(k_sum_us=tk.time_kernel(2, batch, reps) * 1e3, k_solve_us=tk.time_kernel(3, batch, max(reps // 4, 5)) * 1e3)
-    # the dense solve (k_solve: one workgroup = one CU per window) is where a small window spends most of its time; its
-    # arithmetic is the Cholesky factorization and two substitutions of the 172 x 172 reduced system
-    KP = 172
-    solve_flops = batch * (KP ** 3 / 3.0 + 2.0 * KP ** 2) * 2.0
-    solve_tf = solve_flops / (extra["k_solve_us"] * 1e-6) / 1e12
-    cus = min(batch, 256)
-    roofline_solve = dict(bound="mfma", kernel="k_solve (Jacobi scaling, blocked Cholesky on v_mfma_f64_16x16x4_f64, substitutions)",
-                          achieved=solve_tf, peak=FP64_PEAK_TFLOPS, unit="TFLOP/s", frac=solve_tf / FP64_PEAK_TFLOPS,
-                          frac_of_the_cus_it_occupies=solve_tf / (FP64_PEAK_TFLOPS * cus / 256.0), cus=cus,
-                          flops_per_launch=solve_flops, avg_launch_us=extra["k_solve_us"],
-                          note="latency/issue-bound on a single CU per window (DESIGN.md section 5); not the kernel section 8(d) prices")
+    # ---- the outputs of the last timed step, before anything below launches into the same slots
+    if args.dump_outputs and rank == 0:
+        if sharded or batch == 1:
+            last = [(0, sol, prior)] if not stream_mode else [((args.steps - 1) % len(wins),) + outbuf[(args.steps - 1) % len(wins)]]
+        else:
+            last = [(s,) + eng.batch_download(s, wins[s].N) for s in dump_sample(batch)]
+        dump_outputs(args.dump_outputs, last)
+
+    if full:
+        # ---- roofline of the residual/Jacobian sweep kernel (k_lin), measured live with HIP events on the
+        #      library's own stream; algorithmic bytes per launch = 68 (M - N) + 88 N over what the launch sweeps
+        reps = 200 if n_lm <= 1000 else 20
+        tk = grp if sharded else eng  # (the sharded window lives in the group's context)
+        # (a resident batch is linearized window by window — k_linw, which also holds what k_sum did; everything else by k_lin)
+        # (... and a large single window group by group — k_linb, the same strip sweep)
+        # (the library says which one the launch takes; a failure of the timing call itself is a failure of the bench)
+        sweep = tk.sweep_kernel(batch)
+        linw, linb = sweep == 1, sweep == 2
+        lin_ms = tk.time_kernel({0: 0, 1: 12, 2: 15}[sweep], batch, reps)
+        bytes_per_launch = sum(algorithmic_bytes(w.N, w.M) for w in wins[:batch]) if not sharded else algorithmic_bytes(local_N, local_M)
+        achieved = bytes_per_launch / (lin_ms * 1e-3) / 1e9
+        rows = ["k_linw<false>"] if linw else ["k_linb<false>"] if linb else (["k_lin<1, false>", "k_lin<2, false>", "k_lin<8, false>"] if batch >= 64 else ["k_lin<7, false>"])
+        traffic, traffic_src = pmc_traffic(workload if not stream_mode else "window300", rows)
+        kernel_name = ("k_linw (window-resident sweep: IMU + prior factors, every observation once — residual, Jacobian basis, Gram SYRK —, "
+                       "LDS accumulators of H_pp, Schur SYRK; one workgroup per window)") if linw else \
+            ("k_linb (the strip sweep of k_linw over one large window: a workgroup per group of strips of one start frame — every observation once, "
+             "Gram SYRK into LDS accumulators, Schur SYRK over the group —, partial sums added by k_sumb)") if linb else \
+            "k_lin (visual residual/Jacobian sweep: landmark rows + Schur SYRK, Gram chunks, IMU, prior)"
+        roofline = dict(bound="hbm", kernel=kernel_name,
+                        achieved=achieved, peak=HBM_PEAK_GBS, unit="GB/s", frac=achieved / HBM_PEAK_GBS, traffic=traffic,
+                        traffic_source=traffic_src,
+                        algorithmic_bytes_per_launch=bytes_per_launch, avg_launch_us=lin_ms * 1e3,
+                        note=("latency-bound at N=300 (0.1 MB per sweep); see DESIGN.md for the FP64-VALU roofline and the 100k-landmark sweep" if n_lm <= 1000 else
+                              "FP64-issue-bound, not HBM-bound (26 FLOP/B against a ridge of 9.8): VALU issue share and counter traffic in profiles/, DESIGN.md section 5"))
+        if linw or linb:
+            flops = sum(2.0e3 * (w.M - w.N) + 1.6e3 * w.N for w in wins[:batch])  # ~2.0 k per residual block + 1.6 k per landmark
+            roofline.update(note="FP64-bound (SURVEY section 8(d): 26 FLOP/B against a ridge of 9.8): see fp64_*; the HBM figures are kept because the metric's "
+                                 "contract prices this kernel in bytes", fp64_tflops=flops / (lin_ms * 1e-3) / 1e12,
+                            fp64_frac=flops / (lin_ms * 1e-3) / 1e12 / FP64_PEAK_TFLOPS, flops_per_launch=flops)
+            extra = dict(k_solve_us=tk.time_kernel(13 if linw else 3, batch, max(reps // 4, 5)) * 1e3)
+            if linb:
+                extra.update(k_sumb_us=tk.time_kernel(16, batch, reps) * 1e3, k_backsub_wt_us=tk.time_kernel(17, batch, reps) * 1e3)
+        else:
+            extra = dict(k_sum_us=tk.time_kernel(2, batch, reps) * 1e3, k_solve_us=tk.time_kernel(3, batch, max(reps // 4, 5)) * 1e3)
+        # the dense solve (k_solve: one workgroup = one CU per window) is where a small window spends most of its time; its
+        # arithmetic is the Cholesky factorization and two substitutions of the 172 x 172 reduced system
+        KP = 172
+        solve_flops = batch * (KP ** 3 / 3.0 + 2.0 * KP ** 2) * 2.0
+        solve_tf = solve_flops / (extra["k_solve_us"] * 1e-6) / 1e12
+        cus = min(batch, 256)
+        roofline_solve = dict(bound="mfma", kernel="k_solve (Jacobi scaling, blocked Cholesky on v_mfma_f64_16x16x4_f64, substitutions)",
+                              achieved=solve_tf, peak=FP64_PEAK_TFLOPS, unit="TFLOP/s", frac=solve_tf / FP64_PEAK_TFLOPS,
+                              frac_of_the_cus_it_occupies=solve_tf / (FP64_PEAK_TFLOPS * cus / 256.0), cus=cus,
+                              flops_per_launch=solve_flops, avg_launch_us=extra["k_solve_us"],
+                              note="latency/issue-bound on a single CU per window (DESIGN.md section 5); not the kernel section 8(d) prices")
 
     if sharded:
         par = (f"landmark-sharded over {world} GPU(s) by lfvio_group (C++ driver inside the library): ranges balanced on observations, "
@@ -664,11 +732,12 @@ def main():
     cfg.update(extra_cfg)
     out = dict(metric="sliding-window solves/sec (10 KF x N landmarks)", value=value, unit="solves/s", n_gpus=world,
                steps=args.steps, warmup=args.warmup, ms_per_step=elapsed / args.steps * 1e3, higher_is_better=True,
-               scaling="strong" if sharded else "weak", vs_baseline=None, dtype="f64", data="synthetic", config=cfg,
-               roofline=roofline, roofline_k_solve=roofline_solve, kernels_us=extra)
+               scaling="strong" if sharded else "weak", vs_baseline=None, dtype="f64", data="synthetic", config=cfg)
+    if full:
+        out.update(roofline=roofline, roofline_k_solve=roofline_solve, kernels_us=extra)
     if lat is not None:
         out["latency"] = lat
-    if workload == "batch512" and not args.no_secondary:
+    if full and workload == "batch512" and not args.no_secondary:
         # The same 512 windows as two contexts of 256 on the device, two streams side by side (lfvio_group_create_local +
         # lfvio_group_batch_optimize; no collective in batch mode): the line's value is the better of the two forms, the
         # single-stream figure — the one the roofline objects and the kernel statistics of profiles/ describe — stays beside it.
@@ -691,7 +760,7 @@ def main():
             out["streams"] = 1
             if err2:
                 out["two_streams_error"] = err2
-    if stream_mode and world == 1 and not args.no_secondary:
+    if full and stream_mode and world == 1 and not args.no_secondary:
         # The same stream through the split call: lfvio_batch_upload_chained (the next window is packed while the marginalization
         # of the previous one is still running, and collects its prior) + lfvio_batch_optimize_begin (returns with the state).
         # Same windows, same priors bit for bit (the stream was generated by this library); where the list of windows wraps
@@ -735,7 +804,7 @@ def main():
                                                      "window k overlaps the packing of window k + 1")
         except Exception as ex:  # noqa: BLE001
             out["stream_chained"] = dict(error=repr(ex))
-    if sharded and world > 1:
+    if full and sharded and world > 1:
         # the same window, whole, on ONE GPU (rank 0 while the others wait): the figure the sharded rate is a speed-up over
         one = None
         if rank == 0:
@@ -753,7 +822,7 @@ def main():
             out["one_gpu_same_window"] = dict(ms_per_step=one * 1e3, value=1.0 / one, unit="solves/s",
                                               speedup_of_this_run=(1.0 / one) and value / (1.0 / one))
         barrier()
-    if world > 1 and workload == "window300" and not args.no_secondary:
+    if full and world > 1 and workload == "window300" and not args.no_secondary:
         # BASELINE configs[3] next to the weak-scaling headline: ONE 100 000-landmark window sharded over the N ranks through
         # lfvio_group (the C++ driver and the ncclAllReduce inside the library), strong scaling — with the same window's time on
         # ONE GPU measured in the same run (every rank its own copy, no collective), so the speed-up is read off the line.
@@ -799,7 +868,7 @@ def main():
             out["window100k_sharded"] = dict(error=gerr or "another rank could not create its group")
             watchdog.cancel()
             g2 = None
-    if world > 1 and workload == "window300" and not args.no_secondary and out.get("window100k_sharded") is None:
+    if full and world > 1 and workload == "window300" and not args.no_secondary and out.get("window100k_sharded") is None:
         for _ in range(3):
             g2.optimize(flag)
         ns = 20
@@ -832,7 +901,7 @@ def main():
                                                      "window whole on one GPU, slowest rank")
         g2.close()
         watchdog.cancel()
-    if args.batch_secondary or world > 1:
+    if args.batch_secondary or (full and world > 1):
         # The other multi-GPU configuration of BASELINE.json (configs[4]): independent windows, 512 resident per GPU, no
         # data-path collective — weak scaling, next to the strong-scaling figure above.  A secondary figure: it never replaces
         # `value`, and a failure here leaves the line as it is.
@@ -873,7 +942,7 @@ def main():
                                                     "times its own sweeps, the slowest counts")
         else:
             out["batch512_weak"] = dict(error=err or "another rank failed")
-    if world == 1 and workload == "window300" and not args.no_secondary:
+    if full and world == 1 and workload == "window300" and not args.no_secondary:
         # (a) the call a drop-in makes with the SHIPPED configuration: SOLVER_TIME = 0.04 s, i.e. max_solver_time_in_seconds =
         #     0.032 for MARGIN_OLD (estimator.cpp:819-822).  The cap is ~50x the solve: it must not cost the call its single
         #     graph launch, so the figure has to equal ms_per_step.
@@ -960,7 +1029,7 @@ def main():
                 e2.close()
         except Exception as ex:  # noqa: BLE001  (a secondary figure: a failure here leaves the headline as it is)
             out["batch512"] = dict(error=repr(ex))
-    if world == 1 and workload == "window300" and not args.no_secondary:
+    if full and world == 1 and workload == "window300" and not args.no_secondary:
         # (c) the large single window of configs[3] on one GPU and (d) the PCIe-inclusive stream, next to batch512: secondary figures,
         #     a failure leaves the headline as it is
         try:
@@ -978,7 +1047,7 @@ def main():
             out["replay"] = replay_record(replay_dir)
         except Exception as ex:  # noqa: BLE001
             out["replay"] = dict(error=repr(ex))
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(wins[0], flag)
         if isinstance(out.get("replay"), dict) and "error" not in out["replay"]:
             try:  # the trajectory's checker: the same recording over the CPU oracle, outside every timed region

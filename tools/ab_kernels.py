@@ -10,7 +10,7 @@ os.environ["TMPDIR"] = "/tmp"
 other = os.path.abspath(sys.argv[1])
 extra = sys.argv[2:]
 py, bench = sys.executable, os.path.join(ROOT, "bench.py")
-base = [py, bench, "--no-cpu-baseline", "--no-secondary"] + extra
+base = [py, bench, "--full", "--no-cpu-baseline", "--no-secondary"] + extra
 
 
 def line(lib):

@@ -16,7 +16,7 @@ extra = [a for a in sys.argv[2:] if not a.lstrip("-").isdigit() or a.startswith(
 d = "/tmp/call_timeline"
 subprocess.run(["rm", "-rf", d])
 cmd = ["rocprofv3", "--kernel-trace", "--output-format", "csv", "-d", d, "--", sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-secondary",
-       "--steps", "40", "--warmup", "10"] + extra
+       "--full", "--steps", "40", "--warmup", "10"] + extra
 r = subprocess.run(cmd, cwd="/tmp", text=True, capture_output=True)
 line = [l for l in r.stdout.splitlines() if l.startswith("{")]
 f = glob.glob(d + "/**/*kernel_trace.csv", recursive=True)[0]

@@ -60,7 +60,7 @@ def main():
         load_working_us(sys.argv[1])
     for w, args in ({} if pmc_only else WORK).items():
         # 1. the bench line itself (full default length for the headline workload)
-        r = sh([py, bench] + (args + ["--no-cpu-baseline"] if w != "window300" else []))
+        r = sh([py, bench, "--full"] + (args + ["--no-cpu-baseline"] if w != "window300" else []))
         line = [l for l in r.stdout.splitlines() if l.startswith("{")]
         if line:
             open(os.path.join(OUT, f"bench_{w}.json"), "w").write(line[-1] + "\n")
@@ -68,7 +68,7 @@ def main():
             print(r.stdout[-2000:], r.stderr[-2000:])
         # 2. kernel statistics of the same command (shorter run, no CPU baseline leg)
         d = f"/tmp/prof_{w}"
-        sh(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--", py, bench, "--no-cpu-baseline", "--no-secondary"] + args)
+        sh(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--", py, bench, "--full", "--no-cpu-baseline", "--no-secondary"] + args)
         for f in glob.glob(d + "/**/*kernel_stats.csv", recursive=True):
             rows = list(csv.reader(open(f)))
             with open(os.path.join(OUT, f"bench_{w}_kernel_stats.csv"), "w", newline="") as fo:
@@ -116,7 +116,7 @@ def main():
             # its 3 ms limit in front of every kernel of the loop — the passes are what the counters are about, the tail runs serially)
             os.environ["LFVIO_DEBUG"] = "marg_ahead=0"
             sh(["rocprofv3", "--pmc"] + ctrs + ["--output-format", "csv", "-d", d, "--", py, bench, "--no-cpu-baseline",
-                                                 "--no-secondary", "--steps", "10" if w != "batch512" else "4", "--warmup", "2"] + (WORK[w][:2] if w != "window300" else []))
+                                                 "--full", "--no-secondary", "--steps", "10" if w != "batch512" else "4", "--warmup", "2"] + (WORK[w][:2] if w != "window300" else []))
             for f in glob.glob(d + "/**/*counter_collection.csv", recursive=True):
                 for row in csv.DictReader(open(f)):
                     agg[short(row["Kernel_Name"])][row["Counter_Name"]].append(float(row["Counter_Value"]))

@@ -11,7 +11,7 @@ for spec in sys.argv[1:] or [""]:
         env["LFVIO_DEBUG"] = "spec_count=" + spec  # (bench.py applies it: lfvio_debug_configure "env")
     d = f"/tmp/st_{spec or 'a'}"
     r = subprocess.run(["rocprofv3", "--kernel-trace", "--output-format", "csv", "-d", d, "--", sys.executable, os.path.join(ROOT, "bench.py"),
-                        "--no-cpu-baseline", "--no-secondary", "--steps", "100", "--warmup", "10"], cwd="/tmp", env=env, text=True, capture_output=True)
+                        "--full", "--no-cpu-baseline", "--no-secondary", "--steps", "100", "--warmup", "10"], cwd="/tmp", env=env, text=True, capture_output=True)
     line = [l for l in r.stdout.splitlines() if l.startswith("{")]
     import json
     print("spec", spec or "adaptive", "ms_per_step", json.loads(line[-1])["ms_per_step"] if line else r.stderr[-500:])

@@ -8,7 +8,7 @@ os.environ["TMPDIR"] = "/tmp"
 steps, warm, windows = 10, 2, 512
 d = "/tmp/prof_sweep"
 subprocess.run(["rocprofv3", "--kernel-trace", "--output-format", "csv", "-d", d, "--", sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "batch512",
-                "--no-secondary", "--no-cpu-baseline", "--steps", str(steps), "--warmup", str(warm)], cwd="/tmp", capture_output=True, text=True)
+                "--full", "--no-secondary", "--no-cpu-baseline", "--steps", str(steps), "--warmup", str(warm)], cwd="/tmp", capture_output=True, text=True)
 f = glob.glob(d + "/**/*kernel_trace.csv", recursive=True)[0]
 rows = sorted((r for r in csv.DictReader(open(f)) if int(r["Grid_Size_Y"]) == windows), key=lambda r: int(r["Start_Timestamp"]))
 # (the bench's own kernel timings — lfvio_debug_time_kernel — launch ONE kernel over the whole batch many times in a row: runs of
