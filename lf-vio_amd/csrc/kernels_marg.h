@@ -1137,7 +1137,7 @@ DEV void spec_deliver(Slot *S, Slot *S0, int my_word, bool publish) {
 template <bool WORKER>
 __global__ __launch_bounds__(MARG_THREADS) void k_marg_solve(char *base, size_t stride, int flag_bits) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
-  const int flag = flag_bits & 255, force_eig = (flag_bits >> 8) & 1, gated = (flag_bits >> 9) & 1;  // bit 8: debug, see lfvio_debug_force_eig; bit 9: MODE_GATED
+  const int flag = flag_bits & 255, force_eig = (flag_bits >> 8) & 1, gated = (flag_bits >> 9) & 1;  // bit 8: debug, see lfvio_debug_configure "force_eig"; bit 9: MODE_GATED
   const int publish = (flag_bits >> 10) & 1;  // bit 10: the prior goes into the caller's mailbox as well (lfvio_batch_optimize_begin)
   // WORKER: a worker's launch on the second stream (kernels_spec.h) — base is the shadow slot, `stride` its distance from the slot
   // being solved; the prior is handed over at the end if the state it belongs to turns out to be the final one

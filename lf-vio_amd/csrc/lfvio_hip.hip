@@ -29,6 +29,7 @@ constexpr ncclDataType_t ncclDouble = 8;
 #include <cstring>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/lfvio.h"
@@ -160,6 +161,40 @@ struct SlotHostInfo {
   int list_items = -1;
 };
 
+struct Grid {
+  int lm, ch, sc, lw;
+  int ch_raw;  // largest chunk count of a slot before the rounding of `ch` (what decides the two-level sums: upload_window's pre_gram)
+};
+
+// k_setup's launch: grid.x and the bits of its last argument.  A resident batch is bound by the number of workgroups the launch
+// dispatches (21 per window, 16 of them for a prior that ONE workgroup handles there: 10 752 workgroups for 512 windows, ~10 ns each),
+// so it goes out with the compact grid — state, IMU roots, one prior workgroup, inverse depths — when every resident prior fits
+// that workgroup's 4 x 4 tiling (n <= 88: kernels_lin.h).
+struct SetupLaunch {
+  int gx, bits;
+};
+
+// How a launch over the resident slots [0, count) linearizes, decided once (route_for) for every site that enqueues or reports it
+struct Route {
+  enum Sweep { ROLES = 0, LINW = 1, LINB = 2 } sweep;  // k_lin roles + k_sum | k_linw | k_linb + k_sumb (lfvio_debug_query "sweep_kernel")
+  int count;
+  Grid g;
+  size_t role_wgs;    // workgroups of k_lin as one grid of all its roles
+  bool split;         // k_lin goes out role by role (a resident batch)
+  int linb_gx;        // grid.x of k_linb (LINB only)
+  SetupLaunch setup;  // k_setup in front of the sweep
+  int offs;           // slots_offs
+};
+
+// What a captured graph was built for: a graph whose key differs is captured again
+struct GraphKey {
+  int count = 0, lm = 0, ch = 0, sc = 0, sweep = -1, linb_gx = 0, offs = 0, setup = -1, spec = 0, passes = 0;
+  bool operator==(const GraphKey &o) const {
+    return count == o.count && lm == o.lm && ch == o.ch && sc == o.sc && sweep == o.sweep && linb_gx == o.linb_gx && offs == o.offs &&
+           setup == o.setup && spec == o.spec && passes == o.passes;
+  }
+};
+
 }  // namespace
 
 struct lfvio_ctx {
@@ -179,7 +214,7 @@ struct lfvio_ctx {
   std::vector<int> perm_build;  // upload_window builds the next permutation here and swaps it in at its commit point
   // cached graph of the solve loop
   hipGraphExec_t graph = nullptr;
-  int g_batch = 0, g_lm = 0, g_ch = 0, g_sc = 0, g_iters = 0, g_linw = 0, g_offs = 0;
+  GraphKey graph_key;
   // cached graph of one chunk of passes (synchronous entry points: the loop is launched chunk by chunk)
   // [publish]: the variants whose gated gauge fix / marginalization also push state and prior into the caller's mailbox
   // (lfvio_batch_optimize_begin) — a kernel argument, so the plain call pays nothing for the split one
@@ -191,8 +226,7 @@ struct lfvio_ctx {
   bool predicted_early = false;     // lfvio_batch_optimize_begin has fed this call's pass count to predict() already (the join / finish that follows must not again)
   int predict_passes = 4;           // passes the first graph of the next call carries: the most any of the last four calls needed (predict()); tail[flag]: force-done + gated gauge fix + marginalization
   double pass_seconds = 2e-4;       // measured duration of one pass of a continuation chunk (sizes the first graph of a call with a wall-clock cap)
-  int k_batch = 0, k_lm = 0, k_ch = 0, k_sc = 0, k_spec = 0, k_linw = 0, k_offs = 0;
-  int k_setup = -1;  // bits of k_setup's launch the graphs were captured with (setup_launch)  // (k_offs: slots_offs of the captured launches)
+  GraphKey chunk_key;  // of chunk, tail, first and the workers' graphs
   int *d_pending = nullptr, *h_pending = nullptr;  // number of slots whose trust-region loop is not done
   // lfvio_batch_optimize_begin / _finish: the solution of slot 0 arrives in host memory the gated gauge fix writes directly
   // (Slot::mail, dev_types.h MAIL_*) while the marginalization of the same graph is still running; `inflight` from the moment
@@ -221,7 +255,7 @@ struct lfvio_ctx {
   // the copies out of h_stage are awaited by the NEXT user of the staging block, not by the upload that enqueued them
   hipEvent_t stage_event = nullptr;
   bool stage_busy = false;
-  double up_us[4] = {0, 0, 0, 0};  // last upload: host packing | collecting the chained prior | prior + copies enqueued | final synchronization (lfvio_debug_upload_times)
+  double up_us[4] = {0, 0, 0, 0};  // last upload: host packing | collecting the chained prior | prior + copies enqueued | final synchronization (lfvio_debug_query "upload_times")
   std::unique_ptr<LfvioPrior> held;
   bool has_held = false;
   int inflight_flag = 0;        // marg_flag of the call in flight
@@ -230,7 +264,7 @@ struct lfvio_ctx {
   int mail_seq = 0;             // sequence number of the last upload (Slot::mail_seq)
   std::unique_ptr<LfvioPrior> chain_struct;  // the structure-only prior of a device-chained upload
   bool chain_err_told = false;     // the call in flight ran without the prior it was promised and its begin() has said so
-  bool debug_break_chain = false;  // lfvio_debug_break_next_chain: the next device-chained upload promises a prior of another size than the device will find
+  bool debug_break_chain = false;  // lfvio_debug_configure "break_next_chain": the next device-chained upload promises a prior of another size than the device will find
   bool inflight_first = false;  // the flag came out of the first graph: {tail_state, passes_used} land in h_pending[2..3] when it ends
   bool use_graph = true;
   int stat_chunks = 0;  // graph launches of the last synchronous solve loop (debug)
@@ -1056,10 +1090,19 @@ struct CaptureGuard {
   }
 };
 
-struct Grid {
-  int lm, ch, sc, lw;
-  int ch_raw;  // largest chunk count of a slot before the rounding of `ch` (what decides the two-level sums: upload_window's pre_gram)
-};
+// What enqueue() puts on `stream`, captured and instantiated as *out; an error enqueue() returns drops the partial graph
+template <class F>
+int capture_graph(lfvio_ctx *c, hipStream_t stream, hipGraphExec_t *out, F &&enqueue) {
+  hipGraph_t graph;
+  HIPCHK(c, hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
+  CaptureGuard guard(stream);
+  if (int rc = enqueue()) return rc;
+  HIPCHK(c, guard.end(&graph));
+  HIPCHK(c, hipGraphInstantiate(out, graph, nullptr, nullptr, 0));
+  HIPCHK(c, hipGraphDestroy(graph));
+  return LFVIO_OK;
+}
+
 constexpr int CH_BUCKET = 16;
 
 Grid grid_for(lfvio_ctx *c, int count) {
@@ -1079,37 +1122,6 @@ Grid grid_for(lfvio_ctx *c, int count) {
   return g;
 }
 
-// a resident batch: k_lin role by role (and without the transposed copy of W: its k_dogleg reads the compact rows)
-bool lin_split(int count, const Grid &g) {
-  return count >= LIN_SPLIT_MIN_BATCH && (size_t)count * (g.lw + (g.ch + 3) / 4 + LFVIO_WINDOW_SIZE + 1) > LIN_SPLIT_WGS;
-}
-
-// offs: the visual roles in the instantiation that knows the off-sphere flavour (k_lin, kernels_lin.h); the default is the one that is
-// always right, the loop's launches say what they need (slots_offs)
-void launch_lin(lfvio_ctx *c, int count, const Grid &g, int mode, bool offs = true) {
-  const int gram_wgs = (g.ch + 3) / 4;  // one chunk per wave
-  const size_t st = c->L.total;
-  if (lin_split(count, g)) {
-    // A resident batch: the roles go out as separate launches, each of a kernel compiled for that role alone.  Measured at 512 windows of 300 landmarks:
-    // landmark role 115 us + Gram role 175 us + IMU / prior roles 104 us on their own, 679 us as ONE grid — workgroups of four
-    // different code paths side by side on every CU (the sweep is ~30 KB of straight-line code per role) do not share an
-    // instruction cache well; two more launches cost 9 us.
-    if (offs) {
-      hipLaunchKernelGGL((k_lin<LIN_ROLE_LM, true>), dim3(g.lw, count), dim3(LIN_THREADS), 0, c->stream, c->d_base, st, mode, g.lw, 0);
-      hipLaunchKernelGGL((k_lin<LIN_ROLE_GRAM, true>), dim3(gram_wgs, count), dim3(LIN_THREADS), 0, c->stream, c->d_base, st, mode | MODE_NOCOUNT, 0, gram_wgs);
-    } else {
-      hipLaunchKernelGGL((k_lin<LIN_ROLE_LM, false>), dim3(g.lw, count), dim3(LIN_THREADS), 0, c->stream, c->d_base, st, mode, g.lw, 0);
-      hipLaunchKernelGGL((k_lin<LIN_ROLE_GRAM, false>), dim3(gram_wgs, count), dim3(LIN_THREADS), 0, c->stream, c->d_base, st, mode | MODE_NOCOUNT, 0, gram_wgs);
-    }
-    const bool raw = (mode & (MODE_GATED - 1)) == MODE_SOLVE && !(mode & (MODE_GATED | MODE_DECIDE));
-    if (raw) hipLaunchKernelGGL(k_imu_raw, dim3((count * LFVIO_WINDOW_SIZE + 63) / 64), dim3(64), 0, c->stream, c->d_base, st, count);
-    if (raw) hipLaunchKernelGGL((k_lin<LIN_ROLE_POSE_RAW, false>), dim3(LFVIO_WINDOW_SIZE + 1, count), dim3(LIN_THREADS), 0, c->stream, c->d_base, st, mode | MODE_NOCOUNT, 0, 0);
-    else hipLaunchKernelGGL((k_lin<LIN_ROLE_POSE, false>), dim3(LFVIO_WINDOW_SIZE + 1, count), dim3(LIN_THREADS), 0, c->stream, c->d_base, st, mode | MODE_NOCOUNT, 0, 0);
-    return;
-  }
-  if (offs) hipLaunchKernelGGL((k_lin<LIN_ROLE_ALL, true>), dim3(g.lw + gram_wgs + LFVIO_WINDOW_SIZE + 1, count), dim3(LIN_THREADS), 0, c->stream, c->d_base, st, mode, g.lw, gram_wgs);
-  else hipLaunchKernelGGL((k_lin<LIN_ROLE_ALL, false>), dim3(g.lw + gram_wgs + LFVIO_WINDOW_SIZE + 1, count), dim3(LIN_THREADS), 0, c->stream, c->d_base, st, mode, g.lw, gram_wgs);
-}
 // what the sweeps of slots [0, count) need: bit 0 the sweep at the uploaded state, bit 1 every sweep
 int slots_offs(const lfvio_ctx *c, int count) {
   int r = 0;
@@ -1117,8 +1129,92 @@ int slots_offs(const lfvio_ctx *c, int count) {
   return r;
 }
 
+SetupLaunch setup_launch(lfvio_ctx *c, int count, int lm, bool zero_wt) {
+  bool compact = count >= 8;
+  for (int s = 0; compact && s < count; s++) compact = c->info[s].prior_n <= SETUP_TILED_MAXN;
+  return {(compact ? 3 : SETUP_WGS) + (lm + 3) / 4, (zero_wt ? 1 : 0) | (compact ? 4 : 0)};
+}
+
+// How a launch in `mode` over slots [0, count) linearizes:
+//  - k_linw, window by window (kernels_linw.h): a resident batch whose windows all carry a LinwPlan, in the solve passes and the
+//    marginalization's sweep behind them (linw_mode 2: however few windows);
+//  - k_linb + k_sumb, group by group: large single windows that carry a group list, in the solve passes only (the marginalization's
+//    sweep of such a window stays with the roles: one launch per call), and a rank's share of a sharded window under the same
+//    condition (either way its sums land in the exchange buffer);
+//  - k_lin role by role + k_sum otherwise; a resident batch sends the roles out as separate launches (`split`, and without the
+//    transposed copy of W: its k_dogleg reads the compact rows).
+Route route_for(lfvio_ctx *c, int count, int mode) {
+  Route r;
+  r.count = count;
+  r.g = grid_for(c, count);
+  r.role_wgs = (size_t)count * (r.g.lw + (r.g.ch + 3) / 4 + LFVIO_WINDOW_SIZE + 1);
+  r.split = count >= LIN_SPLIT_MIN_BATCH && r.role_wgs > LIN_SPLIT_WGS;
+  bool linw = true, linb = count > 0;
+  int ng = 0;
+  for (int s = 0; s < count; s++) {
+    linw = linw && c->info[s].linw_ok, linb = linb && c->info[s].linb_ok;
+    ng = std::max(ng, c->info[s].linb_ng);
+  }
+  const bool solve = mode == MODE_SOLVE;
+  const bool marg_sweep = (mode & (MODE_GATED - 1)) >= MODE_MARG && !(mode & (MODE_DECIDE | MODE_NOCOUNT));
+  if (c->linw_mode != 0 && !c->shard_active && linw && (solve || marg_sweep) && (c->linw_mode == 2 || r.split)) r.sweep = Route::LINW;
+  else if (c->linw_mode != 0 && solve && linb && (!c->shard_active || count == 1)) r.sweep = Route::LINB;
+  else r.sweep = Route::ROLES;
+  // (grid of k_linb: the groups of the largest resident window and the pose side's workgroup, rounded up so that a captured graph
+  // serves the next window of about that size too — a workgroup past a slot's own count returns at once; part of the graphs' key)
+  r.linb_gx = r.sweep == Route::LINB ? (ng + 1 + 63) / 64 * 64 : 0;
+  r.setup = setup_launch(c, count, r.g.lm, r.sweep == Route::LINW);
+  r.offs = slots_offs(c, count);
+  return r;
+}
+
+// spec: the speculation variant; passes: of a graph that carries a fixed number; with_setup: the graph carries k_setup
+GraphKey graph_key(const Route &r, int spec, int passes, bool with_setup) {
+  GraphKey k;
+  k.count = r.count, k.lm = r.g.lm, k.ch = r.g.ch, k.sc = r.g.sc, k.sweep = r.sweep, k.linb_gx = r.linb_gx, k.offs = r.offs;
+  k.setup = with_setup ? r.setup.bits : 0, k.spec = spec, k.passes = passes;
+  return k;
+}
+
+void launch_setup(lfvio_ctx *c, const Route &r, int mode) {
+  hipLaunchKernelGGL(k_setup, dim3(r.setup.gx, r.count), dim3(256), 0, c->stream, c->d_base, c->L.total, mode, r.setup.bits);
+}
+
+// offs: the visual sweep in the instantiation that knows the off-sphere flavour (k_lin, kernels_lin.h) — launch(std::true_type) —
+// or in the one that does not; the loop's launches say what they need (slots_offs), the one-off sweeps take the one that is always right
+template <class F>
+void with_offs(bool offs, F &&launch) {
+  if (offs) launch(std::true_type());
+  else launch(std::false_type());
+}
+
+void launch_lin(lfvio_ctx *c, const Route &r, int mode, bool offs) {
+  const int count = r.count, lw = r.g.lw, gram_wgs = (r.g.ch + 3) / 4;  // one chunk per wave
+  const size_t st = c->L.total;
+  with_offs(offs, [&](auto o) {
+    if (!r.split) {
+      hipLaunchKernelGGL((k_lin<LIN_ROLE_ALL, decltype(o)::value>), dim3(lw + gram_wgs + LFVIO_WINDOW_SIZE + 1, count), dim3(LIN_THREADS), 0, c->stream, c->d_base, st,
+                         mode, lw, gram_wgs);
+      return;
+    }
+    // A resident batch: the roles go out as separate launches, each of a kernel compiled for that role alone.  Measured at 512 windows of 300 landmarks:
+    // landmark role 115 us + Gram role 175 us + IMU / prior roles 104 us on their own, 679 us as ONE grid — workgroups of four
+    // different code paths side by side on every CU (the sweep is ~30 KB of straight-line code per role) do not share an
+    // instruction cache well; two more launches cost 9 us.
+    hipLaunchKernelGGL((k_lin<LIN_ROLE_LM, decltype(o)::value>), dim3(lw, count), dim3(LIN_THREADS), 0, c->stream, c->d_base, st, mode, lw, 0);
+    hipLaunchKernelGGL((k_lin<LIN_ROLE_GRAM, decltype(o)::value>), dim3(gram_wgs, count), dim3(LIN_THREADS), 0, c->stream, c->d_base, st, mode | MODE_NOCOUNT, 0, gram_wgs);
+  });
+  if (!r.split) return;
+  const bool raw = (mode & (MODE_GATED - 1)) == MODE_SOLVE && !(mode & (MODE_GATED | MODE_DECIDE));
+  if (raw) hipLaunchKernelGGL(k_imu_raw, dim3((count * LFVIO_WINDOW_SIZE + 63) / 64), dim3(64), 0, c->stream, c->d_base, st, count);
+  if (raw) hipLaunchKernelGGL((k_lin<LIN_ROLE_POSE_RAW, false>), dim3(LFVIO_WINDOW_SIZE + 1, count), dim3(LIN_THREADS), 0, c->stream, c->d_base, st, mode | MODE_NOCOUNT, 0, 0);
+  else hipLaunchKernelGGL((k_lin<LIN_ROLE_POSE, false>), dim3(LFVIO_WINDOW_SIZE + 1, count), dim3(LIN_THREADS), 0, c->stream, c->d_base, st, mode | MODE_NOCOUNT, 0, 0);
+}
+
 // fixed-order reduction of the partials; two levels once a single k_sum thread would have to walk hundreds of them
-void launch_sum(lfvio_ctx *c, int count, const Grid &g, int mode) {
+void launch_sum(lfvio_ctx *c, const Route &r, int mode) {
+  const int count = r.count;
+  const Grid &g = r.g;
   const size_t st = c->L.total;
   // (from the unrounded chunk count: a slot has pre_gram set iff ITS count exceeds the limit — with the rounded one a window
   // of 241 or 242 chunks launched k_presum for gather lists that do not use its output)
@@ -1144,9 +1240,22 @@ LinwArgs linw_args(const lfvio_ctx *c) {
   a.asm_tab = c->d_lwt;
   return a;
 }
-void launch_linw(lfvio_ctx *c, int count, int mode_bits = MODE_SOLVE, bool offs = true) {
-  if (offs) hipLaunchKernelGGL(k_linw<true>, dim3(1, count), dim3(LW_THREADS), LW_LDS_BYTES, c->stream, c->d_base, c->L.total, linw_args(c), mode_bits);
-  else hipLaunchKernelGGL(k_linw<false>, dim3(1, count), dim3(LW_THREADS), LW_LDS_BYTES, c->stream, c->d_base, c->L.total, linw_args(c), mode_bits);
+
+// One linearization of the route's slots.  decide: the trust-region bookkeeping of the pass before rides in k_lin's prologue
+void launch_sweep(lfvio_ctx *c, const Route &r, int mode, bool offs, bool decide = false) {
+  if (r.sweep == Route::ROLES) {
+    launch_lin(c, r, mode | (decide ? MODE_DECIDE : 0), offs);
+    launch_sum(c, r, mode);
+    return;
+  }
+  const size_t st = c->L.total;
+  with_offs(offs, [&](auto o) {
+    if (r.sweep == Route::LINW)  // the window-resident sweep: one workgroup per window — pose-side factors, visual sweep, Schur; it counts the pass
+      hipLaunchKernelGGL(k_linw<decltype(o)::value>, dim3(1, r.count), dim3(LW_THREADS), LW_LDS_BYTES, c->stream, c->d_base, st, linw_args(c), mode);
+    else
+      hipLaunchKernelGGL(k_linb<decltype(o)::value>, dim3(r.linb_gx, r.count), dim3(LW_THREADS), LW_LDS_BYTES, c->stream, c->d_base, st, linw_args(c));
+  });
+  if (r.sweep == Route::LINB) hipLaunchKernelGGL(k_sumb, dim3(LINB_SUM_GRID, r.count), dim3(LINB_SUM_THREADS), 0, c->stream, c->d_base, st, linw_args(c));
 }
 
 // lw: the pass was linearized by k_linw — H_pp holds the visual terms of its camera part only, the solve adds the rest on load
@@ -1159,74 +1268,22 @@ void launch_solve(lfvio_ctx *c, int count, bool lw = false) {
     hipLaunchKernelGGL(k_solve_dense<false>, dim3(1, count), dim3(SOLVE_THREADS), SOLVE_LDS, c->stream, c->d_base, st, xo, io, po, (const int *)nullptr);
 }
 
-// A resident batch whose windows all carry a LinwPlan is linearized window by window (kernels_linw.h) instead of role by role.
-bool use_linw(lfvio_ctx *c, int count, const Grid &g, int mode) {
-  // (the solve passes, and the marginalization's sweep behind them)
-  const int m = mode & (MODE_GATED - 1);
-  const bool solve = mode == MODE_SOLVE, marg_sweep = m >= MODE_MARG && !(mode & (MODE_DECIDE | MODE_NOCOUNT));
-  if (!(solve || marg_sweep) || c->linw_mode == 0 || c->shard_active) return false;
-  if (c->linw_mode != 2 && !lin_split(count, g)) return false;
-  for (int s = 0; s < count; s++)
-    if (!c->info[s].linw_ok) return false;
-  return true;
-}
-
-// k_setup's launch: grid.x and the bits of its last argument.  A resident batch is bound by the number of workgroups the launch
-// dispatches (21 per window, 16 of them for a prior that ONE workgroup handles there: 10 752 workgroups for 512 windows, ~10 ns each),
-// so it goes out with the compact grid — state, IMU roots, one prior workgroup, inverse depths — when every resident prior fits
-// that workgroup's 4 x 4 tiling (n <= 88: kernels_lin.h).
-struct SetupLaunch {
-  int gx, bits;
-};
-SetupLaunch setup_launch(lfvio_ctx *c, int count, int lm, bool zero_wt) {
-  bool compact = count >= 8;
-  for (int s = 0; compact && s < count; s++) compact = c->info[s].prior_n <= SETUP_TILED_MAXN;
-  return {(compact ? 3 : SETUP_WGS) + (lm + 3) / 4, (zero_wt ? 1 : 0) | (compact ? 4 : 0)};
-}
-
-// A large single window that carries a group list is linearized group by group (k_linb + k_sumb) instead of role by role; the
-// marginalization's sweep of such a window stays with the roles (one launch per call).
-bool use_linb(lfvio_ctx *c, int count, const Grid &g, int mode) {
-  if (mode != MODE_SOLVE || c->linw_mode == 0 || c->shard_active) return false;
-  for (int s = 0; s < count; s++)
-    if (!c->info[s].linb_ok) return false;
-  return count > 0;
-}
-// (grid of k_linb: the groups of the largest resident window and the pose side's workgroup, rounded up so that a captured graph
-// serves the next window of about that size too — a workgroup past a slot's own count returns at once; part of the graphs' key)
-int linb_grid(const lfvio_ctx *c, int count) {
-  int ng = 0;
-  for (int s = 0; s < count; s++) ng = std::max(ng, c->info[s].linb_ng);
-  return (ng + 1 + 63) / 64 * 64;
-}
-void launch_linb(lfvio_ctx *c, int count, bool offs = true) {
-  if (offs) hipLaunchKernelGGL(k_linb<true>, dim3(linb_grid(c, count), count), dim3(LW_THREADS), LW_LDS_BYTES, c->stream, c->d_base, c->L.total, linw_args(c));
-  else hipLaunchKernelGGL(k_linb<false>, dim3(linb_grid(c, count), count), dim3(LW_THREADS), LW_LDS_BYTES, c->stream, c->d_base, c->L.total, linw_args(c));
-  hipLaunchKernelGGL(k_sumb, dim3(LINB_SUM_GRID, count), dim3(LINB_SUM_THREADS), 0, c->stream, c->d_base, c->L.total, linw_args(c));
-}
-
 // speculate: small windows evaluate the steps for radius, radius / 2, radius / 4 in every pass (dev_types.h, SPEC_EXTRA)
 // first / last: position of the pass in the sequence being issued (a graph, or a plain run of passes).  For small windows
 // the trust-region bookkeeping of a pass rides in the prologue of the NEXT pass's k_lin (MODE_DECIDE, one launch less per
 // pass); k_decide itself is only launched behind the last pass, so that the header is final where the sequence ends.
 // gauge: the gated gauge fix follows this (last) pass — returns true if it went out with the bookkeeping (k_decide_gauge)
-// offs: see launch_lin
-bool launch_iteration(lfvio_ctx *c, int count, const Grid &g, int mode, bool speculate = false, bool first = true, bool last = true, bool gauge = false, bool offs = true) {
+// r: route_for(c, count, mode); offs: see with_offs
+bool launch_iteration(lfvio_ctx *c, const Route &r, int mode, bool speculate = false, bool first = true, bool last = true, bool gauge = false, bool offs = true) {
+  const int count = r.count;
+  const Grid &g = r.g;
   const size_t st = c->L.total;
   const bool solve = (mode & (MODE_GATED - 1)) == MODE_SOLVE && !(mode & MODE_GATED);
   // (latency of few windows only: in a resident batch every workgroup of k_lin repeating the decision costs more of the
   // GPU than the launch it saves)
-  const bool lw = use_linw(c, count, g, mode), lb = !lw && use_linb(c, count, g, mode);
-  const bool merge = solve && !lw && g.lm <= DOGLEG_INLINE_BLOCKS && (size_t)count * (g.lw + (g.ch + 3) / 4 + LFVIO_WINDOW_SIZE + 1) <= LIN_SPLIT_WGS;
-  if (lw) {
-    // the window-resident sweep: one workgroup per window — pose-side factors, visual sweep, Schur; it counts the pass
-    launch_linw(c, count, mode, offs);
-  } else if (lb) {
-    launch_linb(c, count, offs);
-  } else {
-    launch_lin(c, count, g, mode | (merge && !first ? MODE_DECIDE : 0), offs);
-    launch_sum(c, count, g, mode);
-  }
+  const bool lw = r.sweep == Route::LINW, lb = r.sweep == Route::LINB;
+  const bool merge = solve && !lw && g.lm <= DOGLEG_INLINE_BLOCKS && r.role_wgs <= LIN_SPLIT_WGS;
+  launch_sweep(c, r, mode, offs, merge && !first);
   if ((mode & (MODE_GATED - 1)) == MODE_SOLVE) {
     launch_solve(c, count, lw);  // (k_sumb leaves the complete matrix)
     // small windows: the landmark back-substitution rides inside k_dogleg (one launch less per pass)
@@ -1234,7 +1291,7 @@ bool launch_iteration(lfvio_ctx *c, int count, const Grid &g, int mode, bool spe
     const int spec = speculate && inl ? c->spec_count : 1;
     const int nb = g.lm + LFVIO_WINDOW_SIZE + 1;
     // few small windows: the step and the cost of its candidates in one launch (k_step)
-    const bool split = lin_split(count, g) || lw;
+    const bool split = r.split || lw;
     const bool fuse = inl && !split && !c->shard_active && (size_t)count * nb <= 2048;
     // a resident batch on the window-resident path: step, candidate cost and bookkeeping as ONE launch, one workgroup per window
     const bool stepw = lw && inl && spec == 1;
@@ -1314,7 +1371,8 @@ int enqueue_marg(lfvio_ctx *c, int count, int flag, bool standalone, bool gated 
 int enqueue_solve(lfvio_ctx *c, int count, int max_iter, bool adaptive, int fused_flag = -1, bool *tail_done = nullptr,
                   double max_seconds = -1.0, bool early = false) {
   if (int rc = join_inflight(c, early)) return rc;
-  const Grid g = grid_for(c, count);
+  const Route r = route_for(c, count, MODE_SOLVE);
+  const Grid &g = r.g;
   const int passes = std::max(max_iter, 0) + 4;
   if (adaptive && c->use_graph) {
     const bool speculate = (size_t)count * (g.lm + LFVIO_WINDOW_SIZE + 1) <= 512;
@@ -1327,12 +1385,11 @@ int enqueue_solve(lfvio_ctx *c, int count, int max_iter, bool adaptive, int fuse
       HIPCHK(c, hipMalloc((void **)&c->d_pending, 256));
       HIPCHK(c, hipHostMalloc((void **)&c->h_pending, 256, hipHostMallocDefault));
     }
-    const int lwk = (use_linw(c, count, g, MODE_SOLVE) ? 1 : use_linb(c, count, g, MODE_SOLVE) ? 2 + 4 * linb_grid(c, count) : 0);
-    const int offs = slots_offs(c, count);
-    const int setup_bits = setup_launch(c, count, g.lm, lwk == 1).bits;  // (the compact grid of k_setup is part of the captured launch)
-    if (c->k_batch != count || c->k_lm != g.lm || c->k_ch != g.ch || c->k_sc != g.sc || c->k_spec != (int)speculate || c->k_linw != lwk || c->k_offs != offs || c->k_setup != setup_bits) {
-      destroy_graph(c, c->k_batch == count && ((c->k_offs ^ offs) & 2) == 0);  // (the workers' graphs: per context, but for the fixed-extrinsic bit)
-      c->k_batch = count, c->k_lm = g.lm, c->k_ch = g.ch, c->k_sc = g.sc, c->k_spec = (int)speculate, c->k_linw = lwk, c->k_offs = offs, c->k_setup = setup_bits;
+    const int offs = r.offs;
+    const GraphKey key = graph_key(r, (int)speculate, 0, true);
+    if (!(c->chunk_key == key)) {
+      destroy_graph(c, c->chunk_key.count == count && ((c->chunk_key.offs ^ offs) & 2) == 0);  // (the workers' graphs: per context, but for the fixed-extrinsic bit)
+      c->chunk_key = key;
     }
     if (tail_done) *tail_done = false;
     const bool fuse = fused_flag >= 0 && fused_flag < 2;
@@ -1348,40 +1405,30 @@ int enqueue_solve(lfvio_ctx *c, int count, int max_iter, bool adaptive, int fuse
     if (capped) first_passes = std::max(std::min(SOLVE_CHUNK, passes), std::min(first_passes, (int)std::min(max_seconds / c->pass_seconds, 1e6)));
     const int sv = speculate && c->spec_count > 3 ? 1 : 0;  // (both variants stay captured: a stream may alternate)
     hipGraphExec_t &first_graph = c->first[sv][c->publish ? 1 : 0][fuse ? 1 + fused_flag : 0][first_passes];
-    auto capture = [&](hipGraphExec_t *out, bool setup, int npass, int tail_flag) -> int {
-      hipGraph_t graph;
-      int rc = LFVIO_OK;
-      HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-      CaptureGuard guard(c->stream);
-      if (setup)
-        { const SetupLaunch sl_ = setup_launch(c, count, g.lm, use_linw(c, count, g, MODE_SOLVE)); hipLaunchKernelGGL(k_setup, dim3(sl_.gx, count), dim3(256), 0, c->stream, c->d_base, c->L.total, MODE_SOLVE, sl_.bits); }
-      bool gauged = false;
-      // (the sweep behind k_setup linearizes at the uploaded state: the only point of a call that can hold a quaternion off the unit sphere,
-      // a fixed extrinsic aside — slots_offs)
-      for (int it = 0; it < npass; it++)
-        gauged = launch_iteration(c, count, g, MODE_SOLVE, speculate, it == 0, it == npass - 1, tail_flag >= 0, (offs & 2) || (setup && it == 0 && (offs & 1)));
-      if (tail_flag >= 0) {
-        if (!gauged) {
-          hipLaunchKernelGGL(k_gauge, dim3(1 + (g.lm + 1) / 2, count), dim3(128), 0, c->stream, c->d_base, c->L.total, 1);
-          if (c->publish) hipLaunchKernelGGL(k_publish, dim3(1), dim3(256), 0, c->stream, c->d_base, c->L.total);  // (k_decide_gauge does it itself)
+    auto capture = [&](hipGraphExec_t *out, bool setup, int npass, int tail_flag) {
+      return capture_graph(c, c->stream, out, [&]() -> int {
+        if (setup) launch_setup(c, r, MODE_SOLVE);
+        bool gauged = false;
+        // (the sweep behind k_setup linearizes at the uploaded state: the only point of a call that can hold a quaternion off the unit sphere,
+        // a fixed extrinsic aside — slots_offs)
+        for (int it = 0; it < npass; it++)
+          gauged = launch_iteration(c, r, MODE_SOLVE, speculate, it == 0, it == npass - 1, tail_flag >= 0, (offs & 2) || (setup && it == 0 && (offs & 1)));
+        if (tail_flag >= 0) {
+          if (!gauged) {
+            hipLaunchKernelGGL(k_gauge, dim3(1 + (g.lm + 1) / 2, count), dim3(128), 0, c->stream, c->d_base, c->L.total, 1);
+            if (c->publish) hipLaunchKernelGGL(k_publish, dim3(1), dim3(256), 0, c->stream, c->d_base, c->L.total);  // (k_decide_gauge does it itself)
+          }
+          if (int rc = enqueue_marg(c, count, tail_flag, false, true)) return rc;
         }
-        rc = enqueue_marg(c, count, tail_flag, false, true);
-      }
-      if (tail_flag >= 0 && count == 1) {
-        // one window: its {tail_state, passes_used} pair is the answer — copied as it is, no k_pending launch
-        HIPCHK(c, hipMemcpyAsync(c->h_pending + 2, c->d_base + offsetof(Slot, tail_state), 4 * sizeof(int), hipMemcpyDeviceToHost, c->stream));  // (.. chain_err)
-      } else {
-        hipLaunchKernelGGL(k_pending, dim3(1), dim3(64), 0, c->stream, c->d_base, c->L.total, count, c->d_pending, tail_flag >= 0 ? 1 : 0);
-        HIPCHK(c, hipMemcpyAsync(c->h_pending, c->d_pending, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-      }
-      HIPCHK(c, guard.end(&graph));
-      if (rc) {
-        (void)hipGraphDestroy(graph);
-        return rc;
-      }
-      HIPCHK(c, hipGraphInstantiate(out, graph, nullptr, nullptr, 0));
-      HIPCHK(c, hipGraphDestroy(graph));
-      return LFVIO_OK;
+        if (tail_flag >= 0 && count == 1) {
+          // one window: its {tail_state, passes_used} pair is the answer — copied as it is, no k_pending launch
+          HIPCHK(c, hipMemcpyAsync(c->h_pending + 2, c->d_base + offsetof(Slot, tail_state), 4 * sizeof(int), hipMemcpyDeviceToHost, c->stream));  // (.. chain_err)
+        } else {
+          hipLaunchKernelGGL(k_pending, dim3(1), dim3(64), 0, c->stream, c->d_base, c->L.total, count, c->d_pending, tail_flag >= 0 ? 1 : 0);
+          HIPCHK(c, hipMemcpyAsync(c->h_pending, c->d_pending, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        }
+        return LFVIO_OK;
+      });
     };
     if (!first_graph) {
       const int rc = capture(&first_graph, true, first_passes, fuse ? fused_flag : -1);
@@ -1397,38 +1444,36 @@ int enqueue_solve(lfvio_ctx *c, int count, int max_iter, bool adaptive, int fuse
     // (not behind a device-chained upload: there the marginalization already runs beside the host's packing of the next window, and the next
     // window's upload would have to wait for a worker instead of following the stream)
     const bool ahead = fuse && count == 1 && c->info[0].spec_on && c->shadow && c->marg_ahead  && !c->shard_active && !c->pipelined &&
-                       g.lm <= DOGLEG_INLINE_BLOCKS && g.ch_raw <= PRE_CHUNK_LIMIT && g.sc <= 4 * PRE_GROUP && !use_linw(c, count, g, MODE_SOLVE) &&
-                       !use_linb(c, count, g, MODE_SOLVE);
+                       g.lm <= DOGLEG_INLINE_BLOCKS && g.ch_raw <= PRE_CHUNK_LIMIT && g.sc <= 4 * PRE_GROUP && r.sweep == Route::ROLES;
     for (int wk = 0; ahead && wk < lfvio_ctx::WORKERS; wk++) {
       hipGraphExec_t *side_graph = &c->side[wk][fused_flag][c->publish ? 1 : 0];
       if (*side_graph) continue;
       hipStream_t ss = c->sstream[wk];
-      hipGraph_t graph;
-      HIPCHK(c, hipStreamBeginCapture(ss, hipStreamCaptureModeThreadLocal));
-      CaptureGuard guard(ss);
       const size_t back = (size_t)(c->batch + wk) * c->L.total;
       char *sh = c->d_base + back;
       // launch dimensions for the largest window the merged sequence takes (spare workgroups test their index against the slot's own
       // counts and return): one capture serves every window of the context
       const Layout &L = c->L;
       const int mode = (MODE_MARG + fused_flag) | MODE_GATED, gram_wgs = (L.capChunks + 3) / 4, lw_cap = 2 * DOGLEG_INLINE_BLOCKS;
-      const int pre = 0, groups = 1;  // (k_presum is for windows of thousands of landmarks)
-      // (the gather lists are inputs: the shadow's copies of those members lead back into slot 0, and so do these offsets)
+      // (the gather lists are inputs: the shadow's copies of those members lead back into slot 0, and so do these offsets;
+      // no k_presum: that is for windows of thousands of landmarks)
       const SumArgs sa{(long long)L.sum_off - (long long)back, (long long)L.sum_end_marg - (long long)back, (long long)L.sum_items - (long long)back,
                        (long long)L.gram_part, (long long)L.pairG, (long long)L.imu_out, (long long)L.prior_A - (long long)back};
-      for (int r = 0; r < SIDE_ROUNDS; r++) {
-        hipLaunchKernelGGL(k_spec_begin, dim3(1), dim3(128), 0, ss, sh, back);
-        // (a re-anchored state: on the sphere but for a fixed extrinsic)
-        if (offs & 2) hipLaunchKernelGGL((k_lin<LIN_ROLE_ALL, true>), dim3(lw_cap + gram_wgs + LFVIO_WINDOW_SIZE + 1, 1), dim3(LIN_THREADS), 0, ss, sh, back, mode, lw_cap, gram_wgs);
-        else hipLaunchKernelGGL((k_lin<LIN_ROLE_ALL, false>), dim3(lw_cap + gram_wgs + LFVIO_WINDOW_SIZE + 1, 1), dim3(LIN_THREADS), 0, ss, sh, back, mode, lw_cap, gram_wgs);
-        if (pre) hipLaunchKernelGGL(k_presum, dim3(NPAIR + (SCHUR_LEN / 256) * groups + 1, 1), dim3(256), 0, ss, sh, back, mode, groups);
-        hipLaunchKernelGGL(k_sum, dim3(HPP_BLOCKS + SCHUR_LEN / 256 + 1, 1), dim3(256), 0, ss, sh, back, mode, pre, sa);
-        hipLaunchKernelGGL(k_marg_solve<true>, dim3(1, 1), dim3(MARG_THREADS), MARG_LDS, ss, sh, back,
-                           fused_flag | (c->force_eig ? 256 : 0) | 512 | (c->publish ? 1024 : 0));
-      }
-      HIPCHK(c, guard.end(&graph));
-      HIPCHK(c, hipGraphInstantiate(side_graph, graph, nullptr, nullptr, 0));
-      HIPCHK(c, hipGraphDestroy(graph));
+      const int rc = capture_graph(c, ss, side_graph, [&]() -> int {
+        for (int rd = 0; rd < SIDE_ROUNDS; rd++) {
+          hipLaunchKernelGGL(k_spec_begin, dim3(1), dim3(128), 0, ss, sh, back);
+          // (a re-anchored state: on the sphere but for a fixed extrinsic)
+          with_offs(offs & 2, [&](auto o) {
+            hipLaunchKernelGGL((k_lin<LIN_ROLE_ALL, decltype(o)::value>), dim3(lw_cap + gram_wgs + LFVIO_WINDOW_SIZE + 1, 1), dim3(LIN_THREADS), 0, ss, sh, back, mode,
+                               lw_cap, gram_wgs);
+          });
+          hipLaunchKernelGGL(k_sum, dim3(HPP_BLOCKS + SCHUR_LEN / 256 + 1, 1), dim3(256), 0, ss, sh, back, mode, 0, sa);
+          hipLaunchKernelGGL(k_marg_solve<true>, dim3(1, 1), dim3(MARG_THREADS), MARG_LDS, ss, sh, back,
+                             fused_flag | (c->force_eig ? 256 : 0) | 512 | (c->publish ? 1024 : 0));
+        }
+        return LFVIO_OK;
+      });
+      if (rc) return rc;
     }
     c->side_launched = false, c->side_known = false;
     c->stat_chunks = 0;
@@ -1444,7 +1489,7 @@ int enqueue_solve(lfvio_ctx *c, int count, int max_iter, bool adaptive, int fuse
         for (int wk = 0; wk < lfvio_ctx::WORKERS; wk++) HIPCHK(c, hipGraphLaunch(c->side[wk][fused_flag][c->publish ? 1 : 0], c->sstream[wk]));
         c->side_launched = true, c->stat_ahead_calls++;
       }
-      if (c->pipelined && done_passes == 0) c->up_us[1] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_launch).count() * 1e6;  // (debug: lfvio_debug_upload_times)
+      if (c->pipelined && done_passes == 0) c->up_us[1] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_launch).count() * 1e6;  // (debug: lfvio_debug_query "upload_times")
       if (watch && wait_early(c)) {  // the window was done inside the first graph: its tail follows in the same graph
         c->inflight = true, c->inflight_first = true;
         c->side_known = c->side_launched;
@@ -1484,24 +1529,22 @@ int enqueue_solve(lfvio_ctx *c, int count, int max_iter, bool adaptive, int fuse
       if (int rc = wait_side(c)) return rc;
     return LFVIO_OK;
   }
-  { const SetupLaunch sl_ = setup_launch(c, count, grid_for(c, count).lm, use_linw(c, count, g, MODE_SOLVE)); hipLaunchKernelGGL(k_setup, dim3(sl_.gx, count), dim3(256), 0, c->stream, c->d_base, c->L.total, MODE_SOLVE, sl_.bits); }
-  const int offs_s = slots_offs(c, count);  // (the pass behind k_setup sweeps at the uploaded state: launch_lin)
+  launch_setup(c, r, MODE_SOLVE);
+  // (the pass behind k_setup sweeps at the uploaded state: slots_offs)
+  auto loop = [&]() {
+    for (int it = 0; it < passes; it++) launch_iteration(c, r, MODE_SOLVE, false, it == 0, it == passes - 1, false, (r.offs & 2) || (it == 0 && (r.offs & 1)));
+    return LFVIO_OK;
+  };
   if (c->use_graph) {
-    const int lwg = (use_linw(c, count, g, MODE_SOLVE) ? 1 : use_linb(c, count, g, MODE_SOLVE) ? 2 + 4 * linb_grid(c, count) : 0);
-    if (!c->graph || c->g_batch != count || c->g_lm != g.lm || c->g_ch != g.ch || c->g_sc != g.sc || c->g_iters != passes || c->g_linw != lwg || c->g_offs != offs_s) {
+    const GraphKey key = graph_key(r, 0, passes, false);  // (k_setup goes out in front of this graph)
+    if (!c->graph || !(c->graph_key == key)) {
       if (c->graph) (void)hipGraphExecDestroy(c->graph), c->graph = nullptr;
-      hipGraph_t graph;
-      HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-      CaptureGuard guard(c->stream);
-      for (int it = 0; it < passes; it++) launch_iteration(c, count, g, MODE_SOLVE, false, it == 0, it == passes - 1, false, (offs_s & 2) || (it == 0 && (offs_s & 1)));
-      HIPCHK(c, guard.end(&graph));
-      HIPCHK(c, hipGraphInstantiate(&c->graph, graph, nullptr, nullptr, 0));
-      HIPCHK(c, hipGraphDestroy(graph));
-      c->g_batch = count, c->g_lm = g.lm, c->g_ch = g.ch, c->g_sc = g.sc, c->g_iters = passes, c->g_linw = lwg, c->g_offs = offs_s;
+      if (int rc = capture_graph(c, c->stream, &c->graph, loop)) return rc;
+      c->graph_key = key;
     }
     HIPCHK(c, hipGraphLaunch(c->graph, c->stream));
   } else {
-    for (int it = 0; it < passes; it++) launch_iteration(c, count, g, MODE_SOLVE, false, it == 0, it == passes - 1, false, (offs_s & 2) || (it == 0 && (offs_s & 1)));
+    loop();
   }
   HIPCHK(c, hipGetLastError());
   return LFVIO_OK;
@@ -1509,12 +1552,11 @@ int enqueue_solve(lfvio_ctx *c, int count, int max_iter, bool adaptive, int fuse
 
 int enqueue_marg(lfvio_ctx *c, int count, int flag, bool standalone, bool gated) {
   if (int rc = join_inflight(c, gated)) return rc;  // (gated: part of a graph of lfvio_batch_optimize*, which has joined — or may go out behind a pipelined upload)
-  const Grid g = grid_for(c, count);
   const int mode = (MODE_MARG + flag) | (gated ? MODE_GATED : 0);
-  if (standalone)
-    { const SetupLaunch sl_ = setup_launch(c, count, grid_for(c, count).lm, use_linw(c, count, g, mode)); hipLaunchKernelGGL(k_setup, dim3(sl_.gx, count), dim3(256), 0, c->stream, c->d_base, c->L.total, mode, sl_.bits); }
+  const Route r = route_for(c, count, mode);
+  if (standalone) launch_setup(c, r, mode);
   // (standalone: the sweep is at the uploaded state; gated: at the re-anchored solution, on the sphere but for a fixed extrinsic)
-  launch_iteration(c, count, g, mode, false, true, true, false, standalone ? slots_offs(c, count) != 0 : (slots_offs(c, count) & 2) != 0);
+  launch_iteration(c, r, mode, false, true, true, false, standalone ? r.offs != 0 : (r.offs & 2) != 0);
   hipLaunchKernelGGL(k_marg_solve<false>, dim3(1, count), dim3(MARG_THREADS), MARG_LDS, c->stream, c->d_base, c->L.total,
                      flag | (c->force_eig ? 256 : 0) | (gated ? 512 : 0) | (gated && c->publish ? 1024 : 0));
   HIPCHK(c, hipGetLastError());
@@ -1904,20 +1946,13 @@ static int batch_optimize_impl(lfvio_ctx *c, int count, int marg_flag, bool adap
     // some window needed more passes: gauge fix + marginalization for the slots that have not had theirs (gated)
     hipGraphExec_t &tail_graph = c->tail[c->publish ? 1 : 0][marg_flag];
     if (!tail_graph) {
-      hipGraph_t graph;
-      HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-      CaptureGuard guard(c->stream);
-      hipLaunchKernelGGL(k_force_done, dim3((count + 63) / 64), dim3(64), 0, c->stream, c->d_base, c->L.total, count);
-      hipLaunchKernelGGL(k_gauge, dim3(1 + (grid_for(c, count).lm + 1) / 2, count), dim3(128), 0, c->stream, c->d_base, c->L.total, 1);
-      if (c->publish) hipLaunchKernelGGL(k_publish, dim3(1), dim3(256), 0, c->stream, c->d_base, c->L.total);
-      rc = enqueue_marg(c, count, marg_flag, false, true);
-      HIPCHK(c, guard.end(&graph));
-      if (rc) {
-        (void)hipGraphDestroy(graph);
-        return rc;
-      }
-      HIPCHK(c, hipGraphInstantiate(&tail_graph, graph, nullptr, nullptr, 0));
-      HIPCHK(c, hipGraphDestroy(graph));
+      rc = capture_graph(c, c->stream, &tail_graph, [&]() {
+        hipLaunchKernelGGL(k_force_done, dim3((count + 63) / 64), dim3(64), 0, c->stream, c->d_base, c->L.total, count);
+        hipLaunchKernelGGL(k_gauge, dim3(1 + (grid_for(c, count).lm + 1) / 2, count), dim3(128), 0, c->stream, c->d_base, c->L.total, 1);
+        if (c->publish) hipLaunchKernelGGL(k_publish, dim3(1), dim3(256), 0, c->stream, c->d_base, c->L.total);
+        return enqueue_marg(c, count, marg_flag, false, true);
+      });
+      if (rc) return rc;
     }
     const bool watch = c->publish;
     if (watch) __atomic_store_n((int *)c->h_mail + 1, 0, __ATOMIC_RELAXED), __atomic_store_n((int *)c->h_mail, 0, __ATOMIC_RELEASE);
@@ -2161,10 +2196,11 @@ int lfvio_debug_linearize(lfvio_ctx *c, const LfvioWindow *in, double *Hpp, doub
   int rc = reserve(c, 1, in->num_landmarks, in->num_observations);
   if (rc) return rc;
   if ((rc = upload_window(c, 0, in))) return rc;
-  const Grid g = grid_for(c, 1);
-  { const SetupLaunch sl_ = setup_launch(c, 1, grid_for(c, 1).lm, false); hipLaunchKernelGGL(k_setup, dim3(sl_.gx, 1), dim3(256), 0, c->stream, c->d_base, c->L.total, MODE_SOLVE, sl_.bits); }
-  launch_lin(c, 1, g, MODE_SOLVE);
-  launch_sum(c, 1, g, MODE_SOLVE);
+  // the role sweep whatever the route (without the Wt clear of k_linw's k_setup): the packed H_pp read below is k_sum's
+  Route r = route_for(c, 1, MODE_SOLVE);
+  r.sweep = Route::ROLES, r.setup.bits = 0;
+  launch_setup(c, r, MODE_SOLVE);
+  launch_sweep(c, r, MODE_SOLVE, true);
   launch_solve(c, 1);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2208,9 +2244,7 @@ int lfvio_debug_schur_repeat(lfvio_ctx *c, const LfvioWindow *in, double mu, dou
   int rc = reserve(c, 1, in->num_landmarks, in->num_observations);
   if (rc) return rc;
   if ((rc = upload_window(c, 0, in))) return rc;
-  const Grid g = grid_for(c, 1);
-  const bool lw = use_linw(c, 1, g, MODE_SOLVE);  // (lfvio_debug_configure "linw" 2: the window-resident sweep, for one window)
-  const bool lb = !lw && use_linb(c, 1, g, MODE_SOLVE);
+  const Route r = route_for(c, 1, MODE_SOLVE);  // (lfvio_debug_configure "linw" 2: the window-resident sweep, for one window)
   char *d = c->d_base;
   const size_t o_tr = offsetof(Slot, tr);
   auto poke_int = [&](size_t off, int v) { return hipMemcpy(d + o_tr + off, &v, sizeof v, hipMemcpyHostToDevice); };
@@ -2218,27 +2252,20 @@ int lfvio_debug_schur_repeat(lfvio_ctx *c, const LfvioWindow *in, double mu, dou
     HIPCHK(c, hipMemcpy(d + o_tr + offsetof(TRState, mu), &mu, sizeof mu, hipMemcpyHostToDevice));
     HIPCHK(c, poke_int(offsetof(TRState, do_lin), do_lin));
     HIPCHK(c, poke_int(offsetof(TRState, do_schur), 1));
-    if (lw) {
-      launch_linw(c, 1);
-    } else if (lb) {
-      launch_linb(c, 1);
-    } else {
-      launch_lin(c, 1, g, MODE_SOLVE);
-      launch_sum(c, 1, g, MODE_SOLVE);
-    }
+    launch_sweep(c, r, MODE_SOLVE, true);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
     out.resize(SCHUR_LEN);
     HIPCHK(c, hipMemcpy(out.data(), d + c->L.xch + sizeof(double) * XOFF_S, sizeof(double) * SCHUR_LEN, hipMemcpyDeviceToHost));
     return LFVIO_OK;
   };
-  { const SetupLaunch sl_ = setup_launch(c, 1, g.lm, lw); hipLaunchKernelGGL(k_setup, dim3(sl_.gx, 1), dim3(256), 0, c->stream, c->d_base, c->L.total, MODE_SOLVE, sl_.bits); }
+  launch_setup(c, r, MODE_SOLVE);
   HIPCHK(c, hipStreamSynchronize(c->stream));
   std::vector<double> first, repeat, full;
   const double mu1 = mu;
   mu = 1e-8;
   if ((rc = run(1, first))) return rc;   // ordinary first pass (fixes the Jacobi scaling: k_solve does that, so run it)
-  launch_solve(c, 1, lw);
+  launch_solve(c, 1, r.sweep == Route::LINW);
   HIPCHK(c, hipStreamSynchronize(c->stream));
   mu = mu1;
   if ((rc = run(0, repeat))) return rc;  // Schur only, new mu
@@ -2275,12 +2302,11 @@ int lfvio_debug_time_kernel(lfvio_ctx *c, int which, int count, int reps, double
   if (!c || !c->d_base || count <= 0 || count > c->batch || reps <= 0) return LFVIO_ERR_ARG;
   (void)hipSetDevice(c->device);
   if (int rc = join_inflight(c)) return rc;
-  const Grid g = grid_for(c, count);
+  const Route r = route_for(c, count, MODE_SOLVE);
+  const Grid &g = r.g;
   const size_t st = c->L.total;
-  const bool lw = use_linw(c, count, g, MODE_SOLVE);
-  const bool offs = (slots_offs(c, count) & 2) != 0;  // the instantiation the passes behind the first one run (launch_lin)
-  // (a rank of a sharded window sweeps its share group by group under the same condition: shard.inc)
-  const bool lb = !lw && (c->shard_active ? (c->linw_mode != 0 && count == 1 && c->info[0].linb_ok) : use_linb(c, count, g, MODE_SOLVE));
+  const bool lw = r.sweep == Route::LINW, lb = r.sweep == Route::LINB;
+  const bool offs = (r.offs & 2) != 0;  // the instantiation the passes behind the first one run (with_offs)
   // which kernel the launch would take is settled before anything is created or enqueued
   if ((which == 11 || which == 12) && !lw) {
     c->err = "the resident windows are not linearized by k_linw";
@@ -2296,24 +2322,19 @@ int lfvio_debug_time_kernel(lfvio_ctx *c, int which, int count, int reps, double
     (void)hipEventDestroy(e0);
     HIPCHK(c, e);
   }
-  { const SetupLaunch sl_ = setup_launch(c, count, grid_for(c, count).lm, lw); hipLaunchKernelGGL(k_setup, dim3(sl_.gx, count), dim3(256), 0, c->stream, c->d_base, st, MODE_SOLVE, sl_.bits); }
-  // one full linearization so that every kernel has valid inputs
-  if (lw) {
-    launch_linw(c, count, MODE_SOLVE, offs);
-  } else if (lb && which >= 15 && which <= 17) {
-    launch_linb(c, count, offs);
-  } else {
-    launch_lin(c, count, g, MODE_SOLVE, offs);
-    launch_sum(c, count, g, MODE_SOLVE);
-  }
+  launch_setup(c, r, MODE_SOLVE);
+  // one full linearization so that every kernel has valid inputs (the roles but for the k_linb kernels)
+  Route full = r;
+  if (lb && !(which >= 15 && which <= 17)) full.sweep = Route::ROLES;
+  launch_sweep(c, full, MODE_SOLVE, offs);
   if (which == 14) launch_solve(c, count, lw);
   if (which == 17) launch_solve(c, count, false);
 
   HIPCHK(c, hipEventRecord(e0, c->stream));
-  for (int r = 0; r < reps; r++) {
+  for (int rep = 0; rep < reps; rep++) {
     switch (which) {
-      case 0: launch_lin(c, count, g, MODE_SOLVE, offs); break;
-      case 2: launch_sum(c, count, g, MODE_SOLVE); break;  // k_presum + k_sum for large windows
+      case 0: launch_lin(c, r, MODE_SOLVE, offs); break;
+      case 2: launch_sum(c, r, MODE_SOLVE); break;  // k_presum + k_sum for large windows
       case 8: case 9: case 10: case 18: {  // k_lin by role: landmark blocks | Gram chunks | IMU factors + prior | IMU factors alone
         const int gram_wgs = (g.ch + 3) / 4;
         const int gx = which == 8 ? g.lw : which == 9 ? gram_wgs : which == 18 ? LFVIO_WINDOW_SIZE : LFVIO_WINDOW_SIZE + 1;
@@ -2325,12 +2346,12 @@ int lfvio_debug_time_kernel(lfvio_ctx *c, int which, int count, int reps, double
         const int wgs = (sl.bits & 4) ? 3 : SETUP_WGS, gx = which == 4 ? 1 : which == 5 ? 2 : which == 6 ? wgs : sl.gx;
         hipLaunchKernelGGL(k_setup, dim3(gx, count), dim3(256), 0, c->stream, c->d_base, st, MODE_SOLVE, sl.bits);
       } break;
-      case 11: case 12: launch_linw(c, count, MODE_SOLVE, offs); break;  // the window-resident sweep of a batch (k_linw: pose-side factors, visual sweep, Schur)
-      case 13: launch_solve(c, count, use_linw(c, count, g, MODE_SOLVE)); break;
+      case 11: case 12: launch_sweep(c, r, MODE_SOLVE, offs); break;  // the window-resident sweep of a batch (k_linw: pose-side factors, visual sweep, Schur)
+      case 13: launch_solve(c, count, lw); break;
       case 14: hipLaunchKernelGGL(k_stepw, dim3(1, count), dim3(STEPW_LAUNCH_THREADS), 0, c->stream, c->d_base, st); break;  // (not idempotent: a few reps only)
       // a large single window, group by group: 15 the strip sweep (k_linb), 16 the sum of its partials (k_sumb), 17 the landmark
       // back-substitution from the transposed rows (k_backsub_wt)
-      case 15: hipLaunchKernelGGL(k_linb<false>, dim3(linb_grid(c, count), count), dim3(LW_THREADS), LW_LDS_BYTES, c->stream, c->d_base, st, linw_args(c)); break;
+      case 15: hipLaunchKernelGGL(k_linb<false>, dim3(r.linb_gx, count), dim3(LW_THREADS), LW_LDS_BYTES, c->stream, c->d_base, st, linw_args(c)); break;
       case 16: hipLaunchKernelGGL(k_sumb, dim3(LINB_SUM_GRID, count), dim3(LINB_SUM_THREADS), 0, c->stream, c->d_base, st, linw_args(c)); break;
       case 17: hipLaunchKernelGGL(k_backsub_wt, dim3(g.lm, count), dim3(64), 0, c->stream, c->d_base, st, c->L.capLmBlocks * LM_BLOCK); break;
       default: launch_solve(c, count); break;
@@ -2348,11 +2369,7 @@ int lfvio_debug_time_kernel(lfvio_ctx *c, int which, int count, int reps, double
 
 // Which kernel linearizes a launch over the resident slots [0, count): 0 k_lin (+ k_sum), 1 k_linw, 2 k_linb (+ k_sumb).
 static int sweep_kernel_of(lfvio_ctx *c, int count) {
-  if (!c || !c->d_base || count <= 0 || count > c->batch) return LFVIO_ERR_ARG;
-  const Grid g = grid_for(c, count);
-  if (use_linw(c, count, g, MODE_SOLVE)) return 1;
-  const bool lb = c->shard_active ? (c->linw_mode != 0 && count == 1 && c->info[0].linb_ok) : use_linb(c, count, g, MODE_SOLVE);
-  return lb ? 2 : 0;
+  return !c || !c->d_base || count <= 0 || count > c->batch ? LFVIO_ERR_ARG : route_for(c, count, MODE_SOLVE).sweep;
 }
 
 // One linearization + dense solve of the resident slots [0, count) from their uploaded state, by whichever path the launch
@@ -2366,19 +2383,11 @@ int lfvio_debug_resident_pass(lfvio_ctx *c, int count, int slot, double *gp, dou
   if (int rc = join_inflight(c)) return rc;
   for (int s = 0; s < count; s++)
     if (!c->info[s].resident) return LFVIO_ERR_ARG;
-  const Grid g = grid_for(c, count);
   const size_t st = c->L.total;
-  const bool lw = use_linw(c, count, g, MODE_SOLVE), lb = !lw && use_linb(c, count, g, MODE_SOLVE);
-  { const SetupLaunch sl_ = setup_launch(c, count, g.lm, lw); hipLaunchKernelGGL(k_setup, dim3(sl_.gx, count), dim3(256), 0, c->stream, c->d_base, st, MODE_SOLVE, sl_.bits); }
-  if (lw) {
-    launch_linw(c, count);
-  } else if (lb) {
-    launch_linb(c, count);
-  } else {
-    launch_lin(c, count, g, MODE_SOLVE);
-    launch_sum(c, count, g, MODE_SOLVE);
-  }
-  launch_solve(c, count, lw);
+  const Route r = route_for(c, count, MODE_SOLVE);
+  launch_setup(c, r, MODE_SOLVE);
+  launch_sweep(c, r, MODE_SOLVE, true);
+  launch_solve(c, count, r.sweep == Route::LINW);
   HIPCHK(c, hipGetLastError());  // (a launch that was refused — resources, LDS — must not pass as a result left by an earlier one)
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const char *d = c->d_base + (size_t)slot * st;
@@ -2392,7 +2401,7 @@ int lfvio_debug_resident_pass(lfvio_ctx *c, int count, int slot, double *gp, dou
   HIPCHK(c, get(gn_p, offsetof(Slot, gn_p), KP));
   HIPCHK(c, get(q, offsetof(Slot, tr) + offsetof(TRState, q), Q_COUNT));
   HIPCHK(c, get(x_cost, offsetof(Slot, tr) + offsetof(TRState, x_cost), 1));
-  return lw ? 1 : lb ? 2 : 0;
+  return r.sweep;
 }
 
 // Every switch of the debug interface in one call (include/lfvio_debug.h).  The product entry points read no environment: a tool

@@ -18,19 +18,19 @@ double *lfvio_shard_exchange_ptr(lfvio_ctx *c) {
   return (double *)(c->d_base + c->L.xch);
 }
 
-// the shard's sweep: group by group where the rank's share is large enough to carry a group list (k_linb; upload_window), role by
-// role otherwise — either way the sums land in the exchange buffer
-static bool shard_linb(const lfvio_ctx *c) { return c->linw_mode != 0 && c->info[0].linb_ok; }
-static void shard_launch_lin(lfvio_ctx *c, const Grid &g) {
-  if (shard_linb(c)) launch_linb(c, 1);
-  else {
-    launch_lin(c, 1, g, MODE_SOLVE);
-    launch_sum(c, 1, g, MODE_SOLVE);
-  }
+// the dense solve and the back-substitution of the rank's landmarks (from the transposed rows behind k_linb: route_for)
+static void shard_solve(lfvio_ctx *c, const Route &r) {
+  launch_solve(c, 1);
+  if (r.sweep == Route::LINB) hipLaunchKernelGGL(k_backsub_wt, dim3(r.g.lm, 1), dim3(64), 0, c->stream, c->d_base, c->L.total, c->L.capLmBlocks * LM_BLOCK);
+  else hipLaunchKernelGGL(k_backsub, dim3(r.g.lm, 1), dim3(64), 0, c->stream, c->d_base, c->L.total);
 }
-static void shard_launch_backsub(lfvio_ctx *c, const Grid &g) {
-  if (shard_linb(c)) hipLaunchKernelGGL(k_backsub_wt, dim3(g.lm, 1), dim3(64), 0, c->stream, c->d_base, c->L.total, c->L.capLmBlocks * LM_BLOCK);
-  else hipLaunchKernelGGL(k_backsub, dim3(g.lm, 1), dim3(64), 0, c->stream, c->d_base, c->L.total);
+// the dogleg step and the cost of its candidate on the rank's landmarks
+static void shard_candidate(lfvio_ctx *c, const Grid &g) {
+  const size_t st = c->L.total;
+  const int nb = g.lm + LFVIO_WINDOW_SIZE + 1;
+  hipLaunchKernelGGL(k_dogleg<false>, dim3(1, 1), dim3(128), 0, c->stream, c->d_base, st, 1);
+  if (nb <= 2048) hipLaunchKernelGGL(k_cost<4>, dim3(nb, 1), dim3(256), 0, c->stream, c->d_base, st, g.lm, 1);
+  else hipLaunchKernelGGL(k_cost<1>, dim3(nb, 1), dim3(64), 0, c->stream, c->d_base, st, g.lm, 1);
 }
 
 int lfvio_shard_begin(lfvio_ctx *c, const LfvioWindow *in, int lm_begin, int lm_end, int add_pose_side) {
@@ -59,7 +59,7 @@ int lfvio_shard_begin(lfvio_ctx *c, const LfvioWindow *in, int lm_begin, int lm_
   int rc = reserve(c, 1, n, o1 - o0);
   if (rc) return rc;
   if ((rc = upload_window(c, 0, &sub, (add_pose_side & 4) ? 2 : 1, (add_pose_side & 3) == 2 ? 2 : (add_pose_side & 3) ? 1 : 0))) return rc;
-  hipLaunchKernelGGL(k_setup, dim3(SETUP_WGS + (grid_for(c, 1).lm + 3) / 4, 1), dim3(256), 0, c->stream, c->d_base, c->L.total, MODE_SOLVE, 0);
+  launch_setup(c, route_for(c, 1, MODE_SOLVE), MODE_SOLVE);  // (no Wt clear: a rank's share carries no LinwPlan)
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->shard_active = true;
@@ -68,45 +68,30 @@ int lfvio_shard_begin(lfvio_ctx *c, const LfvioWindow *in, int lm_begin, int lm_
   return LFVIO_OK;
 }
 
+// The synchronous phases: lfvio_shard_enqueue's phase, then a wait for it
+static int shard_phase_sync(lfvio_ctx *c, int phase) {
+  if (int rc = lfvio_shard_enqueue(c, phase)) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 1;
+}
+
 // returns 1 when the caller must all-reduce the whole exchange buffer, 0 when nothing was produced
 int lfvio_shard_linearize(lfvio_ctx *c) {
   if (!c || !c->shard_active) return LFVIO_ERR_ARG;
   if (c->shard_state != 0) return 0;
-  const Grid g = grid_for(c, 1);
-  const size_t st = c->L.total;
-  shard_launch_lin(c, g);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return 1;
+  return shard_phase_sync(c, 0);
 }
 
 // returns 1 when the caller must all-reduce the 16-scalar tail
 int lfvio_shard_solve(lfvio_ctx *c) {
   if (!c || !c->shard_active) return LFVIO_ERR_ARG;
   if (c->shard_state != 0) return 0;
-  const Grid g = grid_for(c, 1);
-  const size_t st = c->L.total;
-  launch_solve(c, 1);
-  shard_launch_backsub(c, g);
-  hipLaunchKernelGGL(k_xpack, dim3(1, 1), dim3(256), 0, c->stream, c->d_base, st, 2);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return 1;
+  return shard_phase_sync(c, 1);
 }
 
 int lfvio_shard_candidate(lfvio_ctx *c) {
   if (!c || !c->shard_active) return LFVIO_ERR_ARG;
-  const Grid g = grid_for(c, 1);
-  const size_t st = c->L.total;
-  hipLaunchKernelGGL(k_dogleg<false>, dim3(1, 1), dim3(128), 0, c->stream, c->d_base, st, 1);
-  if (g.lm + LFVIO_WINDOW_SIZE + 1 <= 2048)
-    hipLaunchKernelGGL(k_cost<4>, dim3(g.lm + LFVIO_WINDOW_SIZE + 1, 1), dim3(256), 0, c->stream, c->d_base, st, g.lm, 1);
-  else
-    hipLaunchKernelGGL(k_cost<1>, dim3(g.lm + LFVIO_WINDOW_SIZE + 1, 1), dim3(64), 0, c->stream, c->d_base, st, g.lm, 1);
-  hipLaunchKernelGGL(k_xpack, dim3(1, 1), dim3(256), 0, c->stream, c->d_base, st, 3);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return 1;
+  return shard_phase_sync(c, 2);
 }
 
 // *state: 0 = linearize next, 1 = step rejected: only a new candidate is needed, 2 = terminated
@@ -143,7 +128,7 @@ int lfvio_shard_restart(lfvio_ctx *c) {  // the resident shard again from its up
   (void)hipSetDevice(c->device);
   // decision records still outstanding (a run that ended on an error): their copies must have landed before the ring is reused
   for (; c->flag_tail < c->flag_head; c->flag_tail++) HIPCHK(c, hipEventSynchronize(c->flag_event[c->flag_tail % lfvio_ctx::FLAG_RING]));
-  hipLaunchKernelGGL(k_setup, dim3(SETUP_WGS + (grid_for(c, 1).lm + 3) / 4, 1), dim3(256), 0, c->stream, c->d_base, c->L.total, MODE_SOLVE, 0);
+  launch_setup(c, route_for(c, 1, MODE_SOLVE), MODE_SOLVE);
   HIPCHK(c, hipGetLastError());
   c->shard_active = true;
   c->shard_state = 0;
@@ -154,36 +139,26 @@ int lfvio_shard_restart(lfvio_ctx *c) {  // the resident shard again from its up
 int lfvio_shard_enqueue(lfvio_ctx *c, int phase) {
   if (!c || !c->shard_active || phase < 0 || phase > 4) return LFVIO_ERR_ARG;
   (void)hipSetDevice(c->device);  // a group drives several devices from one thread
-  const Grid g = grid_for(c, 1);
+  const Route r = route_for(c, 1, MODE_SOLVE);
   const size_t st = c->L.total;
   switch (phase) {
-    case 0:
-      shard_launch_lin(c, g);
+    case 0:  // the shard's sweep (route_for) — either way the sums land in the exchange buffer
+      launch_sweep(c, r, MODE_SOLVE, true);
       if (c->shard_group) {  // lfvio_group: what lets every rank form the Gauss-Newton step's landmark norms itself (k_lm_cb2)
         hipLaunchKernelGGL(k_lm_cb2, dim3(XP_WGS, 1), dim3(256), 0, c->stream, c->d_base, st);
       }
       break;
     case 1:
-      launch_solve(c, 1);
-      shard_launch_backsub(c, g);
+      shard_solve(c, r);
       hipLaunchKernelGGL(k_xpack, dim3(1, 1), dim3(256), 0, c->stream, c->d_base, st, 2);
       break;
     case 4:  // phases 1 and 2 as one, the scalars of both in ONE all-reduce (lfvio_group: the window was uploaded with bit 2 of add_pose_side)
-      launch_solve(c, 1);
-      shard_launch_backsub(c, g);
-      hipLaunchKernelGGL(k_dogleg<false>, dim3(1, 1), dim3(128), 0, c->stream, c->d_base, st, 1);
-      if (g.lm + LFVIO_WINDOW_SIZE + 1 <= 2048)
-        hipLaunchKernelGGL(k_cost<4>, dim3(g.lm + LFVIO_WINDOW_SIZE + 1, 1), dim3(256), 0, c->stream, c->d_base, st, g.lm, 1);
-      else
-        hipLaunchKernelGGL(k_cost<1>, dim3(g.lm + LFVIO_WINDOW_SIZE + 1, 1), dim3(64), 0, c->stream, c->d_base, st, g.lm, 1);
+      shard_solve(c, r);
+      shard_candidate(c, r.g);
       hipLaunchKernelGGL(k_xpack, dim3(1, 1), dim3(256), 0, c->stream, c->d_base, st, 6);
       break;
     case 2:
-      hipLaunchKernelGGL(k_dogleg<false>, dim3(1, 1), dim3(128), 0, c->stream, c->d_base, st, 1);
-      if (g.lm + LFVIO_WINDOW_SIZE + 1 <= 2048)
-        hipLaunchKernelGGL(k_cost<4>, dim3(g.lm + LFVIO_WINDOW_SIZE + 1, 1), dim3(256), 0, c->stream, c->d_base, st, g.lm, 1);
-      else
-        hipLaunchKernelGGL(k_cost<1>, dim3(g.lm + LFVIO_WINDOW_SIZE + 1, 1), dim3(64), 0, c->stream, c->d_base, st, g.lm, 1);
+      shard_candidate(c, r.g);
       hipLaunchKernelGGL(k_xpack, dim3(1, 1), dim3(256), 0, c->stream, c->d_base, st, 3);
       break;
     case 3:
@@ -239,10 +214,9 @@ static int shard_marg_enqueue_linearize(lfvio_ctx *c, int flag) {
     return LFVIO_ERR_ARG;
   }
   (void)hipSetDevice(c->device);
-  const Grid g = grid_for(c, 1);
-  hipLaunchKernelGGL(k_gauge, dim3(1 + (g.lm + 1) / 2, 1), dim3(128), 0, c->stream, c->d_base, c->L.total, 0);
-  launch_lin(c, 1, g, MODE_MARG + flag);
-  launch_sum(c, 1, g, MODE_MARG + flag);
+  const Route r = route_for(c, 1, MODE_MARG + flag);  // (the roles: k_linb sweeps the solve passes only)
+  hipLaunchKernelGGL(k_gauge, dim3(1 + (r.g.lm + 1) / 2, 1), dim3(128), 0, c->stream, c->d_base, c->L.total, 0);
+  launch_sweep(c, r, MODE_MARG + flag, true);
   HIPCHK(c, hipGetLastError());
   c->shard_state = 3;
   return 1;
