@@ -194,6 +194,32 @@ int lfvio_solve(lfvio_ctx *ctx, const LfvioWindow *in, LfvioSolution *out);
  * (estimator.cpp:942-943): out->valid is copied from the input prior. */
 int lfvio_marginalize(lfvio_ctx *ctx, const LfvioWindow *in, int flag, LfvioPrior *out);
 
+/* ---- relocalization: the loop-closure branch of optimization() (estimator.cpp:777-808) ------------------------------
+ * A /pose_graph/match_points message stored by Estimator::setReloFrame (estimator.cpp:1133-1151) adds one parameter block,
+ * relo_Pose (7 global / 6 local, PoseLocalParameterization, never constant, never part of the prior or of the
+ * marginalization), and per matched landmark one PLAIN ProjectionFactor (factor/projection_factor.cpp: no td column even
+ * with ESTIMATE_TD, same sqrt_info and CauchyLoss(1.0)) on (para_Pose[start_frame], relo_Pose, para_Ex_Pose, para_Feature[l])
+ * with pts_i = the landmark's first observation and pts_j = (x, y, 1).  The host builds the match list by the reference's walk
+ * (estimator.cpp:782-806): landmarks of the window's list (the LfvioWindow order) with start_frame <= frame, ids matched in
+ * ascending order against match_points. */
+typedef struct LfvioRelo {
+  int frame;                         /* relo_frame_local_index, 0 .. LFVIO_WINDOW_SIZE - 1                        */
+  double relo_pose[LFVIO_SIZE_POSE]; /* initial relo_Pose [p, q xyzw], as setReloFrame copied it from para_Pose  */
+  int num_matches;                   /* K relocalization factors                                                  */
+  const int *landmark;               /* [K] strictly ascending indices into the window's landmark list, each with
+                                        start_frame[l] <= frame                                                     */
+  const double *match_point;         /* [K][2] x, y of match_points: pts_j = (x, y, 1)                             */
+} LfvioRelo;
+/* lfvio_solve with the relocalization factors: the same conventions — outputs are the state before double2vector() (whose
+ * relo tail, estimator.cpp:603-625, stays on the host) plus the solved relo pose; on error nothing is written; the trace
+ * fields and max_solver_time_in_seconds are those of lfvio_solve.  LFVIO_ERR_ARG for a malformed relo (frame out of range,
+ * num_matches < 0, NULL arrays with num_matches > 0, an index out of range, not strictly ascending, or of a landmark with
+ * start_frame > frame) and for windows of more than 2048 landmarks on the relo route.  num_matches == 0 is the plain solve
+ * with relo_pose copied through (Ceres drops a parameter block no residual uses).  The route is one launch sequence per
+ * trust-region pass and one host synchronisation per pass: a relo solve happens once per loop-closure message. */
+int lfvio_solve_relo(lfvio_ctx *ctx, const LfvioWindow *in, const LfvioRelo *relo, LfvioSolution *out,
+                     double relo_pose_out[LFVIO_SIZE_POSE]);
+
 /* ---- device-resident API (throughput / bench; same kernels) -------------
  * upload once, then run the whole optimization() — solve, the gauge fix of
  * double2vector() (estimator.cpp:532-600) and marginalization — without

@@ -31,6 +31,7 @@ extern "C" {
  *                        newly accepted state on worker streams (csrc/kernels_spec.h).  Either way the prior is the same bits
  *   "break_next_chain"   1: the next lfvio_batch_upload_chained_device promises the device a prior of one row more than the
  *                        marginalization in flight will leave — the path a failed marginalization takes, for tests
+ *   "relo_route"         1: lfvio_solve_relo takes its own route (kernels_relo.h) also without a match, instead of lfvio_solve; 0 (default)
  *   "env"                apply LFVIO_DEBUG="key=value,key=value" from the environment (the product entry points read none) */
 int lfvio_debug_configure(lfvio_ctx *ctx, const char *key, double value);
 /* What the last calls left, as doubles into out[0 .. n).

@@ -40,6 +40,7 @@ constexpr ncclDataType_t ncclDouble = 8;
 #include "kernels_linw.h"
 #include "linb_plan.h"
 #include "kernels_stepw.h"
+#include "kernels_relo.h"
 
 #define HIPCHK(ctx, call)                                                                      \
   do {                                                                                         \
@@ -264,6 +265,11 @@ struct lfvio_ctx {
   int mail_seq = 0;             // sequence number of the last upload (Slot::mail_seq)
   std::unique_ptr<LfvioPrior> chain_struct;  // the structure-only prior of a device-chained upload
   bool chain_err_told = false;     // the call in flight ran without the prior it was promised and its begin() has said so
+  // lfvio_solve_relo (relo.inc): the route's device blob and pinned staging blob (grow-only), the loop's `done` word read per pass
+  char *d_relo = nullptr, *h_relo = nullptr;
+  size_t relo_dev_cap = 0, relo_stage_cap = 0;
+  int relo_done_word = 0;
+  bool relo_force = false;  // lfvio_debug_configure "relo_route": the relo route even without a match
   bool debug_break_chain = false;  // lfvio_debug_configure "break_next_chain": the next device-chained upload promises a prior of another size than the device will find
   bool inflight_first = false;  // the flag came out of the first graph: {tail_state, passes_used} land in h_pending[2..3] when it ends
   bool use_graph = true;
@@ -1814,6 +1820,7 @@ lfvio_ctx *lfvio_create(int device) {
       return nullptr;
     }
   }
+  (void)hipFuncSetAttribute((const void *)k_relo_solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)RELO_SOLVE_LDS);
   (void)hipFuncSetAttribute((const void *)k_marg_solve<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MARG_LDS);
   (void)hipFuncSetAttribute((const void *)k_marg_solve<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MARG_LDS);
   return c;
@@ -1829,6 +1836,8 @@ void lfvio_destroy(lfvio_ctx *c) {
   if (c->h_stage) (void)hipHostFree(c->h_stage);
   if (c->h_down) (void)hipHostFree(c->h_down);
   if (c->d_asm) (void)hipFree(c->d_asm);
+  if (c->d_relo) (void)hipFree(c->d_relo);
+  if (c->h_relo) (void)hipHostFree(c->h_relo);
   if (c->d_lwt) (void)hipFree(c->d_lwt);
   if (c->d_pending) (void)hipFree(c->d_pending);
   if (c->h_pending) (void)hipHostFree(c->h_pending);
@@ -2445,6 +2454,7 @@ int lfvio_debug_configure(lfvio_ctx *c, const char *key, double value) {
   else if (k == "force_eig") c->force_eig = iv != 0;  // (a kernel argument of the captured launches)
   else if (k == "marg_ahead") c->marg_ahead = iv != 0;  // (a flag of the upload: Slot::spec_on)
   else if (k == "break_next_chain") c->debug_break_chain = iv != 0;
+  else if (k == "relo_route") c->relo_force = iv != 0;
   else {
     c->err = "lfvio_debug_configure: unknown key '" + k + "'";
     return LFVIO_ERR_ARG;
@@ -2474,6 +2484,8 @@ int lfvio_debug_query(lfvio_ctx *c, const char *key, double *out, int n) {
   return LFVIO_ERR_ARG;
 }
 
+// ---- relocalization: lfvio_solve_relo, declared in lfvio.h, implemented in relo.inc
+#include "relo.inc"
 // ---- landmark-sharded API: declared in lfvio.h, implemented in shard.inc
 #include "shard.inc"
 // ---- multi-GPU groups (RCCL): declared in lfvio.h, implemented in group.inc

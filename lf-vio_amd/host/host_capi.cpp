@@ -295,6 +295,34 @@ void lfvio_host_set_device_mask(unsigned mask) { config().device_mask = mask ? m
 void lfvio_host_set_local_shards(int n) { config().local_shards = n; }
 void lfvio_host_set_split_call(int on) { config().split_call = on != 0; }
 void lfvio_host_set_device_chain(int on) { config().device_chain = on != 0; }
+
+// Estimator::setReloFrame (estimator.cpp:1133-1151): pts n x (x, y, id), relo_r row-major
+void lfvio_host_set_relo_frame(void *h, double stamp, int index, int n, const double *pts, const double *relo_t, const double *relo_r) {
+  std::vector<Vector3d> mp;
+  for (int k = 0; k < n; k++) mp.push_back(v3(pts + 3 * k));
+  Matrix3d R;
+  setM(R, relo_r);
+  E(h)->setReloFrame(stamp, index, mp, v3(relo_t), R);
+}
+// the relocalization members: out[30] = relocalization_info, relo_frame_local_index, relo_Pose[7], drift_correct_r[9] (row-major),
+// drift_correct_t[3], relo_relative_t[3], relo_relative_q[4] (x y z w), relo_relative_yaw, relo_solves
+void lfvio_host_get_relo(void *h, double *out) {
+  WindowEstimator *e = E(h);
+  out[0] = e->relocalization_info, out[1] = e->relo_frame_local_index;
+  for (int k = 0; k < 7; k++) out[2 + k] = e->relo_Pose[k];
+  getM(e->drift_correct_r, out + 9);
+  for (int k = 0; k < 3; k++) out[18 + k] = e->drift_correct_t(k), out[21 + k] = e->relo_relative_t(k);
+  out[24] = e->relo_relative_q.x(), out[25] = e->relo_relative_q.y(), out[26] = e->relo_relative_q.z(), out[27] = e->relo_relative_q.w();
+  out[28] = e->relo_relative_yaw, out[29] = e->relo_solves;
+}
+// the match list optimization() would build now: landmark[cap], xy[cap][2]; returns K (at most cap written)
+int lfvio_host_relo_matches(void *h, int cap, int *landmark, double *xy) {
+  std::vector<int> l;
+  std::vector<double> p;
+  const int K = E(h)->reloMatches(&l, &p);
+  for (int k = 0; k < K && k < cap; k++) landmark[k] = l[k], xy[2 * k] = p[2 * k], xy[2 * k + 1] = p[2 * k + 1];
+  return K;
+}
 // waits for the marginalization a split optimization() left running and adopts its prior (what the next pack() would do)
 int lfvio_host_collect_prior(void *h) { return E(h)->collectPrior() ? 0 : E(h)->status; }
 void lfvio_host_get_timers(void *h, double *out6, int reset) {

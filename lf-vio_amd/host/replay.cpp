@@ -74,6 +74,20 @@ bool Trace::load(const char *path) {
       boots.push_back(tb);
     } else if (head[0] == 5) {
       restarts.push_back(images.size());
+    } else if (head[0] == 6 && head[1] >= 10 * sizeof(double) && (head[1] - 10 * sizeof(double)) % (3 * sizeof(double)) == 0) {
+      // stamp, frame index, relo_t[3], relo_q[4] (x y z w), K, K x (x, y, id)
+      TraceRelo r;
+      r.stamp = d[0], r.index = (int)d[1];
+      std::memcpy(r.t, d + 2, sizeof r.t), std::memcpy(r.q, d + 5, sizeof r.q);
+      const size_t K = (head[1] - 10 * sizeof(double)) / (3 * sizeof(double));
+      if ((size_t)d[9] != K) {
+        error = "relocalization record with a wrong length";
+        std::fclose(f);
+        return false;
+      }
+      for (size_t k = 0; k < K; k++) r.points.push_back(Vector3d(d[10 + 3 * k], d[11 + 3 * k], d[12 + 3 * k]));
+      r.at_image = images.size();
+      relos.push_back(std::move(r));
     }
   }
   std::fclose(f);
@@ -119,7 +133,8 @@ int replay(WindowEstimator &est, const Trace &trace, const char *traj_path, int 
       for (int j = 0; j < 3; j++) est.ric(i, j) = trace.ric[3 * i + j];
     est.td = trace.td;
   }
-  size_t next_boot = 0, next_restart = 0, image_index = 0;
+  size_t next_boot = 0, next_restart = 0, image_index = 0, next_relo = 0;
+  const int relo_solves0 = est.relo_solves;
   const std::vector<TraceImu> &imu = trace.imu;
   size_t front = 0;         // head of the IMU queue
   double clock = -1;        // time of the last sample handed over
@@ -177,11 +192,20 @@ int replay(WindowEstimator &est, const Trace &trace, const char *traj_path, int 
       }
     }
     decodeFeatures(msg, &img);
+    {  // process(), estimator_node.cpp:262-284: of the relocalization messages buffered before this image only the LAST one is used
+      const TraceRelo *relo = nullptr;
+      for (; next_relo < trace.relos.size() && trace.relos[next_relo].at_image < image_index; next_relo++) relo = &trace.relos[next_relo];
+      if (relo) {
+        const Quaterniond q(relo->q[3], relo->q[0], relo->q[1], relo->q[2]);
+        est.setReloFrame(relo->stamp, relo->index, relo->points, Vector3d(relo->t[0], relo->t[1], relo->t[2]), q.normalized().toRotationMatrix());
+      }
+    }
     const bool was_running = est.phase == WindowEstimator::NON_LINEAR;
     est.status = LFVIO_OK;
     est.pushImage(msg.t, (int)img.ids.size(), img.ids.data(), img.pts.data());
     if (image_ms) image_ms->push_back(std::chrono::duration<double>(std::chrono::steady_clock::now() - t_image).count() * 1e3);
     st.images++;
+    st.relocalizations = est.relo_solves - relo_solves0;
     if (est.status != LFVIO_OK) {
       st.last_status = est.status;
       return finish(-2);  // a device call failed: no silent continuation

@@ -44,7 +44,15 @@ struct TraceBoot {
   double stamp;      // NaN: take it at the first full window
   size_t at_image;   // images recorded before it
 };
+struct TraceRelo {  // record type 6: a /pose_graph/match_points message (estimator_node.cpp:260-284)
+  double stamp;
+  int index;
+  double t[3], q[4];               // relo_t, relo_q [x y z w]
+  std::vector<Vector3d> points;    // (x, y, id), sorted by id as the pose graph sends them
+  size_t at_image;                 // images recorded before it
+};
 struct Trace {
+  std::vector<TraceRelo> relos;       // in file order
   std::vector<TraceImu> imu;
   std::vector<TraceImage> images;
   std::vector<TraceBoot> boots;       // in file order
@@ -58,7 +66,7 @@ struct Trace {
 };
 
 struct ReplayStats {
-  int images, thrown, keyframes, non_keyframes, poses, failures, last_status, iterations, restarts, bootstraps;
+  int images, thrown, keyframes, non_keyframes, poses, failures, last_status, iterations, restarts, bootstraps, relocalizations;
 };
 
 // feature message -> what WindowEstimator::pushImage() takes (estimator_node.cpp:292-312): feature ids ascending (the

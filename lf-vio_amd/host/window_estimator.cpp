@@ -1,5 +1,9 @@
 // window_estimator.cpp — see window_estimator.h.  Reference lines are relative to /root/reference/vins_estimator/src.
 #include "window_estimator.h"
+// A weak reference: the host sources are also linked against a C-ABI that has no relocalization entry point (the CPU oracle of
+// the tests, oracle/abi_shim.cpp); there optimization() with a relocalization message reports LFVIO_ERR_DEVICE instead of loading
+// with an unresolved symbol.
+#pragma weak lfvio_solve_relo
 
 #include <algorithm>
 #include <cmath>
@@ -271,6 +275,7 @@ void WindowEstimator::reset() {
   td = c.td;
   phase = INITIAL;
   first_imu = false;
+  relocalization_info = 0;
   slides_old = slides_new = 0;
   frame_count = 0;
   initial_timestamp = 0;
@@ -518,7 +523,7 @@ void WindowEstimator::vector2double() {  // estimator.cpp:488-530
   if (config().estimate_td) para_Td[0][0] = td;
 }
 
-void WindowEstimator::double2vector() {  // estimator.cpp:532-600 (the relocalization tail :603-625 is dead as shipped)
+void WindowEstimator::double2vector() {  // estimator.cpp:532-600, and the relocalization tail :603-625
   Vector3d origin_R0 = yawPitchRollDeg(kf(0).R);
   Vector3d origin_P0 = kf(0).P;
   if (failure_occur) {
@@ -550,6 +555,58 @@ void WindowEstimator::double2vector() {  // estimator.cpp:532-600 (the relocaliz
     tracks.setSolveFlag(s, 1);                     // both branches of the reference set 1
   }
   if (config().estimate_td) td = para_Td[0][0];
+  if (relocalization_info) {  // relative info between two loop frames, estimator.cpp:603-625
+    const Matrix3d relo_r = rot_diff * quat(relo_Pose).normalized().toRotationMatrix();
+    const Vector3d relo_t =
+        rot_diff * Vector3d(relo_Pose[0] - para_Pose[0][0], relo_Pose[1] - para_Pose[0][1], relo_Pose[2] - para_Pose[0][2]) + origin_P0;
+    const double drift_correct_yaw = yawPitchRollDeg(prev_relo_r).x() - yawPitchRollDeg(relo_r).x();
+    drift_correct_r = fromYawPitchRollDeg(Vector3d(drift_correct_yaw, 0, 0));
+    drift_correct_t = prev_relo_t - drift_correct_r * relo_t;
+    const Keyframe &f = kf(relo_frame_local_index);
+    relo_relative_t = relo_r.transpose() * (f.P - relo_t);
+    relo_relative_q = Quaterniond(relo_r.transpose() * f.R);
+    double a = yawPitchRollDeg(f.R).x() - yawPitchRollDeg(relo_r).x();  // Utility::normalizeAngle
+    a = a > 0 ? a - 360.0 * std::floor((a + 180.0) / 360.0) : a + 360.0 * std::floor((-a + 180.0) / 360.0);
+    relo_relative_yaw = a;
+    relocalization_info = 0;
+  }
+}
+
+// estimator.cpp:1133-1151, literally: the relo pose starts from para_Pose[i] AS IT STANDS — after a slide that is the row of the
+// frame that was at i BEFORE the slide (slideWindow() shifts Ps / Rs, not para_Pose; vector2double() refreshes it only in the next
+// optimization()).  It is only the initial value of relo_Pose, but an iteration-capped solve ends elsewhere with another one.
+void WindowEstimator::setReloFrame(double stamp, int index, const std::vector<Vector3d> &points, const Vector3d &relo_t, const Matrix3d &relo_r) {
+  relo_frame_stamp = stamp;
+  relo_frame_index = index;
+  match_points = points;
+  prev_relo_t = relo_t;
+  prev_relo_r = relo_r;
+  for (int i = 0; i < WINDOW_SIZE; i++) {
+    if (relo_frame_stamp == kf(i).stamp) {
+      relo_frame_local_index = i;
+      relocalization_info = 1;
+      for (int j = 0; j < LFVIO_SIZE_POSE; j++) relo_Pose[j] = para_Pose[i][j];
+    }
+  }
+}
+
+int WindowEstimator::reloMatches(std::vector<int> *landmark, std::vector<double> *xy) const {
+  landmark->clear(), xy->clear();
+  const size_t K = match_points.size();
+  size_t k = 0;
+  int l = -1;
+  for (int s : tracks.order()) {
+    if (!tracks.solvable(s)) continue;
+    ++l;
+    if (tracks.start(s) > relo_frame_local_index) continue;
+    while (k < K && (int)match_points[k].z() < tracks.id(s)) k++;
+    if (k < K && (int)match_points[k].z() == tracks.id(s)) {
+      landmark->push_back(l);
+      xy->push_back(match_points[k].x()), xy->push_back(match_points[k].y());
+      k++;
+    }
+  }
+  return (int)landmark->size();
 }
 
 void WindowEstimator::pack(LfvioWindow *w) {
@@ -608,6 +665,10 @@ void WindowEstimator::pack(LfvioWindow *w) {
 void WindowEstimator::optimization() {
   status = LFVIO_OK;
   if (!device() || !refreshSpans(false)) return;
+  if (relocalization_info) {
+    optimizationRelo();
+    return;
+  }
   // The marginalization behind the previous call's early state may still be running.  On one device with one upload the
   // window is packed and its tables are built while it finishes: the upload collects the prior itself (chained); every other
   // route waits for it here.
@@ -709,6 +770,51 @@ void WindowEstimator::optimization() {
   status = lfvio_marginalize(gpu, &w, marg_flag, &next);
   if (status != LFVIO_OK) return;
   assign_prior(&prior, &next), has_prior = next.valid != 0;
+}
+
+// The relocalization branch (estimator.cpp:777-808) in the reference's two-call form on the first context (of the group, if any):
+// the prior of the last call is collected first, then lfvio_solve_relo, double2vector() with its relo tail, vector2double() and
+// lfvio_marginalize.  The next window goes back to the configured route: nothing of this call stays in flight.
+void WindowEstimator::optimizationRelo() {
+  if (!collectPrior()) return;
+  Stopwatch sw(&timers[0]);
+  timers[5] += 1.0;
+  vector2double();
+  LfvioWindow w;
+  pack(&w);
+  Staging &st = stage_;
+  st.lam_out.assign(w.num_landmarks > 0 ? w.num_landmarks : 1, 0.0);
+  const int K = reloMatches(&relo_lm_, &relo_xy_);
+  LfvioRelo r;
+  r.frame = relo_frame_local_index;
+  std::memcpy(r.relo_pose, relo_Pose, sizeof r.relo_pose);
+  r.num_matches = K;
+  r.landmark = K ? relo_lm_.data() : nullptr;
+  r.match_point = K ? relo_xy_.data() : nullptr;
+  const bool marginalize = marg_flag == LFVIO_MARGIN_OLD || (marg_flag == LFVIO_MARGIN_SECOND_NEW && has_prior && prior.valid);
+  double relo_out[LFVIO_SIZE_POSE];
+  if (!lfvio_solve_relo) {
+    status = LFVIO_ERR_DEVICE;
+    return;
+  }
+  summary.inv_depth = st.lam_out.data();
+  status = lfvio_solve_relo(gpu, &w, &r, &summary, relo_out);
+  summary.inv_depth = nullptr;
+  if (status != LFVIO_OK) return;
+  std::memcpy(para_Pose, summary.para_pose, sizeof para_Pose);
+  std::memcpy(para_SpeedBias, summary.para_speed_bias, sizeof para_SpeedBias);
+  std::memcpy(para_Ex_Pose[0], summary.para_ex_pose, sizeof para_Ex_Pose[0]);
+  if (config().estimate_td) para_Td[0][0] = summary.para_td;
+  std::copy(st.lam_out.begin(), st.lam_out.begin() + w.num_landmarks, para_Feature.begin());
+  std::memcpy(relo_Pose, relo_out, sizeof relo_Pose);
+  double2vector();  // :830, with the relo tail; clears relocalization_info
+  relo_solves++;
+  if (!marginalize) return;
+  vector2double();
+  pack(&w);
+  status = lfvio_marginalize(gpu, &w, marg_flag, &next_);
+  if (status != LFVIO_OK) return;
+  assign_prior(&prior, &next_), has_prior = next_.valid != 0;
 }
 
 }  // namespace lfvio

@@ -157,6 +157,26 @@ class WindowEstimator {
   void optimization();   // estimator.cpp:676-1009 over include/lfvio.h
   bool collectPrior();   // waits for a marginalization still in flight (split_call) and adopts its prior; false + status on error
 
+  // ---- relocalization (estimator.cpp:1133-1151, the branch of optimization() at :777-808, the tail of double2vector() at :603-625)
+  void setReloFrame(double stamp, int index, const std::vector<Vector3d> &match_points, const Vector3d &relo_t, const Matrix3d &relo_r);
+  // the reference's walk (estimator.cpp:782-806): solvable landmarks in list order with start_frame <= relo_frame_local_index, ids
+  // matched in ascending order against match_points; unlike the reference the walk stops at the end of match_points.  landmark:
+  // index in the window's landmark list, xy: (x, y) of the match.  Returns the number of matches.
+  int reloMatches(std::vector<int> *landmark, std::vector<double> *xy) const;
+  int relocalization_info = 0;
+  double relo_frame_stamp = 0;
+  int relo_frame_index = 0, relo_frame_local_index = 0;
+  std::vector<Vector3d> match_points;
+  Vector3d prev_relo_t;
+  Matrix3d prev_relo_r;
+  double relo_Pose[LFVIO_SIZE_POSE] = {0, 0, 0, 0, 0, 0, 1};
+  Matrix3d drift_correct_r;
+  Vector3d drift_correct_t;
+  Vector3d relo_relative_t;
+  Quaterniond relo_relative_q;
+  double relo_relative_yaw = 0;
+  int relo_solves = 0;  // optimization() calls that carried a relocalization message (replay statistics)
+
   // ---- the loop around it: processIMU / processImage / solveOdometry / slideWindow / failureDetection
   void reset();                                                     // clearState() + setParameter()
   void pushImu(double dt, const double acc[3], const double gyr[3]);
@@ -218,6 +238,9 @@ class WindowEstimator {
   bool prior_on_device_ = false;  // the resident window took its prior over on the device (lfvio_batch_upload_chained_device): `prior` is stale
   bool device();
   bool applyBootstrap();
+  void optimizationRelo();  // optimization() with relocalization_info set: lfvio_solve_relo, double2vector(), lfvio_marginalize
+  std::vector<int> relo_lm_;
+  std::vector<double> relo_xy_;
   FrameRing ring_;
   Keyframe frames_[FRAMES];
   ImuSpan spans_[FRAMES];

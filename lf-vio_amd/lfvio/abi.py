@@ -14,6 +14,7 @@ NUM_FRAMES = 11
 MAX_PRIOR_BLOCKS = 24
 MAX_PRIOR_DIM = 172
 MAX_TRACE = 64
+SIZE_POSE = 7
 
 OK = 0
 MARGIN_OLD = 0
@@ -243,6 +244,39 @@ class Window:
         return w
 
 
+class ReloC(C.Structure):
+    """LfvioRelo (include/lfvio.h): one relocalization message as the solve consumes it."""
+    _fields_ = [("frame", C.c_int), ("relo_pose", C.c_double * SIZE_POSE), ("num_matches", C.c_int),
+                ("landmark", C.POINTER(C.c_int)), ("match_point", C.POINTER(C.c_double))]
+
+
+class Relo:
+    """Owns the arrays behind a ReloC: frame, initial relo pose [p, q xyzw], landmark indices [K], match points [K][2]."""
+
+    def __init__(self, frame, relo_pose, landmark=(), match_point=()):
+        self.frame = int(frame)
+        self.relo_pose = np.ascontiguousarray(relo_pose, dtype=np.float64).reshape(SIZE_POSE)
+        self.landmark = np.ascontiguousarray(landmark, dtype=np.int32).reshape(-1)
+        self.match_point = np.ascontiguousarray(match_point, dtype=np.float64).reshape(-1, 2)
+        self._c = None
+
+    @property
+    def K(self):
+        return int(self.landmark.size)
+
+    def c(self, num_matches=None, null_arrays=False):
+        r = ReloC()
+        r.frame = self.frame
+        for k in range(SIZE_POSE):
+            r.relo_pose[k] = float(self.relo_pose[k])
+        r.num_matches = self.K if num_matches is None else int(num_matches)
+        if not null_arrays and self.K > 0:
+            r.landmark = _ptr(self.landmark, C.c_int)
+            r.match_point = _ptr(self.match_point, C.c_double)
+        self._c = r
+        return r
+
+
 class Solution:
     def __init__(self, n_landmarks):
         self.inv_depth = np.zeros(max(n_landmarks, 1), dtype=np.float64)
@@ -338,7 +372,7 @@ class TriangulateIn:
 
 
 HIP_SYMBOLS = [
-    "lfvio_create", "lfvio_destroy", "lfvio_last_error", "lfvio_version", "lfvio_solve", "lfvio_marginalize",
+    "lfvio_create", "lfvio_destroy", "lfvio_last_error", "lfvio_version", "lfvio_solve", "lfvio_solve_relo", "lfvio_marginalize",
     "lfvio_batch_reserve", "lfvio_batch_upload", "lfvio_batch_optimize", "lfvio_batch_optimize_async",
     "lfvio_batch_sync", "lfvio_batch_download", "lfvio_stream",
     "lfvio_batch_optimize_begin", "lfvio_batch_optimize_finish", "lfvio_batch_optimize_pending", "lfvio_batch_upload_chained", "lfvio_batch_upload_chained_device",
@@ -377,6 +411,7 @@ def load_hip_library(path=None):
     lib.lfvio_last_error.argtypes = [C.c_void_p]
     lib.lfvio_version.restype = C.c_char_p
     lib.lfvio_solve.argtypes = [C.c_void_p, C.POINTER(WindowC), C.POINTER(SolutionC)]
+    lib.lfvio_solve_relo.argtypes = [C.c_void_p, C.POINTER(WindowC), C.POINTER(ReloC), C.POINTER(SolutionC), C.POINTER(C.c_double)]
     lib.lfvio_marginalize.argtypes = [C.c_void_p, C.POINTER(WindowC), C.c_int, C.POINTER(Prior)]
     lib.lfvio_batch_reserve.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
     lib.lfvio_batch_upload.argtypes = [C.c_void_p, C.c_int, C.POINTER(WindowC)]

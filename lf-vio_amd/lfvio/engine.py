@@ -103,6 +103,20 @@ class Engine:
         self._check(self.lib.lfvio_solve(self.ctx, C.byref(win.c()), C.byref(sol.c)), "lfvio_solve")
         return sol
 
+    def solve_relo(self, win, frame, relo_pose, landmark=(), match_point=()):
+        """lfvio_solve_relo: the solve with the relocalization factors of one loop-closure message.  Returns
+        (abi.Solution, solved relo pose [p, q xyzw])."""
+        rc_ = abi.Relo(frame, relo_pose, landmark, match_point).c()
+        sol = abi.Solution(win.N)
+        out = np.zeros(abi.SIZE_POSE)
+        self._check(self.lib.lfvio_solve_relo(self.ctx, C.byref(win.c()), C.byref(rc_), C.byref(sol.c), _p(out)), "lfvio_solve_relo")
+        return sol, out
+
+    def solve_relo_rc(self, win, relo, sol, out, num_matches=None, null_arrays=False):
+        """The raw return code of lfvio_solve_relo (argument-error tests): outputs are written only on success."""
+        rc_ = relo.c(num_matches=num_matches, null_arrays=null_arrays)
+        return int(self.lib.lfvio_solve_relo(self.ctx, C.byref(win.c()), C.byref(rc_), C.byref(sol.c), _p(out)))
+
     def marginalize(self, win, flag):
         prior = abi.Prior()
         self._check(self.lib.lfvio_marginalize(self.ctx, C.byref(win.c()), flag, C.byref(prior)), "lfvio_marginalize")

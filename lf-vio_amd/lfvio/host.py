@@ -180,18 +180,19 @@ class HostEstimator:
         self.L.lfvio_host_get_buffers(self.h, _p(st), ns.ctypes.data_as(ip), hp.ctypes.data_as(ip), _p(sd))
         return dict(stamps=st, num_samples=ns, has_pre=hp, sum_dt=sd)
 
-    STATS = ("images", "thrown", "keyframes", "non_keyframes", "poses", "failures", "last_status", "iterations", "restarts", "bootstraps")
+    STATS = ("images", "thrown", "keyframes", "non_keyframes", "poses", "failures", "last_status", "iterations", "restarts", "bootstraps",
+             "relocalizations")
 
     def replay(self, trace_path, traj_path="", max_images=0):
         """-> (rc, stats dict); rc 0 ok, -2 a device call failed (stats['last_status']), -3 unreadable trace."""
-        o = np.zeros(10, dtype=np.int32)
+        o = np.zeros(len(self.STATS), dtype=np.int32)
         rc = self.L.lfvio_host_replay(self.h, str(trace_path).encode(), str(traj_path).encode(), int(max_images),
                                       o.ctypes.data_as(C.POINTER(C.c_int)))
         return rc, dict(zip(self.STATS, (int(x) for x in o)))
 
     def replay_timed(self, trace_path, traj_path="", max_images=0, cap=65536):
         """replay() with the wall-clock milliseconds the loop spent on every image it handed over -> (rc, stats, ms[n])."""
-        o, ms, n = np.zeros(10, dtype=np.int32), np.zeros(cap), C.c_int(0)
+        o, ms, n = np.zeros(len(self.STATS), dtype=np.int32), np.zeros(cap), C.c_int(0)
         self.L.lfvio_host_replay_timed.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_int), _dp, C.c_int, C.POINTER(C.c_int)]
         rc = self.L.lfvio_host_replay_timed(self.h, str(trace_path).encode(), str(traj_path).encode(), int(max_images),
                                             o.ctypes.data_as(C.POINTER(C.c_int)), _p(ms), cap, C.byref(n))
@@ -253,6 +254,37 @@ class HostEstimator:
         d = np.zeros(max(n, 1))
         self.L.lfvio_host_get_depths(self.h, _p(d))
         return d[:n]
+
+    # ---- relocalization (estimator.cpp:1133-1151, 603-625, 777-808)
+    def set_relo_frame(self, stamp, index, match_points, relo_t, relo_r):
+        """Estimator::setReloFrame: match_points [K, 3] = (x, y, id) sorted by id, relo_t [3], relo_r [3, 3]."""
+        mp = _f(np.asarray(match_points, dtype=np.float64).reshape(-1, 3))
+        self.L.lfvio_host_set_relo_frame.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_int, _dp, _dp, _dp]
+        self.L.lfvio_host_set_relo_frame(self.h, float(stamp), int(index), len(mp), _p(mp), _p(_f(relo_t)), _p(_f(relo_r)))
+
+    def relo(self):
+        """The relocalization members after optimization(): dict of relocalization_info, relo_frame_local_index, relo_Pose,
+        drift_correct_r / t, relo_relative_t / q (x y z w) / yaw, relo_solves."""
+        o = np.zeros(30)
+        self.L.lfvio_host_get_relo.argtypes = [C.c_void_p, _dp]
+        self.L.lfvio_host_get_relo(self.h, _p(o))
+        return dict(relocalization_info=int(o[0]), relo_frame_local_index=int(o[1]), relo_Pose=o[2:9].copy(),
+                    drift_correct_r=o[9:18].reshape(3, 3).copy(), drift_correct_t=o[18:21].copy(), relo_relative_t=o[21:24].copy(),
+                    relo_relative_q=o[24:28].copy(), relo_relative_yaw=float(o[28]), relo_solves=int(o[29]))
+
+    def relo_matches(self, cap=4096):
+        """The match list of the reference's walk as optimization() would build it now -> (landmark[K], xy[K, 2])."""
+        lm, xy = np.zeros(cap, dtype=np.int32), np.zeros((cap, 2))
+        self.L.lfvio_host_relo_matches.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), _dp]
+        K = self.L.lfvio_host_relo_matches(self.h, cap, lm.ctypes.data_as(C.POINTER(C.c_int)), _p(xy))
+        return lm[:min(K, cap)].copy(), xy[:min(K, cap)].copy()
+
+    def set_split_call(self, on):
+        self.L.lfvio_host_set_split_call(int(on))
+
+    def set_device_chain(self, on):
+        self.L.lfvio_host_set_device_chain.argtypes = [C.c_int]
+        self.L.lfvio_host_set_device_chain(int(on))
 
     def optimization(self, flag, fused=True):
         self.L.lfvio_host_set_flag(self.h, flag)

@@ -91,6 +91,34 @@ def de_pointcloud(buf):
     return stamp, rec
 
 
+def ser_match_points(seq, stamp, xyid, t_q_index, frame_id=b"world"):
+    """/pose_graph/match_points (sensor_msgs/PointCloud): points = (x, y, id); channels[0] = t.x t.y t.z q.w q.x q.y q.z index."""
+    a = np.asarray(xyid, dtype="<f4").reshape(-1, 3)
+    v = np.asarray(t_q_index, dtype="<f4").reshape(-1)
+    return _header(seq, stamp, frame_id) + struct.pack("<I", len(a)) + a.tobytes() + struct.pack("<I", 1) + _string(b"") + \
+        struct.pack("<I", len(v)) + v.tobytes()
+
+
+def de_match_points(buf):
+    """-> (stamp, frame index, relo_t[3], relo_q[4] x y z w, [K, 3] (x, y, id)) of a /pose_graph/match_points message, read as
+    estimator_node.cpp:260-284 reads it (channels[0]: t, q as w x y z, index)."""
+    stamp, o = _read_header(buf, 0)
+    (n,) = struct.unpack_from("<I", buf, o)
+    o += 4
+    pts = np.frombuffer(buf, dtype="<f4", count=3 * n, offset=o).reshape(n, 3).astype(np.float64)
+    o += 12 * n
+    (m,) = struct.unpack_from("<I", buf, o)
+    o += 4
+    assert m >= 1, "match_points carries t, q and the frame index in channels[0]"
+    (ln,) = struct.unpack_from("<I", buf, o)
+    o += 4 + ln
+    (k,) = struct.unpack_from("<I", buf, o)
+    o += 4
+    v = np.frombuffer(buf, dtype="<f4", count=k, offset=o).astype(np.float64)
+    assert k >= 8, "channels[0] = t.x t.y t.z q.w q.x q.y q.z index"
+    return stamp, int(v[7]), v[0:3].copy(), np.array([v[4], v[5], v[6], v[3]]), pts
+
+
 def ser_bool(v):
     return struct.pack("<B", 1 if v else 0)
 

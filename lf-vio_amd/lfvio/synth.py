@@ -486,3 +486,63 @@ def make_window_with_prior(seed, n_landmarks, optimize_fn, warm_landmarks=None, 
     st = continue_state(scene, 1, sol.pose, sol.speed_bias, sol.ex_pose, sol.td, rng)
     win = make_window(seed, n_landmarks, kf0=1, scene=scene, prior=prior, init_state=st, **kw)
     return win, warm
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# relocalization messages (/pose_graph/match_points, estimator_node.cpp:260-284) with a known answer
+# ---------------------------------------------------------------------------------------------------------------
+def _quat_R(q_xyzw):
+    x, y, z, w = q_xyzw
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                     [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                     [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+
+
+def relo_message(win, frame, n_matches, drift_yaw_deg=0.0, drift_t=(0.0, 0.0, 0.0), offset=None, noise=0.0, seed=0,
+                 state=None):
+    """A loop-closure message for window frame `frame` with a known answer.
+
+    The "truth" is the window's state (state: dict(pose, ex_pose, inv_depth) overrides it) and the landmarks it implies (first
+    observation / inverse depth, in the anchor frame).  The old keyframe of the pose graph is frame `frame` moved by `offset`
+    = (t[3], yaw_deg) in the VIO frame; its pose in the pose graph's frame is that pose with a drift applied —
+    R_drift = Rz(drift_yaw), t_drift = drift_t:  R_old = R_drift R,  P_old = R_drift P + t_drift (the inverse of what
+    double2vector's drift_correct_r / drift_correct_t undo).  The matched landmarks are projected into the old keyframe's
+    camera and kept in front of it (the pose graph sends normalized-plane points), up to n_matches of those with
+    start_frame <= frame, in list order.  `noise` is the standard deviation added to x, y.
+
+    Returns dict(landmark[K], match_point[K, 2], ids[K] (the landmark index as its id), relo_t, relo_r (the old keyframe in
+    the pose graph's frame: what setReloFrame receives), old_pose [7] (the answer in the VIO frame), drift_yaw_deg, drift_r,
+    drift_t)."""
+    rng = np.random.default_rng([seed, 31337])
+    pose = np.array(state["pose"] if state else win.pose, dtype=np.float64)
+    ex = np.array(state["ex_pose"] if state else win.ex_pose, dtype=np.float64)
+    lam = np.array(state["inv_depth"] if state else win.inv_depth, dtype=np.float64)
+    ric, tic = _quat_R(ex[3:7]), ex[:3]
+    P, R = pose[frame, :3], _quat_R(pose[frame, 3:7])
+    if offset is None:
+        offset = (np.zeros(3), 0.0)
+    Ryaw = exp_so3(np.array([0.0, 0.0, np.deg2rad(offset[1])]))
+    R_old, P_old = Ryaw @ R, P + np.asarray(offset[0], dtype=np.float64)
+    Rc_old, Pc_old = R_old @ ric, R_old @ tic + P_old
+    lms, pts = [], []
+    for l in range(win.N):
+        if len(lms) >= n_matches:
+            break
+        s = int(win.start_frame[l])
+        if s > frame:
+            continue
+        o0 = int(win.obs_offset[l])
+        Xc = win.obs_point[o0] / lam[l]
+        Rs, Ps = _quat_R(pose[s, 3:7]), pose[s, :3]
+        Xw = Rs @ (ric @ Xc + tic) + Ps
+        Xo = Rc_old.T @ (Xw - Pc_old)
+        if Xo[2] <= 0.1:
+            continue
+        lms.append(l)
+        pts.append(Xo[:2] / Xo[2] + rng.normal(0.0, noise, 2) if noise > 0 else Xo[:2] / Xo[2])
+    Rd = exp_so3(np.array([0.0, 0.0, np.deg2rad(drift_yaw_deg)]))
+    td = np.asarray(drift_t, dtype=np.float64)
+    old_pose = pose_block(P_old, R_old)
+    return dict(landmark=np.array(lms, dtype=np.int32), match_point=np.array(pts, dtype=np.float64).reshape(-1, 2),
+                ids=np.array(lms, dtype=np.int64), relo_r=Rd @ R_old, relo_t=Rd @ P_old + td, old_pose=old_pose,
+                drift_yaw_deg=float(drift_yaw_deg), drift_r=Rd, drift_t=td)

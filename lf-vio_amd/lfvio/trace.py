@@ -10,7 +10,7 @@ import numpy as np
 from . import abi, synth
 
 MAGIC = b"LFVT"
-REC_IMU, REC_FEATURES, REC_BOOTSTRAP, REC_TRUTH, REC_RESTART = 1, 2, 3, 4, 5
+REC_IMU, REC_FEATURES, REC_BOOTSTRAP, REC_TRUTH, REC_RESTART, REC_RELO = 1, 2, 3, 4, 5, 6
 
 
 class TraceWriter:
@@ -52,6 +52,11 @@ class TraceWriter:
         """std_msgs/Bool(true) on the tracker's restart topic (restart_callback, estimator_node.cpp:187-204)."""
         self._rec(REC_RESTART, struct.pack("<d", t) if t is not None else b"")
 
+    def relo(self, stamp, index, relo_t, relo_q_xyzw, match_points):
+        """A /pose_graph/match_points message: stamp, frame index, relo_t[3], relo_q[4] (x y z w), K x (x, y, id)."""
+        mp = np.asarray(match_points, dtype=np.float64).reshape(-1, 3)
+        self._rec(REC_RELO, np.concatenate([[stamp, index], np.ravel(relo_t), np.ravel(relo_q_xyzw), [len(mp)], mp.ravel()]).astype("<f8").tobytes())
+
     def truth(self, t, p, q_xyzw):
         self._rec(REC_TRUTH, struct.pack("<8d", t, *p, *q_xyzw))
 
@@ -61,7 +66,7 @@ class TraceWriter:
 
 def read_trace(path):
     """-> dict(imu [n,7], images [(t, array[n,9] float32)], bootstrap array or None, truth [n,8])"""
-    out = dict(imu=[], images=[], bootstrap=None, bootstraps=[], restarts=[], truth=[], order=[])
+    out = dict(imu=[], images=[], bootstrap=None, bootstraps=[], restarts=[], truth=[], relos=[], order=[])
     with open(path, "rb") as f:
         head = f.read(8)
         assert head[:4] == MAGIC and struct.unpack("<I", head[4:])[0] == 1
@@ -83,6 +88,10 @@ def read_trace(path):
                     out["bootstrap"] = out["bootstraps"][0]
             elif kind == REC_RESTART:
                 out["restarts"].append(len(out["images"]))
+            elif kind == REC_RELO:
+                d = np.frombuffer(p, dtype="<f8")
+                out["relos"].append(dict(at_image=len(out["images"]), stamp=float(d[0]), index=int(d[1]), relo_t=d[2:5].copy(),
+                                         relo_q=d[5:9].copy(), match_points=d[10:].reshape(-1, 3).copy()))
             elif kind == REC_TRUTH:
                 out["truth"].append(struct.unpack("<8d", p))
     out["imu"] = np.array(out["imu"]).reshape(-1, 7)

@@ -2,13 +2,15 @@
 """rosbag -> LFVT (lf-vio_amd/host/replay.h): the one command between a recorded run of the reference and
 `lfvio_host_replay` / tools/replay_stream.py / tools/ate.py — BASELINE configs[2] (PALVIO ID01) once the bag exists.
 
-    rosbag record -O id01_topics.bag /imu0 /feature_tracker/feature /feature_tracker/restart /vins_estimator/lfvt_bootstrap
+    rosbag record -O id01_topics.bag /imu0 /feature_tracker/feature /feature_tracker/restart /vins_estimator/lfvt_bootstrap \
+        /pose_graph/match_points
     python tools/bag_to_lfvt.py id01_topics.bag id01.lfvt [--imu /imu0] [--truth gt.txt]
 
 The first three topics are the node's own inputs (estimator_node.cpp:352-356); the fourth is the dump hook of
 INTEGRATION.md section 3 (one std_msgs/Float64MultiArray per successful initialStructure()).  Messages are written in the
 order the bag received them, contents unchanged (float32 bearings and channels stay float32).  --truth adds ground-truth
-records from a `stamp x y z qx qy qz qw` text file for tools/ate.py.  No ROS installation is needed."""
+records from a `stamp x y z qx qy qz qw` text file for tools/ate.py.  /pose_graph/match_points (a pose-graph node's loop
+closures, estimator_node.cpp:197-201) becomes record type 6.  No ROS installation is needed."""
 import argparse
 import os
 import sys
@@ -18,12 +20,12 @@ sys.path.insert(0, os.path.join(ROOT, "lf-vio_amd"))
 
 
 def convert(bag_path, out_path, imu_topic="/imu0", feature_topic="/feature_tracker/feature", restart_topic="/feature_tracker/restart",
-            bootstrap_topic="/vins_estimator/lfvt_bootstrap", truth_path=None):
+            bootstrap_topic="/vins_estimator/lfvt_bootstrap", truth_path=None, relo_topic="/pose_graph/match_points"):
     import numpy as np
     from lfvio import rosmsg, trace
 
     w = trace.TraceWriter(out_path)
-    n = dict(imu=0, images=0, restarts=0, bootstraps=0, other=0)
+    n = dict(imu=0, images=0, restarts=0, bootstraps=0, other=0)  # (+ relocalizations, when the bag has match_points)
     for topic, mtype, t, payload in rosmsg.read_bag(bag_path):
         if topic == imu_topic:
             stamp, acc, gyr = rosmsg.de_imu(payload)
@@ -40,6 +42,10 @@ def convert(bag_path, out_path, imu_topic="/imu0", feature_topic="/feature_track
         elif topic == bootstrap_topic:
             w.bootstrap_payload(rosmsg.de_f64_array(payload))
             n["bootstraps"] += 1
+        elif topic == relo_topic:  # relo_callback, estimator_node.cpp:197-201; used in process() :260-284
+            stamp, index, relo_t, relo_q, pts = rosmsg.de_match_points(payload)
+            w.relo(stamp, index, relo_t, relo_q, pts)
+            n["relocalizations"] = n.get("relocalizations", 0) + 1
         else:
             n["other"] += 1
     if truth_path:
@@ -58,5 +64,6 @@ if __name__ == "__main__":
     ap.add_argument("--restart", default="/feature_tracker/restart")
     ap.add_argument("--bootstrap", default="/vins_estimator/lfvt_bootstrap")
     ap.add_argument("--truth", default=None)
+    ap.add_argument("--relo", default="/pose_graph/match_points")
     a = ap.parse_args()
-    print(convert(a.bag, a.out, a.imu, a.features, a.restart, a.bootstrap, a.truth))
+    print(convert(a.bag, a.out, a.imu, a.features, a.restart, a.bootstrap, a.truth, a.relo))
