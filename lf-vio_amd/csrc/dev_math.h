@@ -252,3 +252,49 @@ DEV double wave_max(double v) {
   v = fmax(v, dpp_f64<0x140>(v));
   return fmax(fmax(readlane_f64(v, 0), readlane_f64(v, 16)), fmax(readlane_f64(v, 32), readlane_f64(v, 48)));
 }
+
+// Workgroup reductions over NT threads: every thread gets the result, in a fixed order (butterfly inside the wave, then the
+// wave totals in order).  scratch: NT / 64 doubles in LDS (NV * NT / 64 for block_sum_n).  No barrier behind the result.
+// (The loops over the wave totals unroll by four: all sixteen of a 1024-thread workgroup in flight at once doubled the
+// registers of k_relo_solve and slowed its factorization loop.)
+template <int NT>
+DEV double block_sum(double v, double *scratch, int tid) {
+  v = wave_sum(v);
+  __syncthreads();
+  if ((tid & 63) == 0) scratch[tid >> 6] = v;
+  __syncthreads();
+  double s = 0;
+#pragma unroll 4
+  for (int w = 0; w < NT / 64; w++) s += scratch[w];
+  return s;
+}
+// several sums at once: one pair of barriers for all of them (same association as block_sum)
+template <int NT, int NV>
+DEV void block_sum_n(double (&v)[NV], double *scratch, int tid) {
+#pragma unroll
+  for (int k = 0; k < NV; k++) v[k] = wave_sum(v[k]);
+  __syncthreads();
+  if ((tid & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < NV; k++) scratch[(tid >> 6) * NV + k] = v[k];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < NV; k++) {
+    double s = 0;
+#pragma unroll 4
+    for (int w = 0; w < NT / 64; w++) s += scratch[w * NV + k];
+    v[k] = s;
+  }
+}
+template <int NT>
+DEV double block_max(double v, double *scratch, int tid) {
+  v = wave_max(v);
+  __syncthreads();
+  if ((tid & 63) == 0) scratch[tid >> 6] = v;
+  __syncthreads();
+  double s = 0;
+#pragma unroll 4
+  for (int w = 0; w < NT / 64; w++) s = fmax(s, scratch[w]);
+  return s;
+}

@@ -50,24 +50,7 @@ __global__ __launch_bounds__(256, 4) void k_setup(char *base, size_t stride, int
     for (int k = tid; k < (int)(sizeof(FrameState) / 8); k += 256) dst[k] = src[k];
     if (tid == 0) {
       TRState *t = &S->tr;
-      t->radius = S->init_radius;
-      t->function_tolerance = S->fn_tol;
-      t->mu = 1e-8;
-      t->x_cost = t->cand_cost = t->model_cost_change = t->dogleg_step_norm = t->alpha = 0.0;
-      t->iteration = 0;
-      t->cur = 0;
-      t->do_lin = 1;
-      t->do_schur = 1;
-      t->done = 0;
-      t->termination = LFVIO_NO_CONVERGENCE;
-      t->chol_fail = 0;
-      t->scaled = 0;
-      t->num_succ = t->num_unsucc = t->consec_invalid = t->trace_len = 0;
-      t->step_valid = 0;
-      t->skip_step = 0;
-      t->error = 0;
-      t->new_point = 0;
-      t->spec_n = 1;
+      tr_init(t, S->init_radius, S->fn_tol);
       S->tail_state = 0;
       S->passes_used = 0;
       S->dec_pending = 0;

@@ -8,7 +8,7 @@
 //
 // This route is separate from the resident ones (k_lin / k_linw / k_linb + k_solve_dense): a relo solve happens once per
 // loop-closure message, not per frame, so it is laid out for clarity and a bounded size rather than for the last microsecond:
-//   k_relo_setup    IMU sqrt_info (LLT of the inverse covariance), state and trust-region header
+//   k_relo_setup    IMU sqrt_info (LLT of the inverse covariance), state and trust-region header (tr_init, as k_setup)
 //   k_relo_eval     one lane per landmark: its visual factors + its relo factor, Cauchy-corrected; the camera-side Jacobian
 //                   rows go to a dense row table [178 columns | r], the landmark column straight into w_l, h_l, g_l, cost.
 //                   Behind the landmark workgroups: one workgroup per IMU factor and one for the prior.  Cost-only form for
@@ -19,10 +19,12 @@
 //                   gradient max-norm, Cauchy-point terms; phase 1: packed Cholesky of the reduced system in LDS (retries with a
 //                   raised mu form it there), back-substitution,
 //                   the dogleg and the candidate x (+) delta
-//   k_relo_decide   TrustRegionMinimizer's accept / reject / terminate policy (the one of tr_decide.h, one candidate per pass)
+//   k_relo_decide   TrustRegionMinimizer's accept / reject / terminate policy: decide_walk of tr_decide.h, one candidate per pass
+// The loop header is the resident routes' TRState; the workgroup reductions are dev_math.h's.
 // Semantics: tests/relo_ref.py, a numpy statement of the same Ceres 1.12 loop over the augmented state.
 #pragma once
 #include "dev_factors.h"
+#include "tr_decide.h"
 
 constexpr int RK = KP + 6;     // reduced system: 172 + relo tangent
 constexpr int RO = KP;         // first column of the relo tangent
@@ -44,15 +46,8 @@ struct ReloX {  // one point of the augmented state
   double relo[7];
 };
 
-struct ReloTR {
-  double radius, mu, x_cost, x_norm, cand_cost, cand_xnorm, model, dsn, step_norm, alpha, initial_cost;
-  double fn_tol;
-  int iteration, invalid, done, term, trace_len, num_succ, num_unsucc, chol_fail, need_lin, need_gn, cur, first, max_iter;
-  LfvioIterationSummary trace[LFVIO_MAX_TRACE];
-};
-
 struct ReloDev {
-  int N, M, K, R, est_ex, est_td, relo_on, prior_n, prior_nb;
+  int N, M, K, R, est_ex, est_td, relo_on, prior_n, prior_nb, max_iter;
   int row_relo, row_imu, row_prior;
   double sqrt_info, tr_ro, row, g[3];  // tr_ro: TR, the rolling-shutter read-out time
   // inputs
@@ -82,7 +77,10 @@ struct ReloDev {
   double scale[RK], diag[RK], gn[RK], stp[RK];
   double *scale_l, *diag_l, *gn_l, *stp_l, *hs, *gsl;  // [N]
   int act[RK];
-  ReloTR tr;
+  double mlin, mquad;  // the candidate's model terms s.g and s^T H s (k_relo_solve; decide_walk's DecideSums)
+  // the loop header.  Only a part of it is used: one candidate per pass (cg = cn = 0 and q[] = 0, the whole step is in mlin / mquad);
+  // step_sq_pose, xn2_pose_cand: |delta|^2 and |x (+) delta|^2 of the whole augmented state; scaled: IterationZero is behind
+  TRState tr;
 };
 
 // ProjectionTdFactor / ProjectionFactor::Evaluate (projection_td_factor.cpp:36-151, projection_factor.cpp:21-121), one
@@ -185,7 +183,7 @@ DEV void relo_put_factor(const ReloDev *D, int row, const double *r, const doubl
 template <bool LIN>
 __global__ void __launch_bounds__(64) k_relo_eval(ReloDev *D) {
   const int tid = threadIdx.x, nlw = (D->N + RELO_LM_WG - 1) / RELO_LM_WG;
-  if (D->tr.done || (LIN ? !D->tr.need_lin : D->tr.chol_fail)) return;  // (a pass that keeps its linearization / has no candidate)
+  if (D->tr.done || (LIN ? !D->tr.do_lin : D->tr.chol_fail)) return;  // (a pass that keeps its linearization / has no candidate)
   const int cur = LIN ? D->tr.cur : (D->tr.cur ^ 1);
   const ReloX *X = &D->x[cur];
   const double *lam = D->lam[cur];
@@ -336,7 +334,7 @@ __global__ void __launch_bounds__(64) k_relo_eval(ReloDev *D) {
 
 // [H_cc | g_c] partial sums: block (tile, chunk); thread (i, j) of the 16 x 16 tile sums its entry over the chunk's rows.
 __global__ void __launch_bounds__(256) k_relo_gram(ReloDev *D) {
-  if (D->tr.done || !D->tr.need_lin) return;
+  if (D->tr.done || !D->tr.do_lin) return;
   const int t = blockIdx.x, ch = blockIdx.y;
   int a = 0;
   while ((a + 1) * (a + 2) / 2 <= t) a++;
@@ -350,32 +348,9 @@ __global__ void __launch_bounds__(256) k_relo_gram(ReloDev *D) {
   D->gpart[((size_t)ch * RG + i) * RG + j] = s;
 }
 
-DEV double relo_block_sum(double v, double *red) {  // every thread of the workgroup gets the sum (fixed order)
-  const int tid = threadIdx.x, nw = blockDim.x >> 6;
-  v = wave_sum(v);
-  __syncthreads();
-  if ((tid & 63) == 0) red[tid >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-  for (int k = 0; k < nw; k++) s += red[k];
-  __syncthreads();
-  return s;
-}
-DEV double relo_block_max(double v, double *red) {
-  const int tid = threadIdx.x, nw = blockDim.x >> 6;
-  v = wave_max(v);
-  __syncthreads();
-  if ((tid & 63) == 0) red[tid >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-  for (int k = 0; k < nw; k++) s = fmax(s, red[k]);
-  __syncthreads();
-  return s;
-}
-
 DEV int relo_pk(int i, int j) { return i * (i + 1) / 2 + j; }  // j <= i
 
-// the whole augmented state as Ceres' x vector, squared norm of (a) or of (a - b)
+// the whole augmented state as Ceres' x vector, squared norm of (a) or of (a - b); k_relo_solve's workgroup
 DEV double relo_xsq(const ReloDev *D, const ReloX *a, const double *la, const ReloX *b, const double *lb, double *red) {
   const int tid = threadIdx.x;
   double s = 0.0;
@@ -393,8 +368,10 @@ DEV double relo_xsq(const ReloDev *D, const ReloX *a, const double *la, const Re
     if (D->relo_on)
       for (int k = 0; k < 7; k++) acc(a->relo[k], b ? b->relo[k] : 0.0);
   }
-  for (int l = tid; l < D->N; l += blockDim.x) acc(la[l], lb ? lb[l] : 0.0);
-  return relo_block_sum(s, red);
+  for (int l = tid; l < D->N; l += RELO_SOLVE_THREADS) acc(la[l], lb ? lb[l] : 0.0);
+  s = block_sum<RELO_SOLVE_THREADS>(s, red, tid);
+  __syncthreads();
+  return s;
 }
 
 // The reduced system of the Gauss-Newton step at the current mu, over 16 x 16 tiles of its lower triangle + the rhs column:
@@ -402,8 +379,8 @@ DEV double relo_xsq(const ReloDev *D, const ReloX *a, const double *la, const Re
 // (inactive columns: identity rows, zero rhs).  k_relo_solve factors it; a retry with a raised mu inside k_relo_solve forms
 // it there itself.
 __global__ void __launch_bounds__(256) k_relo_schur(ReloDev *D) {
-  const ReloTR *T = &D->tr;
-  if (T->done || !T->need_gn) return;
+  const TRState *T = &D->tr;
+  if (T->done || !T->do_schur) return;
   const int t = blockIdx.x;
   int i, j;
   if (t == RELO_GTILES) {  // the last workgroup: the rhs column
@@ -435,17 +412,18 @@ __global__ void __launch_bounds__(256) k_relo_schur(ReloDev *D) {
   if (t == 0 && threadIdx.x == 0) D->Sg_mu = mu;
 }
 
-// One pass of the loop up to the candidate.  D->tr.need_lin: a new linearization lies in the row table / W / h / g (its
-// gradient closes the last trace entry); D->tr.need_gn: the Gauss-Newton step has to be (re)computed with the current mu.
+// One pass of the loop up to the candidate.  D->tr.do_lin: a new linearization lies in the row table / W / h / g (its
+// gradient closes the last trace entry); D->tr.do_schur: the Gauss-Newton step has to be (re)computed with the current mu.
 __global__ void __launch_bounds__(RELO_SOLVE_THREADS) k_relo_solve(ReloDev *D, int phase) {
   extern __shared__ double lds[];
   double *A = lds, *rhs = lds + RPACK, *hinv = rhs + RK, *red = hinv + RELO_MAX_LM;
   const int tid = threadIdx.x, nt = blockDim.x, N = D->N;
-  ReloTR *T = &D->tr;
+  TRState *T = &D->tr;
   if (T->done) return;
   const int cur = T->cur;
   if (phase == 0) {
-    if (!T->need_lin) return;
+    if (!T->do_lin) return;
+    const bool first = !T->scaled;  // the start point: IterationZero
     // H_cc | g_c from the chunk partials (fixed order), unscaled
     for (int e = tid; e < RK * RK; e += nt) {
       const int i = e / RK, j = e % RK, a = max(i, j), b = min(i, j);
@@ -477,9 +455,10 @@ __global__ void __launch_bounds__(RELO_SOLVE_THREADS) k_relo_solve(ReloDev *D, i
     else if (tid == LFVIO_NUM_FRAMES + 2 && D->est_td) gm = fabs(D->gs[off_td()]);
     if (tid < 99) gm = fmax(gm, fabs(D->gs[off_sb(0) + tid]));
     for (int l = tid; l < N; l += nt) gm = fmax(gm, fabs(D->gl[l]));
-    gm = relo_block_max(gm, red);
+    gm = block_max<RELO_SOLVE_THREADS>(gm, red, tid);
+    __syncthreads();
     // Jacobi scaling, fixed at the start point (trust_region_minimizer.cc: jacobian_scaling = 1 / (1 + |J_col|))
-    if (T->first) {
+    if (first) {
       if (tid < RK) D->scale[tid] = D->act[tid] ? 1.0 / (1.0 + sqrt(D->Hs[tid * RK + tid])) : 1.0;
       for (int l = tid; l < N; l += nt) D->scale_l[l] = 1.0 / (1.0 + sqrt(D->h[l]));
       __syncthreads();
@@ -522,11 +501,12 @@ __global__ void __launch_bounds__(RELO_SOLVE_THREADS) k_relo_solve(ReloDev *D, i
       q += 2.0 * vl * wv + D->hs[l] * vl * vl;
       g2 += (D->gsl[l] / dl) * (D->gsl[l] / dl);
     }
-    g2 = relo_block_sum(g2, red);
-    q = relo_block_sum(q, red);
+    double gq[2] = {g2, q};
+    block_sum_n<RELO_SOLVE_THREADS>(gq, red, tid);
+    __syncthreads();
     if (tid == 0) {
-      T->alpha = g2 / q;
-      if (T->first) {
+      T->alpha = gq[0] / gq[1];
+      if (first) {
         double c = 0.0;
         for (int l = 0; l < N; l++) c += D->lcost[l];
         for (int k = 0; k < RELO_PCOST; k++) c += D->pcost[k];
@@ -539,19 +519,22 @@ __global__ void __launch_bounds__(RELO_SOLVE_THREADS) k_relo_solve(ReloDev *D, i
       } else if (T->trace_len > 0 && T->trace_len <= LFVIO_MAX_TRACE) {
         T->trace[T->trace_len - 1].gradient_max_norm = gm;
       }
-      if (gm <= 1e-10) T->term = LFVIO_CONVERGENCE, T->done = 1;  // GradientToleranceReached
-      if (T->first && !T->done && T->iteration >= T->max_iter) T->term = LFVIO_NO_CONVERGENCE, T->done = 1;
+      if (gm <= 1e-10) T->termination = LFVIO_CONVERGENCE, T->done = 1;  // GradientToleranceReached
+      if (first && !T->done && T->iteration >= D->max_iter) T->termination = LFVIO_NO_CONVERGENCE, T->done = 1;
     }
-    if (T->first) {
+    if (first) {
       const double xn = relo_xsq(D, &D->x[cur], D->lam[cur], nullptr, nullptr, red);
       if (tid == 0) T->x_norm = sqrt(xn);
     }
     __syncthreads();
-    if (tid == 0) T->need_lin = 0, T->first = 0;
+    if (tid == 0) {
+      T->do_lin = 0;
+      if (first) T->scaled = 1, T->iteration = 1;  // (the candidate of the next pass is Ceres' iteration 1: decide_walk counts from there)
+    }
     __syncthreads();
     return;
   }
-  if (T->need_gn) {
+  if (T->do_schur) {
     // Gauss-Newton step of (J^T J + mu D^T D) y = J^T r through the Schur complement of the (diagonal) landmark block;
     // a failed factorization raises mu (LinearSolver failure -> mu *= 10 while mu < 1: dogleg_strategy.cc ComputeGaussNewtonStep)
     bool ok = false;
@@ -648,7 +631,8 @@ __global__ void __launch_bounds__(RELO_SOLVE_THREADS) k_relo_solve(ReloDev *D, i
           if (!isfinite(y)) bad = 1;
           D->gn_l[l] = -D->diag_l[l] * y;
         }
-        const double nb = relo_block_max((double)bad, red);
+        const double nb = block_max<RELO_SOLVE_THREADS>((double)bad, red, tid);
+        __syncthreads();
         if (nb == 0.0) {
           ok = true;
           break;
@@ -661,24 +645,24 @@ __global__ void __launch_bounds__(RELO_SOLVE_THREADS) k_relo_solve(ReloDev *D, i
     if (tid == 0) {
       T->mu = mu;
       T->chol_fail = ok ? 0 : 1;
-      T->need_gn = 0;
+      T->do_schur = 0;
     }
     __syncthreads();
   }
   if (T->chol_fail) return;
   // dogleg (dogleg_strategy.cc ComputeTraditionalDoglegStep): step = cg grad + cn gn in the D-scaled space
-  double gg = 0.0, nn = 0.0, gnv = 0.0;
+  double dn[3] = {0.0, 0.0, 0.0};  // |g / D|^2, |gn|^2, (g / D).gn
   if (tid < RK && D->act[tid]) {
     const double gr = D->gs[tid] / D->diag[tid];
-    gg += gr * gr, nn += D->gn[tid] * D->gn[tid], gnv += gr * D->gn[tid];
+    dn[0] += gr * gr, dn[1] += D->gn[tid] * D->gn[tid], dn[2] += gr * D->gn[tid];
   }
   for (int l = tid; l < N; l += nt) {
     const double gr = D->gsl[l] / D->diag_l[l];
-    gg += gr * gr, nn += D->gn_l[l] * D->gn_l[l], gnv += gr * D->gn_l[l];
+    dn[0] += gr * gr, dn[1] += D->gn_l[l] * D->gn_l[l], dn[2] += gr * D->gn_l[l];
   }
-  gg = relo_block_sum(gg, red);
-  nn = relo_block_sum(nn, red);
-  gnv = relo_block_sum(gnv, red);
+  block_sum_n<RELO_SOLVE_THREADS>(dn, red, tid);
+  __syncthreads();
+  const double gg = dn[0], nn = dn[1], gnv = dn[2];
   const double radius = T->radius, alpha = T->alpha, gnorm = sqrt(gg), gnn = sqrt(nn);
   double cg, cn, dsn;
   if (gnn <= radius) {
@@ -697,21 +681,21 @@ __global__ void __launch_bounds__(RELO_SOLVE_THREADS) k_relo_solve(ReloDev *D, i
   if (tid < RK) D->stp[tid] = D->act[tid] ? (cg * D->gs[tid] / D->diag[tid] + cn * D->gn[tid]) / D->diag[tid] : 0.0;
   for (int l = tid; l < N; l += nt) D->stp_l[l] = (cg * D->gsl[l] / D->diag_l[l] + cn * D->gn_l[l]) / D->diag_l[l];
   __syncthreads();
-  double lin = 0.0, quad = 0.0;
+  double mq[2] = {0.0, 0.0};  // s.g, s^T H s
   if (tid < RK && D->act[tid]) {
     double hv = 0.0;
     for (int k = 0; k < RK; k++) hv += D->Hs[tid * RK + k] * D->stp[k];
-    lin += D->stp[tid] * D->gs[tid], quad += D->stp[tid] * hv;
+    mq[0] += D->stp[tid] * D->gs[tid], mq[1] += D->stp[tid] * hv;
   }
   for (int l = tid; l < N; l += nt) {
     const double *w = D->W + (size_t)l * RK;
     double wv = 0.0;
     for (int k = 0; k < RK; k++) wv += w[k] * D->stp[k];
     const double sl = D->stp_l[l];
-    lin += sl * D->gsl[l], quad += 2.0 * sl * wv + D->hs[l] * sl * sl;
+    mq[0] += sl * D->gsl[l], mq[1] += 2.0 * sl * wv + D->hs[l] * sl * sl;
   }
-  lin = relo_block_sum(lin, red);
-  quad = relo_block_sum(quad, red);
+  block_sum_n<RELO_SOLVE_THREADS>(mq, red, tid);
+  __syncthreads();
   // candidate x (+) (s * scale)
   const ReloX *X = &D->x[cur];
   ReloX *Y = &D->x[cur ^ 1];
@@ -743,79 +727,32 @@ __global__ void __launch_bounds__(RELO_SOLVE_THREADS) k_relo_solve(ReloDev *D, i
   const double sn2 = relo_xsq(D, Y, D->lam[cur ^ 1], X, D->lam[cur], red);
   const double xn2 = relo_xsq(D, Y, D->lam[cur ^ 1], nullptr, nullptr, red);
   if (tid == 0) {
-    T->model = -lin - 0.5 * quad;
-    T->dsn = dsn;
-    T->step_norm = sqrt(sn2);
-    T->cand_xnorm = sqrt(xn2);
+    D->mlin = mq[0], D->mquad = mq[1];
+    T->dogleg_step_norm = dsn;
+    T->step_sq_pose = sn2;
+    T->xn2_pose_cand = xn2;
   }
 }
 
-// TrustRegionMinimizer's bookkeeping for the candidate of the pass (one lane; the policy of tr_decide.h::decide_walk)
+// TrustRegionMinimizer's bookkeeping for the candidate of the pass: decide_walk on one lane, as k_decide's decide_body does, with
+// one candidate whose whole model terms, step and state norms are in mlin / mquad, step_sq_pose and xn2_pose_cand.  (Its retry
+// branch, chol_fail with mu < 1, is not met here: k_relo_solve raises mu to 1 before it reports a failed factorization.)
 __global__ void k_relo_decide(ReloDev *D) {
-  if (threadIdx.x != 0) return;
-  ReloTR *T = &D->tr;
-  if (T->done) return;
-  LfvioIterationSummary it;
-  it.cost = T->x_cost, it.cost_change = 0, it.gradient_max_norm = 0, it.step_norm = 0, it.relative_decrease = 0;
-  it.step_is_valid = 0, it.step_is_successful = 0;
-  T->iteration++;
-  const bool valid = !T->chol_fail && T->model > 0.0;
-  if (!valid) {
-    if (++T->invalid >= 5) {
-      T->term = LFVIO_FAILURE, T->done = 1;
-      return;
-    }
-    T->mu *= 10.0;
-    T->chol_fail = 0;
-    T->need_gn = 1;
-  } else {
-    T->invalid = 0;
-    double cc = 0.0;
-    for (int l = 0; l < D->N; l++) cc += D->lcost[l];
-    for (int k = 0; k < RELO_PCOST; k++) cc += D->pcost[k];
-    const double cand = isfinite(cc) ? cc : 1.79769313486231570815e+308;
-    T->cand_cost = cand;
-    it.step_is_valid = 1;
-    it.step_norm = T->step_norm;
-    if (T->step_norm <= 1e-8 * (T->x_norm + 1e-8)) {
-      T->term = LFVIO_CONVERGENCE, T->done = 1;
-      return;
-    }
-    it.cost_change = T->x_cost - cand;
-    if (fabs(it.cost_change) <= T->fn_tol * T->x_cost) {
-      T->term = LFVIO_CONVERGENCE, T->done = 1;
-      return;
-    }
-    it.relative_decrease = it.cost_change / T->model;
-    if (it.relative_decrease > 1e-3) {
-      T->cur ^= 1;
-      T->x_norm = T->cand_xnorm;
-      T->x_cost = cand;
-      it.cost = cand;
-      it.step_is_successful = 1;
-      it.gradient_max_norm = __builtin_nan("");  // the next linearization writes it (include/lfvio.h)
-      if (it.relative_decrease < 0.25) T->radius *= 0.5;
-      if (it.relative_decrease > 0.75) T->radius = fmax(T->radius, 3.0 * T->dsn);
-      T->mu = fmax(1e-8, 2.0 * T->mu / 10.0);
-      T->need_lin = 1;
-      T->need_gn = 1;
-    } else {
-      T->radius *= 0.5;
-      it.cost = cand;
-    }
-  }
-  if (it.step_is_successful) T->num_succ++;
-  else T->num_unsucc++;
-  it.trust_region_radius = T->radius;
-  if (T->trace_len < LFVIO_MAX_TRACE) T->trace[T->trace_len] = it;
-  T->trace_len++;
-  if (T->iteration >= T->max_iter) T->term = LFVIO_NO_CONVERGENCE, T->done = 1;
-  else if (T->radius <= 1e-32) T->term = LFVIO_CONVERGENCE, T->done = 1;
+  if (threadIdx.x != 0 || D->tr.done) return;
+  DecideSums sm = {};
+  for (int l = 0; l < D->N; l++) sm.cost[0] += D->lcost[l];
+  for (int k = 0; k < RELO_PCOST; k++) sm.cost[0] += D->pcost[k];
+  sm.mlin[0] = D->mlin, sm.mquad[0] = D->mquad;
+  TRHead t = *reinterpret_cast<const TRHead *>(&D->tr);
+  decide_walk(t, sm, 1, 0, D->max_iter, &D->tr);
+  TRDecision d;
+  decision_from(d, t, 0);
+  decision_to_header(&D->tr, d);
 }
 
 // IMU sqrt_info = LLT(covariance^-1).matrixL()^T (imu_factor.h:37-38): Gauss-Jordan inverse with partial pivoting, then the
 // column Cholesky; one lane per interval.  State and header of the loop.
-__global__ void __launch_bounds__(64) k_relo_setup(ReloDev *D, double init_radius, double fn_tol, int max_iter) {
+__global__ void __launch_bounds__(64) k_relo_setup(ReloDev *D, double init_radius, double fn_tol) {
   __shared__ double M[LFVIO_WINDOW_SIZE][15][30];
   const int f = threadIdx.x;
   if (f < LFVIO_WINDOW_SIZE) {
@@ -872,15 +809,11 @@ __global__ void __launch_bounds__(64) k_relo_setup(ReloDev *D, double init_radiu
   if (threadIdx.x == 0) {
     D->x[0] = D->x0;
     D->x[1] = D->x0;
-    ReloTR *T = &D->tr;
-    T->radius = init_radius, T->mu = 1e-8, T->x_cost = 0, T->x_norm = 0, T->cand_cost = 0, T->cand_xnorm = 0, T->model = 0, T->dsn = 0;
-    T->step_norm = 0, T->alpha = 0, T->initial_cost = 0, T->fn_tol = fn_tol;
-    T->iteration = 0, T->invalid = 0, T->done = 0, T->term = LFVIO_NO_CONVERGENCE, T->trace_len = 0, T->num_succ = 0, T->num_unsucc = 0;
-    T->chol_fail = 0, T->need_lin = 1, T->need_gn = 1, T->cur = 0, T->first = 1, T->max_iter = max_iter;
+    tr_init(&D->tr, init_radius, fn_tol);  // (the host zeroed the rest of the header)
   }
 }
 
 // "Maximum solver time reached": the loop ends where it is, termination NO_CONVERGENCE
 __global__ void k_relo_stop(ReloDev *D) {
-  if (threadIdx.x == 0 && !D->tr.done) D->tr.done = 1, D->tr.term = LFVIO_NO_CONVERGENCE;
+  if (threadIdx.x == 0 && !D->tr.done) D->tr.done = 1, D->tr.termination = LFVIO_NO_CONVERGENCE;
 }

@@ -51,44 +51,6 @@ DEV double quarter_bcast(double x, int t) {  // t: compile-time after unrolling
 #define SOLVE_KEEP(v) asm volatile("" ::"v"(v))
 #define STAMP(S, k) do { if (threadIdx.x == 0) (S)->dbg[k] = (long long)__builtin_readcyclecounter(); } while (0)
 
-DEV double block_sum(double v, double *scratch, int tid) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((tid & 63) == 0) scratch[tid >> 6] = v;
-  __syncthreads();
-  double s = 0;
-  for (int w = 0; w < SOLVE_THREADS / 64; w++) s += scratch[w];
-  return s;
-}
-// several sums at once: one pair of barriers for all of them (same association as block_sum: butterfly inside the wave,
-// then the four wave totals in order)
-template <int NV>
-DEV void block_sum_n(double (&v)[NV], double *scratch, int tid) {
-#pragma unroll
-  for (int k = 0; k < NV; k++) v[k] = wave_sum(v[k]);
-  __syncthreads();
-  if ((tid & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < NV; k++) scratch[(tid >> 6) * NV + k] = v[k];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < NV; k++) {
-    double s = 0;
-    for (int w = 0; w < SOLVE_THREADS / 64; w++) s += scratch[w * NV + k];
-    v[k] = s;
-  }
-}
-DEV double block_max(double v, double *scratch, int tid) {
-  v = wave_max(v);
-  __syncthreads();
-  if ((tid & 63) == 0) scratch[tid >> 6] = v;
-  __syncthreads();
-  double s = 0;
-  for (int w = 0; w < SOLVE_THREADS / 64; w++) s = fmax(s, scratch[w]);
-  return s;
-}
-
 // ---------------------------------------------------------------------------
 // Blocked Cholesky and back-substitution of a symmetric system held in LDS as the lower 16 x 16 tiles of a 16 TN x 16 TN matrix
 // (tile layout above), TK pivots, the rhs as row TK (so the forward substitution rides along).  Shared by the dense solve of the
@@ -711,7 +673,7 @@ DEV void solve_body(Slot *S, double *smem, long long xch_off, long long imu_off,
       if (tid < KC) cross = scross * Gd[tid];  // z2 . G_c
     }
     double sums[3] = {qgg_part, gs, cross};
-    block_sum_n(sums, scratch, tid);
+    block_sum_n<SOLVE_THREADS>(sums, scratch, tid);
     const double q_gg = sums[0], gsq = sums[1], cr = sums[2];
     if (tid == 0) {
       const double Jg2 = q_gg + 2.0 * cr + ls[2];
@@ -732,7 +694,7 @@ DEV void solve_body(Slot *S, double *smem, long long xch_off, long long imu_off,
   STAMP(S, 4);
   {
     double f = bad ? 1.0 : 0.0;
-    f = block_max(f, scratch, tid);
+    f = block_max<SOLVE_THREADS>(f, scratch, tid);
     bad = f > 0.0;
   }
   STAMP(S, 5);
@@ -742,7 +704,7 @@ DEV void solve_body(Slot *S, double *smem, long long xch_off, long long imu_off,
   {
     double f = 0.0;
     if (tid < KP && !isfinite(yv[tid])) f = 1.0;
-    f = block_max(f, scratch, tid);
+    f = block_max<SOLVE_THREADS>(f, scratch, tid);
     if (f > 0.0) bad = true;
   }
   if (bad) {
@@ -809,7 +771,7 @@ DEV void solve_body(Slot *S, double *smem, long long xch_off, long long imu_off,
     double pcb = 0, pnc = 0;  // (k_lm_cb2's partials, reduced over the ranks: a pair per thread)
     if (sharded == 2 && tid < XP_WGS) pcb = xch[XOFF_P + 2 * tid], pnc = xch[XOFF_P + 2 * tid + 1];
     double sums[11] = {gn2, ggn, gG, gN, zt * zt, grhs_part, nsn, z1n, pcb, pnc, gcn};
-    block_sum_n(sums, scratch, tid);
+    block_sum_n<SOLVE_THREADS>(sums, scratch, tid);
     gn2 = sums[0], ggn = sums[1], gG = sums[2], gN = sums[3];
     const double qnn = sums[4] - mu * gn2 + sums[6], qgn = -sums[5] - mu * ggn + sums[10];
     STAMP(S, 7);

@@ -575,6 +575,36 @@ constexpr int LINB_MAX_GROUPS = 500;     // ... in at most this many groups (two
 constexpr int LINB_MIN_LM = 40960;
 constexpr int LIN_SPLIT_MIN_BATCH = 8;   // ... when they are a batch: ONE large window (100 000 landmarks: 64 us as one grid, 54 + 35 + 14 role by role) is better off with its roles overlapping
 
+// The window's own sizes and arrays (lfvio_solve and the others that upload, lfvio_solve_relo); its prior is the caller's to check.
+int check_window(lfvio_ctx *c, const LfvioWindow *w) {
+  if (!w || w->num_landmarks < 0 || w->num_observations < 0) {
+    c->err = "null window / negative sizes";
+    return LFVIO_ERR_ARG;
+  }
+  const int N = w->num_landmarks, M = w->num_observations;
+  if (N > 0 && (!w->start_frame || !w->obs_offset || !w->inv_depth || !w->obs_point || !w->obs_velocity ||
+                !w->obs_cur_td || !w->obs_uv_y)) {
+    c->err = "null landmark / observation arrays";
+    return LFVIO_ERR_ARG;
+  }
+  if (N > 0 && (w->obs_offset[0] != 0 || w->obs_offset[N] != M)) {
+    c->err = "obs_offset is not a CSR over num_observations";
+    return LFVIO_ERR_ARG;
+  }
+  for (int l = 0; l < N; l++) {
+    const int k = w->obs_offset[l + 1] - w->obs_offset[l], s = w->start_frame[l];
+    if (k < 2 || s < 0 || s + k > LFVIO_NUM_FRAMES) {  // used_num >= 2, track inside the window
+      c->err = "landmark with fewer than 2 observations or a track leaving the window";
+      return LFVIO_ERR_ARG;
+    }
+  }
+  if (w->estimate_td && !(w->row > 0.0)) {  // row_i = uv.y - ROW / 2 and TR / ROW (projection_td_factor.cpp:20-21, 54-55)
+    c->err = "estimate_td needs row > 0";
+    return LFVIO_ERR_ARG;
+  }
+  return LFVIO_OK;
+}
+
 // Pack one window into the pinned staging blob and upload it to slot `slot`.
 // chain (lfvio_batch_upload_chained): the window's prior is *chain, and if a call is still in flight on the context (the
 // marginalization behind an early state), it is THAT call's prior: the landmark tables and gather lists of the new window —
@@ -612,35 +642,12 @@ int upload_window(lfvio_ctx *c, int slot, const LfvioWindow *w, int sharded = 0,
   };
   if (!chained && !device_chain)
     if (int rc = join_inflight(c)) return rc;
-  if (!w || w->num_landmarks < 0 || w->num_observations < 0) {
-    c->err = "null window / negative sizes";
-    return LFVIO_ERR_ARG;
-  }
+  if (int rc = check_window(c, w)) return rc;
   const int N = w->num_landmarks, M = w->num_observations;
-  if (N > 0 && (!w->start_frame || !w->obs_offset || !w->inv_depth || !w->obs_point || !w->obs_velocity ||
-                !w->obs_cur_td || !w->obs_uv_y)) {
-    c->err = "null landmark / observation arrays";
-    return LFVIO_ERR_ARG;
-  }
-  if (N > 0 && (w->obs_offset[0] != 0 || w->obs_offset[N] != M)) {
-    c->err = "obs_offset is not a CSR over num_observations";
-    return LFVIO_ERR_ARG;
-  }
-  for (int l = 0; l < N; l++) {
-    const int k = w->obs_offset[l + 1] - w->obs_offset[l], s = w->start_frame[l];
-    if (k < 2 || s < 0 || s + k > LFVIO_NUM_FRAMES) {  // used_num >= 2, track inside the window
-      c->err = "landmark with fewer than 2 observations or a track leaving the window";
-      return LFVIO_ERR_ARG;
-    }
-  }
   const LfvioPrior *given = chain ? chain : w->prior;
   const LfvioPrior *pr = (given && given->valid) ? given : nullptr;  // (chained: not known before the prior section below)
   if (!chained)
     if (int rc = check_input_prior(c, pr)) return rc;
-  if (w->estimate_td && !(w->row > 0.0)) {  // row_i = uv.y - ROW / 2 and TR / ROW (projection_td_factor.cpp:20-21, 54-55)
-    c->err = "estimate_td needs row > 0";
-    return LFVIO_ERR_ARG;
-  }
   const Layout &L = c->L;
   char *h = c->h_stage;
   char *d = c->d_base + (size_t)slot * L.total;
@@ -1620,19 +1627,17 @@ int fetch(lfvio_ctx *c, int slot, bool want_sol, bool want_prior, Fetched *f) {
 }
 
 // nothing is written to the caller's outputs before the result is known to be usable (the header promises untouched
-// outputs on error): check_* first, then unpack_*
-int check_solution(lfvio_ctx *c, int slot, const Fetched &f) {
-  const SlotHostInfo &info = c->info[slot];
-  const TRState *tr = f.tr;
+// outputs on error): check_* first, then unpack_*.  The solution of a loop: its header tr, the state x[tr->cur] (nx doubles:
+// a FrameState, or the relo route's ReloX), lam[tr->cur] (N inverse depths, device order; perm[dl]: the caller's index,
+// nullptr: the caller's order)
+int check_solution(lfvio_ctx *c, const TRState *tr, const double *x, int nx, const double *lam, int N) {
   if (tr->error) {
     c->err = "non-finite cost";
     return tr->error;
   }
-  const FrameState &x = f.xs[tr->cur];
-  const double *lam = f.lam[tr->cur];
   bool finite = std::isfinite(tr->x_cost);
-  for (int k = 0; finite && k < (int)(sizeof(FrameState) / 8); k++) finite = std::isfinite(((const double *)&x)[k]);
-  for (int dl = 0; finite && dl < info.N; dl++) finite = std::isfinite(lam[dl]);
+  for (int k = 0; finite && k < nx; k++) finite = std::isfinite(x[k]);
+  for (int dl = 0; finite && dl < N; dl++) finite = std::isfinite(lam[dl]);
   if (!finite) {
     c->err = "non-finite state";
     return LFVIO_ERR_NONFINITE;
@@ -1640,17 +1645,13 @@ int check_solution(lfvio_ctx *c, int slot, const Fetched &f) {
   return LFVIO_OK;
 }
 
-void unpack_solution(lfvio_ctx *c, int slot, const Fetched &f, LfvioSolution *out) {
-  const SlotHostInfo &info = c->info[slot];
-  const TRState *tr = f.tr;
-  const FrameState &x = f.xs[tr->cur];
-  const double *lam = f.lam[tr->cur];
+void unpack_solution(const TRState *tr, const FrameState &x, const double *lam, int N, const int *perm, LfvioSolution *out) {
   std::memcpy(out->para_pose, x.pose, sizeof x.pose);
   std::memcpy(out->para_speed_bias, x.sb, sizeof x.sb);
   std::memcpy(out->para_ex_pose, x.ex, sizeof x.ex);
   out->para_td = x.td;
   if (out->inv_depth)
-    for (int dl = 0; dl < info.N; dl++) out->inv_depth[info.perm[dl]] = lam[dl];
+    for (int dl = 0; dl < N; dl++) out->inv_depth[perm ? perm[dl] : dl] = lam[dl];
   out->num_iterations = tr->trace_len;
   out->num_successful_steps = tr->num_succ;
   out->num_unsuccessful_steps = tr->num_unsucc;
@@ -1718,9 +1719,11 @@ int download(lfvio_ctx *c, int slot, LfvioSolution *sol, LfvioPrior *prior) {
   int rc = fetch(c, slot, sol != nullptr, prior != nullptr, &f);
   if (rc) return rc;
   bool pass = false;
-  if (sol && (rc = check_solution(c, slot, f))) return rc;
+  const SlotHostInfo &info = c->info[slot];
+  const int cur = sol ? f.tr->cur : 0;
+  if (sol && (rc = check_solution(c, f.tr, (const double *)&f.xs[cur], sizeof(FrameState) / 8, f.lam[cur], info.N))) return rc;
   if (prior && (rc = check_prior(c, slot, f, &pass))) return rc;
-  if (sol) unpack_solution(c, slot, f, sol);
+  if (sol) unpack_solution(f.tr, f.xs[cur], f.lam[cur], info.N, info.perm.data(), sol);
   if (prior && pass && (rc = fetch_device_prior(c, slot, nullptr))) return rc;
   if (prior) unpack_prior(c, slot, f, pass, prior);
   return LFVIO_OK;
@@ -2019,8 +2022,9 @@ int lfvio_batch_optimize_begin(lfvio_ctx *c, int marg_flag, LfvioSolution *sol) 
   }
   f.xs = (const FrameState *)(m + MAIL_X), f.tr = (const TRState *)(m + MAIL_TR);
   f.lam[0] = (const double *)(m + MAIL_LAM), f.lam[1] = (const double *)(m + MAIL_LAM + MAIL_LAM_STRIDE), f.prior = nullptr;
-  if ((rc = check_solution(c, 0, f))) return rc;
-  unpack_solution(c, 0, f, sol);
+  const int cur = f.tr->cur, N = c->info[0].N;
+  if ((rc = check_solution(c, f.tr, (const double *)&f.xs[cur], sizeof(FrameState) / 8, f.lam[cur], N))) return rc;
+  unpack_solution(f.tr, f.xs[cur], f.lam[cur], N, c->info[0].perm.data(), sol);
   return LFVIO_OK;
 }
 

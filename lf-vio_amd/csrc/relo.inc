@@ -9,21 +9,18 @@
 
 namespace {
 
+int relo_refused(lfvio_ctx *c, int rc) {  // (the error text of a shared check, marked as this entry point's)
+  c->err = "lfvio_solve_relo: " + c->err;
+  return rc;
+}
+
 int relo_check(lfvio_ctx *c, const LfvioWindow *in, const LfvioRelo *relo) {
   auto bad = [&](const char *what) {
     c->err = std::string("lfvio_solve_relo: ") + what;
     return LFVIO_ERR_ARG;
   };
-  if (!in || in->num_landmarks < 0 || in->num_observations < 0) return bad("null window / negative sizes");
-  const int N = in->num_landmarks, M = in->num_observations;
-  if (N > 0 && (!in->start_frame || !in->obs_offset || !in->inv_depth || !in->obs_point || !in->obs_velocity || !in->obs_cur_td || !in->obs_uv_y))
-    return bad("null landmark / observation arrays");
-  if (N > 0 && (in->obs_offset[0] != 0 || in->obs_offset[N] != M)) return bad("obs_offset is not a CSR over num_observations");
-  for (int l = 0; l < N; l++) {
-    const int k = in->obs_offset[l + 1] - in->obs_offset[l], s = in->start_frame[l];
-    if (k < 2 || s < 0 || s + k > LFVIO_NUM_FRAMES) return bad("landmark with fewer than 2 observations or a track leaving the window");
-  }
-  if (in->estimate_td && !(in->row > 0.0)) return bad("estimate_td needs row > 0");
+  if (int rc = check_window(c, in)) return relo_refused(c, rc);
+  const int N = in->num_landmarks;
   const LfvioPrior *pr = (in->prior && in->prior->valid) ? in->prior : nullptr;
   if (int rc = check_input_prior(c, pr)) return rc;
   if (!relo) return bad("null relo");
@@ -99,7 +96,7 @@ int relo_route(lfvio_ctx *c, const LfvioWindow *in, const LfvioRelo *relo, Lfvio
   // header
   ReloDev *H = (ReloDev *)h;
   std::memset((void *)H, 0, sizeof(ReloDev));
-  H->N = N, H->M = M, H->K = K, H->R = R;
+  H->N = N, H->M = M, H->K = K, H->R = R, H->max_iter = in->max_num_iterations;
   H->est_ex = in->estimate_extrinsic != 0, H->est_td = in->estimate_td != 0, H->relo_on = K > 0;
   H->prior_n = pn, H->prior_nb = pr ? pr->num_blocks : 0;
   H->row_relo = row_relo, H->row_imu = row_imu, H->row_prior = row_prior;
@@ -151,7 +148,7 @@ int relo_route(lfvio_ctx *c, const LfvioWindow *in, const LfvioRelo *relo, Lfvio
   }
   ReloDev *Dd = (ReloDev *)d;
   HIPCHK(c, hipMemcpyAsync(d, h, L.in_end, hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(k_relo_setup, dim3(1), dim3(64), 0, c->stream, Dd, c->init_radius, c->fn_tol, in->max_num_iterations);
+  hipLaunchKernelGGL(k_relo_setup, dim3(1), dim3(64), 0, c->stream, Dd, c->init_radius, c->fn_tol);
   HIPCHK(c, hipGetLastError());
   const int lm_wgs = (N + RELO_LM_WG - 1) / RELO_LM_WG;
   const bool capped = in->max_solver_time_in_seconds > 0.0;
@@ -184,35 +181,16 @@ int relo_route(lfvio_ctx *c, const LfvioWindow *in, const LfvioRelo *relo, Lfvio
   HIPCHK(c, hipMemcpyAsync(hd.data(), d, sizeof(ReloDev), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const ReloDev *R0 = (const ReloDev *)hd.data();
-  const ReloTR &T = R0->tr;
-  const int cur = T.cur & 1;
+  const TRState *T = &R0->tr;
+  const int cur = T->cur & 1;
   std::vector<double> lam((size_t)std::max(N, 1));
   if (N > 0) {
     HIPCHK(c, hipMemcpyAsync(lam.data(), d + (cur ? L.lam1w : L.lam0w), (size_t)N * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
   const ReloX &x = R0->x[cur];
-  bool finite = std::isfinite(T.x_cost);
-  for (int k = 0; finite && k < (int)(sizeof(ReloX) / 8); k++) finite = std::isfinite(((const double *)&x)[k]);
-  for (int l = 0; finite && l < N; l++) finite = std::isfinite(lam[l]);
-  if (!finite) {
-    c->err = "lfvio_solve_relo: non-finite state";
-    return LFVIO_ERR_NONFINITE;
-  }
-  std::memcpy(out->para_pose, x.f.pose, sizeof x.f.pose);
-  std::memcpy(out->para_speed_bias, x.f.sb, sizeof x.f.sb);
-  std::memcpy(out->para_ex_pose, x.f.ex, sizeof x.f.ex);
-  out->para_td = x.f.td;
-  if (out->inv_depth)
-    for (int l = 0; l < N; l++) out->inv_depth[l] = lam[l];
-  out->num_iterations = T.trace_len;
-  out->num_successful_steps = T.num_succ;
-  out->num_unsuccessful_steps = T.num_unsucc;
-  out->termination = T.term;
-  out->initial_cost = T.initial_cost;
-  out->final_cost = T.x_cost;
-  std::memset(out->trace, 0, sizeof out->trace);
-  for (int k = 0; k < T.trace_len && k < LFVIO_MAX_TRACE; k++) out->trace[k] = T.trace[k];
+  if (int rc = check_solution(c, T, (const double *)&x, sizeof(ReloX) / 8, lam.data(), N)) return relo_refused(c, rc);
+  unpack_solution(T, x.f, lam.data(), N, nullptr, out);
   std::memcpy(relo_pose_out, x.relo, sizeof x.relo);
   return LFVIO_OK;
 }

@@ -28,6 +28,28 @@ DEV TRFlags tr_flags_decided(const Slot *S) {
   return f;
 }
 
+// TrustRegionMinimizer::Init / DoglegStrategy's constructor: the loop header at the start point (k_setup, k_relo_setup)
+DEV void tr_init(TRState *t, double radius, double function_tolerance) {
+  t->radius = radius;
+  t->function_tolerance = function_tolerance;
+  t->mu = 1e-8;
+  t->x_cost = t->cand_cost = t->model_cost_change = t->dogleg_step_norm = t->alpha = 0.0;
+  t->iteration = 0;
+  t->cur = 0;
+  t->do_lin = 1;
+  t->do_schur = 1;
+  t->done = 0;
+  t->termination = LFVIO_NO_CONVERGENCE;
+  t->chol_fail = 0;
+  t->scaled = 0;
+  t->num_succ = t->num_unsucc = t->consec_invalid = t->trace_len = 0;
+  t->step_valid = 0;
+  t->skip_step = 0;
+  t->error = 0;
+  t->new_point = 0;
+  t->spec_n = 1;
+}
+
 struct DecideSums {
   double cost[1 + SPEC_EXTRA], mlin[1 + SPEC_EXTRA], mquad[1 + SPEC_EXTRA], dn[1 + SPEC_EXTRA], xn[1 + SPEC_EXTRA];
 };
