@@ -106,7 +106,8 @@ class Engine:
     def solve_relo(self, win, frame, relo_pose, landmark=(), match_point=()):
         """lfvio_solve_relo: the solve with the relocalization factors of one loop-closure message.  Returns
         (abi.Solution, solved relo pose [p, q xyzw])."""
-        rc_ = abi.Relo(frame, relo_pose, landmark, match_point).c()
+        relo = abi.Relo(frame, relo_pose, landmark, match_point)  # (owns the arrays the ReloC points into: held across the call)
+        rc_ = relo.c()
         sol = abi.Solution(win.N)
         out = np.zeros(abi.SIZE_POSE)
         self._check(self.lib.lfvio_solve_relo(self.ctx, C.byref(win.c()), C.byref(rc_), C.byref(sol.c), _p(out)), "lfvio_solve_relo")

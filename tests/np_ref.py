@@ -45,10 +45,15 @@ def qinv(q):
     return np.array([q[0], -q[1], -q[2], -q[3]]) / np.dot(q, q)
 
 
+def cross3(a, b):
+    """np.cross of two 3-vectors, term for term (a1 b2 - a2 b1, ...: the same roundings) without its axis handling."""
+    return np.array([a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]])
+
+
 def qrot(q, v):
     u = q[1:]
-    uv = 2.0 * np.cross(u, v)
-    return v + q[0] * uv + np.cross(u, uv)
+    uv = 2.0 * cross3(u, v)
+    return v + q[0] * uv + cross3(u, uv)
 
 
 def qR(q):
@@ -96,7 +101,7 @@ def tangent_base(pts_j):
         tmp = np.array([1.0, 0.0, 0.0])
     b1 = tmp - a * (a @ tmp)
     b1 = b1 / np.linalg.norm(b1)
-    b2 = np.cross(a, b1)
+    b2 = cross3(a, b1)
     return np.stack([b1, b2])
 
 

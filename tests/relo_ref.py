@@ -96,8 +96,11 @@ def grad_max_norm(w, st, relo_pose, relo, g):
     return m
 
 
-def solve(w, relo, radius=1e4, function_tolerance=1e-6):
-    """Ceres 1.12 TrustRegionMinimizer + TRADITIONAL_DOGLEG over the augmented state (np_ref.solve, literal)."""
+def solve(w, relo, radius=1e4, function_tolerance=1e-6, cases=None):
+    """Ceres 1.12 TrustRegionMinimizer + TRADITIONAL_DOGLEG over the augmented state (np_ref.solve, literal).
+
+    cases: optional list; every dogleg step appends its case: 0 Gauss-Newton, 1 Cauchy point, 2 interpolation with the
+    beta = (d - c) / |b - a|^2 form (c <= 0), 3 interpolation with the beta = (r^2 - |a|^2) / (d + c) form (c > 0)."""
     act = active_mask(w, relo)
     N = w.N
     x = St(w)
@@ -153,8 +156,10 @@ def solve(w, relo, radius=1e4, function_tolerance=1e-6):
             gnorm, gnn = np.linalg.norm(grad), np.linalg.norm(gn)
             if gnn <= radius:
                 step, dogleg_step_norm = gn.copy(), gnn
+                case = 0
             elif gnorm * alpha >= radius:
                 step, dogleg_step_norm = -(radius / gnorm) * grad, radius
+                case = 1
             else:
                 b_dot_a = -alpha * (grad @ gn)
                 a2 = (alpha * gnorm) ** 2
@@ -162,8 +167,11 @@ def solve(w, relo, radius=1e4, function_tolerance=1e-6):
                 c = b_dot_a - a2
                 d = np.sqrt(c * c + bma2 * (radius ** 2 - a2))
                 beta = (d - c) / bma2 if c <= 0 else (radius * radius - a2) / (d + c)
+                case = 2 if c <= 0 else 3
                 step = (-alpha * (1 - beta)) * grad + beta * gn
                 dogleg_step_norm = np.linalg.norm(step)
+            if cases is not None:
+                cases.append(case)
             step = step / diag
             mr = J @ step
             model_cost_change = -mr @ (r + mr / 2.0)
