@@ -155,8 +155,10 @@ __global__ __launch_bounds__(256) void k_shift_depth(int n, const double *uv_i, 
 //     covariance' = F G + Q                   4 MFMAs   (wave 0, accumulator preloaded with Q)
 // v_mfma_f64_16x16x4_f64 is pipe-bound on gfx950 (64 cycles each, dependent or not: tools/micro/mfma64.hip), which makes
 // the covariance recursion (8 per sample) the critical path: ~0.4 us per sample, 17 us for a 10 x 20-sample window.
-// Results agree with the restatement in oracle/ to ~1e-15 relative (fused multiply-adds and a reciprocal square root in
-// the quaternion normalization differ from it in the last bits); tests/test_preintegration.py holds 1e-12.
+// Against a 50-digit restatement every 3x3 block of jacobian and covariance, delta_p and delta_v are within 3.3e-15 of
+// their own magnitude and delta_q within 7.8e-16 — what the double-precision restatements in oracle/ and numpy reach
+// (another association and a reciprocal square root in the quaternion normalization differ from them in the last bits);
+// tests/test_feature_hp.py holds each block to 16 x the restatements' own error (table in its docstring).
 // ---------------------------------------------------------------------------------------------------------------
 struct ImuJob {
   int n, off;  // samples [off, off + n) of the packed dt / acc / gyr arrays
