@@ -320,6 +320,47 @@ typedef struct {
 } LfvioImuInterval;
 int lfvio_preintegrate(lfvio_ctx *ctx, int num_intervals, const LfvioImuInterval *in, const double noise[4], LfvioPreintegration *out);
 
+/* lfvio_two_view: the two-view step of ESTIMATE_EXTRINSIC == 2 — InitialEXRotation::solveRelativeR for >= 9 matches
+ * (initial/initial_ex_rotation.cpp:157-284; cv::findFundamentalMat and the prints of :226-264 have no effect there and are
+ * not restated).  An 8-point RANSAC on BEARING vectors (rays with z <= 0 are ordinary inputs): per sample set the null
+ * vector of the 8 x 9 epipolar system, projected to rank 2 (compute_E_21, :69-100), scored by check_inliers (:101-155: the
+ * float threshold 0.00872653549837f, a float score taking its double terms in match order); the first hypothesis with the
+ * largest score > 0 wins (:197-202); compute_E_21 again over its inliers and check_inliers again (:204-218: that mask is
+ * the one returned); decomposeE (:321-336) to R1 = U W V^T, R2 = U W^T V^T, t = +-u_2 (proper rotations: the reference
+ * negates E and decomposes again when det R1 = -1, here u_2 and v_2 are the cross products of the other two columns —
+ * the same four candidates; which of the two rotations is called R1 depends on the signs an SVD gives its vectors and is
+ * not pinned); testTriangulation (:289-319, :338-353) of the four candidates in bearing form, IEEE semantics kept (a
+ * null vector with a zero fourth entry gives inf / NaN and the match does not count); R_rel is the return value of
+ * solveRelativeR: ratio1 > ratio2 ? R1 : R2, transposed (:276-284).
+ * The sample sets are an INPUT (the reference draws them from std::random_device, util::create_random_array(8, 0, N - 1)),
+ * which makes the call a function of its arguments.
+ * Deviations from the reference: where no hypothesis scores above 0 the reference reads an uninitialised matrix and
+ * throws from vector::at; where the winner has fewer than 8 inliers its refit is under-determined.  Both return
+ * status = 1 here (best_sample = -1 and num_inliers = 0 in the first case, the winner and its count in the second), and
+ * E, R_cand, t_cand, front, R_rel and the mask are left as the caller had them.
+ * LFVIO_ERR_ARG (outputs untouched): null pointers, num_matches outside [8, 4096], num_samples outside [1, 1024], a sample
+ * index outside [0, num_matches).  Runs on the feature stream like lfvio_triangulate: it does not wait for an
+ * optimization in flight. */
+typedef struct {
+  int num_matches;            /* N, 8 <= N <= 4096 */
+  const double *bearing_l;    /* [N][3] FeaturePerFrame::point of the older frame, as stored (not renormalised) */
+  const double *bearing_r;    /* [N][3] ... of the newer frame */
+  int num_samples;            /* S hypotheses, 1 <= S <= 1024; the reference: 100 */
+  const int *samples;         /* [S][8] indices into the matches */
+} LfvioTwoViewIn;
+typedef struct {
+  int status;                 /* 0 model found; 1 no hypothesis scored > 0 or fewer than 8 inliers */
+  int best_sample;            /* index of the winning hypothesis (first one wins a tie) */
+  int num_inliers;
+  double best_score;          /* of the winning hypothesis, before the refit */
+  double E[9];                /* best_E_21 after the refit on its inliers, row-major, sign free */
+  double R_cand[2][9], t_cand[3]; /* R1, R2 (both proper rotations), t = u_2; the four candidates are (R1|R2, +-t) */
+  double front[4];            /* testTriangulation of (R1,t) (R1,-t) (R2,t) (R2,-t): front_count / N */
+  double R_rel[9];            /* solveRelativeR()'s return value (the chosen candidate, transposed) */
+} LfvioTwoViewOut;
+int lfvio_two_view(lfvio_ctx *ctx, const LfvioTwoViewIn *in, unsigned char *inlier /* [N], after the refit */,
+                   LfvioTwoViewOut *out, double *E_all /* [S][9] or NULL */, float *score_all /* [S] or NULL */);
+
 /* ---- landmark-sharded API (multi-GPU) ------------------------
  * Every rank passes the same window but linearizes only landmarks [lm_begin, lm_end) (caller order);
  * IMU factors and the prior are added on the rank(s) with add_pose_side != 0 — exactly one rank.

@@ -41,6 +41,7 @@ constexpr ncclDataType_t ncclDouble = 8;
 #include "linb_plan.h"
 #include "kernels_stepw.h"
 #include "kernels_relo.h"
+#include "kernels_twoview.h"
 
 #define HIPCHK(ctx, call)                                                                      \
   do {                                                                                         \
@@ -2490,6 +2491,8 @@ int lfvio_debug_query(lfvio_ctx *c, const char *key, double *out, int n) {
 
 // ---- relocalization: lfvio_solve_relo, declared in lfvio.h, implemented in relo.inc
 #include "relo.inc"
+
+#include "twoview.inc"
 // ---- landmark-sharded API: declared in lfvio.h, implemented in shard.inc
 #include "shard.inc"
 // ---- multi-GPU groups (RCCL): declared in lfvio.h, implemented in group.inc

@@ -1,6 +1,7 @@
 // host_capi.cpp — extern "C" driver of the host side (window_estimator.h), so that the Python tests and tools can
 // exercise it the way estimator_node.cpp drives the reference's Estimator.  Frames are addressed by their LOGICAL
 // index 0..10 (oldest..newest); the ring underneath is not visible here.
+#include <algorithm>
 #include <cstring>
 
 #include "replay.h"
@@ -333,6 +334,69 @@ void lfvio_host_get_timers(void *h, double *out6, int reset) {
   }
 }
 int lfvio_host_uses_group(void *h) { return E(h)->group != nullptr; }
+
+// ---- ESTIMATE_EXTRINSIC == 2: the online camera-IMU rotation calibration
+// RANSAC settings of the two-view step (process-wide, like the other parameters); seed 0 = std::random_device
+void lfvio_host_set_ransac(unsigned seed, int iterations) { config().ransac_seed = seed, config().ransac_iterations = iterations; }
+// the process-wide mode and configured extrinsic as they are NOW (a successful calibration rewrites both)
+int lfvio_host_get_estimate_extrinsic(void) { return config().estimate_extrinsic; }
+void lfvio_host_set_estimate_extrinsic(int mode) { config().estimate_extrinsic = mode; }
+void lfvio_host_get_extrinsic(double *tic, double *ric) {
+  std::memcpy(tic, config().tic, sizeof config().tic);
+  std::memcpy(ric, config().ric, sizeof config().ric);
+}
+// CalibrationExRotation alone, no device: Rc row-major, delta_q = (x, y, z, w); ric_out[9], sv_out[4]; returns 1 on success
+int lfvio_host_exrot_push(void *h, const double *Rc, const double *delta_q, double *ric_out, double *sv_out) {
+  ExRotationCalibrator &x = E(h)->exrot;
+  Matrix3d R, calib;
+  setM(R, Rc);
+  const bool ok = x.push(R, Quaterniond(delta_q[3], delta_q[0], delta_q[1], delta_q[2]), &calib);
+  getM(x.ric, ric_out);
+  std::memcpy(sv_out, x.sv, sizeof x.sv);
+  return ok ? 1 : 0;
+}
+// frame_count of the calibrator; its ric and last singular values
+int lfvio_host_exrot_state(void *h, double *ric_out, double *sv_out) {
+  const ExRotationCalibrator &x = E(h)->exrot;
+  getM(x.ric, ric_out);
+  std::memcpy(sv_out, x.sv, sizeof x.sv);
+  return x.frame_count;
+}
+void lfvio_host_exrot_clear(void *h) { E(h)->exrot.clear(); }
+// the pair the last push added: Rc (solveRelativeR's return value) and Rimu (delta_q as a matrix), row-major
+void lfvio_host_exrot_last(void *h, double *Rc, double *Rimu) {
+  const ExRotationCalibrator &x = E(h)->exrot;
+  getM(x.Rc.back(), Rc), getM(x.Rimu.back(), Rimu);
+}
+// What the last image of mode 2 handed to lfvio_two_view: counts[2] = {matches, sample sets (0: fewer than 9 matches, no device
+// call)}; the arrays (any may be null) take at most cap_matches matches / cap_samples sets.  Returns the number of device calls so far.
+long long lfvio_host_last_two_view(void *h, int cap_matches, int cap_samples, int *counts, double *bl, double *br, int *samples,
+                                   unsigned char *mask, LfvioTwoViewOut *out) {
+  const WindowEstimator::LastTwoView &t = E(h)->last_two_view;
+  const int N = (int)t.bl.size() / 3, S = t.called ? (int)t.samples.size() / 8 : 0;
+  counts[0] = N, counts[1] = S;
+  const size_t n = (size_t)std::min(N, cap_matches), s = (size_t)std::min(S, cap_samples);
+  if (bl && n) std::memcpy(bl, t.bl.data(), n * 24);
+  if (br && n) std::memcpy(br, t.br.data(), n * 24);
+  if (samples && s) std::memcpy(samples, t.samples.data(), s * 32);
+  if (mask && n && t.called) std::memcpy(mask, t.mask.data(), n);
+  if (out && t.called) *out = t.out;
+  return E(h)->two_view_calls;
+}
+long long lfvio_host_two_view_calls(void *h) { return E(h)->two_view_calls; }
+// getCorresponding(l, r): bl, br [cap][3]; returns the number of matches
+int lfvio_host_corresponding(void *h, int l, int r, int cap, double *bl, double *br) {
+  std::vector<double> a, b;
+  const int n = E(h)->tracks.corresponding(l, r, &a, &b);
+  const size_t k = (size_t)std::min(n, cap);
+  if (k) std::memcpy(bl, a.data(), k * 24), std::memcpy(br, b.data(), k * 24);
+  return n;
+}
+// util::create_random_array(8, 0, n - 1), `count` sets from a generator seeded with `seed`
+void lfvio_host_draw_samples(unsigned seed, int n, int count, int *out) {
+  std::mt19937 rng(seed);
+  for (int k = 0; k < count; k++) drawSampleSet(rng, n, out + 8 * k);
+}
 
 int lfvio_host_optimization(void *h) {
   WindowEstimator *e = E(h);

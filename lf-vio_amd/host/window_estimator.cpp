@@ -4,10 +4,13 @@
 // the tests, oracle/abi_shim.cpp); there optimization() with a relocalization message reports LFVIO_ERR_DEVICE instead of loading
 // with an unresolved symbol.
 #pragma weak lfvio_solve_relo
+// ... nor a two-view entry point: there ESTIMATE_EXTRINSIC == 2 reports LFVIO_ERR_DEVICE on the first image that needs it.
+#pragma weak lfvio_two_view
 
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <functional>
 #include <numeric>
 
 namespace lfvio {
@@ -96,6 +99,16 @@ void TrackTable::append(int s, const double *pt8, double cur_td) {
   std::memcpy(r, pt8, 8 * sizeof(double));
   r[8] = cur_td;
   count_[s]++;
+}
+
+int TrackTable::corresponding(int l, int r, std::vector<double> *bl, std::vector<double> *br) const {  // feature_manager.cpp:118-137
+  bl->clear(), br->clear();
+  for (int s : order_) {
+    if (!(start_[s] <= l && start_[s] + count_[s] - 1 >= r)) continue;
+    const double *a = obs(s, l - start_[s]), *b = obs(s, r - start_[s]);
+    bl->insert(bl->end(), a, a + 3), br->insert(br->end(), b, b + 3);
+  }
+  return (int)bl->size() / 3;
 }
 
 int TrackTable::appendFrame(int frame_count, int n, const int *ids, const double *pts8, double td) {
@@ -336,9 +349,191 @@ bool WindowEstimator::applyBootstrap() {
   return true;
 }
 
+// ---------------------------------------------------------------------------------------------------- ExRotationCalibrator
+namespace {
+
+Matrix3d inverse3(const Matrix3d &a) {  // by the adjugate
+  Matrix3d r;
+  r(0, 0) = a(1, 1) * a(2, 2) - a(1, 2) * a(2, 1), r(0, 1) = a(0, 2) * a(2, 1) - a(0, 1) * a(2, 2), r(0, 2) = a(0, 1) * a(1, 2) - a(0, 2) * a(1, 1);
+  r(1, 0) = a(1, 2) * a(2, 0) - a(1, 0) * a(2, 2), r(1, 1) = a(0, 0) * a(2, 2) - a(0, 2) * a(2, 0), r(1, 2) = a(0, 2) * a(1, 0) - a(0, 0) * a(1, 2);
+  r(2, 0) = a(1, 0) * a(2, 1) - a(1, 1) * a(2, 0), r(2, 1) = a(0, 1) * a(2, 0) - a(0, 0) * a(2, 1), r(2, 2) = a(0, 0) * a(1, 1) - a(0, 1) * a(1, 0);
+  const double det = a(0, 0) * r(0, 0) + a(0, 1) * r(1, 0) + a(0, 2) * r(2, 0);
+  return (1.0 / det) * r;
+}
+
+double angularDistance(const Quaterniond &a, const Quaterniond &b) {  // Eigen: 2 atan2(|vec|, |w|) of a * conj(b)
+  const Quaterniond d = a * Quaterniond(b.w(), -b.x(), -b.y(), -b.z());
+  return 2.0 * std::atan2(d.vec().norm(), std::abs(d.w()));
+}
+
+// singular values (falling) and right singular vectors of an m x 4 matrix (row-major, overwritten): one-sided Jacobi
+void svd4(std::vector<double> &A, int m, double sv[4], double V[4][4]) {
+  for (int i = 0; i < 4; i++)
+    for (int j = 0; j < 4; j++) V[i][j] = i == j;
+  for (int sweep = 0; sweep < 60; sweep++) {
+    bool rotated = false;
+    for (int p = 0; p < 3; p++)
+      for (int q = p + 1; q < 4; q++) {
+        double al = 0, be = 0, ga = 0;
+        for (int r = 0; r < m; r++) {
+          const double x = A[4 * r + p], y = A[4 * r + q];
+          al += x * x, be += y * y, ga += x * y;
+        }
+        if (ga == 0.0 || std::abs(ga) <= 2.3e-16 * std::sqrt(al * be)) continue;
+        rotated = true;
+        const double zeta = (be - al) / (2.0 * ga);
+        const double t = (zeta >= 0 ? 1.0 : -1.0) / (std::abs(zeta) + std::sqrt(1.0 + zeta * zeta));
+        const double c = 1.0 / std::sqrt(1.0 + t * t), s = c * t;
+        for (int r = 0; r < m; r++) {
+          const double x = A[4 * r + p], y = A[4 * r + q];
+          A[4 * r + p] = c * x - s * y, A[4 * r + q] = s * x + c * y;
+        }
+        for (int r = 0; r < 4; r++) {
+          const double x = V[r][p], y = V[r][q];
+          V[r][p] = c * x - s * y, V[r][q] = s * x + c * y;
+        }
+      }
+    if (!rotated) break;
+  }
+  double n[4];
+  int order[4] = {0, 1, 2, 3};
+  for (int c = 0; c < 4; c++) {
+    double s = 0;
+    for (int r = 0; r < m; r++) s += A[4 * r + c] * A[4 * r + c];
+    n[c] = std::sqrt(s);
+  }
+  std::stable_sort(order, order + 4, [&](int a, int b) { return n[a] > n[b]; });
+  double Vs[4][4];
+  for (int c = 0; c < 4; c++) {
+    sv[c] = n[order[c]];
+    for (int r = 0; r < 4; r++) Vs[r][c] = V[r][order[c]];
+  }
+  std::memcpy(V, Vs, sizeof Vs);
+}
+
+}  // namespace
+
+void ExRotationCalibrator::clear() {  // initial_ex_rotation.cpp:4-11
+  frame_count = 0;
+  Rc.assign(1, Matrix3d::Identity()), Rimu.assign(1, Matrix3d::Identity()), Rc_g.assign(1, Matrix3d::Identity());
+  ric.setIdentity();
+  sv[0] = sv[1] = sv[2] = sv[3] = 0;
+}
+
+bool ExRotationCalibrator::push(const Matrix3d &Rc_new, const Quaterniond &delta_q, Matrix3d *calib_ric) {  // :13-67
+  frame_count++;
+  Rc.push_back(Rc_new);
+  Rimu.push_back(delta_q.toRotationMatrix());
+  Rc_g.push_back(inverse3(ric) * delta_q.toRotationMatrix() * ric);
+  std::vector<double> A((size_t)frame_count * 16, 0.0);
+  for (int i = 1; i <= frame_count; i++) {
+    const Quaterniond r1(Rc[i]), r2(Rc_g[i]);
+    const double angular_distance = 180.0 / M_PI * angularDistance(r1, r2);
+    const double huber = angular_distance > 5.0 ? 5.0 / angular_distance : 1.0;
+    double L[4][4], R[4][4];
+    auto fill = [](double M[4][4], double w, const Vector3d &q, double sgn) {  // w I +- [q]x | q ; -q^T | w
+      const double sk[3][3] = {{0, -q.z(), q.y()}, {q.z(), 0, -q.x()}, {-q.y(), q.x(), 0}};
+      for (int a = 0; a < 3; a++) {
+        for (int b = 0; b < 3; b++) M[a][b] = (a == b ? w : 0.0) + sgn * sk[a][b];
+        M[a][3] = q(a), M[3][a] = -q(a);
+      }
+      M[3][3] = w;
+    };
+    fill(L, r1.w(), r1.vec(), 1.0);
+    const Quaterniond R_ij(Rimu[i]);
+    fill(R, R_ij.w(), R_ij.vec(), -1.0);
+    for (int a = 0; a < 4; a++)
+      for (int b = 0; b < 4; b++) A[(size_t)(i - 1) * 16 + 4 * a + b] = huber * (L[a][b] - R[a][b]);
+  }
+  double V[4][4];
+  svd4(A, 4 * frame_count, sv, V);
+  const Quaterniond estimated_R(V[3][3], V[0][3], V[1][3], V[2][3]);  // x = V.col(3) holds (x, y, z, w)
+  ric = inverse3(estimated_R.toRotationMatrix());
+  if (frame_count >= WINDOW_SIZE && sv[2] > 0.25) {
+    *calib_ric = ric;
+    return true;
+  }
+  return false;
+}
+
+void drawSampleSet(std::mt19937 &rng, int n, int out[8]) {
+  std::uniform_int_distribution<int> dist(0, n - 1);
+  const size_t size = 8, make_size = 9;  // static_cast<size_t>(8 * 1.2)
+  std::vector<int> v;
+  v.reserve(make_size);
+  while (v.size() != size) {
+    while (v.size() < make_size) v.push_back(dist(rng));
+    std::sort(v.begin(), v.end());
+    auto unique_end = std::unique(v.begin(), v.end());
+    if (size < (size_t)std::distance(v.begin(), unique_end)) unique_end = std::next(v.begin(), size);
+    v.erase(unique_end, v.end());
+  }
+  std::shuffle(v.begin(), v.end(), rng);
+  std::copy(v.begin(), v.end(), out);
+}
+
+int WindowEstimator::calibrateExtrinsicRotation() {  // estimator.cpp:142-159
+  Config &c = config();
+  status = LFVIO_OK;
+  if (!refreshSpans(false)) return status != LFVIO_OK ? status : LFVIO_ERR_DEVICE;
+  const LfvioPreintegration &pre = span(frame_count).pre;
+  const Quaterniond delta_q(pre.delta_q[3], pre.delta_q[0], pre.delta_q[1], pre.delta_q[2]);
+  LastTwoView &tv = last_two_view;
+  const int N = tracks.corresponding(frame_count - 1, frame_count, &tv.bl, &tv.br);
+  tv.called = false;
+  tv.samples.clear(), tv.mask.assign((size_t)N, 0);
+  Matrix3d Rc = Matrix3d::Identity();  // fewer than 9 matches (initial_ex_rotation.cpp:223, :286)
+  if (N >= 9) {
+    if (!lfvio_two_view || !device()) return LFVIO_ERR_DEVICE;  // no fallback: without the device entry the mode cannot run
+    if (!ransac_seeded_ || ransac_seed_used_ != c.ransac_seed) {
+      if (c.ransac_seed != 0) {
+        ransac_rng_.seed(c.ransac_seed);
+      } else {  // random_array.cc:12-19
+        std::random_device rd;
+        std::vector<std::uint_least32_t> v(10);
+        std::generate(v.begin(), v.end(), std::ref(rd));
+        std::seed_seq seq(v.begin(), v.end());
+        ransac_rng_.seed(seq);
+      }
+      ransac_seeded_ = true, ransac_seed_used_ = c.ransac_seed;
+    }
+    const int S = std::max(1, c.ransac_iterations);
+    tv.samples.resize((size_t)S * 8);
+    for (int k = 0; k < S; k++) drawSampleSet(ransac_rng_, N, &tv.samples[(size_t)8 * k]);
+    LfvioTwoViewIn in;
+    in.num_matches = N, in.bearing_l = tv.bl.data(), in.bearing_r = tv.br.data(), in.num_samples = S, in.samples = tv.samples.data();
+    std::memset(&tv.out, 0, sizeof tv.out);
+    const int rc = lfvio_two_view(gpu, &in, tv.mask.data(), &tv.out, nullptr, nullptr);
+    two_view_calls++;
+    tv.called = true;
+    if (rc != LFVIO_OK) return rc;
+    if (tv.out.status == 0)  // status 1 (no model; include/lfvio.h): Rc = I, as for too few matches
+      for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) Rc(i, j) = tv.out.R_rel[3 * i + j];
+  }
+  Matrix3d calib_ric;
+  if (exrot.push(Rc, delta_q, &calib_ric)) {
+    ric = calib_ric;  // ric[0] = calib_ric; RIC[0] = calib_ric; ESTIMATE_EXTRINSIC = 1
+    for (int i = 0; i < 3; i++)
+      for (int j = 0; j < 3; j++) c.ric[3 * i + j] = calib_ric(i, j);
+    c.estimate_extrinsic = 1;
+  }
+  return LFVIO_OK;
+}
+
 void WindowEstimator::pushImage(double stamp, int n, const int *ids, const double *pts8) {  // estimator.cpp:122-220
   marg_flag = keyframeTest(frame_count, n, ids, pts8, td) ? LFVIO_MARGIN_OLD : LFVIO_MARGIN_SECOND_NEW;
   kf(frame_count).stamp = stamp;
+  if (config().estimate_extrinsic == 2 && frame_count != 0) {
+    const int calib = calibrateExtrinsicRotation();
+    advanceWindow(stamp);
+    if (calib != LFVIO_OK) status = calib;
+    return;
+  }
+  advanceWindow(stamp);
+}
+
+void WindowEstimator::advanceWindow(double stamp) {  // estimator.cpp:161-220
   auto remember = [&] { last_R = kf(WINDOW_SIZE).R, last_P = kf(WINDOW_SIZE).P, last_R0 = kf(0).R, last_P0 = kf(0).P; };
   if (phase == INITIAL) {
     if (frame_count < WINDOW_SIZE) {

@@ -18,6 +18,7 @@
 // and INTEGRATION.md maps the reference's members onto it.
 #pragma once
 #include <chrono>
+#include <random>
 #include <unordered_map>
 #include <vector>
 
@@ -56,6 +57,11 @@ struct Config {
   // marginalization without waiting for it, the prior never crosses PCIe.  The host's copy (`prior`) is then only refreshed when
   // something asks for it (collectPrior()).  false: the upload collects the prior and sends it back up (lfvio_batch_upload_chained).
   bool device_chain = true;
+  // ESTIMATE_EXTRINSIC == 2: the two-view RANSAC of every image draws `ransac_iterations` sample sets (the reference: 100,
+  // initial_ex_rotation.cpp:171).  ransac_seed == 0 seeds the generator from std::random_device like the reference
+  // (random_array.cc:12-19); any other value makes the draws, and with them the calibration, reproducible.
+  int ransac_iterations = 100;
+  unsigned ransac_seed = 0;
 };
 Config &config();
 
@@ -117,6 +123,9 @@ class TrackTable {
   int create(int feature_id, int start_frame);
   void append(int s, const double *pt8, double cur_td);
 
+  // getCorresponding (feature_manager.cpp:118-137): the bearings of every track seen in both frames l and r, list order;
+  // bl / br receive 3 doubles per match; returns the number of matches
+  int corresponding(int l, int r, std::vector<double> *bl, std::vector<double> *br) const;
   // feature_manager.cpp:45-95: the frame's observations (ids ascending, first occurrence of an id wins) are appended;
   // returns the number of continued tracks
   int appendFrame(int frame_count, int n, const int *ids, const double *pts8, double td);
@@ -144,6 +153,25 @@ class TrackTable {
   std::unordered_map<int, int> slot_of_;
   bool holes_ = false;
 };
+
+// InitialEXRotation (initial/initial_ex_rotation.h): the state of the online camera-IMU rotation calibration and
+// CalibrationExRotation (initial_ex_rotation.cpp:13-67).  The relative camera rotation of every image (solveRelativeR) comes
+// from the device (lfvio_two_view); what is left is one 4F x 4 singular value problem per image, F <= a few hundred.
+struct ExRotationCalibrator {
+  int frame_count = 0;
+  std::vector<Matrix3d> Rc, Rimu, Rc_g;
+  Matrix3d ric;
+  double sv[4] = {0, 0, 0, 0};  // singular values of the last stack, falling
+  ExRotationCalibrator() { clear(); }
+  void clear();
+  // one image: Rc = solveRelativeR's return value, delta_q = the span's pre-integrated rotation.  true (and *calib_ric) when
+  // frame_count >= WINDOW_SIZE and the third-largest singular value exceeds 0.25 (:60)
+  bool push(const Matrix3d &Rc_new, const Quaterniond &delta_q, Matrix3d *calib_ric);
+};
+
+// util::create_random_array(8, 0, n - 1) (initial/random_array.cc:22-49): 9 draws, sorted, made unique, cut to 8, drawn again
+// until there are 8, shuffled
+void drawSampleSet(std::mt19937 &rng, int n, int out[8]);
 
 class WindowEstimator {
  public:
@@ -187,6 +215,19 @@ class WindowEstimator {
   void triangulate();
   void reanchorDepths(const Matrix3d &old_R, const Vector3d &old_P, const Matrix3d &new_R, const Vector3d &new_P,
                       const std::vector<TrackTable::Shifted> &tracks);
+  // ESTIMATE_EXTRINSIC == 2 (estimator.cpp:142-159): the newest span's delta_q, lfvio_two_view on the matches of the two
+  // newest frames, the calibrator; on success ric and the CONFIGURED ric become the calibrated one and the mode becomes 1.
+  // Returns the status of the device calls.
+  int calibrateExtrinsicRotation();
+  ExRotationCalibrator exrot;
+  struct LastTwoView {  // what the last image handed to lfvio_two_view and got back (tests, tools)
+    std::vector<double> bl, br;
+    std::vector<int> samples;
+    std::vector<unsigned char> mask;
+    LfvioTwoViewOut out;
+    bool called = false;  // false: fewer than 9 matches, Rc = I without a device call
+  } last_two_view;
+  long long two_view_calls = 0;
   bool refreshSpans(bool all, const Vector3d *ba = nullptr, const Vector3d *bg = nullptr);  // device pre-integration of dirty spans
   void pack(LfvioWindow *w);
 
@@ -238,6 +279,10 @@ class WindowEstimator {
   bool prior_on_device_ = false;  // the resident window took its prior over on the device (lfvio_batch_upload_chained_device): `prior` is stale
   bool device();
   bool applyBootstrap();
+  void advanceWindow(double stamp);  // processImage() behind the keyframe test and the calibration (estimator.cpp:161-220)
+  std::mt19937 ransac_rng_;
+  bool ransac_seeded_ = false;
+  unsigned ransac_seed_used_ = 0;
   void optimizationRelo();  // optimization() with relocalization_info set: lfvio_solve_relo, double2vector(), lfvio_marginalize
   std::vector<int> relo_lm_;
   std::vector<double> relo_xy_;

@@ -371,6 +371,38 @@ class TriangulateIn:
         self.c = c
 
 
+class TwoViewInC(C.Structure):
+    """LfvioTwoViewIn (include/lfvio.h)."""
+    _fields_ = [
+        ("num_matches", C.c_int),
+        ("bearing_l", C.POINTER(C.c_double)),
+        ("bearing_r", C.POINTER(C.c_double)),
+        ("num_samples", C.c_int),
+        ("samples", C.POINTER(C.c_int)),
+    ]
+
+
+class TwoViewOutC(C.Structure):
+    """LfvioTwoViewOut (include/lfvio.h)."""
+    _fields_ = [
+        ("status", C.c_int),
+        ("best_sample", C.c_int),
+        ("num_inliers", C.c_int),
+        ("best_score", C.c_double),
+        ("E", C.c_double * 9),
+        ("R_cand", (C.c_double * 9) * 2),
+        ("t_cand", C.c_double * 3),
+        ("front", C.c_double * 4),
+        ("R_rel", C.c_double * 9),
+    ]
+
+    def as_dict(self):
+        a = lambda x: np.array(x, dtype=np.float64)
+        return dict(status=int(self.status), best_sample=int(self.best_sample), num_inliers=int(self.num_inliers),
+                    best_score=float(self.best_score), E=a(self.E), R_cand=np.array([list(self.R_cand[0]), list(self.R_cand[1])]).reshape(2, 3, 3),
+                    t_cand=a(self.t_cand), front=a(self.front), R_rel=a(self.R_rel).reshape(3, 3))
+
+
 HIP_SYMBOLS = [
     "lfvio_create", "lfvio_destroy", "lfvio_last_error", "lfvio_version", "lfvio_solve", "lfvio_solve_relo", "lfvio_marginalize",
     "lfvio_batch_reserve", "lfvio_batch_upload", "lfvio_batch_optimize", "lfvio_batch_optimize_async",
@@ -379,6 +411,7 @@ HIP_SYMBOLS = [
     "lfvio_shard_begin", "lfvio_shard_exchange_len", "lfvio_shard_scalar_offset", "lfvio_shard_exchange_ptr", "lfvio_shard_linearize",
     "lfvio_shard_solve", "lfvio_shard_candidate", "lfvio_shard_decide", "lfvio_shard_marg_linearize", "lfvio_shard_marg_finish",
     "lfvio_shard_finish", "lfvio_shard_restart", "lfvio_shard_enqueue", "lfvio_shard_poll", "lfvio_triangulate", "lfvio_shift_depth", "lfvio_preintegrate",
+    "lfvio_two_view",
     "lfvio_group_create", "lfvio_group_unique_id", "lfvio_group_create_rank", "lfvio_group_create_local", "lfvio_group_destroy",
     "lfvio_group_last_error", "lfvio_group_size", "lfvio_group_local", "lfvio_group_rank", "lfvio_group_ctx", "lfvio_group_backend",
     "lfvio_group_solve", "lfvio_group_upload", "lfvio_group_optimize", "lfvio_group_download", "lfvio_group_range",
@@ -442,6 +475,7 @@ def load_hip_library(path=None):
     lib.lfvio_triangulate.argtypes = [C.c_void_p, C.POINTER(TriangulateInC), _dp]
     lib.lfvio_shift_depth.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp, C.c_double, _dp]
     lib.lfvio_preintegrate.argtypes = [C.c_void_p, C.c_int, C.POINTER(ImuIntervalC), _dp, C.POINTER(Preintegration)]
+    lib.lfvio_two_view.argtypes = [C.c_void_p, C.POINTER(TwoViewInC), C.POINTER(C.c_ubyte), C.POINTER(TwoViewOutC), _dp, C.POINTER(C.c_float)]
     lib.lfvio_shard_marg_linearize.argtypes = [C.c_void_p, C.c_int]
     lib.lfvio_shard_marg_finish.argtypes = [C.c_void_p, C.c_int, C.POINTER(Prior)]
     # multi-GPU groups (RCCL inside the library)

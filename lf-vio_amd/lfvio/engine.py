@@ -244,6 +244,32 @@ class Engine:
         self._check(self.lib.lfvio_preintegrate(self.ctx, K, arr, _p(nz), out), "lfvio_preintegrate")
         return [out[k] for k in range(K)]
 
+    def two_view(self, bl, br, samples, all_hypotheses=False, out=None, inlier=None, check=True):
+        """lfvio_two_view: the two-view RANSAC of ESTIMATE_EXTRINSIC == 2 on bearing pairs bl, br [N, 3] and sample sets
+        [S, 8].  Returns the fields of LfvioTwoViewOut as a dict, plus `mask` and, with all_hypotheses, `E_all` [S, 9] and
+        `score_all` [S].  out / inlier: a TwoViewOutC / uint8 array to be written (a test of what a failed call leaves
+        alone passes its own); check=False returns the error code under `rc` instead of raising."""
+        bl = np.ascontiguousarray(bl, dtype=np.float64).reshape(-1, 3)
+        br = np.ascontiguousarray(br, dtype=np.float64).reshape(-1, 3)
+        sm = np.ascontiguousarray(samples, dtype=np.int32).reshape(-1, 8)
+        tin = abi.TwoViewInC()
+        tin.num_matches, tin.num_samples = len(bl), len(sm)
+        tin.bearing_l, tin.bearing_r, tin.samples = _p(bl), _p(br), sm.ctypes.data_as(C.POINTER(C.c_int))
+        out = abi.TwoViewOutC() if out is None else out
+        mask = np.zeros(len(bl), dtype=np.uint8) if inlier is None else inlier
+        E_all = np.zeros((len(sm), 9)) if all_hypotheses else None
+        score_all = np.zeros(len(sm), dtype=np.float32) if all_hypotheses else None
+        rc = self.lib.lfvio_two_view(self.ctx, C.byref(tin), mask.ctypes.data_as(C.POINTER(C.c_ubyte)), C.byref(out),
+                                     _p(E_all) if all_hypotheses else None,
+                                     score_all.ctypes.data_as(C.POINTER(C.c_float)) if all_hypotheses else None)
+        if check:
+            self._check(rc, "lfvio_two_view")
+        res = out.as_dict()
+        res.update(rc=rc, mask=mask)
+        if all_hypotheses:
+            res.update(E_all=E_all, score_all=score_all)
+        return res
+
     def time_kernel(self, which, count, reps):
         ms = np.zeros(1)
         self._check(self.lib.lfvio_debug_time_kernel(self.ctx, which, count, reps, _p(ms)), "time_kernel")

@@ -279,6 +279,97 @@ class HostEstimator:
         K = self.L.lfvio_host_relo_matches(self.h, cap, lm.ctypes.data_as(C.POINTER(C.c_int)), _p(xy))
         return lm[:min(K, cap)].copy(), xy[:min(K, cap)].copy()
 
+    # ---- ESTIMATE_EXTRINSIC == 2: the online camera-IMU rotation calibration (estimator.cpp:142-159, initial_ex_rotation.cpp)
+    def set_params(self, p9, estimate_extrinsic, estimate_td, num_iterations):
+        """The process-wide parameters: p9 = ACC_N, GYR_N, ACC_W, GYR_W, g, TR, ROW, SOLVER_TIME, TD."""
+        self.L.lfvio_host_set_params(_p(_f(p9)), int(estimate_extrinsic), int(estimate_td), int(num_iterations))
+
+    def set_extrinsic(self, tic, ric):
+        """The CONFIGURED extrinsic (what a reset restores)."""
+        self.L.lfvio_host_set_extrinsic.argtypes = [_dp, _dp]
+        self.L.lfvio_host_set_extrinsic(_p(_f(tic)), _p(_f(ric).reshape(9)))
+
+    def get_extrinsic(self):
+        tic, ric = np.zeros(3), np.zeros(9)
+        self.L.lfvio_host_get_extrinsic.argtypes = [_dp, _dp]
+        self.L.lfvio_host_get_extrinsic(_p(tic), _p(ric))
+        return tic, ric.reshape(3, 3)
+
+    def estimate_extrinsic(self):
+        return int(self.L.lfvio_host_get_estimate_extrinsic())
+
+    def set_estimate_extrinsic(self, mode):
+        self.L.lfvio_host_set_estimate_extrinsic.argtypes = [C.c_int]
+        self.L.lfvio_host_set_estimate_extrinsic(int(mode))
+
+    def exrot_last(self):
+        """The pair the calibrator's last push added -> (Rc, Rimu)."""
+        a, b = np.zeros(9), np.zeros(9)
+        self.L.lfvio_host_exrot_last.argtypes = [C.c_void_p, _dp, _dp]
+        self.L.lfvio_host_exrot_last(self.h, _p(a), _p(b))
+        return a.reshape(3, 3), b.reshape(3, 3)
+
+    def set_ransac(self, seed, iterations=100):
+        self.L.lfvio_host_set_ransac.argtypes = [C.c_uint, C.c_int]
+        self.L.lfvio_host_set_ransac(int(seed), int(iterations))
+
+    def set_ric(self, ric):
+        """The estimator's current ric alone (through lfvio_host_set_state, everything else as it is)."""
+        s = self.state()
+        self.L.lfvio_host_set_state(self.h, _p(_f(s["Ps"])), _p(_f(s["Rs"])), _p(_f(s["Vs"])), _p(_f(s["Bas"])), _p(_f(s["Bgs"])),
+                                    _p(_f(s["tic"])), _p(_f(ric).reshape(9)), s["td"])
+
+    def exrot_push(self, Rc, delta_q_xyzw):
+        """CalibrationExRotation alone (no device) -> (success, ric [3, 3], singular values [4])."""
+        ric, sv = np.zeros(9), np.zeros(4)
+        self.L.lfvio_host_exrot_push.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp]
+        ok = self.L.lfvio_host_exrot_push(self.h, _p(_f(Rc).reshape(9)), _p(_f(delta_q_xyzw)), _p(ric), _p(sv))
+        return bool(ok), ric.reshape(3, 3), sv
+
+    def exrot_state(self):
+        """-> (frame_count, ric, singular values) of the calibrator."""
+        ric, sv = np.zeros(9), np.zeros(4)
+        self.L.lfvio_host_exrot_state.argtypes = [C.c_void_p, _dp, _dp]
+        n = self.L.lfvio_host_exrot_state(self.h, _p(ric), _p(sv))
+        return int(n), ric.reshape(3, 3), sv
+
+    def exrot_clear(self):
+        self.L.lfvio_host_exrot_clear.argtypes = [C.c_void_p]
+        self.L.lfvio_host_exrot_clear(self.h)
+
+    def two_view_calls(self):
+        self.L.lfvio_host_two_view_calls.argtypes = [C.c_void_p]
+        self.L.lfvio_host_two_view_calls.restype = C.c_longlong
+        return int(self.L.lfvio_host_two_view_calls(self.h))
+
+    def last_two_view(self, cap_matches=4096, cap_samples=1024):
+        """What the last image of mode 2 handed to lfvio_two_view and got back: dict(bl, br, samples, mask, out (the fields of
+        LfvioTwoViewOut, None without a device call), calls)."""
+        cnt = np.zeros(2, dtype=np.int32)
+        bl, br = np.zeros((cap_matches, 3)), np.zeros((cap_matches, 3))
+        sm, mask, out = np.zeros((cap_samples, 8), dtype=np.int32), np.zeros(cap_matches, dtype=np.uint8), abi.TwoViewOutC()
+        ip = C.POINTER(C.c_int)
+        self.L.lfvio_host_last_two_view.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, _dp, _dp, ip, C.POINTER(C.c_ubyte), C.POINTER(abi.TwoViewOutC)]
+        self.L.lfvio_host_last_two_view.restype = C.c_longlong
+        calls = self.L.lfvio_host_last_two_view(self.h, cap_matches, cap_samples, cnt.ctypes.data_as(ip), _p(bl), _p(br), sm.ctypes.data_as(ip),
+                                                mask.ctypes.data_as(C.POINTER(C.c_ubyte)), C.byref(out))
+        N, S = int(cnt[0]), int(cnt[1])
+        return dict(bl=bl[:N].copy(), br=br[:N].copy(), samples=sm[:S].copy(), mask=mask[:N].copy(), out=out.as_dict() if S else None, calls=int(calls))
+
+    def corresponding(self, l, r, cap=4096):
+        """FeatureManager::getCorresponding(l, r) -> (bl [n, 3], br [n, 3])."""
+        bl, br = np.zeros((cap, 3)), np.zeros((cap, 3))
+        self.L.lfvio_host_corresponding.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, _dp]
+        n = self.L.lfvio_host_corresponding(self.h, int(l), int(r), cap, _p(bl), _p(br))
+        return bl[:n].copy(), br[:n].copy()
+
+    def draw_samples(self, seed, n, count):
+        """util::create_random_array(8, 0, n - 1), `count` times from std::mt19937(seed) -> [count, 8]."""
+        o = np.zeros((count, 8), dtype=np.int32)
+        self.L.lfvio_host_draw_samples.argtypes = [C.c_uint, C.c_int, C.c_int, C.POINTER(C.c_int)]
+        self.L.lfvio_host_draw_samples(int(seed), int(n), int(count), o.ctypes.data_as(C.POINTER(C.c_int)))
+        return o
+
     def set_split_call(self, on):
         self.L.lfvio_host_set_split_call(int(on))
 

@@ -186,7 +186,7 @@ class Trajectory:
     motion: "full"; "rotate" (no translation: every baseline is zero, depth is unobservable); "static" (camera at rest).
     The random draws are the same for every motion, so a seed names one scene family."""
 
-    def __init__(self, rng, n_keyframes, motion="full"):
+    def __init__(self, rng, n_keyframes, motion="full", w_scale=1.0):
         self.n_kf = n_keyframes
         n_s = (n_keyframes - 1) * SAMPLES + 1
         self.t = np.arange(n_s) * IMU_DT
@@ -201,6 +201,8 @@ class Trajectory:
         wph = rng.uniform(0, 2 * np.pi, size=(3, 2))
         if motion == "static":
             wamp = wamp * 0.0
+        if w_scale != 1.0:  # angular-rate factor: the online extrinsic calibration needs rotation (estimator.cpp:144)
+            wamp = wamp * float(w_scale)
         self._wa = (wamp, wfrq, wph)
         # integrate attitude with 10 sub-steps per IMU sample
         R = exp_so3(rng.normal(0, 0.2, 3))
@@ -255,10 +257,10 @@ def _bearing_f32(v):
 class Scene:
     """Truth trajectory of `n_total` keyframes with IMU measurements."""
 
-    def __init__(self, seed, n_total=12, motion="full"):
+    def __init__(self, seed, n_total=12, motion="full", w_scale=1.0):
         self.rng = np.random.default_rng(seed)
         rng = self.rng
-        self.traj = Trajectory(rng, n_total, motion)
+        self.traj = Trajectory(rng, n_total, motion, w_scale)
         self.n_total = n_total
         self.g = np.array([0.0, 0.0, G_NORM])
         self.ba = rng.normal(0, 0.02, 3)

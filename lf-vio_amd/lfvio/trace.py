@@ -100,9 +100,11 @@ def read_trace(path):
 
 
 def make_stream(path, seed=0, n_frames=40, n_points=600, max_cnt=150, cam_offset=0.0023, pixel_noise=1.0, boot_noise=(0.02, 0.5),
-                restart_at=None, spike_at=None, spike=2.0e4, frame_dt=None, camera="sphere"):
+                restart_at=None, spike_at=None, spike=2.0e4, frame_dt=None, camera="sphere", w_scale=1.0):
     """Write a synthetic recording of `n_frames` images at 10 Hz with 200 Hz IMU and return what was written.
 
+    w_scale: factor on the trajectory's angular rate (default 1.0, about 0.3 rad/s: the recording every other test uses, bit for
+    bit); the online extrinsic calibration (ESTIMATE_EXTRINSIC == 2) needs more rotation than that to finish within a test.
     frame_dt: seconds between images (default synth.KF_DT = 0.1; PALVIO's camera runs at 15 Hz: 1 / 15 — README.md:76,193).
     camera = "ocam": every bearing goes through the reference's camera model like a tracked corner does — projected to a pixel by
     the inverse polynomial, disturbed by `pixel_noise` pixels, lifted back by the polynomial (ScaramuzzaCamera.cc:623-674 with the
@@ -120,7 +122,7 @@ def make_stream(path, seed=0, n_frames=40, n_points=600, max_cnt=150, cam_offset
     estimator refills its window with the next ten images and a STAMPED bootstrap record — what the node's dump hook
     writes when initialStructure() succeeds again — follows for the eleventh."""
     fdt = synth.KF_DT if frame_dt is None else float(frame_dt)
-    scene = synth.Scene(seed, n_total=n_frames + 2 if frame_dt is None else int(np.ceil(n_frames * fdt / synth.KF_DT)) + 3)
+    scene = synth.Scene(seed, n_total=n_frames + 2 if frame_dt is None else int(np.ceil(n_frames * fdt / synth.KF_DT)) + 3, w_scale=w_scale)
     rng = np.random.default_rng([seed, 104729])
     traj = scene.traj
     # world points and their visibility spans
