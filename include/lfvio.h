@@ -361,6 +361,49 @@ typedef struct {
 int lfvio_two_view(lfvio_ctx *ctx, const LfvioTwoViewIn *in, unsigned char *inlier /* [N], after the refit */,
                    LfvioTwoViewOut *out, double *E_all /* [S][9] or NULL */, float *score_all /* [S] or NULL */);
 
+/* lfvio_vi_align: the visual-inertial alignment of Estimator::initialStructure — VisualIMUAlignment
+ * (initial/initial_aligment.cpp:3-216), literally as written, on poses of every image of the window that are known up to
+ * scale in the camera frame of one keyframe (what relativePose / GlobalSFM::construct / the PnP loop leave in
+ * all_image_frame, estimator.cpp:250-357).  The rest of Estimator::visualInitialAlign (:380-437) is the caller's.
+ *   solveGyroscopeBias (:3-36): over the F - 1 consecutive pairs q_ij = Quaterniond(R_i^T R_j) (Eigen's matrix-to-quaternion
+ *     branches), tmp_A = jacobian(O_R, O_BG), tmp_b = 2 (delta_q^-1 (x) q_ij).vec(), the 3 x 3 normal equations summed in pair
+ *     order; then EVERY span is integrated again with ba = 0 and bg = Bgs[0] + delta_bg (:34), where Bgs[0] is
+ *     span[1].linearized_bg as passed (the spans' own linearized_ba / linearized_bg are used by the first integration only).
+ *   LinearAlignment (:121-206): the 6 x 10 blocks, n = 3F + 4, the / 100 on the scale column, x 1000 on A and b, both gates.
+ *   RefineGravity (:53-119): TangentBasis with its exact `a == tmp` comparison, four iterations, n = 3F + 3.  A and b are zeroed
+ *     ONCE, before the loop (:61-64), and scaled by 1000 inside it (:111-112): iteration k solves the sum of all blocks so far,
+ *     each earlier set weighted 1000 x more than the next.  Kept as written; g_iter shows it.
+ * Deviation from the reference: Eigen's ldlt() pivots and tolerates a semidefinite matrix; the device factors the arrowhead
+ * (block-tridiagonal velocity part, dense border) without pivoting and returns status = 3 with every output but `status`
+ * untouched when a pivot is not > 0 (e.g. all T equal: the scale column is zero).  With status 1 or 2 the fields computed before
+ * the gate are written (delta_bg, g_linear, s_linear; with 2 also g_iter, g, s — the reference has moved Bgs by then); x and
+ * pre are left as the caller had them.
+ * LFVIO_ERR_ARG (outputs untouched): null pointers, num_frames outside [4, LFVIO_MAX_IMAGE_FRAMES], a span k >= 1 with no
+ * samples or sum_dt == 0.  F >= 4 because below it the systems are singular by counting: 6 (F - 1) equations against 3F + 4
+ * unknowns (the reference only calls this with the full window, F >= 11).
+ * One upload, one download and four launches in between (k_preintegrate twice, unchanged); runs on the feature stream like
+ * lfvio_triangulate: it does not wait for an optimization in flight. */
+#define LFVIO_MAX_IMAGE_FRAMES 128
+typedef struct {
+  int num_frames;               /* F in [4, LFVIO_MAX_IMAGE_FRAMES]: all_image_frame in stamp order */
+  const double *R;              /* [F][9] ImageFrame::R, row-major (body rotation in the SfM frame, estimator.cpp:299,355) */
+  const double *T;              /* [F][3] ImageFrame::T (camera position in the SfM frame, unscaled, :300,356) */
+  const LfvioImuInterval *span; /* [F]    span[k]: the samples between image k - 1 and image k, constructor arguments as
+                                          ImageFrame::pre_integration had them; span[0] is not read */
+  double noise[4], tic[3], g_norm; /* ACC_N, GYR_N, ACC_W, GYR_W; TIC[0]; G.norm() */
+} LfvioViAlignIn;
+typedef struct {
+  int status;                   /* 0 aligned; 1 first gate of LinearAlignment (initial_aligment.cpp:186);
+                                   2 s < 0 after RefineGravity (:201); 3 a pivot that is not > 0 (deviation, above) */
+  double delta_bg[3];           /* solveGyroscopeBias (:25) */
+  double g_linear[3], s_linear; /* LinearAlignment before the refinement (:179-181) */
+  double g_iter[4][3];          /* g0 after each of RefineGravity's four iterations (:115) */
+  double g[3], s;               /* :118, :197 */
+} LfvioViAlignOut;
+int lfvio_vi_align(lfvio_ctx *ctx, const LfvioViAlignIn *in, LfvioViAlignOut *out,
+                   double *x /* [3F] velocities of the last solve, body frames */,
+                   LfvioPreintegration *pre /* [F] after the re-propagation, pre[0] untouched; or NULL */);
+
 /* ---- landmark-sharded API (multi-GPU) ------------------------
  * Every rank passes the same window but linearizes only landmarks [lm_begin, lm_end) (caller order);
  * IMU factors and the prior are added on the rank(s) with add_pose_side != 0 — exactly one rank.

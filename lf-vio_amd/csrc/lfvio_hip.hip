@@ -42,6 +42,7 @@ constexpr ncclDataType_t ncclDouble = 8;
 #include "kernels_stepw.h"
 #include "kernels_relo.h"
 #include "kernels_twoview.h"
+#include "kernels_vialign.h"
 
 #define HIPCHK(ctx, call)                                                                      \
   do {                                                                                         \
@@ -2493,6 +2494,8 @@ int lfvio_debug_query(lfvio_ctx *c, const char *key, double *out, int n) {
 #include "relo.inc"
 
 #include "twoview.inc"
+
+#include "vialign.inc"
 // ---- landmark-sharded API: declared in lfvio.h, implemented in shard.inc
 #include "shard.inc"
 // ---- multi-GPU groups (RCCL): declared in lfvio.h, implemented in group.inc

@@ -40,6 +40,9 @@ void lfvio_host_set_extrinsic(const double *tic, const double *ric) {
   std::memcpy(config().tic, tic, sizeof config().tic);
   std::memcpy(config().ric, ric, sizeof config().ric);
 }
+// the configured time offset (TD of the YAML file) on its own: what a reset restores.  A recording whose initialization comes from
+// SfM records carries no extrinsic or td (a bootstrap record does): they are configured, as in the node
+void lfvio_host_set_td(double td) { config().td = td; }
 // SOLVER_TIME on its own (<= 0: no wall-clock cap — what a test on a loaded machine wants: Ceres' max_solver_time_in_seconds makes the
 // number of iterations depend on the clock)
 void lfvio_host_set_solver_time(double seconds) { config().solver_time = seconds; }
@@ -167,7 +170,14 @@ void lfvio_host_set_bootstrap(void *h, const double *Ps, const double *Rs, const
     setM(b.kf[i].R, Rs + 9 * i);
   }
   b.g = v3(g);
+  b.depth_ids.clear(), b.depths.clear();  // a state set without depths has none (lfvio_host_set_bootstrap_depths comes after this call)
   b.valid = true;
+}
+
+// optional, after lfvio_host_set_bootstrap: the depths that belong to that state, by feature id (Bootstrap::depths)
+void lfvio_host_set_bootstrap_depths(void *h, int n, const int *ids, const double *depths) {
+  WindowEstimator::Bootstrap &b = E(h)->bootstrap;
+  b.depth_ids.assign(ids, ids + n), b.depths.assign(depths, depths + n);
 }
 
 // the window is already filled from outside (set_state / add_feature / set_imu): continue in the running phase
@@ -396,6 +406,62 @@ int lfvio_host_corresponding(void *h, int l, int r, int cap, double *bl, double 
 void lfvio_host_draw_samples(unsigned seed, int n, int count, int *out) {
   std::mt19937 rng(seed);
   for (int k = 0; k < count; k++) drawSampleSet(rng, n, out + 8 * k);
+}
+
+// ---- initialization from SfM poses (WindowEstimator::visualInitialAlign)
+// SfmResult: n frames, stamps[n], R[n][9] row-major (ImageFrame::R), T[n][3] (ImageFrame::T); used by the next full-window image
+void lfvio_host_set_sfm(void *h, int n, const double *stamps, const double *R, const double *T) {
+  WindowEstimator::SfmResult &s = E(h)->sfm;
+  s.stamps.assign(stamps, stamps + n), s.R.assign(R, R + 9 * (size_t)n), s.T.assign(T, T + 3 * (size_t)n);
+  s.valid = true;
+}
+// all_image_frame: stamps[cap], samples per entry [cap]; returns the length of the list
+int lfvio_host_image_frames(void *h, int cap, double *stamps, int *num_samples) {
+  const std::vector<WindowEstimator::ImageFrame> &l = E(h)->image_frames;
+  for (int k = 0; k < (int)l.size() && k < cap; k++) stamps[k] = l[k].stamp, num_samples[k] = (int)l[k].dt.size();
+  return (int)l.size();
+}
+// What the last attempt handed to lfvio_vi_align and got back.  info[4] = {frames F, samples in all spans, device call made, its
+// return code}; the arrays (any may be null) take at most cap_frames frames / cap_samples samples: stamps[F], R[F][9], T[F][3],
+// counts[F], head[F][12] (linearized_ba, linearized_bg, acc_0, gyr_0 per span), dt / acc / gyr of all spans in order,
+// params[8] = noise[4], tic[3], g_norm; out and x[3F] as the call left them.  Returns the number of device calls so far.
+long long lfvio_host_last_vi_align(void *h, int cap_frames, int cap_samples, int *info, double *stamps, double *R, double *T, int *counts,
+                                   double *head, double *dt, double *acc, double *gyr, double *params, LfvioViAlignOut *out, double *x) {
+  const WindowEstimator::LastViAlign &v = E(h)->last_vi_align;
+  const int F = (int)v.stamps.size(), S = (int)v.dt.size();
+  info[0] = F, info[1] = S, info[2] = v.called ? 1 : 0, info[3] = v.rc;
+  const size_t f = (size_t)std::min(F, cap_frames), s = (size_t)std::min(S, cap_samples);
+  if (stamps && f) std::memcpy(stamps, v.stamps.data(), f * 8);
+  if (R && f) std::memcpy(R, v.R.data(), f * 72);
+  if (T && f) std::memcpy(T, v.T.data(), f * 24);
+  if (counts && f) std::memcpy(counts, v.counts.data(), f * 4);
+  if (head && f) std::memcpy(head, v.head.data(), f * 96);
+  if (dt && s) std::memcpy(dt, v.dt.data(), s * 8);
+  if (acc && s) std::memcpy(acc, v.acc.data(), s * 24);
+  if (gyr && s) std::memcpy(gyr, v.gyr.data(), s * 24);
+  if (params) std::memcpy(params, v.noise, 32), std::memcpy(params + 4, v.tic, 24), params[7] = v.g_norm;
+  if (out) *out = v.out;
+  if (x && f && v.x.size() >= 3 * f) std::memcpy(x, v.x.data(), f * 24);
+  return E(h)->vi_align_calls;
+}
+// tests: processImage() returns right behind a successful visualInitialAlign(), the window as the alignment left it (still
+// initializing: no optimization(), no slide); gravity as aligned: lfvio_host_get_gravity
+void lfvio_host_set_stop_after_align(void *h, int on) { E(h)->stop_after_align = on != 0; }
+void lfvio_host_get_gravity(void *h, double *g) {
+  for (int k = 0; k < 3; k++) g[k] = E(h)->g(k);
+}
+// out[2] = {attempts that reached the device, attempts that aligned}
+void lfvio_host_vi_align_counts(void *h, long long *out) { out[0] = E(h)->vi_align_calls, out[1] = E(h)->vi_align_ok; }
+// the SfM records of a trace file: stamps[cap] of the records, frames[cap] in each; returns their number, -1: unreadable
+int lfvio_host_trace_sfms(const char *trace_path, int cap, double *stamps, int *frames, double *first_R, double *first_T, int cap_first) {
+  Trace trace;
+  if (!trace.load(trace_path)) return -1;
+  for (int k = 0; k < (int)trace.sfms.size() && k < cap; k++) stamps[k] = trace.sfms[k].stamp, frames[k] = (int)trace.sfms[k].sfm.stamps.size();
+  if (!trace.sfms.empty() && first_R && first_T) {
+    const size_t n = std::min(trace.sfms[0].sfm.stamps.size(), (size_t)cap_first);
+    std::memcpy(first_R, trace.sfms[0].sfm.R.data(), n * 72), std::memcpy(first_T, trace.sfms[0].sfm.T.data(), n * 24);
+  }
+  return (int)trace.sfms.size();
 }
 
 int lfvio_host_optimization(void *h) {

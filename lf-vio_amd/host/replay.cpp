@@ -88,6 +88,25 @@ bool Trace::load(const char *path) {
       for (size_t k = 0; k < K; k++) r.points.push_back(Vector3d(d[10 + 3 * k], d[11 + 3 * k], d[12 + 3 * k]));
       r.at_image = images.size();
       relos.push_back(std::move(r));
+    } else if (head[0] == 7 && head[1] >= 12) {
+      uint32_t n;
+      std::memcpy(&n, buf.data() + 8, 4);
+      if (head[1] != 12 + (size_t)n * 13 * sizeof(double)) {
+        error = "SfM record with a wrong length";
+        std::fclose(f);
+        return false;
+      }
+      TraceSfm s;
+      s.stamp = d[0];
+      for (uint32_t k = 0; k < n; k++) {
+        double v[13];
+        std::memcpy(v, buf.data() + 12 + (size_t)k * sizeof v, sizeof v);
+        s.sfm.stamps.push_back(v[0]);
+        s.sfm.R.insert(s.sfm.R.end(), v + 1, v + 10), s.sfm.T.insert(s.sfm.T.end(), v + 10, v + 13);
+      }
+      s.sfm.valid = true;
+      s.at_image = images.size();
+      sfms.push_back(std::move(s));
     }
   }
   std::fclose(f);
@@ -133,7 +152,7 @@ int replay(WindowEstimator &est, const Trace &trace, const char *traj_path, int 
       for (int j = 0; j < 3; j++) est.ric(i, j) = trace.ric[3 * i + j];
     est.td = trace.td;
   }
-  size_t next_boot = 0, next_restart = 0, image_index = 0, next_relo = 0;
+  size_t next_boot = 0, next_restart = 0, image_index = 0, next_relo = 0, next_sfm = 0;
   const int relo_solves0 = est.relo_solves;
   const std::vector<TraceImu> &imu = trace.imu;
   size_t front = 0;         // head of the IMU queue
@@ -163,6 +182,11 @@ int replay(WindowEstimator &est, const Trace &trace, const char *traj_path, int 
           st.bootstraps++;
         }
       }
+    }
+    // ... and the next SfM record in the same way (a bootstrap record for the same image wins inside the estimator)
+    if (est.phase == WindowEstimator::INITIAL) {
+      while (next_sfm < trace.sfms.size() && trace.sfms[next_sfm].stamp < msg.t - 1e-6) next_sfm++;
+      if (next_sfm < trace.sfms.size() && !(trace.sfms[next_sfm].stamp > msg.t + 1e-6)) est.sfm = trace.sfms[next_sfm++].sfm;
     }
     // getMeasurements(), estimator_node.cpp:96-134, against the CURRENT time-offset estimate
     const double img_t = msg.t + est.td;

@@ -19,6 +19,14 @@
 //   type 5 = restart                  [f64 stamp] — std_msgs/Bool(true) on the tracker's restart topic: restart_callback
 //                                     (estimator_node.cpp:187-204) clears the buffers, clearState(), setParameter()
 //
+//   type 6 = relocalization           a /pose_graph/match_points message (TraceRelo below)
+//   type 7 = SfM result               f64 stamp (Headers[WINDOW_SIZE] when GlobalSFM::construct() and the PnP loop had succeeded),
+//                                     u32 F, F x { f64 stamp, R[9] (row-major), T[3] }: all_image_frame's R, T just before
+//                                     visualInitialAlign() (estimator.cpp:358).  Handed to an initializing estimator exactly as
+//                                     bootstrap records are (records that describe a time before a reboot are skipped); the
+//                                     estimator aligns it with its own IMU data (WindowEstimator::visualInitialAlign).  A
+//                                     bootstrap record for the same image wins.
+//
 // Unknown record types are skipped, so a recorder can add its own.
 #pragma once
 #include <cstdint>
@@ -51,7 +59,13 @@ struct TraceRelo {  // record type 6: a /pose_graph/match_points message (estima
   std::vector<Vector3d> points;    // (x, y, id), sorted by id as the pose graph sends them
   size_t at_image;                 // images recorded before it
 };
+struct TraceSfm {  // record type 7
+  double stamp;
+  WindowEstimator::SfmResult sfm;
+  size_t at_image;  // images recorded before it
+};
 struct Trace {
+  std::vector<TraceSfm> sfms;         // in file order
   std::vector<TraceRelo> relos;       // in file order
   std::vector<TraceImu> imu;
   std::vector<TraceImage> images;

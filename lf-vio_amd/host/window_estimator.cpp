@@ -6,6 +6,7 @@
 #pragma weak lfvio_solve_relo
 // ... nor a two-view entry point: there ESTIMATE_EXTRINSIC == 2 reports LFVIO_ERR_DEVICE on the first image that needs it.
 #pragma weak lfvio_two_view
+#pragma weak lfvio_vi_align
 
 #include <algorithm>
 #include <cmath>
@@ -296,6 +297,10 @@ void WindowEstimator::reset() {
   tracks.clear();
   failure_occur = false;
   bootstrap.valid = false;
+  bootstrap.depth_ids.clear(), bootstrap.depths.clear();
+  sfm.valid = false;
+  image_frames.clear();  // clearState(): all_image_frame.clear(), tmp_pre_integration = nullptr (estimator.cpp:60-66)
+  pending_ = ImageFrame();
 }
 
 void WindowEstimator::pushImu(double dt, const double acc[3], const double gyr[3]) {  // estimator.cpp:86-120
@@ -309,6 +314,7 @@ void WindowEstimator::pushImu(double dt, const double acc[3], const double gyr[3
   if (!sp.present) sp.open(acc_prev, gyr_prev, f.Ba, f.Bg);
   if (frame_count != 0) {
     sp.push(dt, acc, gyr);
+    pending_.dt.push_back(dt), pending_.acc.insert(pending_.acc.end(), acc, acc + 3), pending_.gyr.insert(pending_.gyr.end(), gyr, gyr + 3);  // :103
     // mid-point dead reckoning of the newest keyframe
     const Vector3d a0 = f.R * (acc_prev - f.Ba) - g;
     const Vector3d wm = 0.5 * (gyr_prev + w) - f.Bg;
@@ -346,6 +352,141 @@ bool WindowEstimator::applyBootstrap() {
   for (int i = 0; i < FRAMES; i++) bg[i] = kf(i).Bg;
   if (!refreshSpans(true, zero, bg)) return false;
   for (int s : tracks.order()) tracks.setDepth(s, -1.0);
+  for (size_t k = 0; k < bootstrap.depth_ids.size() && k < bootstrap.depths.size(); k++) {
+    const int s = tracks.find(bootstrap.depth_ids[k]);
+    if (s >= 0) tracks.setDepth(s, bootstrap.depths[k]);
+  }
+  return true;
+}
+
+namespace {
+Matrix3d g2R(const Vector3d &g) {  // Utility::g2R (utility.cpp:3-13): FromTwoVectors(g / |g|, z), its yaw taken out
+  const Vector3d v0 = g / g.norm(), v1(0, 0, 1);
+  const double c = v1.dot(v0);
+  Quaterniond q;
+  if (c < -1.0 + 1e-12) {  // antiparallel (Eigen takes the axis from an SVD there): half a turn about x
+    q = Quaterniond(0, 1, 0, 0);
+  } else {
+    const Vector3d axis(v0.y() * v1.z() - v0.z() * v1.y(), v0.z() * v1.x() - v0.x() * v1.z(), v0.x() * v1.y() - v0.y() * v1.x());
+    const double s = std::sqrt((1.0 + c) * 2.0), invs = 1.0 / s;
+    q = Quaterniond(s * 0.5, axis.x() * invs, axis.y() * invs, axis.z() * invs);
+  }
+  const Matrix3d R0 = q.toRotationMatrix();
+  const double yaw = yawPitchRollDeg(R0).x();
+  return fromYawPitchRollDeg(Vector3d(-yaw, 0, 0)) * R0;
+}
+}  // namespace
+
+bool WindowEstimator::visualInitialAlign() {  // estimator.cpp:367-443 on the SfM poses of `sfm`; VisualIMUAlignment on the device
+  const Config &c = config();
+  LastViAlign &lv = last_vi_align;
+  lv.called = false;
+  const int F = (int)image_frames.size();
+  if (F < 1 || F > LFVIO_MAX_IMAGE_FRAMES) return false;
+  // ImageFrame::R, T of every frame of the list, by stamp; a frame the result does not cover: no attempt
+  lv.stamps.assign(F, 0.0), lv.R.assign(9 * (size_t)F, 0.0), lv.T.assign(3 * (size_t)F, 0.0);
+  for (int k = 0; k < F; k++) {
+    size_t j = 0;
+    while (j < sfm.stamps.size() && sfm.stamps[j] != image_frames[k].stamp) j++;
+    if (j == sfm.stamps.size() || sfm.R.size() < 9 * (j + 1) || sfm.T.size() < 3 * (j + 1)) return false;
+    lv.stamps[k] = image_frames[k].stamp;
+    std::memcpy(&lv.R[9 * (size_t)k], &sfm.R[9 * j], 72), std::memcpy(&lv.T[3 * (size_t)k], &sfm.T[3 * j], 24);
+  }
+  std::vector<LfvioImuInterval> spans(F);
+  lv.counts.assign(F, 0), lv.head.assign(12 * (size_t)F, 0.0), lv.dt.clear(), lv.acc.clear(), lv.gyr.clear();
+  for (int k = 0; k < F; k++) {
+    const ImageFrame &f = image_frames[k];
+    LfvioImuInterval &iv = spans[k];
+    std::memset(&iv, 0, sizeof iv);
+    if (k == 0) continue;  // span[0] is not read
+    iv.num_samples = (int)f.dt.size(), iv.dt = f.dt.data(), iv.acc = f.acc.data(), iv.gyr = f.gyr.data();
+    std::memcpy(iv.acc_0, f.acc0, 24), std::memcpy(iv.gyr_0, f.gyr0, 24), std::memcpy(iv.linearized_ba, f.lin_ba, 24), std::memcpy(iv.linearized_bg, f.lin_bg, 24);
+    lv.counts[k] = iv.num_samples;
+    std::memcpy(&lv.head[12 * (size_t)k], f.lin_ba, 24), std::memcpy(&lv.head[12 * (size_t)k + 3], f.lin_bg, 24);
+    std::memcpy(&lv.head[12 * (size_t)k + 6], f.acc0, 24), std::memcpy(&lv.head[12 * (size_t)k + 9], f.gyr0, 24);
+    lv.dt.insert(lv.dt.end(), f.dt.begin(), f.dt.end()), lv.acc.insert(lv.acc.end(), f.acc.begin(), f.acc.end()), lv.gyr.insert(lv.gyr.end(), f.gyr.begin(), f.gyr.end());
+  }
+  LfvioViAlignIn in;
+  in.num_frames = F, in.R = lv.R.data(), in.T = lv.T.data(), in.span = spans.data();
+  in.noise[0] = c.acc_n, in.noise[1] = c.gyr_n, in.noise[2] = c.acc_w, in.noise[3] = c.gyr_w;
+  const Vector3d G(c.gravity[0], c.gravity[1], c.gravity[2]);
+  for (int k = 0; k < 3; k++) in.tic[k] = c.tic[k];
+  in.g_norm = G.norm();
+  std::memcpy(lv.noise, in.noise, sizeof lv.noise), std::memcpy(lv.tic, in.tic, sizeof lv.tic), lv.g_norm = in.g_norm;
+  std::memset(&lv.out, 0, sizeof lv.out);
+  lv.x.assign(3 * (size_t)F, 0.0);
+  if (!lfvio_vi_align || !device()) {  // no fallback: over an ABI without the entry the attempt fails and the window slides
+    status = LFVIO_ERR_DEVICE;
+    lv.rc = LFVIO_ERR_DEVICE;
+    return false;
+  }
+  lv.rc = lfvio_vi_align(gpu, &in, &lv.out, lv.x.data(), nullptr);
+  lv.called = true;
+  vi_align_calls++;
+  if (lv.rc != LFVIO_OK) {
+    status = lv.rc;
+    return false;
+  }
+  if (lv.out.status == 3) return false;  // (deviation of include/lfvio.h: nothing was computed)
+  // solveGyroscopeBias has moved every Bgs and re-propagated every frame's integration before LinearAlignment can fail
+  // (initial_aligment.cpp:28-35)
+  const Vector3d dbg(lv.out.delta_bg[0], lv.out.delta_bg[1], lv.out.delta_bg[2]);
+  for (int i = 0; i <= WINDOW_SIZE; i++) kf(i).Bg += dbg;
+  for (int k = 1; k < F; k++)
+    for (int d = 0; d < 3; d++) image_frames[k].lin_ba[d] = 0.0, image_frames[k].lin_bg[d] = kf(0).Bg(d);
+  if (lv.out.status != 0) return false;
+  auto frameOf = [&](double stamp) {
+    int k = 0;
+    while (k < F && image_frames[k].stamp != stamp) k++;
+    return k;
+  };
+  for (int i = 0; i <= frame_count; i++) {  // :380-387
+    const int k = frameOf(kf(i).stamp);
+    if (k == F) return false;
+    Keyframe &f = kf(i);
+    f.P = Vector3d(lv.T[3 * k], lv.T[3 * k + 1], lv.T[3 * k + 2]);
+    for (int a = 0; a < 3; a++)
+      for (int b = 0; b < 3; b++) f.R(a, b) = lv.R[9 * (size_t)k + 3 * a + b];
+  }
+  for (int s : tracks.order())  // :389-392 (getDepthVector: the solvable tracks)
+    if (tracks.solvable(s)) tracks.setDepth(s, -1.0);
+  {  // :394-400: triangulate on camera poses, no tic, the configured ric
+    const Vector3d tic_kept = tic;
+    tic.setZero();
+    for (int i = 0; i < 3; i++)
+      for (int j = 0; j < 3; j++) ric(i, j) = c.ric[3 * i + j];
+    triangulate();
+    tic = tic_kept;
+    if (status != LFVIO_OK) return false;
+  }
+  const double s = lv.out.s;  // :402
+  Vector3d zero[FRAMES], bg[FRAMES];
+  for (int i = 0; i < FRAMES; i++) bg[i] = kf(i).Bg;
+  if (!refreshSpans(true, zero, bg)) return false;  // :403-406
+  const Vector3d TIC(c.tic[0], c.tic[1], c.tic[2]);
+  for (int i = frame_count; i >= 0; i--) kf(i).P = s * kf(i).P - kf(i).R * TIC - (s * kf(0).P - kf(0).R * TIC);  // :407-408
+  // :409-418, kept as written: kv counts KEYFRAMES but indexes x, which is laid out over ALL frames of the list — with a
+  // non-keyframe in the list the later keyframes take the velocity solved for an earlier frame
+  int kv = -1;
+  for (int k = 0; k < F; k++) {
+    bool key = false;
+    for (int i = 0; i <= frame_count; i++) key = key || kf(i).stamp == image_frames[k].stamp;
+    if (!key) continue;
+    kv++;
+    Matrix3d Rk;
+    for (int a = 0; a < 3; a++)
+      for (int b = 0; b < 3; b++) Rk(a, b) = lv.R[9 * (size_t)k + 3 * a + b];
+    kf(kv).V = Rk * Vector3d(lv.x[3 * kv], lv.x[3 * kv + 1], lv.x[3 * kv + 2]);
+  }
+  for (int t : tracks.order())  // :419-425
+    if (tracks.solvable(t)) tracks.setDepth(t, tracks.depth(t) * s);
+  g = Vector3d(lv.out.g[0], lv.out.g[1], lv.out.g[2]);
+  Matrix3d R0 = g2R(g);  // :427-438
+  const double yaw = yawPitchRollDeg(R0 * kf(0).R).x();
+  R0 = fromYawPitchRollDeg(Vector3d(-yaw, 0, 0)) * R0;
+  g = R0 * g;
+  for (int i = 0; i <= frame_count; i++) kf(i).P = R0 * kf(i).P, kf(i).R = R0 * kf(i).R, kf(i).V = R0 * kf(i).V;
+  vi_align_ok++;
   return true;
 }
 
@@ -524,6 +665,13 @@ int WindowEstimator::calibrateExtrinsicRotation() {  // estimator.cpp:142-159
 void WindowEstimator::pushImage(double stamp, int n, const int *ids, const double *pts8) {  // estimator.cpp:122-220
   marg_flag = keyframeTest(frame_count, n, ids, pts8, td) ? LFVIO_MARGIN_OLD : LFVIO_MARGIN_SECOND_NEW;
   kf(frame_count).stamp = stamp;
+  {  // estimator.cpp:137-140: the image takes tmp_pre_integration, a new one starts at the last IMU sample with this frame's biases
+    pending_.stamp = stamp;
+    image_frames.push_back(std::move(pending_));
+    pending_ = ImageFrame();
+    const Keyframe &f = kf(frame_count);
+    for (int k = 0; k < 3; k++) pending_.acc0[k] = acc_prev(k), pending_.gyr0[k] = gyr_prev(k), pending_.lin_ba[k] = f.Ba(k), pending_.lin_bg[k] = f.Bg(k);
+  }
   if (config().estimate_extrinsic == 2 && frame_count != 0) {
     const int calib = calibrateExtrinsicRotation();
     advanceWindow(stamp);
@@ -542,7 +690,18 @@ void WindowEstimator::advanceWindow(double stamp) {  // estimator.cpp:161-220
     }
     bool aligned = false;
     if (config().estimate_extrinsic != 2 && stamp - initial_timestamp > 0.1) {
-      aligned = applyBootstrap();
+      // a bootstrap record wins (every recording made before there were SfM records replays as it did; it stays valid until the
+      // next reset()); otherwise the SfM result of this image goes through the alignment.  The SfM result described this image's
+      // list: it is dropped whether or not it was used
+      bool from_sfm = false;
+      if (bootstrap.valid) {
+        aligned = applyBootstrap();
+      } else if (sfm.valid) {
+        aligned = visualInitialAlign();
+        from_sfm = aligned;
+      }
+      sfm.valid = false;
+      if (from_sfm && stop_after_align) return;
       initial_timestamp = stamp;
     }
     if (!aligned) {
@@ -584,6 +743,12 @@ void WindowEstimator::slide() {  // estimator.cpp:1011-1131
   if (marg_flag == LFVIO_MARGIN_OLD) {
     const Matrix3d old_R = kf(0).R;
     const Vector3d old_P = kf(0).P;
+    {  // estimator.cpp:1051-1067: everything up to and including Headers[0] leaves all_image_frame
+      const double t_0 = kf(0).stamp;
+      size_t keep = 0;
+      while (keep < image_frames.size() && image_frames[keep].stamp <= t_0) keep++;
+      image_frames.erase(image_frames.begin(), image_frames.begin() + keep);
+    }
     // the ring turns: frame 1 becomes frame 0, ...; the slot of the old frame 0 becomes the new newest frame, which starts
     // as a copy of its predecessor with an empty span
     const Keyframe prev = newest;

@@ -256,7 +256,46 @@ class WindowEstimator {
     bool valid = false;
     Keyframe kf[FRAMES];
     Vector3d g;
+    // optional: the depths visualInitialAlign() left (estimator.cpp:389-425: triangulated on the SfM poses, then x s), by feature
+    // id.  Tracks not listed start unknown (-1) and are triangulated on the aligned state, as all of them are without this.
+    std::vector<int> depth_ids;
+    std::vector<double> depths;
   } bootstrap;
+
+  // ---- initialization without a bootstrap record: visualInitialAlign() (estimator.cpp:367-443) on SfM poses from outside
+  // all_image_frame (estimator.cpp:137-140): per image its stamp and the IMU samples since the previous image with the
+  // constructor arguments of its IntegrationBase (tmp_pre_integration); erased as slideWindow() erases it (:1051-1067: a
+  // MARGIN_OLD slide drops everything up to and including Headers[0], MARGIN_SECOND_NEW keeps the entry), cleared by reset().
+  // The samples are appended as they arrive whether or not an SfM result is ever set (three push_backs per IMU sample; the
+  // spans of the ring cannot be shared: MARGIN_SECOND_NEW merges two of them, the list keeps them apart).
+  struct ImageFrame {
+    double stamp = 0;
+    std::vector<double> dt, acc, gyr;
+    double acc0[3] = {0, 0, 0}, gyr0[3] = {0, 0, 0}, lin_ba[3] = {0, 0, 0}, lin_bg[3] = {0, 0, 0};
+  };
+  std::vector<ImageFrame> image_frames;
+  // What relativePose() + GlobalSFM::construct() + the PnP loop leave in all_image_frame (estimator.cpp:250-357): per image
+  // ImageFrame::R (body rotation in the SfM frame) and ImageFrame::T (camera position there, unscaled), matched to the list
+  // BY STAMP.  A result that does not cover every frame of the list, or a list of more than LFVIO_MAX_IMAGE_FRAMES frames, is
+  // not applied: initialization fails for that image and the window slides, as after a failed initialStructure().
+  struct SfmResult {
+    bool valid = false;
+    std::vector<double> stamps, R, T;  // n | 9n row-major | 3n
+  } sfm;
+  struct LastViAlign {  // what the last attempt passed to lfvio_vi_align and got back (tests, tools)
+    bool called = false;
+    int rc = LFVIO_OK;
+    std::vector<double> stamps, R, T, x;
+    std::vector<int> counts;                // samples per span, [0] = 0
+    std::vector<double> head, dt, acc, gyr;  // per span linearized_ba, linearized_bg, acc_0, gyr_0 (12 doubles); the samples
+    double noise[4] = {0, 0, 0, 0}, tic[3] = {0, 0, 0}, g_norm = 0;
+    LfvioViAlignOut out;
+  } last_vi_align;
+  long long vi_align_calls = 0, vi_align_ok = 0;
+  // true: the window holds the aligned state the first optimization() starts from.  The IMU-excitation check of
+  // initialStructure() (estimator.cpp:224-249) only logs in the reference and is left out.
+  bool visualInitialAlign();
+  bool stop_after_align = false;  // tests: advanceWindow() returns behind a successful alignment, before the first optimization()
 
   // the flat parameter arrays Ceres sees (estimator.h:107-113)
   double para_Pose[FRAMES][LFVIO_SIZE_POSE];
@@ -279,6 +318,7 @@ class WindowEstimator {
   bool prior_on_device_ = false;  // the resident window took its prior over on the device (lfvio_batch_upload_chained_device): `prior` is stale
   bool device();
   bool applyBootstrap();
+  ImageFrame pending_;  // tmp_pre_integration: the samples since the last image
   void advanceWindow(double stamp);  // processImage() behind the keyframe test and the calibration (estimator.cpp:161-220)
   std::mt19937 ransac_rng_;
   bool ransac_seeded_ = false;

@@ -403,6 +403,40 @@ class TwoViewOutC(C.Structure):
                     t_cand=a(self.t_cand), front=a(self.front), R_rel=a(self.R_rel).reshape(3, 3))
 
 
+MAX_IMAGE_FRAMES = 128  # LFVIO_MAX_IMAGE_FRAMES
+
+
+class ViAlignInC(C.Structure):
+    """LfvioViAlignIn (include/lfvio.h)."""
+    _fields_ = [
+        ("num_frames", C.c_int),
+        ("R", C.POINTER(C.c_double)),
+        ("T", C.POINTER(C.c_double)),
+        ("span", C.POINTER(ImuIntervalC)),
+        ("noise", C.c_double * 4),
+        ("tic", C.c_double * 3),
+        ("g_norm", C.c_double),
+    ]
+
+
+class ViAlignOutC(C.Structure):
+    """LfvioViAlignOut (include/lfvio.h)."""
+    _fields_ = [
+        ("status", C.c_int),
+        ("delta_bg", C.c_double * 3),
+        ("g_linear", C.c_double * 3),
+        ("s_linear", C.c_double),
+        ("g_iter", (C.c_double * 3) * 4),
+        ("g", C.c_double * 3),
+        ("s", C.c_double),
+    ]
+
+    def as_dict(self):
+        a = lambda x: np.array(x, dtype=np.float64)
+        return dict(status=int(self.status), delta_bg=a(self.delta_bg), g_linear=a(self.g_linear), s_linear=float(self.s_linear),
+                    g_iter=np.array([list(r) for r in self.g_iter], dtype=np.float64), g=a(self.g), s=float(self.s))
+
+
 HIP_SYMBOLS = [
     "lfvio_create", "lfvio_destroy", "lfvio_last_error", "lfvio_version", "lfvio_solve", "lfvio_solve_relo", "lfvio_marginalize",
     "lfvio_batch_reserve", "lfvio_batch_upload", "lfvio_batch_optimize", "lfvio_batch_optimize_async",
@@ -411,7 +445,7 @@ HIP_SYMBOLS = [
     "lfvio_shard_begin", "lfvio_shard_exchange_len", "lfvio_shard_scalar_offset", "lfvio_shard_exchange_ptr", "lfvio_shard_linearize",
     "lfvio_shard_solve", "lfvio_shard_candidate", "lfvio_shard_decide", "lfvio_shard_marg_linearize", "lfvio_shard_marg_finish",
     "lfvio_shard_finish", "lfvio_shard_restart", "lfvio_shard_enqueue", "lfvio_shard_poll", "lfvio_triangulate", "lfvio_shift_depth", "lfvio_preintegrate",
-    "lfvio_two_view",
+    "lfvio_two_view", "lfvio_vi_align",
     "lfvio_group_create", "lfvio_group_unique_id", "lfvio_group_create_rank", "lfvio_group_create_local", "lfvio_group_destroy",
     "lfvio_group_last_error", "lfvio_group_size", "lfvio_group_local", "lfvio_group_rank", "lfvio_group_ctx", "lfvio_group_backend",
     "lfvio_group_solve", "lfvio_group_upload", "lfvio_group_optimize", "lfvio_group_download", "lfvio_group_range",
@@ -476,6 +510,8 @@ def load_hip_library(path=None):
     lib.lfvio_shift_depth.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp, C.c_double, _dp]
     lib.lfvio_preintegrate.argtypes = [C.c_void_p, C.c_int, C.POINTER(ImuIntervalC), _dp, C.POINTER(Preintegration)]
     lib.lfvio_two_view.argtypes = [C.c_void_p, C.POINTER(TwoViewInC), C.POINTER(C.c_ubyte), C.POINTER(TwoViewOutC), _dp, C.POINTER(C.c_float)]
+    if hasattr(lib, "lfvio_vi_align"):  # (an A/B run may load a build from before the entry existed; build() checks the product's symbols)
+        lib.lfvio_vi_align.argtypes = [C.c_void_p, C.POINTER(ViAlignInC), C.POINTER(ViAlignOutC), _dp, C.POINTER(Preintegration)]
     lib.lfvio_shard_marg_linearize.argtypes = [C.c_void_p, C.c_int]
     lib.lfvio_shard_marg_finish.argtypes = [C.c_void_p, C.c_int, C.POINTER(Prior)]
     # multi-GPU groups (RCCL inside the library)

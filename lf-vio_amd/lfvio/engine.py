@@ -270,6 +270,44 @@ class Engine:
             res.update(E_all=E_all, score_all=score_all)
         return res
 
+    def vi_align(self, R, T, spans, noise, tic, g_norm, with_pre=False, out=None, x=None, pre=None, check=True):
+        """lfvio_vi_align: VisualIMUAlignment on the poses R [F, 3, 3], T [F, 3] of every image of the window and the IMU
+        samples between them; spans[k] = (linearized_ba, linearized_bg, acc_0, gyr_0, dt[], acc[][3], gyr[][3]) as for
+        preintegrate(), spans[0] is not read (None will do).  Returns the fields of LfvioViAlignOut as a dict plus `x` [3F],
+        `rc` and, with with_pre, `pre` (the abi.Preintegration array, entry 0 untouched).  out / x / pre: buffers to be
+        written (a test of what a failed call leaves alone passes its own); check=False returns the error code under `rc`
+        instead of raising."""
+        f = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+        R, T = f(R).reshape(-1, 9), f(T).reshape(-1, 3)
+        F = len(spans)
+        arr = (abi.ImuIntervalC * max(F, 1))()
+        keep = []
+        for k, sp in enumerate(spans):
+            if k == 0 or sp is None:
+                continue
+            ba, bg, a0, g0, dts, accs, gyrs = sp
+            dts, accs, gyrs = f(dts).reshape(-1), f(accs).reshape(-1, 3), f(gyrs).reshape(-1, 3)
+            keep.append((dts, accs, gyrs))
+            arr[k].num_samples = len(dts)
+            arr[k].dt, arr[k].acc, arr[k].gyr = _p(dts), _p(accs), _p(gyrs)
+            for name, v in (("acc_0", a0), ("gyr_0", g0), ("linearized_ba", ba), ("linearized_bg", bg)):
+                setattr(arr[k], name, (C.c_double * 3)(*[float(v_) for v_ in v]))
+        vin = abi.ViAlignInC()
+        vin.num_frames, vin.R, vin.T, vin.span = F, _p(R), _p(T), arr
+        vin.noise = (C.c_double * 4)(*[float(v) for v in noise])
+        vin.tic = (C.c_double * 3)(*[float(v) for v in tic])
+        vin.g_norm = float(g_norm)
+        out = abi.ViAlignOutC() if out is None else out
+        x = np.zeros(3 * max(F, 1)) if x is None else x
+        if pre is None and with_pre:
+            pre = (abi.Preintegration * max(F, 1))()
+        rc = self.lib.lfvio_vi_align(self.ctx, C.byref(vin), C.byref(out), _p(x), pre)
+        if check:
+            self._check(rc, "lfvio_vi_align")
+        res = out.as_dict()
+        res.update(rc=rc, x=x, pre=pre)
+        return res
+
     def time_kernel(self, which, count, reps):
         ms = np.zeros(1)
         self._check(self.lib.lfvio_debug_time_kernel(self.ctx, which, count, reps, _p(ms)), "time_kernel")

@@ -143,9 +143,15 @@ class HostEstimator:
         return bool(self.L.lfvio_host_add_feature_check_parallax(self.h, frame_count, len(ids), ids.ctypes.data_as(C.POINTER(C.c_int)),
                                                                  _p(pts), float(td)))
 
-    def set_bootstrap(self, Ps, Rs, Vs, Bas, Bgs, g):
+    def set_bootstrap(self, Ps, Rs, Vs, Bas, Bgs, g, depth_ids=None, depths=None):
+        """depth_ids / depths (optional): the depths that belong to the state, by feature id — what visualInitialAlign() leaves
+        beside Ps .. g (estimator.cpp:389-425); without them every track is triangulated on the state."""
         a = [_f(x) for x in (Ps, Rs, Vs, Bas, Bgs, g)]
         self.L.lfvio_host_set_bootstrap(self.h, *[_p(x) for x in a])
+        if depth_ids is not None:
+            ids, d = np.ascontiguousarray(depth_ids, dtype=np.int32), _f(depths)
+            self.L.lfvio_host_set_bootstrap_depths.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), _dp]
+            self.L.lfvio_host_set_bootstrap_depths(self.h, len(ids), ids.ctypes.data_as(C.POINTER(C.c_int)), _p(d))
 
     def set_running(self, stamps, acc_0, gyr_0, g):
         a = [_f(x) for x in (stamps, acc_0, gyr_0, g)]
@@ -341,6 +347,65 @@ class HostEstimator:
         self.L.lfvio_host_two_view_calls.argtypes = [C.c_void_p]
         self.L.lfvio_host_two_view_calls.restype = C.c_longlong
         return int(self.L.lfvio_host_two_view_calls(self.h))
+
+    # ---- initialization from SfM poses
+    def set_sfm(self, stamps, R, T):
+        """An SfM result for the next full-window image: per frame its stamp, ImageFrame::R [n, 3, 3], ImageFrame::T [n, 3]."""
+        st, R, T = _f(stamps).reshape(-1), _f(R).reshape(-1, 9), _f(T).reshape(-1, 3)
+        self.L.lfvio_host_set_sfm.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp]
+        self.L.lfvio_host_set_sfm(self.h, len(st), _p(st), _p(R), _p(T))
+
+    def set_td(self, td):
+        """The CONFIGURED time offset (what a reset restores); with set_extrinsic() what a recording without bootstrap records needs."""
+        self.L.lfvio_host_set_td.argtypes = [C.c_double]
+        self.L.lfvio_host_set_td(float(td))
+
+    def set_stop_after_align(self, on):
+        """Tests: process_image() returns right behind a successful visualInitialAlign(), the window as the alignment left it."""
+        self.L.lfvio_host_set_stop_after_align.argtypes = [C.c_void_p, C.c_int]
+        self.L.lfvio_host_set_stop_after_align(self.h, int(on))
+
+    def gravity(self):
+        g = np.zeros(3)
+        self.L.lfvio_host_get_gravity.argtypes = [C.c_void_p, _dp]
+        self.L.lfvio_host_get_gravity(self.h, _p(g))
+        return g
+
+    def image_frames(self, cap=1024):
+        """all_image_frame: (stamps, samples per entry)."""
+        st, ns = np.zeros(cap), np.zeros(cap, dtype=np.int32)
+        self.L.lfvio_host_image_frames.argtypes = [C.c_void_p, C.c_int, _dp, C.POINTER(C.c_int)]
+        n = self.L.lfvio_host_image_frames(self.h, cap, _p(st), ns.ctypes.data_as(C.POINTER(C.c_int)))
+        return st[:n].copy(), ns[:n].copy()
+
+    def vi_align_counts(self):
+        """(attempts that reached lfvio_vi_align, attempts that aligned)."""
+        o = np.zeros(2, dtype=np.int64)
+        self.L.lfvio_host_vi_align_counts.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
+        self.L.lfvio_host_vi_align_counts(self.h, o.ctypes.data_as(C.POINTER(C.c_longlong)))
+        return int(o[0]), int(o[1])
+
+    def last_vi_align(self, cap_frames=128, cap_samples=1 << 16):
+        """What the last attempt passed to lfvio_vi_align and got back: dict(R, T, stamps, spans (the tuples Engine.vi_align
+        takes, entry 0 None), noise, tic, G, out (the fields of LfvioViAlignOut), x, called, rc, calls)."""
+        info = np.zeros(4, dtype=np.int32)
+        st, R, T = np.zeros(cap_frames), np.zeros((cap_frames, 9)), np.zeros((cap_frames, 3))
+        cnt, head = np.zeros(cap_frames, dtype=np.int32), np.zeros((cap_frames, 12))
+        dt, acc, gyr = np.zeros(cap_samples), np.zeros((cap_samples, 3)), np.zeros((cap_samples, 3))
+        prm, x, out = np.zeros(8), np.zeros(3 * cap_frames), abi.ViAlignOutC()
+        ip = C.POINTER(C.c_int)
+        self.L.lfvio_host_last_vi_align.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, _dp, _dp, _dp, ip, _dp, _dp, _dp, _dp, _dp, C.POINTER(abi.ViAlignOutC), _dp]
+        self.L.lfvio_host_last_vi_align.restype = C.c_longlong
+        calls = self.L.lfvio_host_last_vi_align(self.h, cap_frames, cap_samples, info.ctypes.data_as(ip), _p(st), _p(R), _p(T), cnt.ctypes.data_as(ip),
+                                                _p(head), _p(dt), _p(acc), _p(gyr), _p(prm), C.byref(out), _p(x))
+        F = int(info[0])
+        spans, o = [None], 0
+        for k in range(1, F):
+            n = int(cnt[k])
+            spans.append((head[k, 0:3].copy(), head[k, 3:6].copy(), head[k, 6:9].copy(), head[k, 9:12].copy(), dt[o:o + n].copy(), acc[o:o + n].copy(), gyr[o:o + n].copy()))
+            o += n
+        return dict(stamps=st[:F].copy(), R=R[:F].reshape(F, 3, 3).copy(), T=T[:F].copy(), spans=spans, noise=prm[0:4].copy(), tic=prm[4:7].copy(),
+                    G=float(prm[7]), out=out.as_dict(), x=x[:3 * F].copy(), called=bool(info[2]), rc=int(info[3]), calls=int(calls))
 
     def last_two_view(self, cap_matches=4096, cap_samples=1024):
         """What the last image of mode 2 handed to lfvio_two_view and got back: dict(bl, br, samples, mask, out (the fields of

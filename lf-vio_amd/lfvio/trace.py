@@ -10,7 +10,7 @@ import numpy as np
 from . import abi, synth
 
 MAGIC = b"LFVT"
-REC_IMU, REC_FEATURES, REC_BOOTSTRAP, REC_TRUTH, REC_RESTART, REC_RELO = 1, 2, 3, 4, 5, 6
+REC_IMU, REC_FEATURES, REC_BOOTSTRAP, REC_TRUTH, REC_RESTART, REC_RELO, REC_SFM = 1, 2, 3, 4, 5, 6, 7
 
 
 class TraceWriter:
@@ -57,6 +57,14 @@ class TraceWriter:
         mp = np.asarray(match_points, dtype=np.float64).reshape(-1, 3)
         self._rec(REC_RELO, np.concatenate([[stamp, index], np.ravel(relo_t), np.ravel(relo_q_xyzw), [len(mp)], mp.ravel()]).astype("<f8").tobytes())
 
+    def sfm(self, stamp, stamps, R, T):
+        """An SfM result (type 7): stamp of the image it belongs to (Headers[WINDOW_SIZE]), then per frame of all_image_frame its
+        stamp, ImageFrame::R [3, 3] (body rotation in the SfM frame) and ImageFrame::T [3] (camera position there, unscaled)."""
+        stamps, R, T = np.asarray(stamps, np.float64).reshape(-1), np.asarray(R, np.float64).reshape(-1, 9), np.asarray(T, np.float64).reshape(-1, 3)
+        assert len(stamps) == len(R) == len(T)
+        body = np.concatenate([stamps[:, None], R, T], axis=1).astype("<f8")
+        self._rec(REC_SFM, struct.pack("<dI", stamp, len(stamps)) + body.tobytes())
+
     def truth(self, t, p, q_xyzw):
         self._rec(REC_TRUTH, struct.pack("<8d", t, *p, *q_xyzw))
 
@@ -66,7 +74,7 @@ class TraceWriter:
 
 def read_trace(path):
     """-> dict(imu [n,7], images [(t, array[n,9] float32)], bootstrap array or None, truth [n,8])"""
-    out = dict(imu=[], images=[], bootstrap=None, bootstraps=[], restarts=[], truth=[], relos=[], order=[])
+    out = dict(imu=[], images=[], bootstrap=None, bootstraps=[], restarts=[], truth=[], relos=[], sfms=[], order=[])
     with open(path, "rb") as f:
         head = f.read(8)
         assert head[:4] == MAGIC and struct.unpack("<I", head[4:])[0] == 1
@@ -92,6 +100,11 @@ def read_trace(path):
                 d = np.frombuffer(p, dtype="<f8")
                 out["relos"].append(dict(at_image=len(out["images"]), stamp=float(d[0]), index=int(d[1]), relo_t=d[2:5].copy(),
                                          relo_q=d[5:9].copy(), match_points=d[10:].reshape(-1, 3).copy()))
+            elif kind == REC_SFM:
+                stamp, n = struct.unpack("<dI", p[:12])
+                body = np.frombuffer(p[12:], dtype="<f8").reshape(n, 13)
+                out["sfms"].append(dict(at_image=len(out["images"]), stamp=stamp, stamps=body[:, 0].copy(), R=body[:, 1:10].reshape(n, 3, 3).copy(),
+                                        T=body[:, 10:13].copy()))
             elif kind == REC_TRUTH:
                 out["truth"].append(struct.unpack("<8d", p))
     out["imu"] = np.array(out["imu"]).reshape(-1, 7)
@@ -230,3 +243,68 @@ def make_stream(path, seed=0, n_frames=40, n_points=600, max_cnt=150, cam_offset
             boot_record(boots_due[k], stamp=stamp)
     w.close()
     return dict(scene=scene, truth=truth, images=images, bootstrap=boot, n_ids=next_id)
+
+
+def sfm_from_truth(stamps, Ps, Rs, keyframe=0, scale=1.0, rot_noise_deg=0.0, pos_noise=0.0, seed=0, tic=None, ric=None):
+    """What the vision-only half of initialStructure() would leave in all_image_frame, made from true body poses Ps [n, 3], Rs
+    [n, 3, 3] of the images `stamps`: the camera poses expressed in the camera frame of image `keyframe`, positions divided by
+    `scale`; ImageFrame::R = R_cl<-body (estimator.cpp:299, 355), ImageFrame::T = the camera position (:300, :356).  Optional
+    noise: a rotation of rot_noise_deg (sigma per axis) on every R, a relative pos_noise on every T.  -> (stamps, R, T)."""
+    tic = synth.TIC if tic is None else np.asarray(tic, float)
+    ric = synth.RIC if ric is None else np.asarray(ric, float)
+    rng = np.random.default_rng([seed, 7919])
+    Ps, Rs = np.asarray(Ps, float).reshape(-1, 3), np.asarray(Rs, float).reshape(-1, 3, 3)
+    R_wcl, p_cl = Rs[keyframe] @ ric, Ps[keyframe] + Rs[keyframe] @ tic
+    R, T = np.zeros_like(Rs), np.zeros_like(Ps)
+    for k in range(len(Ps)):
+        R[k] = R_wcl.T @ Rs[k]
+        T[k] = R_wcl.T @ (Ps[k] + Rs[k] @ tic - p_cl) / scale
+        if rot_noise_deg > 0:
+            R[k] = R[k] @ synth.exp_so3(rng.normal(0, np.deg2rad(rot_noise_deg), 3))
+        if pos_noise > 0:
+            T[k] = T[k] * (1.0 + pos_noise * rng.standard_normal(3))
+    return np.asarray(stamps, float), R, T
+
+
+def bootstraps_to_sfm(src, dst, keyframe=0, scale=1.0, rot_noise_deg=0.0, pos_noise=0.0, seed=0, history=40, repeat=2):
+    """Copy the recording `src` to `dst` with every bootstrap record replaced by an SfM record made from the recording's ground
+    truth (type 4): the record belongs to the image the bootstrap record belonged to (its stamp, or the first full window) and
+    covers the last `history` images up to it — the estimator picks the frames of its list by stamp.  `repeat` records are written,
+    for that image and the ones behind it: the node's hook publishes at every image whose vision-only half succeeded, and a window
+    that refills after a failureDetection() reboot is full one image later than make_stream's bootstrap record assumes (the
+    bootstrap path does not look at stamps, the alignment does); a record for an image the estimator is no longer initializing at is
+    never handed over.  -> the list of records written for the FIRST image of each group (dicts of stamp, stamps, R, T)."""
+    tr = read_trace(src)
+    truth = tr["truth"]
+    img_stamps = [t for t, _ in tr["images"]]
+    w = TraceWriter(dst)
+    written, n_img = [], 0
+    with open(src, "rb") as f:
+        f.read(8)
+        while True:
+            h = f.read(8)
+            if len(h) < 8:
+                break
+            kind, nbytes = struct.unpack("<II", h)
+            p = f.read(nbytes)
+            if kind != REC_BOOTSTRAP:
+                w._rec(kind, p)
+                n_img += kind == REC_FEATURES
+                continue
+            d = np.frombuffer(p, dtype="<f8")
+            stamp = float(d[247]) if d.size == 248 else img_stamps[max(n_img, abi.WINDOW_SIZE)]
+            last0 = int(np.argmin(np.abs(truth[:, 0] - stamp)))
+            for rep in range(repeat):
+                last = last0 + rep
+                if last >= len(truth):
+                    break
+                first = max(0, last - history + 1)
+                q = truth[first:last + 1, 4:8]
+                Rs = np.array([synth.q_to_R(np.array([c[3], c[0], c[1], c[2]])) for c in q])
+                st, R, T = sfm_from_truth(truth[first:last + 1, 0], truth[first:last + 1, 1:4], Rs, keyframe=min(keyframe, last - first), scale=scale,
+                                          rot_noise_deg=rot_noise_deg, pos_noise=pos_noise, seed=seed + len(written))
+                w.sfm(float(truth[last, 0]), st, R, T)  # (where the bootstrap record stood: the replay finds a record by its stamp)
+                if rep == 0:
+                    written.append(dict(stamp=float(truth[last, 0]), stamps=st, R=R, T=T))
+    w.close()
+    return written

@@ -10,7 +10,8 @@ The first three topics are the node's own inputs (estimator_node.cpp:352-356); t
 INTEGRATION.md section 3 (one std_msgs/Float64MultiArray per successful initialStructure()).  Messages are written in the
 order the bag received them, contents unchanged (float32 bearings and channels stay float32).  --truth adds ground-truth
 records from a `stamp x y z qx qy qz qw` text file for tools/ate.py.  /pose_graph/match_points (a pose-graph node's loop
-closures, estimator_node.cpp:197-201) becomes record type 6.  No ROS installation is needed."""
+closures, estimator_node.cpp:197-201) becomes record type 6; /vins_estimator/lfvt_sfm (the SfM hook of INTEGRATION.md section 3:
+all_image_frame's stamps, R, T just before visualInitialAlign()) becomes record type 7.  No ROS installation is needed."""
 import argparse
 import os
 import sys
@@ -20,12 +21,13 @@ sys.path.insert(0, os.path.join(ROOT, "lf-vio_amd"))
 
 
 def convert(bag_path, out_path, imu_topic="/imu0", feature_topic="/feature_tracker/feature", restart_topic="/feature_tracker/restart",
-            bootstrap_topic="/vins_estimator/lfvt_bootstrap", truth_path=None, relo_topic="/pose_graph/match_points"):
+            bootstrap_topic="/vins_estimator/lfvt_bootstrap", truth_path=None, relo_topic="/pose_graph/match_points",
+            sfm_topic="/vins_estimator/lfvt_sfm"):
     import numpy as np
     from lfvio import rosmsg, trace
 
     w = trace.TraceWriter(out_path)
-    n = dict(imu=0, images=0, restarts=0, bootstraps=0, other=0)  # (+ relocalizations, when the bag has match_points)
+    n = dict(imu=0, images=0, restarts=0, bootstraps=0, other=0)  # (+ relocalizations / sfms, when the bag has those topics)
     for topic, mtype, t, payload in rosmsg.read_bag(bag_path):
         if topic == imu_topic:
             stamp, acc, gyr = rosmsg.de_imu(payload)
@@ -46,6 +48,14 @@ def convert(bag_path, out_path, imu_topic="/imu0", feature_topic="/feature_track
             stamp, index, relo_t, relo_q, pts = rosmsg.de_match_points(payload)
             w.relo(stamp, index, relo_t, relo_q, pts)
             n["relocalizations"] = n.get("relocalizations", 0) + 1
+        elif topic == sfm_topic:  # the SfM hook of INTEGRATION.md section 3: stamp, F, F x { stamp, R[9], T[3] } -> record type 7
+            d = np.asarray(rosmsg.de_f64_array(payload), dtype=np.float64)
+            F = int(d[1]) if d.size >= 2 else -1
+            if F < 0 or d[1] != F or d.size != 2 + 13 * F:
+                raise ValueError(f"{topic}: {d.size} doubles are not stamp, F, F x 13")
+            body = d[2:].reshape(F, 13)
+            w.sfm(d[0], body[:, 0], body[:, 1:10], body[:, 10:13])
+            n["sfms"] = n.get("sfms", 0) + 1
         else:
             n["other"] += 1
     if truth_path:
@@ -65,5 +75,6 @@ if __name__ == "__main__":
     ap.add_argument("--bootstrap", default="/vins_estimator/lfvt_bootstrap")
     ap.add_argument("--truth", default=None)
     ap.add_argument("--relo", default="/pose_graph/match_points")
+    ap.add_argument("--sfm", default="/vins_estimator/lfvt_sfm")
     a = ap.parse_args()
-    print(convert(a.bag, a.out, a.imu, a.features, a.restart, a.bootstrap, a.truth, a.relo))
+    print(convert(a.bag, a.out, a.imu, a.features, a.restart, a.bootstrap, a.truth, a.relo, a.sfm))
