@@ -404,6 +404,55 @@ int lfvio_vi_align(lfvio_ctx *ctx, const LfvioViAlignIn *in, LfvioViAlignOut *ou
                    double *x /* [3F] velocities of the last solve, body frames */,
                    LfvioPreintegration *pre /* [F] after the re-propagation, pre[0] untouched; or NULL */);
 
+/* lfvio_pnp: PnpSolver::compute_pose (vins_estimator/src/pnp_solver.cpp) for num_frames frames at once — the EPnP on BEARING
+ * vectors that poses every non-keyframe in the PnP loop of Estimator::initialStructure (estimator.cpp:288-357) and every keyframe
+ * inside GlobalSFM::solveFrameByPnP (initial/initial_sfm.cpp:23-71).  Internal parameters are the reference's only call form,
+ * set_internal_parameters(0, 0, 1, 1).  Frame f owns the correspondences offset[f] .. offset[f + 1] (a CSR): the SfM point and
+ * FeaturePerFrame::point as stored (not renormalised; z <= 0 is an ordinary input).  Restated literally, quirks included:
+ *   choose_control_points (:45-75): the mean, JacobiSVD of the 3 x 3 PW0^T PW0, k = sqrt(DC / n);
+ *   compute_barycentric_coordinates (:76-96); M with its division by us(i, 2) (:313-325); M^T M and its four smallest singular
+ *   vectors Ut(11 - i) (:326-333); compute_L_6x10 and compute_rho (:101-144);
+ *   find_betas_0 / _1 / _2 (:145-230) over colPivHouseholderQr().solve with Eigen's rank threshold (a pivot column whose norm
+ *     falls below eps x the largest column norm x sqrt((rows - k) / rows) ends the factorization; the dropped components are 0);
+ *     `B5[0] = -B5[0]` of :226-227 comes after the last use of B5[0] and changes nothing — Betas[0] is NOT negated there;
+ *   gauss_newton (:388-405): exactly 15 iterations, no convergence test;
+ *   solve_for_sign (:246-254): the sign of the FIRST correspondence only;
+ *   estimate_R_and_t (:255-284): R = U V^T with no determinant fix (a reflection is returned as such);
+ *   reprojection_error (:285-296): the un-normalised camera point R p + T subtracted from the bearing, mean of squares;
+ *   the winner (:355-369): strict <, the first candidate wins a tie.
+ * R and T are what compute_pose returns (world to camera, before the caller's transpose of estimator.cpp:353-356).
+ * After the 15 Gauss-Newton steps the three candidates usually agree to rounding, so `chosen` is decided by rounding: hold
+ * R, T and err[chosen], not chosen.
+ * Deviations from the reference:
+ *   1. a non-finite value among err[0..2] or the winner's R, T (a bearing with z == 0; coplanar points, whose CC is singular)
+ *      returns status = 1 for that frame and leaves R, T, err and chosen of that frame as the caller had them; the other frames
+ *      of the call are not affected;
+ *   2. the signs an SVD gives its vectors are not Eigen's.  For the null vectors of M^T M and the vectors of W the result does
+ *      not depend on them beyond rounding.  For the principal axes of choose_control_points it does: flipping an axis moves a
+ *      control point, and with noisy bearings the pose changes at the level of the noise (measured 1.4e-2 in R at 1 px,
+ *      f = 160; below 2e-14 with exact bearings).  Here each axis gets the sign that makes its largest component (the first of
+ *      equal ones) positive; which sign Eigen's JacobiSVD returns is not reproduced;
+ *   3. M^T M is summed as the 40 distinct sums a_j a_k {1, x, y, x^2 + y^2}, x = (0 - u_0) / u_2, y = (0 - u_1) / u_2; these, W and
+ *      the means are summed in the device's own fixed order (no atomics): a call returns the same bits every time and a
+ *      batch of F frames returns the bits of F single-frame calls.
+ * LFVIO_ERR_ARG (outputs untouched): null pointers, num_frames outside [1, LFVIO_MAX_IMAGE_FRAMES], offset[0] != 0, a frame
+ * with fewer than 6 or more than 4096 correspondences (which covers an offset array that is not ascending).
+ * One upload, one launch (one workgroup per frame), one download; runs on the feature stream like lfvio_triangulate: it
+ * does not wait for an optimization in flight. */
+typedef struct {
+  int num_frames;        /* F in [1, LFVIO_MAX_IMAGE_FRAMES] */
+  const int *offset;     /* [F + 1] offset[0] = 0, 6 <= offset[f + 1] - offset[f] <= 4096 */
+  const double *point_w; /* [M][3] SfM points, M = offset[F] */
+  const double *bearing; /* [M][3] FeaturePerFrame::point of the frame, as stored */
+} LfvioPnpIn;
+typedef struct {
+  int status;            /* 0 posed; 1 a non-finite value (deviation 1) */
+  int chosen;            /* index of the winning candidate (decided by rounding, see above) */
+  double R[9], T[3];     /* compute_pose's R (row-major) and T: x_cam = R x_w + T */
+  double err[3];         /* reprojection_error of the candidates of find_betas_0 / _1 / _2 */
+} LfvioPnpOut;
+int lfvio_pnp(lfvio_ctx *ctx, const LfvioPnpIn *in, LfvioPnpOut *out /* [F] */);
+
 /* ---- landmark-sharded API (multi-GPU) ------------------------
  * Every rank passes the same window but linearizes only landmarks [lm_begin, lm_end) (caller order);
  * IMU factors and the prior are added on the rank(s) with add_pose_side != 0 — exactly one rank.

@@ -43,6 +43,7 @@ constexpr ncclDataType_t ncclDouble = 8;
 #include "kernels_relo.h"
 #include "kernels_twoview.h"
 #include "kernels_vialign.h"
+#include "kernels_pnp.h"
 
 #define HIPCHK(ctx, call)                                                                      \
   do {                                                                                         \
@@ -2496,6 +2497,8 @@ int lfvio_debug_query(lfvio_ctx *c, const char *key, double *out, int n) {
 #include "twoview.inc"
 
 #include "vialign.inc"
+
+#include "pnp.inc"
 // ---- landmark-sharded API: declared in lfvio.h, implemented in shard.inc
 #include "shard.inc"
 // ---- multi-GPU groups (RCCL): declared in lfvio.h, implemented in group.inc

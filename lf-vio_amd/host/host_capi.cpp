@@ -415,6 +415,45 @@ void lfvio_host_set_sfm(void *h, int n, const double *stamps, const double *R, c
   s.stamps.assign(stamps, stamps + n), s.R.assign(R, R + 9 * (size_t)n), s.T.assign(T, T + 3 * (size_t)n);
   s.valid = true;
 }
+// SfmStructure (what GlobalSFM::construct() returns): K keyframes stamps[K], Q[K][4] (w x y z), T[K][3]; P points ids[P], xyz[P][3];
+// used by the next full-window image when neither a bootstrap record nor an SfM result is set
+void lfvio_host_set_sfm_structure(void *h, int K, const double *stamps, const double *Q, const double *T, int P, const int *ids, const double *xyz) {
+  WindowEstimator::SfmStructure &s = E(h)->structure;
+  s.stamps.assign(stamps, stamps + K), s.Q.assign(Q, Q + 4 * (size_t)K), s.T.assign(T, T + 3 * (size_t)K);
+  s.ids.assign(ids, ids + P), s.xyz.assign(xyz, xyz + 3 * (size_t)P);
+  s.valid = true;
+}
+// ImageFrame::points of entry k of all_image_frame: ids[cap], pts[cap][3]; returns their number, -1: no such entry
+int lfvio_host_image_frame_points(void *h, int k, int cap, int *ids, double *pts) {
+  const std::vector<WindowEstimator::ImageFrame> &l = E(h)->image_frames;
+  if (k < 0 || k >= (int)l.size()) return -1;
+  const size_t n = std::min(l[k].ids.size(), (size_t)std::max(cap, 0));
+  if (n && ids) std::memcpy(ids, l[k].ids.data(), n * 4);
+  if (n && pts) std::memcpy(pts, l[k].pts.data(), n * 24);
+  return (int)l[k].ids.size();
+}
+// What the last attempt handed to lfvio_pnp and got back.  info[4] = {non-keyframes F, correspondences M, device call made, its
+// return code}; the arrays (any may be null) take at most cap_frames / cap_points: stamps[F], offset[F + 1], pw[M][3], us[M][3],
+// out[F].  Returns the number of device calls so far.
+long long lfvio_host_last_pnp(void *h, int cap_frames, int cap_points, int *info, double *stamps, int *offset, double *pw, double *us, LfvioPnpOut *out) {
+  const WindowEstimator::LastPnp &v = E(h)->last_pnp;
+  const int F = (int)v.stamps.size(), M = (int)(v.us.size() / 3);
+  info[0] = F, info[1] = M, info[2] = v.called ? 1 : 0, info[3] = v.rc;
+  const size_t f = (size_t)std::min(F, cap_frames), m = (size_t)std::min(M, cap_points);
+  if (stamps && f) std::memcpy(stamps, v.stamps.data(), f * 8);
+  if (offset && f && f == (size_t)F) std::memcpy(offset, v.offset.data(), (f + 1) * 4);
+  if (pw && m) std::memcpy(pw, v.pw.data(), m * 24);
+  if (us && m) std::memcpy(us, v.us.data(), m * 24);
+  if (out && f && v.out.size() >= f) std::memcpy(out, v.out.data(), f * sizeof(LfvioPnpOut));
+  return E(h)->pnp_calls;
+}
+// the SfM result as the estimator holds it (after solvePnpFrames(): every frame of the list): returns n; stamps[cap], R[cap][9], T[cap][3]
+int lfvio_host_get_sfm(void *h, int cap, double *stamps, double *R, double *T) {
+  const WindowEstimator::SfmResult &s = E(h)->sfm;
+  const size_t n = std::min(s.stamps.size(), (size_t)std::max(cap, 0));
+  if (n) std::memcpy(stamps, s.stamps.data(), n * 8), std::memcpy(R, s.R.data(), n * 72), std::memcpy(T, s.T.data(), n * 24);
+  return (int)s.stamps.size();
+}
 // all_image_frame: stamps[cap], samples per entry [cap]; returns the length of the list
 int lfvio_host_image_frames(void *h, int cap, double *stamps, int *num_samples) {
   const std::vector<WindowEstimator::ImageFrame> &l = E(h)->image_frames;
@@ -462,6 +501,27 @@ int lfvio_host_trace_sfms(const char *trace_path, int cap, double *stamps, int *
     std::memcpy(first_R, trace.sfms[0].sfm.R.data(), n * 72), std::memcpy(first_T, trace.sfms[0].sfm.T.data(), n * 24);
   }
   return (int)trace.sfms.size();
+}
+
+// the SfM structure records of a trace file: stamps[cap] of the records, counts[cap][2] = {keyframes, points} in each; of the
+// first record (any may be null) kf[cap_kf][8] = {stamp, q w x y z, T} and pts[cap_pts][4] = {id, xyz}; returns their number, -1: unreadable
+int lfvio_host_trace_structures(const char *trace_path, int cap, double *stamps, int *counts, double *kf, int cap_kf, double *pts, int cap_pts) {
+  Trace trace;
+  if (!trace.load(trace_path)) return -1;
+  const std::vector<TraceStructure> &v = trace.structures;
+  for (int k = 0; k < (int)v.size() && k < cap; k++) stamps[k] = v[k].stamp, counts[2 * k] = (int)v[k].st.stamps.size(), counts[2 * k + 1] = (int)v[k].st.ids.size();
+  if (!v.empty()) {
+    const WindowEstimator::SfmStructure &s = v[0].st;
+    for (size_t k = 0; kf && k < s.stamps.size() && k < (size_t)cap_kf; k++) {
+      kf[8 * k] = s.stamps[k];
+      std::memcpy(kf + 8 * k + 1, &s.Q[4 * k], 32), std::memcpy(kf + 8 * k + 5, &s.T[3 * k], 24);
+    }
+    for (size_t k = 0; pts && k < s.ids.size() && k < (size_t)cap_pts; k++) {
+      pts[4 * k] = s.ids[k];
+      std::memcpy(pts + 4 * k + 1, &s.xyz[3 * k], 24);
+    }
+  }
+  return (int)v.size();
 }
 
 int lfvio_host_optimization(void *h) {

@@ -107,6 +107,32 @@ bool Trace::load(const char *path) {
       s.sfm.valid = true;
       s.at_image = images.size();
       sfms.push_back(std::move(s));
+    } else if (head[0] == 8 && head[1] >= 16) {
+      uint32_t kp[2];
+      std::memcpy(kp, buf.data() + 8, 8);
+      if (head[1] != 16 + ((size_t)kp[0] * 8 + (size_t)kp[1] * 4) * sizeof(double)) {
+        error = "SfM structure record with a wrong length";
+        std::fclose(f);
+        return false;
+      }
+      TraceStructure s;
+      s.stamp = d[0];
+      const char *p = buf.data() + 16;
+      for (uint32_t k = 0; k < kp[0]; k++, p += 64) {
+        double v[8];
+        std::memcpy(v, p, sizeof v);
+        s.st.stamps.push_back(v[0]);
+        s.st.Q.insert(s.st.Q.end(), v + 1, v + 5), s.st.T.insert(s.st.T.end(), v + 5, v + 8);
+      }
+      for (uint32_t k = 0; k < kp[1]; k++, p += 32) {
+        double v[4];
+        std::memcpy(v, p, sizeof v);
+        s.st.ids.push_back((int)v[0]);
+        s.st.xyz.insert(s.st.xyz.end(), v + 1, v + 4);
+      }
+      s.st.valid = true;
+      s.at_image = images.size();
+      structures.push_back(std::move(s));
     }
   }
   std::fclose(f);
@@ -152,7 +178,7 @@ int replay(WindowEstimator &est, const Trace &trace, const char *traj_path, int 
       for (int j = 0; j < 3; j++) est.ric(i, j) = trace.ric[3 * i + j];
     est.td = trace.td;
   }
-  size_t next_boot = 0, next_restart = 0, image_index = 0, next_relo = 0, next_sfm = 0;
+  size_t next_boot = 0, next_restart = 0, image_index = 0, next_relo = 0, next_sfm = 0, next_structure = 0;
   const int relo_solves0 = est.relo_solves;
   const std::vector<TraceImu> &imu = trace.imu;
   size_t front = 0;         // head of the IMU queue
@@ -187,6 +213,10 @@ int replay(WindowEstimator &est, const Trace &trace, const char *traj_path, int 
     if (est.phase == WindowEstimator::INITIAL) {
       while (next_sfm < trace.sfms.size() && trace.sfms[next_sfm].stamp < msg.t - 1e-6) next_sfm++;
       if (next_sfm < trace.sfms.size() && !(trace.sfms[next_sfm].stamp > msg.t + 1e-6)) est.sfm = trace.sfms[next_sfm++].sfm;
+      // ... and the next SfM structure record (an SfM result for the same image wins inside the estimator)
+      while (next_structure < trace.structures.size() && trace.structures[next_structure].stamp < msg.t - 1e-6) next_structure++;
+      if (next_structure < trace.structures.size() && !(trace.structures[next_structure].stamp > msg.t + 1e-6))
+        est.structure = trace.structures[next_structure++].st;
     }
     // getMeasurements(), estimator_node.cpp:96-134, against the CURRENT time-offset estimate
     const double img_t = msg.t + est.td;

@@ -27,6 +27,13 @@
 //                                     estimator aligns it with its own IMU data (WindowEstimator::visualInitialAlign).  A
 //                                     bootstrap record for the same image wins.
 //
+//   type 8 = SfM structure            f64 stamp (Headers[WINDOW_SIZE] when GlobalSFM::construct() had succeeded), u32 K, u32 P,
+//                                     K x { f64 stamp, q[4] (w x y z), T[3] }: Q[i], T[i] of the window's keyframes as construct()
+//                                     returns them (estimator.cpp:268-286), P x { f64 id, xyz[3] }: sfm_tracked_points.  Handed
+//                                     over as type 7 is; the estimator runs the PnP loop (estimator.cpp:288-357,
+//                                     WindowEstimator::solvePnpFrames) and then the same alignment.  A bootstrap record or an
+//                                     SfM result for the same image wins.
+//
 // Unknown record types are skipped, so a recorder can add its own.
 #pragma once
 #include <cstdint>
@@ -64,8 +71,14 @@ struct TraceSfm {  // record type 7
   WindowEstimator::SfmResult sfm;
   size_t at_image;  // images recorded before it
 };
+struct TraceStructure {  // record type 8
+  double stamp;
+  WindowEstimator::SfmStructure st;
+  size_t at_image;  // images recorded before it
+};
 struct Trace {
   std::vector<TraceSfm> sfms;         // in file order
+  std::vector<TraceStructure> structures;  // in file order
   std::vector<TraceRelo> relos;       // in file order
   std::vector<TraceImu> imu;
   std::vector<TraceImage> images;

@@ -7,6 +7,7 @@
 // ... nor a two-view entry point: there ESTIMATE_EXTRINSIC == 2 reports LFVIO_ERR_DEVICE on the first image that needs it.
 #pragma weak lfvio_two_view
 #pragma weak lfvio_vi_align
+#pragma weak lfvio_pnp
 
 #include <algorithm>
 #include <cmath>
@@ -299,6 +300,7 @@ void WindowEstimator::reset() {
   bootstrap.valid = false;
   bootstrap.depth_ids.clear(), bootstrap.depths.clear();
   sfm.valid = false;
+  structure.valid = false;
   image_frames.clear();  // clearState(): all_image_frame.clear(), tmp_pre_integration = nullptr (estimator.cpp:60-66)
   pending_ = ImageFrame();
 }
@@ -376,6 +378,90 @@ Matrix3d g2R(const Vector3d &g) {  // Utility::g2R (utility.cpp:3-13): FromTwoVe
   return fromYawPitchRollDeg(Vector3d(-yaw, 0, 0)) * R0;
 }
 }  // namespace
+
+bool WindowEstimator::solvePnpFrames() {  // estimator.cpp:288-357
+  const Config &c = config();
+  LastPnp &lp = last_pnp;
+  lp.called = false, lp.rc = LFVIO_OK;
+  lp.stamps.clear(), lp.offset.assign(1, 0), lp.pw.clear(), lp.us.clear(), lp.out.clear();
+  sfm.valid = false;
+  const SfmStructure &st = structure;
+  const int F = (int)image_frames.size(), K = (int)st.stamps.size();
+  if (F < 1 || F > LFVIO_MAX_IMAGE_FRAMES || st.Q.size() < 4 * (size_t)K || st.T.size() < 3 * (size_t)K || st.xyz.size() < 3 * st.ids.size()) return false;
+  Matrix3d RIC;
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++) RIC(i, j) = c.ric[3 * i + j];
+  // every keyframe of the window must be in the structure
+  for (int i = 0; i <= frame_count; i++)
+    if (std::find(st.stamps.begin(), st.stamps.end(), kf(i).stamp) == st.stamps.end()) return false;
+  std::vector<int> by_id(st.ids.size());  // sfm_tracked_points.find()
+  std::iota(by_id.begin(), by_id.end(), 0);
+  std::sort(by_id.begin(), by_id.end(), [&](int a, int b) { return st.ids[a] < st.ids[b]; });
+  auto findPoint = [&](int id) {
+    auto it = std::lower_bound(by_id.begin(), by_id.end(), id, [&](int a, int v) { return st.ids[a] < v; });
+    return it != by_id.end() && st.ids[*it] == id ? *it : -1;
+  };
+  sfm.stamps.assign(F, 0.0), sfm.R.assign(9 * (size_t)F, 0.0), sfm.T.assign(3 * (size_t)F, 0.0);
+  std::vector<int> frame_of;  // list index of each non-keyframe
+  for (int k = 0; k < F; k++) {
+    const ImageFrame &f = image_frames[k];
+    sfm.stamps[k] = f.stamp;
+    bool key = false;
+    for (int i = 0; i <= frame_count; i++) key = key || kf(i).stamp == f.stamp;
+    if (key) {  // :296-303
+      const int j = (int)(std::find(st.stamps.begin(), st.stamps.end(), f.stamp) - st.stamps.begin());
+      const Matrix3d R = Quaterniond(st.Q[4 * j], st.Q[4 * j + 1], st.Q[4 * j + 2], st.Q[4 * j + 3]).toRotationMatrix() * RIC.transpose();
+      for (int a = 0; a < 3; a++)
+        for (int b = 0; b < 3; b++) sfm.R[9 * (size_t)k + 3 * a + b] = R(a, b);
+      std::memcpy(&sfm.T[3 * (size_t)k], &st.T[3 * (size_t)j], 24);
+      continue;
+    }
+    for (size_t m = 0; m < f.ids.size(); m++) {  // :318-333
+      const int p = findPoint(f.ids[m]);
+      if (p < 0) continue;
+      lp.us.insert(lp.us.end(), &f.pts[3 * m], &f.pts[3 * m] + 3);
+      lp.pw.insert(lp.pw.end(), &st.xyz[3 * (size_t)p], &st.xyz[3 * (size_t)p] + 3);
+    }
+    const int n = (int)(lp.us.size() / 3) - lp.offset.back();
+    lp.stamps.push_back(f.stamp), lp.offset.push_back(lp.offset.back() + n), frame_of.push_back(k);
+    if (n < 6 || n > 4096) return false;  // :335-340 "Not enough points for solve pnp !" (4096: the device entry's limit)
+  }
+  const int NF = (int)frame_of.size();
+  if (NF > 0) {
+    if (!lfvio_pnp || !device()) {  // no fallback: over an ABI without the entry the attempt fails and the window slides
+      status = LFVIO_ERR_DEVICE;
+      lp.rc = LFVIO_ERR_DEVICE;
+      return false;
+    }
+    lp.out.resize(NF);
+    std::memset(lp.out.data(), 0, sizeof(LfvioPnpOut) * (size_t)NF);
+    LfvioPnpIn in;
+    in.num_frames = NF, in.offset = lp.offset.data(), in.point_w = lp.pw.data(), in.bearing = lp.us.data();
+    lp.rc = lfvio_pnp(gpu, &in, lp.out.data());
+    lp.called = true;
+    pnp_calls++;
+    if (lp.rc != LFVIO_OK) {
+      status = lp.rc;
+      return false;
+    }
+    for (int q = 0; q < NF; q++) {
+      const LfvioPnpOut &o = lp.out[q];
+      if (o.status != 0) return false;
+      Matrix3d tmp;
+      for (int a = 0; a < 3; a++)
+        for (int b = 0; b < 3; b++) tmp(a, b) = o.R[3 * a + b];
+      const Matrix3d R_pnp = tmp.transpose();                             // :353
+      const Vector3d T_pnp = R_pnp * (-Vector3d(o.T[0], o.T[1], o.T[2]));  // :354
+      const Matrix3d R = R_pnp * RIC.transpose();                         // :355
+      const int k = frame_of[q];
+      for (int a = 0; a < 3; a++)
+        for (int b = 0; b < 3; b++) sfm.R[9 * (size_t)k + 3 * a + b] = R(a, b);
+      for (int a = 0; a < 3; a++) sfm.T[3 * (size_t)k + a] = T_pnp(a);
+    }
+  }
+  sfm.valid = true;
+  return true;
+}
 
 bool WindowEstimator::visualInitialAlign() {  // estimator.cpp:367-443 on the SfM poses of `sfm`; VisualIMUAlignment on the device
   const Config &c = config();
@@ -667,6 +753,16 @@ void WindowEstimator::pushImage(double stamp, int n, const int *ids, const doubl
   kf(frame_count).stamp = stamp;
   {  // estimator.cpp:137-140: the image takes tmp_pre_integration, a new one starts at the last IMU sample with this frame's biases
     pending_.stamp = stamp;
+    {  // :134 ImageFrame(image, header): the points, in the order of the reference's map
+      std::vector<int> order(n);
+      std::iota(order.begin(), order.end(), 0);
+      std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return ids[a] < ids[b]; });
+      pending_.ids.resize(n), pending_.pts.resize(3 * (size_t)n);
+      for (int k = 0; k < n; k++) {
+        pending_.ids[k] = ids[order[k]];
+        std::memcpy(&pending_.pts[3 * (size_t)k], pts8 + 8 * (size_t)order[k], 24);
+      }
+    }
     image_frames.push_back(std::move(pending_));
     pending_ = ImageFrame();
     const Keyframe &f = kf(frame_count);
@@ -699,8 +795,12 @@ void WindowEstimator::advanceWindow(double stamp) {  // estimator.cpp:161-220
       } else if (sfm.valid) {
         aligned = visualInitialAlign();
         from_sfm = aligned;
+      } else if (structure.valid) {  // the PnP loop first, then the same path
+        aligned = solvePnpFrames() && visualInitialAlign();
+        from_sfm = aligned;
       }
       sfm.valid = false;
+      structure.valid = false;
       if (from_sfm && stop_after_align) return;
       initial_timestamp = stamp;
     }

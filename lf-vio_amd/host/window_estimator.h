@@ -272,6 +272,10 @@ class WindowEstimator {
     double stamp = 0;
     std::vector<double> dt, acc, gyr;
     double acc0[3] = {0, 0, 0}, gyr0[3] = {0, 0, 0}, lin_ba[3] = {0, 0, 0}, lin_bg[3] = {0, 0, 0};
+    // ImageFrame::points (estimator.cpp:134): the image's feature ids in ascending order (the iteration order of the reference's
+    // std::map) and their bearings x y z as stored; kept and erased with the entry
+    std::vector<int> ids;
+    std::vector<double> pts;  // 3 per id
   };
   std::vector<ImageFrame> image_frames;
   // What relativePose() + GlobalSFM::construct() + the PnP loop leave in all_image_frame (estimator.cpp:250-357): per image
@@ -282,6 +286,31 @@ class WindowEstimator {
     bool valid = false;
     std::vector<double> stamps, R, T;  // n | 9n row-major | 3n
   } sfm;
+  // What GlobalSFM::construct() returns through its arguments (initial/initial_sfm.cpp:128-287; estimator.cpp:268-286): Q[i], T[i]
+  // of the window's keyframes (camera rotation and position in the frame of keyframe l, unscaled) and sfm_tracked_points.  The
+  // PnP loop of initialStructure() (estimator.cpp:288-357) turns it into an SfmResult: solvePnpFrames().
+  struct SfmStructure {
+    bool valid = false;
+    std::vector<double> stamps, Q, T;  // K | 4K (w x y z) | 3K
+    std::vector<int> ids;              // P, sfm_tracked_points' keys
+    std::vector<double> xyz;           // 3P
+  } structure;
+  // estimator.cpp:288-357 on `structure`: a frame of the list whose stamp is a keyframe's takes R = Q[i] RIC^T, T = T[i]; every
+  // other frame gathers (SfM point, bearing) for its features that the structure holds, in ascending id order, and ALL of them are
+  // posed by ONE lfvio_pnp call; R_pnp^T RIC^T and R_pnp^T (-T_pnp) as :353-356 have them.  Fills `sfm` and returns true; false
+  // (initialization fails for this image, the window slides) when the structure misses a keyframe of the window, a non-keyframe
+  // has fewer than 6 correspondences (:335-340) or more than 4096, the list is longer than LFVIO_MAX_IMAGE_FRAMES, or a frame comes
+  // back with status 1 (include/lfvio.h, deviation 1).  The initial guess of :308-312 is never read by the solver and is not formed.
+  bool solvePnpFrames();
+  struct LastPnp {  // what the last attempt passed to lfvio_pnp and got back (tests, tools)
+    bool called = false;
+    int rc = LFVIO_OK;
+    std::vector<double> stamps;  // of the non-keyframes, in list order
+    std::vector<int> offset;     // CSR over them
+    std::vector<double> pw, us;
+    std::vector<LfvioPnpOut> out;
+  } last_pnp;
+  long long pnp_calls = 0;
   struct LastViAlign {  // what the last attempt passed to lfvio_vi_align and got back (tests, tools)
     bool called = false;
     int rc = LFVIO_OK;

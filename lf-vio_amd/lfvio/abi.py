@@ -437,6 +437,33 @@ class ViAlignOutC(C.Structure):
                     g_iter=np.array([list(r) for r in self.g_iter], dtype=np.float64), g=a(self.g), s=float(self.s))
 
 
+class PnpInC(C.Structure):
+    """LfvioPnpIn (include/lfvio.h)."""
+    _fields_ = [
+        ("num_frames", C.c_int),
+        ("offset", C.POINTER(C.c_int)),
+        ("point_w", C.POINTER(C.c_double)),
+        ("bearing", C.POINTER(C.c_double)),
+    ]
+
+
+class PnpOutC(C.Structure):
+    """LfvioPnpOut (include/lfvio.h)."""
+    _fields_ = [
+        ("status", C.c_int),
+        ("chosen", C.c_int),
+        ("R", C.c_double * 9),
+        ("T", C.c_double * 3),
+        ("err", C.c_double * 3),
+    ]
+
+    def as_dict(self):
+        a = lambda x: np.array(x, dtype=np.float64)
+        return dict(status=int(self.status), chosen=int(self.chosen), R=a(self.R).reshape(3, 3), T=a(self.T), err=a(self.err))
+
+
+PNP_MIN_POINTS, PNP_MAX_POINTS = 6, 4096
+
 HIP_SYMBOLS = [
     "lfvio_create", "lfvio_destroy", "lfvio_last_error", "lfvio_version", "lfvio_solve", "lfvio_solve_relo", "lfvio_marginalize",
     "lfvio_batch_reserve", "lfvio_batch_upload", "lfvio_batch_optimize", "lfvio_batch_optimize_async",
@@ -445,7 +472,7 @@ HIP_SYMBOLS = [
     "lfvio_shard_begin", "lfvio_shard_exchange_len", "lfvio_shard_scalar_offset", "lfvio_shard_exchange_ptr", "lfvio_shard_linearize",
     "lfvio_shard_solve", "lfvio_shard_candidate", "lfvio_shard_decide", "lfvio_shard_marg_linearize", "lfvio_shard_marg_finish",
     "lfvio_shard_finish", "lfvio_shard_restart", "lfvio_shard_enqueue", "lfvio_shard_poll", "lfvio_triangulate", "lfvio_shift_depth", "lfvio_preintegrate",
-    "lfvio_two_view", "lfvio_vi_align",
+    "lfvio_two_view", "lfvio_vi_align", "lfvio_pnp",
     "lfvio_group_create", "lfvio_group_unique_id", "lfvio_group_create_rank", "lfvio_group_create_local", "lfvio_group_destroy",
     "lfvio_group_last_error", "lfvio_group_size", "lfvio_group_local", "lfvio_group_rank", "lfvio_group_ctx", "lfvio_group_backend",
     "lfvio_group_solve", "lfvio_group_upload", "lfvio_group_optimize", "lfvio_group_download", "lfvio_group_range",
@@ -512,6 +539,8 @@ def load_hip_library(path=None):
     lib.lfvio_two_view.argtypes = [C.c_void_p, C.POINTER(TwoViewInC), C.POINTER(C.c_ubyte), C.POINTER(TwoViewOutC), _dp, C.POINTER(C.c_float)]
     if hasattr(lib, "lfvio_vi_align"):  # (an A/B run may load a build from before the entry existed; build() checks the product's symbols)
         lib.lfvio_vi_align.argtypes = [C.c_void_p, C.POINTER(ViAlignInC), C.POINTER(ViAlignOutC), _dp, C.POINTER(Preintegration)]
+    if hasattr(lib, "lfvio_pnp"):
+        lib.lfvio_pnp.argtypes = [C.c_void_p, C.POINTER(PnpInC), C.POINTER(PnpOutC)]
     lib.lfvio_shard_marg_linearize.argtypes = [C.c_void_p, C.c_int]
     lib.lfvio_shard_marg_finish.argtypes = [C.c_void_p, C.c_int, C.POINTER(Prior)]
     # multi-GPU groups (RCCL inside the library)

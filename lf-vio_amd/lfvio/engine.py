@@ -308,6 +308,25 @@ class Engine:
         res.update(rc=rc, x=x, pre=pre)
         return res
 
+    def pnp(self, offset, point_w, bearing, out=None, check=True):
+        """lfvio_pnp: PnpSolver::compute_pose for the F frames of a CSR of correspondences — offset [F + 1], point_w [M, 3] (SfM
+        points), bearing [M, 3] (FeaturePerFrame::point as stored).  Returns a list of F dicts with the fields of LfvioPnpOut
+        (R [3, 3] and T as compute_pose returns them).  out: an array of abi.PnpOutC to be written (a test of what a failed
+        call or a status-1 frame leaves alone passes its own); check=False returns (rc, list) instead of raising."""
+        off = np.ascontiguousarray(offset, dtype=np.int32).reshape(-1)
+        pw = np.ascontiguousarray(point_w, dtype=np.float64).reshape(-1, 3)
+        us = np.ascontiguousarray(bearing, dtype=np.float64).reshape(-1, 3)
+        F = len(off) - 1
+        pin = abi.PnpInC()
+        pin.num_frames, pin.offset, pin.point_w, pin.bearing = F, off.ctypes.data_as(C.POINTER(C.c_int)), _p(pw), _p(us)
+        out = (abi.PnpOutC * max(F, 1))() if out is None else out
+        rc = self.lib.lfvio_pnp(self.ctx, C.byref(pin), out)
+        res = [out[f].as_dict() for f in range(max(F, 0))]
+        if check:
+            self._check(rc, "lfvio_pnp")
+            return res
+        return rc, res
+
     def time_kernel(self, which, count, reps):
         ms = np.zeros(1)
         self._check(self.lib.lfvio_debug_time_kernel(self.ctx, which, count, reps, _p(ms)), "time_kernel")

@@ -355,6 +355,46 @@ class HostEstimator:
         self.L.lfvio_host_set_sfm.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp]
         self.L.lfvio_host_set_sfm(self.h, len(st), _p(st), _p(R), _p(T))
 
+    def set_sfm_structure(self, stamps, Q, T, ids, xyz):
+        """What GlobalSFM::construct() returns, for the next full-window image: the window's keyframes (stamps [K], Q [K, 4] as
+        w x y z, T [K, 3]: camera rotation and position in the SfM frame) and sfm_tracked_points (ids [P], xyz [P, 3]).  The
+        estimator runs the PnP loop on it (lfvio_pnp) and then the alignment."""
+        st, Q, T, xyz = _f(stamps).reshape(-1), _f(Q).reshape(-1, 4), _f(T).reshape(-1, 3), _f(xyz).reshape(-1, 3)
+        ids = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        assert len(st) == len(Q) == len(T) and len(ids) == len(xyz)
+        ip = C.POINTER(C.c_int)
+        self.L.lfvio_host_set_sfm_structure.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, C.c_int, ip, _dp]
+        self.L.lfvio_host_set_sfm_structure.restype = None
+        self.L.lfvio_host_set_sfm_structure(self.h, len(st), _p(st), _p(Q), _p(T), len(ids), ids.ctypes.data_as(ip), _p(xyz))
+
+    def sfm(self, cap=1024):
+        """The SfM result the estimator holds (after the PnP loop: every frame of all_image_frame): (stamps, R [n, 3, 3], T [n, 3])."""
+        st, R, T = np.zeros(cap), np.zeros((cap, 9)), np.zeros((cap, 3))
+        self.L.lfvio_host_get_sfm.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp]
+        n = min(self.L.lfvio_host_get_sfm(self.h, cap, _p(st), _p(R), _p(T)), cap)
+        return st[:n].copy(), R[:n].reshape(n, 3, 3).copy(), T[:n].copy()
+
+    def image_frame_points(self, k, cap=4096):
+        """ImageFrame::points of entry k of all_image_frame: (ids ascending, bearings [n, 3]); None when there is no such entry."""
+        ids, pts = np.zeros(cap, dtype=np.int32), np.zeros((cap, 3))
+        self.L.lfvio_host_image_frame_points.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), _dp]
+        n = self.L.lfvio_host_image_frame_points(self.h, int(k), cap, ids.ctypes.data_as(C.POINTER(C.c_int)), _p(pts))
+        return None if n < 0 else (ids[:n].copy(), pts[:n].copy())
+
+    def last_pnp(self, cap_frames=128, cap_points=1 << 17):
+        """What the last attempt passed to lfvio_pnp and got back: dict(stamps (of the non-keyframes), offset, pw, us, out (a list of
+        the fields of LfvioPnpOut), called, rc, calls)."""
+        info = np.zeros(4, dtype=np.int32)
+        st, off = np.zeros(cap_frames), np.zeros(cap_frames + 1, dtype=np.int32)
+        pw, us, out = np.zeros((cap_points, 3)), np.zeros((cap_points, 3)), (abi.PnpOutC * cap_frames)()
+        ip = C.POINTER(C.c_int)
+        self.L.lfvio_host_last_pnp.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, _dp, ip, _dp, _dp, C.POINTER(abi.PnpOutC)]
+        self.L.lfvio_host_last_pnp.restype = C.c_longlong
+        calls = self.L.lfvio_host_last_pnp(self.h, cap_frames, cap_points, info.ctypes.data_as(ip), _p(st), off.ctypes.data_as(ip), _p(pw), _p(us), out)
+        F, M = int(info[0]), int(info[1])
+        return dict(stamps=st[:F].copy(), offset=off[:F + 1].copy(), pw=pw[:M].copy(), us=us[:M].copy(),
+                    out=[out[f].as_dict() for f in range(F)] if info[2] else [], called=bool(info[2]), rc=int(info[3]), calls=int(calls))
+
     def set_td(self, td):
         """The CONFIGURED time offset (what a reset restores); with set_extrinsic() what a recording without bootstrap records needs."""
         self.L.lfvio_host_set_td.argtypes = [C.c_double]

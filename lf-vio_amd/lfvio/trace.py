@@ -10,7 +10,7 @@ import numpy as np
 from . import abi, synth
 
 MAGIC = b"LFVT"
-REC_IMU, REC_FEATURES, REC_BOOTSTRAP, REC_TRUTH, REC_RESTART, REC_RELO, REC_SFM = 1, 2, 3, 4, 5, 6, 7
+REC_IMU, REC_FEATURES, REC_BOOTSTRAP, REC_TRUTH, REC_RESTART, REC_RELO, REC_SFM, REC_STRUCTURE = 1, 2, 3, 4, 5, 6, 7, 8
 
 
 class TraceWriter:
@@ -65,6 +65,17 @@ class TraceWriter:
         body = np.concatenate([stamps[:, None], R, T], axis=1).astype("<f8")
         self._rec(REC_SFM, struct.pack("<dI", stamp, len(stamps)) + body.tobytes())
 
+    def structure(self, stamp, stamps, Q, T, ids, xyz):
+        """An SfM structure (type 8): stamp of the image it belongs to (Headers[WINDOW_SIZE]), then what GlobalSFM::construct() returns:
+        per keyframe of the window its stamp, Q [4] (w x y z) and T [3] (camera rotation and position in the SfM frame, unscaled),
+        and sfm_tracked_points as (id, xyz)."""
+        stamps, Q, T = np.asarray(stamps, np.float64).reshape(-1), np.asarray(Q, np.float64).reshape(-1, 4), np.asarray(T, np.float64).reshape(-1, 3)
+        ids, xyz = np.asarray(ids, np.float64).reshape(-1), np.asarray(xyz, np.float64).reshape(-1, 3)
+        assert len(stamps) == len(Q) == len(T) and len(ids) == len(xyz)
+        kf = np.concatenate([stamps[:, None], Q, T], axis=1).astype("<f8")
+        pt = np.concatenate([ids[:, None], xyz], axis=1).astype("<f8")
+        self._rec(REC_STRUCTURE, struct.pack("<dII", stamp, len(stamps), len(ids)) + kf.tobytes() + pt.tobytes())
+
     def truth(self, t, p, q_xyzw):
         self._rec(REC_TRUTH, struct.pack("<8d", t, *p, *q_xyzw))
 
@@ -74,7 +85,7 @@ class TraceWriter:
 
 def read_trace(path):
     """-> dict(imu [n,7], images [(t, array[n,9] float32)], bootstrap array or None, truth [n,8])"""
-    out = dict(imu=[], images=[], bootstrap=None, bootstraps=[], restarts=[], truth=[], relos=[], sfms=[], order=[])
+    out = dict(imu=[], images=[], bootstrap=None, bootstraps=[], restarts=[], truth=[], relos=[], sfms=[], structures=[], order=[])
     with open(path, "rb") as f:
         head = f.read(8)
         assert head[:4] == MAGIC and struct.unpack("<I", head[4:])[0] == 1
@@ -105,6 +116,12 @@ def read_trace(path):
                 body = np.frombuffer(p[12:], dtype="<f8").reshape(n, 13)
                 out["sfms"].append(dict(at_image=len(out["images"]), stamp=stamp, stamps=body[:, 0].copy(), R=body[:, 1:10].reshape(n, 3, 3).copy(),
                                         T=body[:, 10:13].copy()))
+            elif kind == REC_STRUCTURE:
+                stamp, K, P = struct.unpack("<dII", p[:16])
+                kf = np.frombuffer(p[16:16 + 64 * K], dtype="<f8").reshape(K, 8)
+                pt = np.frombuffer(p[16 + 64 * K:], dtype="<f8").reshape(P, 4)
+                out["structures"].append(dict(at_image=len(out["images"]), stamp=stamp, stamps=kf[:, 0].copy(), Q=kf[:, 1:5].copy(), T=kf[:, 5:8].copy(),
+                                              ids=pt[:, 0].astype(np.int64), xyz=pt[:, 1:4].copy()))
             elif kind == REC_TRUTH:
                 out["truth"].append(struct.unpack("<8d", p))
     out["imu"] = np.array(out["imu"]).reshape(-1, 7)
@@ -242,7 +259,7 @@ def make_stream(path, seed=0, n_frames=40, n_points=600, max_cnt=150, cam_offset
         if k in boots_due:  # the estimator has refilled its window after a reboot: the hook's record for THIS image
             boot_record(boots_due[k], stamp=stamp)
     w.close()
-    return dict(scene=scene, truth=truth, images=images, bootstrap=boot, n_ids=next_id)
+    return dict(scene=scene, truth=truth, images=images, bootstrap=boot, n_ids=next_id, Xw=Xw, id_point=sp_pt[np.argsort(sp_id)])
 
 
 def sfm_from_truth(stamps, Ps, Rs, keyframe=0, scale=1.0, rot_noise_deg=0.0, pos_noise=0.0, seed=0, tic=None, ric=None):
@@ -306,5 +323,80 @@ def bootstraps_to_sfm(src, dst, keyframe=0, scale=1.0, rot_noise_deg=0.0, pos_no
                 w.sfm(float(truth[last, 0]), st, R, T)  # (where the bootstrap record stood: the replay finds a record by its stamp)
                 if rep == 0:
                     written.append(dict(stamp=float(truth[last, 0]), stamps=st, R=R, T=T))
+    w.close()
+    return written
+
+
+def structure_from_truth(stamps, Ps, Rs, ids, Xw, keyframe=0, scale=1.0, rot_noise_deg=0.0, pos_noise=0.0, point_noise=0.0, seed=0, tic=None, ric=None):
+    """What GlobalSFM::construct() would return, made from true body poses Ps [K, 3], Rs [K, 3, 3] of the window's keyframes and
+    the true landmark positions Xw [P, 3] (world frame): camera rotations Q (w x y z) and positions T in the camera frame of
+    keyframe `keyframe`, and the landmarks there, everything divided by `scale`.  Optional noise: a rotation of rot_noise_deg
+    (sigma per axis) on every Q, a relative pos_noise on every T, point_noise (relative, per coordinate) on every landmark.
+    -> (stamps, Q [K, 4], T [K, 3], ids, xyz [P, 3])."""
+    tic = synth.TIC if tic is None else np.asarray(tic, float)
+    ric = synth.RIC if ric is None else np.asarray(ric, float)
+    rng = np.random.default_rng([seed, 104723])
+    Ps, Rs, Xw = np.asarray(Ps, float).reshape(-1, 3), np.asarray(Rs, float).reshape(-1, 3, 3), np.asarray(Xw, float).reshape(-1, 3)
+    R_wcl, p_cl = Rs[keyframe] @ ric, Ps[keyframe] + Rs[keyframe] @ tic
+    Q, T = np.zeros((len(Ps), 4)), np.zeros_like(Ps)
+    for k in range(len(Ps)):
+        Rk = R_wcl.T @ Rs[k] @ ric
+        T[k] = R_wcl.T @ (Ps[k] + Rs[k] @ tic - p_cl) / scale
+        if rot_noise_deg > 0:
+            Rk = Rk @ synth.exp_so3(rng.normal(0, np.deg2rad(rot_noise_deg), 3))
+        if pos_noise > 0:
+            T[k] = T[k] * (1.0 + pos_noise * rng.standard_normal(3))
+        Q[k] = synth.R_to_q(Rk)
+    xyz = (Xw - p_cl) @ R_wcl / scale
+    if point_noise > 0:
+        xyz = xyz * (1.0 + point_noise * rng.standard_normal(xyz.shape))
+    return np.asarray(stamps, float), Q, T, np.asarray(ids, np.int64), xyz
+
+
+def bootstraps_to_structure(src, dst, made, keyframe=0, scale=1.0, rot_noise_deg=0.0, pos_noise=0.0, point_noise=0.0, seed=0, repeat=2,
+                            skip=0):
+    """Copy the recording `src` (written by make_stream, whose return value is `made`: the landmark of every feature id is needed)
+    to `dst` with every bootstrap record replaced by SfM structure records made from ground truth, as bootstraps_to_sfm() does for
+    type 7.  Which images are the window's keyframes is the estimator's decision (the parallax test): `made["keyframes_of"]`, if
+    present, is a function stamp -> the stamps of the window's keyframes when the image `stamp` arrives; without it the eleven
+    images up to the record's are taken (right for a recording whose every image is a keyframe).  The points are the landmarks of
+    every feature id seen in those keyframes.  skip: the first record is written for the image `skip` images behind the bootstrap
+    record's (a list with non-keyframes needs a few slides first).  -> the records written for the FIRST image of each group."""
+    tr = read_trace(src)
+    truth = tr["truth"]
+    img_stamps = [t for t, _ in tr["images"]]
+    id_point, Xw = made["id_point"], made["Xw"]
+    keyframes_of = made.get("keyframes_of")
+    w = TraceWriter(dst)
+    written, n_img = [], 0
+    with open(src, "rb") as f:
+        f.read(8)
+        while True:
+            h = f.read(8)
+            if len(h) < 8:
+                break
+            kind, nbytes = struct.unpack("<II", h)
+            p = f.read(nbytes)
+            if kind != REC_BOOTSTRAP:
+                w._rec(kind, p)
+                n_img += kind == REC_FEATURES
+                continue
+            d = np.frombuffer(p, dtype="<f8")
+            stamp = float(d[247]) if d.size == 248 else img_stamps[max(n_img, abi.WINDOW_SIZE)]
+            last0 = int(np.argmin(np.abs(truth[:, 0] - stamp)))
+            for rep in range(skip, skip + repeat):
+                last = last0 + rep
+                if last >= len(truth):
+                    break
+                ks = keyframes_of(float(truth[last, 0])) if keyframes_of else truth[max(0, last - abi.WINDOW_SIZE):last + 1, 0]
+                rows = [int(np.argmin(np.abs(truth[:, 0] - s_))) for s_ in ks]
+                q = truth[rows, 4:8]
+                Rs = np.array([synth.q_to_R(np.array([c[3], c[0], c[1], c[2]])) for c in q])
+                seen = sorted({int(i) for r in rows for i in tr["images"][r][1][:, 3].astype(np.int64)})
+                st = structure_from_truth(truth[rows, 0], truth[rows, 1:4], Rs, seen, Xw[[id_point[i] for i in seen]], keyframe=min(keyframe, len(rows) - 1),
+                                          scale=scale, rot_noise_deg=rot_noise_deg, pos_noise=pos_noise, point_noise=point_noise, seed=seed + len(written))
+                w.structure(float(truth[last, 0]), *st)
+                if rep == skip:
+                    written.append(dict(stamp=float(truth[last, 0]), stamps=st[0], Q=st[1], T=st[2], ids=st[3], xyz=st[4]))
     w.close()
     return written
