@@ -3,9 +3,9 @@
 //   k_triangulate : FeatureManager::triangulate            feature_manager.cpp:199-253
 //   k_shift_depth : FeatureManager::removeBackShiftDepth   feature_manager.cpp:271-310 (the depth arithmetic)
 //   k_preintegrate: IntegrationBase::push_back / propagate / midPointIntegration   factor/integration_base.h:29-158
-// One thread per landmark.
+// One thread per landmark.  The SVD of k_triangulate is the Jacobi from dev_smallmat.h.
 #pragma once
-#include "dev_math.h"
+#include "dev_smallmat.h"
 
 struct FeatFrames {  // frame poses + extrinsics of one call
   double Ps[LFVIO_NUM_FRAMES][3];
@@ -62,46 +62,10 @@ __global__ __launch_bounds__(TRI_THREADS) void k_triangulate(const FeatFrames *F
       }
     }
   }
-  // one-sided Jacobi SVD of the 2k x 4 matrix: orthogonalize the columns, accumulate V.  Rows beyond 2k are zero and
-  // add exact zeros to the sums, so the arithmetic is the one of a 2k-row loop.
+  // SVD of the 2k x 4 matrix.  Rows beyond 2k are zero and add exact zeros to the sums, so the arithmetic is the one of a
+  // 2k-row loop.
   double V[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; i++)
-#pragma unroll
-    for (int j = 0; j < 4; j++) V[i][j] = i == j ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < 30; sweep++) {
-    bool rotated = false;
-#pragma unroll
-    for (int p = 0; p < 3; p++)
-#pragma unroll
-      for (int q = p + 1; q < 4; q++) {
-        double al = 0, be = 0, ga = 0;
-#pragma unroll
-        for (int r = 0; r < TRI_ROWS; r++) {
-          const double x = A[r][p], y = A[r][q];
-          al += x * x, be += y * y, ga += x * y;
-        }
-        if (!(ga == 0.0 || fabs(ga) <= 1e-15 * sqrt(al * be))) {
-          rotated = true;
-          const double zeta = (be - al) / (2.0 * ga);
-          const double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-          const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
-#pragma unroll
-          for (int r = 0; r < TRI_ROWS; r++) {
-            const double x = A[r][p], y = A[r][q];
-            A[r][p] = c * x - s * y;
-            A[r][q] = s * x + c * y;
-          }
-#pragma unroll
-          for (int r = 0; r < 4; r++) {
-            const double x = V[r][p], y = V[r][q];
-            V[r][p] = c * x - s * y;
-            V[r][q] = s * x + c * y;
-          }
-        }
-      }
-    if (!rotated) break;
-  }
+  jacobi_cols<TRI_ROWS, 4>(A, V, 1e-15);
   // the column with the smallest norm belongs to the smallest singular value (Eigen: matrixV().rightCols<1>())
   double v0 = 0, v1 = 0, v2 = 0, v3 = 0, bn = 0;
 #pragma unroll

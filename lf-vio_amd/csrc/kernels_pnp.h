@@ -4,7 +4,7 @@
 //   k_pnp : grid F x 256, one workgroup per frame of a CSR of correspondences
 //     1  means and the 3 x 3 moment of the world points (block sums), its Jacobi SVD, the control points        :45-75
 //     2  barycentric coordinates per correspondence (kept in a device array), the 40 distinct sums of M^T M      :76-96, :313-330
-//     3  wave 0: one-sided Jacobi on the 12 x 12 M^T M, lane r holding row r; the four smallest vectors          :331-333
+//     3  wave 0: Jacobi from dev_smallmat.h on the 12 x 12 M^T M, lane r holding row r; the four smallest vectors :331-333
 //     4  waves 0 - 2: L_6x10, rho, find_betas_<wave>, 15 Gauss-Newton steps (every lane the same numbers)        :101-230, :388-440
 //     5  all threads, the three candidates side by side: pcs, their mean, solve_for_sign, W, R = U V^T, T,
 //        reprojection_error (block sums)                                                                        :231-296
@@ -17,8 +17,7 @@
 // largest remaining column norm, zeros for the dropped components); columns move by compare-exchange, never by a computed
 // index (which would put the matrix in scratch memory).
 #pragma once
-#include "dev_math.h"
-#include "kernels_twoview.h"
+#include "dev_smallmat.h"
 
 constexpr int PNP_THREADS = 256, PNP_MIN_POINTS = 6, PNP_MAX_POINTS = 4096;
 
@@ -26,11 +25,6 @@ struct PnpRecord {  // LfvioPnpOut, as the kernel writes it
   int status, chosen;
   double R[9], T[3], err[3];
 };
-
-DEV void pnp_cswap_i(bool c, int &a, int &b) {
-  const int x = c ? b : a, y = c ? a : b;
-  a = x, b = y;
-}
 
 // x = A.colPivHouseholderQr().solve(b) for a 6 x NC matrix (Eigen/src/QR/ColPivHouseholderQR.h, computeInPlace and
 // _solve_impl), thread-private and fully unrolled.
@@ -62,9 +56,9 @@ DEV void pnp_colpiv_solve(double (&A)[6][NC], double (&b)[6], double (&x)[NC]) {
 #pragma unroll
     for (int c = k + 1; c < NC; c++) {
       const bool sw = big == c;
-      tv_cswap(sw, nu[k], nu[c]), tv_cswap(sw, nd[k], nd[c]), pnp_cswap_i(sw, perm[k], perm[c]);
+      cswap(sw, nu[k], nu[c]), cswap(sw, nd[k], nd[c]), cswap(sw, perm[k], perm[c]);
 #pragma unroll
-      for (int r = 0; r < NR; r++) tv_cswap(sw, A[r][k], A[r][c]);
+      for (int r = 0; r < NR; r++) cswap(sw, A[r][k], A[r][c]);
     }
     // makeHouseholderInPlace on rows k .. 5 of column k
     double tail = 0;
@@ -160,34 +154,11 @@ DEV void pnp_gauss_newton(const double (&L)[6][10], const double (&rho)[6], doub
 }
 
 // wave 0: the eigenvectors of the four smallest eigenvalues of the symmetric 12 x 12 G (lane r < 12 passes row r, the other
-// lanes zeros), smallest first, by one-sided Jacobi G V = B: |column c of B| = |lambda_c|, column c of V its vector.
+// lanes zeros), smallest first, by jacobi_wave's G V = B: |column c of B| = |lambda_c|, column c of V its vector.
 // Lane r < 12 writes ut[i][r].
 DEV void pnp_null4(double (&G)[12], int lane, double (*ut)[12]) {
-  double W[12];
-#pragma unroll
-  for (int c = 0; c < 12; c++) W[c] = c == lane ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < 30; sweep++) {
-    bool rotated = false;
-#pragma unroll
-    for (int p = 0; p < 11; p++)
-#pragma unroll
-      for (int q = p + 1; q < 12; q++) {
-        const double al = wave_sum(G[p] * G[p]), be = wave_sum(G[q] * G[q]), ga = wave_sum(G[p] * G[q]);
-        if (!(ga == 0.0 || fabs(ga) <= 2.3e-16 * sqrt(al * be))) {
-          rotated = true;
-          const double zeta = (be - al) / (2.0 * ga);
-          const double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-          const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
-          const double x = G[p], y = G[q], vx = W[p], vy = W[q];
-          G[p] = c * x - s * y, G[q] = s * x + c * y;
-          W[p] = c * vx - s * vy, W[q] = s * vx + c * vy;
-        }
-      }
-    if (!rotated) break;
-  }
-  double n2[12];
-#pragma unroll
-  for (int c = 0; c < 12; c++) n2[c] = wave_sum(G[c] * G[c]);
+  double W[12], n2[12];
+  jacobi_wave<12>(G, W, n2, lane);
   unsigned taken = 0;
 #pragma unroll
   for (int i = 0; i < 4; i++) {
@@ -205,13 +176,9 @@ DEV void pnp_null4(double (&G)[12], int lane, double (*ut)[12]) {
 // the other two with the sign of its own column of B, which is what its normalised column is wherever that is defined).
 DEV m33 pnp_uvt(double (&B)[3][3]) {
   double V[3][3], n2[3];
-  tv_jacobi<3, 3>(B, V);
-#pragma unroll
-  for (int c = 0; c < 3; c++) n2[c] = B[0][c] * B[0][c] + B[1][c] * B[1][c] + B[2][c] * B[2][c];
-  tv_sort_cols<0, 1>(B, V, n2), tv_sort_cols<1, 2>(B, V, n2), tv_sort_cols<0, 1>(B, V, n2);
-  const double i1 = 1.0 / sqrt(n2[0]), i2 = 1.0 / sqrt(n2[1]);
-  const d3 u1 = i1 * mk3(B[0][0], B[1][0], B[2][0]), u2 = i2 * mk3(B[0][1], B[1][1], B[2][1]);
-  d3 u3 = cross(u1, u2);
+  d3 u1, u2, u3;
+  svd3_sorted(B, V, n2);
+  svd3_u(B, n2, u1, u2, u3);
   if (u3.x * B[0][2] + u3.y * B[1][2] + u3.z * B[2][2] < 0.0) u3 = -u3;
   const double U1[3] = {u1.x, u1.y, u1.z}, U2[3] = {u2.x, u2.y, u2.z}, U3[3] = {u3.x, u3.y, u3.z};
   m33 R;
@@ -260,10 +227,7 @@ __global__ __launch_bounds__(PNP_THREADS) void k_pnp(const int *offset, const do
   d3 cw[4];
   {
     double B[3][3] = {{s6[0], s6[1], s6[2]}, {s6[1], s6[3], s6[4]}, {s6[2], s6[4], s6[5]}}, V[3][3], n2[3];
-    tv_jacobi<3, 3>(B, V);
-#pragma unroll
-    for (int c = 0; c < 3; c++) n2[c] = B[0][c] * B[0][c] + B[1][c] * B[1][c] + B[2][c] * B[2][c];
-    tv_sort_cols<0, 1>(B, V, n2), tv_sort_cols<1, 2>(B, V, n2), tv_sort_cols<0, 1>(B, V, n2);
+    svd3_sorted(B, V, n2);
     cw[0] = c0;
     const d3 v[3] = {pnp_pin_axis(mk3(V[0][0], V[1][0], V[2][0])), pnp_pin_axis(mk3(V[0][1], V[1][1], V[2][1])), pnp_pin_axis(mk3(V[0][2], V[1][2], V[2][2]))};
     const double k[3] = {sqrt(sqrt(n2[0]) / dn), sqrt(sqrt(n2[1]) / dn), sqrt(sqrt(n2[2]) / dn)};

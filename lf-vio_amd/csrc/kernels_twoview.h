@@ -9,12 +9,13 @@
 // The essential matrix is estimated on bearing vectors, so rays with z <= 0 are ordinary inputs.  Null vectors come from
 // Householder factorizations of the systems themselves (never of A^T A): of the 9 x 8 transpose for a sample, whose last
 // column of Q is the null vector; of the n x 9 inlier system down to a 9 x 9 triangle for the refit, whose smallest right
-// singular vector a one-sided Jacobi finds.  Rows of matches that are not inliers enter the refit as zero rows: they add
-// exact zeros to every sum, so the triangle is the one of the compacted system and no inlier list is needed.
+// singular vector the wave-wide Jacobi from dev_smallmat.h finds.  Rows of matches that are not inliers enter the refit as
+// zero rows: they add exact zeros to every sum, so the triangle is the one of the compacted system and no inlier list is
+// needed.
 // The score is the reference's: a FLOAT accumulator taking double terms match by match, in match order, against the FLOAT
 // threshold — one lane walks the terms the others left in LDS.
 #pragma once
-#include "dev_math.h"
+#include "dev_smallmat.h"
 
 constexpr int TV_HYP_THREADS = 64, TV_FIT_THREADS = 256, TV_CHUNK = 1024;
 constexpr int TV_MAX_MATCHES = 4096, TV_MAX_SAMPLES = 1024;
@@ -59,72 +60,15 @@ DEV void tv_null9(double (&M)[9][8], double (&v)[9]) {
   }
 }
 
-// One-sided Jacobi on a matrix with NR rows and NC columns held in registers: B <- B V with orthogonal columns.
-template <int NR, int NC>
-DEV void tv_jacobi(double (&B)[NR][NC], double (&V)[NC][NC]) {
-#pragma unroll
-  for (int i = 0; i < NC; i++)
-#pragma unroll
-    for (int j = 0; j < NC; j++) V[i][j] = i == j ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < 30; sweep++) {
-    bool rotated = false;
-#pragma unroll
-    for (int p = 0; p < NC - 1; p++)
-#pragma unroll
-      for (int q = p + 1; q < NC; q++) {
-        double al = 0, be = 0, ga = 0;
-#pragma unroll
-        for (int r = 0; r < NR; r++) {
-          const double x = B[r][p], y = B[r][q];
-          al += x * x, be += y * y, ga += x * y;
-        }
-        if (!(ga == 0.0 || fabs(ga) <= 2.3e-16 * sqrt(al * be))) {
-          rotated = true;
-          const double zeta = (be - al) / (2.0 * ga);
-          const double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-          const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
-#pragma unroll
-          for (int r = 0; r < NR; r++) {
-            const double x = B[r][p], y = B[r][q];
-            B[r][p] = c * x - s * y;
-            B[r][q] = s * x + c * y;
-          }
-#pragma unroll
-          for (int r = 0; r < NC; r++) {
-            const double x = V[r][p], y = V[r][q];
-            V[r][p] = c * x - s * y;
-            V[r][q] = s * x + c * y;
-          }
-        }
-      }
-    if (!rotated) break;
-  }
-}
-
 // E_0 = v read as a row-major 3 x 3; its SVD as B = E_0 V (columns of B: sigma_c u_c), columns sorted by falling norm;
 // E = E_0 with the smallest singular value dropped (:89-97).  B, V and the squared column norms are returned for
-// decomposeE.  (The sort swaps whole columns by compare-exchange: picking a column by a computed index puts B and V in
-// scratch memory.)
-DEV void tv_cswap(bool c, double &a, double &b) {
-  const double x = c ? b : a, y = c ? a : b;
-  a = x, b = y;
-}
-template <int P, int Q>
-DEV void tv_sort_cols(double (&B)[3][3], double (&V)[3][3], double (&n2)[3]) {
-  const bool c = n2[P] < n2[Q];
-  tv_cswap(c, n2[P], n2[Q]);
-#pragma unroll
-  for (int r = 0; r < 3; r++) tv_cswap(c, B[r][P], B[r][Q]), tv_cswap(c, V[r][P], V[r][Q]);
-}
+// decomposeE.
 DEV void tv_rank2(const double (&v)[9], double (&E)[9], double (&B)[3][3], double (&V)[3][3], double (&n2)[3]) {
 #pragma unroll
   for (int i = 0; i < 3; i++)
 #pragma unroll
     for (int j = 0; j < 3; j++) B[i][j] = v[3 * i + j];
-  tv_jacobi<3, 3>(B, V);
-#pragma unroll
-  for (int c = 0; c < 3; c++) n2[c] = B[0][c] * B[0][c] + B[1][c] * B[1][c] + B[2][c] * B[2][c];
-  tv_sort_cols<0, 1>(B, V, n2), tv_sort_cols<1, 2>(B, V, n2), tv_sort_cols<0, 1>(B, V, n2);
+  svd3_sorted(B, V, n2);
 #pragma unroll
   for (int i = 0; i < 3; i++)
 #pragma unroll
@@ -290,36 +234,16 @@ __global__ __launch_bounds__(TV_FIT_THREADS) void k_tv_fit(int N, int S, const d
   tv_qr_step<NT, 3>(A, NR, red, tid), tv_qr_step<NT, 4>(A, NR, red, tid), tv_qr_step<NT, 5>(A, NR, red, tid);
   tv_qr_step<NT, 6>(A, NR, red, tid), tv_qr_step<NT, 7>(A, NR, red, tid), tv_qr_step<NT, 8>(A, NR, red, tid);
   __syncthreads();
-  // smallest right singular vector of the triangle: one-sided Jacobi in wave 0, lane r holds row r of R and of V
+  // smallest right singular vector of the triangle, in wave 0: lane r holds row r of R and of V
   if (tid < 64) {
-    double G[9], W[9];
+    double G[9], W[9], g2[9];
 #pragma unroll
-    for (int c = 0; c < 9; c++) G[c] = (tid < 9 && c >= tid) ? A[9 * (size_t)min(tid, 8) + c] : 0.0, W[c] = c == tid ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < 30; sweep++) {
-      bool rotated = false;
-#pragma unroll
-      for (int p = 0; p < 8; p++)
-#pragma unroll
-        for (int q = p + 1; q < 9; q++) {
-          const double al = wave_sum(G[p] * G[p]), be = wave_sum(G[q] * G[q]), ga = wave_sum(G[p] * G[q]);
-          if (!(ga == 0.0 || fabs(ga) <= 2.3e-16 * sqrt(al * be))) {
-            rotated = true;
-            const double zeta = (be - al) / (2.0 * ga);
-            const double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-            const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
-            const double x = G[p], y = G[q], vx = W[p], vy = W[q];
-            G[p] = c * x - s * y, G[q] = s * x + c * y;
-            W[p] = c * vx - s * vy, W[q] = s * vx + c * vy;
-          }
-        }
-      if (!rotated) break;
-    }
+    for (int c = 0; c < 9; c++) G[c] = (tid < 9 && c >= tid) ? A[9 * (size_t)min(tid, 8) + c] : 0.0;
+    jacobi_wave<9>(G, W, g2, tid);
     double bn = 0, vv = 0;
 #pragma unroll
-    for (int c = 0; c < 9; c++) {
-      const double n2 = wave_sum(G[c] * G[c]);
-      if (c == 0 || n2 < bn) bn = n2, vv = W[c];
-    }
+    for (int c = 0; c < 9; c++)
+      if (c == 0 || g2[c] < bn) bn = g2[c], vv = W[c];
     if (tid < 9) sv[tid] = vv;
   }
   __syncthreads();
@@ -338,8 +262,8 @@ __global__ __launch_bounds__(TV_FIT_THREADS) void k_tv_fit(int N, int S, const d
   n_in = block_sum<NT>(n_in, red, tid);
   // decomposeE (:321-336) from the SVD the projection already holds: E = sigma_1 u_1 v_1^T + sigma_2 u_2 v_2^T.  u_3 and
   // v_3 are the cross products, so det U = det V = +1 and both candidates are proper rotations.
-  const double is1 = 1.0 / sqrt(n2[0]), is2 = 1.0 / sqrt(n2[1]);
-  const d3 u1 = is1 * mk3(B[0][0], B[1][0], B[2][0]), u2 = is2 * mk3(B[0][1], B[1][1], B[2][1]), u3 = cross(u1, u2);
+  d3 u1, u2, u3;
+  svd3_u(B, n2, u1, u2, u3);
   const d3 v1 = mk3(V[0][0], V[1][0], V[2][0]), v2 = mk3(V[0][1], V[1][1], V[2][1]), v3 = cross(v1, v2);
   const double U1[3] = {u1.x, u1.y, u1.z}, U2[3] = {u2.x, u2.y, u2.z}, U3[3] = {u3.x, u3.y, u3.z};
   const double V1[3] = {v1.x, v1.y, v1.z}, V2[3] = {v2.x, v2.y, v2.z}, V3[3] = {v3.x, v3.y, v3.z};
@@ -370,7 +294,7 @@ __global__ __launch_bounds__(TV_FIT_THREADS) void k_tv_fit(int N, int S, const d
         D[2][c] = r.x * P2[c] - r.z * P0[c];  // :345
         D[3][c] = r.y * P2[c] - r.z * P1[c];  // :346
       }
-      tv_jacobi<4, 4>(D, Q);
+      jacobi_cols<4, 4>(D, Q, 2.3e-16);
       double q0 = 0, q1 = 0, q2 = 0, q3 = 0, bn = 0;
 #pragma unroll
       for (int c = 0; c < 4; c++) {

@@ -2074,136 +2074,6 @@ int lfvio_batch_optimize_finish(lfvio_ctx *c, LfvioPrior *prior) {
 
 int lfvio_batch_optimize_pending(const lfvio_ctx *c) { return c && (c->inflight || c->has_held) ? 1 : 0; }
 
-// ---- the landmark-parallel steps either side of optimization()
-static int feat_reserve(lfvio_ctx *c, size_t bytes) {
-  if (bytes <= c->feat_bytes) return LFVIO_OK;
-  if (c->d_feat) (void)hipFree(c->d_feat);
-  if (c->h_feat) (void)hipHostFree(c->h_feat);
-  c->d_feat = nullptr, c->h_feat = nullptr, c->feat_bytes = 0;
-  bytes = align_up(bytes + bytes / 4, 4096);
-  if (hipMalloc(&c->d_feat, bytes) != hipSuccess || hipHostMalloc((void **)&c->h_feat, bytes, hipHostMallocDefault) != hipSuccess) {
-    c->err = "out of memory (feature scratch)";
-    return LFVIO_ERR_DEVICE;
-  }
-  c->feat_bytes = bytes;
-  return LFVIO_OK;
-}
-
-int lfvio_triangulate(lfvio_ctx *c, const LfvioTriangulateIn *in, double *estimated_depth) {
-  if (!c || !in || in->num_landmarks < 0 || in->num_observations < 0) return LFVIO_ERR_ARG;
-  const int N = in->num_landmarks, M = in->num_observations;
-  if (N == 0) return LFVIO_OK;
-  if (!estimated_depth || !in->start_frame || !in->obs_offset || !in->obs_point || in->obs_offset[0] != 0 || in->obs_offset[N] != M) {
-    c->err = "triangulate: null arrays or obs_offset is not a CSR over num_observations";
-    return LFVIO_ERR_ARG;
-  }
-  for (int l = 0; l < N; l++) {
-    const int k = in->obs_offset[l + 1] - in->obs_offset[l], s = in->start_frame[l];
-    if (k < 2 || s < 0 || s + k > LFVIO_NUM_FRAMES) {
-      c->err = "triangulate: landmark with fewer than 2 observations or a track leaving the window";
-      return LFVIO_ERR_ARG;
-    }
-  }
-  (void)hipSetDevice(c->device);
-  hipStream_t fs = c->fstream ? c->fstream : c->stream;  // not behind the tail of an optimization still in flight
-  const size_t oF = 0, oS = align_up(sizeof(FeatFrames), 256), oO = align_up(oS + (size_t)N * 4, 256),
-               oP = align_up(oO + (size_t)(N + 1) * 4, 256), oD = align_up(oP + (size_t)M * 24, 256), total = oD + (size_t)N * 8;
-  int rc = feat_reserve(c, total);
-  if (rc) return rc;
-  FeatFrames F;
-  std::memcpy(F.Ps, in->Ps, sizeof F.Ps), std::memcpy(F.Rs, in->Rs, sizeof F.Rs);
-  std::memcpy(F.tic, in->tic, sizeof F.tic), std::memcpy(F.ric, in->ric, sizeof F.ric);
-  F.init_depth = in->init_depth;
-  char *d = c->d_feat, *h = c->h_feat;  // (a copy from pageable memory costs ~20 us each on this runtime: one packed pinned block instead of five)
-  std::memcpy(h + oF, &F, sizeof F);
-  std::memcpy(h + oS, in->start_frame, (size_t)N * 4);
-  std::memcpy(h + oO, in->obs_offset, (size_t)(N + 1) * 4);
-  std::memcpy(h + oP, in->obs_point, (size_t)M * 24);
-  std::memcpy(h + oD, estimated_depth, (size_t)N * 8);
-  HIPCHK(c, hipMemcpyAsync(d, h, total, hipMemcpyHostToDevice, fs));
-  hipLaunchKernelGGL(k_triangulate, dim3((N + TRI_THREADS - 1) / TRI_THREADS), dim3(TRI_THREADS), 0, fs, (const FeatFrames *)(d + oF), N,
-                     (const int *)(d + oS), (const int *)(d + oO), (const double *)(d + oP), (double *)(d + oD));
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(h + oD, d + oD, (size_t)N * 8, hipMemcpyDeviceToHost, fs));
-  HIPCHK(c, hipStreamSynchronize(fs));
-  std::memcpy(estimated_depth, h + oD, (size_t)N * 8);
-  return LFVIO_OK;
-}
-
-int lfvio_shift_depth(lfvio_ctx *c, int n, const double *uv_i, const double marg_R[9], const double marg_P[3], const double new_R[9],
-                      const double new_P[3], double init_depth, double *estimated_depth) {
-  if (!c || n < 0) return LFVIO_ERR_ARG;
-  if (n == 0) return LFVIO_OK;
-  if (!uv_i || !marg_R || !marg_P || !new_R || !new_P || !estimated_depth) return LFVIO_ERR_ARG;
-  (void)hipSetDevice(c->device);
-  hipStream_t fs = c->fstream ? c->fstream : c->stream;  // not behind the tail of an optimization still in flight
-  const size_t oT = 0, oU = 256, oD = align_up(oU + (size_t)n * 24, 256), total = oD + (size_t)n * 8;
-  int rc = feat_reserve(c, total);
-  if (rc) return rc;
-  double T[25];
-  std::memcpy(T, marg_R, 72), std::memcpy(T + 9, marg_P, 24), std::memcpy(T + 12, new_R, 72), std::memcpy(T + 21, new_P, 24);
-  T[24] = init_depth;
-  char *d = c->d_feat, *h = c->h_feat;
-  std::memcpy(h + oT, T, sizeof T);
-  std::memcpy(h + oU, uv_i, (size_t)n * 24);
-  std::memcpy(h + oD, estimated_depth, (size_t)n * 8);
-  HIPCHK(c, hipMemcpyAsync(d, h, total, hipMemcpyHostToDevice, fs));
-  hipLaunchKernelGGL(k_shift_depth, dim3((n + 255) / 256), dim3(256), 0, fs, n, (const double *)(d + oU), (const double *)(d + oT),
-                     (double *)(d + oD));
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(h + oD, d + oD, (size_t)n * 8, hipMemcpyDeviceToHost, fs));
-  HIPCHK(c, hipStreamSynchronize(fs));
-  std::memcpy(estimated_depth, h + oD, (size_t)n * 8);
-  return LFVIO_OK;
-}
-
-int lfvio_preintegrate(lfvio_ctx *c, int num_intervals, const LfvioImuInterval *in, const double noise[4], LfvioPreintegration *out) {
-  if (!c || num_intervals < 0) return LFVIO_ERR_ARG;
-  if (num_intervals == 0) return LFVIO_OK;
-  if (!in || !noise || !out) return LFVIO_ERR_ARG;
-  size_t S = 0;
-  for (int k = 0; k < num_intervals; k++) {
-    if (in[k].num_samples < 0 || (in[k].num_samples > 0 && (!in[k].dt || !in[k].acc || !in[k].gyr))) {
-      c->err = "preintegrate: interval with a negative sample count or null sample arrays";
-      return LFVIO_ERR_ARG;
-    }
-    S += (size_t)in[k].num_samples;
-  }
-  (void)hipSetDevice(c->device);
-  hipStream_t fs = c->fstream ? c->fstream : c->stream;  // not behind the tail of an optimization still in flight
-  const size_t K = (size_t)num_intervals;
-  const size_t oJ = 0, oN = align_up(K * sizeof(ImuJob), 256), oT = oN + 256, oA = align_up(oT + S * 8, 256), oG = align_up(oA + S * 24, 256),
-               oO = align_up(oG + S * 24, 256), total = oO + K * sizeof(LfvioPreintegration);
-  int rc = feat_reserve(c, total);
-  if (rc) return rc;
-  // one packed (pinned) staging block -> one host-to-device copy
-  char *h = c->h_feat;
-  size_t off = 0;
-  for (int k = 0; k < num_intervals; k++) {
-    ImuJob *jb = (ImuJob *)(h + oJ) + k;
-    const size_t n = (size_t)in[k].num_samples;
-    jb->n = (int)n, jb->off = (int)off;
-    std::memcpy(jb->acc_0, in[k].acc_0, 24), std::memcpy(jb->gyr_0, in[k].gyr_0, 24);
-    std::memcpy(jb->ba, in[k].linearized_ba, 24), std::memcpy(jb->bg, in[k].linearized_bg, 24);
-    if (n) {
-      std::memcpy(h + oT + off * 8, in[k].dt, n * 8);
-      std::memcpy(h + oA + off * 24, in[k].acc, n * 24);
-      std::memcpy(h + oG + off * 24, in[k].gyr, n * 24);
-    }
-    off += n;
-  }
-  std::memcpy(h + oN, noise, 32);
-  char *d = c->d_feat;
-  HIPCHK(c, hipMemcpyAsync(d, h, oO, hipMemcpyHostToDevice, fs));
-  hipLaunchKernelGGL(k_preintegrate, dim3(num_intervals), dim3(PRE_THREADS), 0, fs, (const ImuJob *)(d + oJ), (const double *)(d + oT),
-                     (const double *)(d + oA), (const double *)(d + oG), (const double *)(d + oN), (LfvioPreintegration *)(d + oO));
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(h + oO, d + oO, K * sizeof(LfvioPreintegration), hipMemcpyDeviceToHost, fs));
-  HIPCHK(c, hipStreamSynchronize(fs));
-  std::memcpy(out, h + oO, K * sizeof(LfvioPreintegration));
-  return LFVIO_OK;
-}
-
 // ---- debug / parity hooks (include/lfvio_debug.h)
 int lfvio_debug_linearize(lfvio_ctx *c, const LfvioWindow *in, double *Hpp, double *gp, double *a, double *b, double *W,
                           double *cost) {
@@ -2493,6 +2363,8 @@ int lfvio_debug_query(lfvio_ctx *c, const char *key, double *out, int n) {
 
 // ---- relocalization: lfvio_solve_relo, declared in lfvio.h, implemented in relo.inc
 #include "relo.inc"
+// ---- the calls on the feature stream: feat.inc holds their staging and the three feature steps
+#include "feat.inc"
 
 #include "twoview.inc"
 

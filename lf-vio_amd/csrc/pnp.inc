@@ -1,9 +1,8 @@
 // pnp.inc — host side of lfvio_pnp (include/lfvio.h): PnpSolver::compute_pose (pnp_solver.cpp) for F frames at once on
 // k_pnp (kernels_pnp.h).  Included by lfvio_hip.hip inside its extern "C" block.
 //
-// One call: validate the CSR, pack [offset | point_w | bearing] into the pinned feature staging block, one copy up, one
-// launch (grid F), one copy down of the F records.  Stream: the feature stream, like lfvio_triangulate — an optimization
-// in flight is not waited for.
+// One call: validate the CSR, pack [offset | point_w | bearing] into the staging block of feat.inc, one copy up, one
+// launch (grid F), one copy down of the F records.
 
 int lfvio_pnp(lfvio_ctx *c, const LfvioPnpIn *in, LfvioPnpOut *out) {
   static_assert(sizeof(PnpRecord) == sizeof(LfvioPnpOut), "the kernel writes LfvioPnpOut");
@@ -25,22 +24,19 @@ int lfvio_pnp(lfvio_ctx *c, const LfvioPnpIn *in, LfvioPnpOut *out) {
     }
   }
   const size_t M = (size_t)in->offset[F];
-  (void)hipSetDevice(c->device);
-  hipStream_t fs = c->fstream ? c->fstream : c->stream;  // not behind the tail of an optimization still in flight
-  const size_t oF = 0, oP = align_up(oF + (size_t)(F + 1) * 4, 256), oU = align_up(oP + M * 24, 256), in_end = oU + M * 24;
-  const size_t oA = align_up(in_end, 256), oO = align_up(oA + M * 32, 256), total = oO + (size_t)F * sizeof(LfvioPnpOut);
-  int rc = feat_reserve(c, total);
-  if (rc) return rc;
-  char *d = c->d_feat, *h = c->h_feat;
+  FeatStage st(c);
+  const size_t oF = st.take((size_t)(F + 1) * 4), oP = st.take(M * 24), oU = st.take(M * 24), in_end = st.end;
+  const size_t oA = st.take(M * 32), oO = st.take((size_t)F * sizeof(LfvioPnpOut));
+  if (int rc = st.reserve()) return rc;
+  char *d = st.d, *h = st.h;
   std::memcpy(h + oF, in->offset, (size_t)(F + 1) * 4);
   std::memcpy(h + oP, in->point_w, M * 24);
   std::memcpy(h + oU, in->bearing, M * 24);
-  HIPCHK(c, hipMemcpyAsync(d, h, in_end, hipMemcpyHostToDevice, fs));
-  hipLaunchKernelGGL(k_pnp, dim3(F), dim3(PNP_THREADS), 0, fs, (const int *)(d + oF), (const double *)(d + oP), (const double *)(d + oU),
+  if (int rc = st.up(in_end)) return rc;
+  hipLaunchKernelGGL(k_pnp, dim3(F), dim3(PNP_THREADS), 0, st.fs, (const int *)(d + oF), (const double *)(d + oP), (const double *)(d + oU),
                      (double *)(d + oA), (PnpRecord *)(d + oO));
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(h + oO, d + oO, (size_t)F * sizeof(LfvioPnpOut), hipMemcpyDeviceToHost, fs));
-  HIPCHK(c, hipStreamSynchronize(fs));
+  if (int rc = st.down(oO, st.end)) return rc;
   const LfvioPnpOut *o = (const LfvioPnpOut *)(h + oO);
   for (int f = 0; f < F; f++) {
     if (o[f].status == 0)

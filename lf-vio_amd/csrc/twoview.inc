@@ -2,9 +2,8 @@
 // (initial/initial_ex_rotation.cpp:157-284) on the kernels of kernels_twoview.h.  Included by lfvio_hip.hip inside its
 // extern "C" block.
 //
-// One call: validate, pack bearings and sample sets into the pinned feature staging block, one copy up, k_tv_hyp (grid S),
+// One call: validate, pack bearings and sample sets into the staging block of feat.inc, one copy up, k_tv_hyp (grid S),
 // k_tv_fit (one workgroup), one copy down of [LfvioTwoViewOut | mask | scores | hypotheses] as far as the caller asked.
-// Stream: the feature stream, like lfvio_triangulate — an optimization in flight is not waited for.
 
 int lfvio_two_view(lfvio_ctx *c, const LfvioTwoViewIn *in, unsigned char *inlier, LfvioTwoViewOut *out, double *E_all, float *score_all) {
   if (!c || !in || !inlier || !out) return LFVIO_ERR_ARG;
@@ -18,29 +17,25 @@ int lfvio_two_view(lfvio_ctx *c, const LfvioTwoViewIn *in, unsigned char *inlier
       c->err = "lfvio_two_view: sample index outside [0, num_matches)";
       return LFVIO_ERR_ARG;
     }
-  (void)hipSetDevice(c->device);
-  hipStream_t fs = c->fstream ? c->fstream : c->stream;  // not behind the tail of an optimization still in flight
+  FeatStage st(c);
   const size_t NR = (size_t)std::max(N, 9);
-  const size_t oL = 0, oR = align_up(oL + (size_t)N * 24, 256), oS = align_up(oR + (size_t)N * 24, 256), in_end = oS + (size_t)S * 32;
-  const size_t oA = align_up(in_end, 256), oO = align_up(oA + NR * 72, 256), oM = oO + align_up(sizeof(LfvioTwoViewOut), 256),
-               oC = align_up(oM + (size_t)N, 256), oE = align_up(oC + (size_t)S * 4, 256), total = oE + (size_t)S * 72;
-  int rc = feat_reserve(c, total);
-  if (rc) return rc;
-  char *d = c->d_feat, *h = c->h_feat;
+  const size_t oL = st.take((size_t)N * 24), oR = st.take((size_t)N * 24), oS = st.take((size_t)S * 32), in_end = st.end;
+  const size_t oA = st.take(NR * 72), oO = st.take(sizeof(LfvioTwoViewOut)), oM = st.take((size_t)N), oC = st.take((size_t)S * 4),
+               oE = st.take((size_t)S * 72);
+  if (int rc = st.reserve()) return rc;
+  char *d = st.d, *h = st.h;
   std::memcpy(h + oL, in->bearing_l, (size_t)N * 24);
   std::memcpy(h + oR, in->bearing_r, (size_t)N * 24);
   std::memcpy(h + oS, in->samples, (size_t)S * 32);
-  HIPCHK(c, hipMemcpyAsync(d, h, in_end, hipMemcpyHostToDevice, fs));
-  hipLaunchKernelGGL(k_tv_hyp, dim3(S), dim3(TV_HYP_THREADS), 0, fs, N, (const double *)(d + oL), (const double *)(d + oR),
+  if (int rc = st.up(in_end)) return rc;
+  hipLaunchKernelGGL(k_tv_hyp, dim3(S), dim3(TV_HYP_THREADS), 0, st.fs, N, (const double *)(d + oL), (const double *)(d + oR),
                      (const int *)(d + oS), (double *)(d + oE), (float *)(d + oC));
   HIPCHK(c, hipGetLastError());
-  hipLaunchKernelGGL(k_tv_fit, dim3(1), dim3(TV_FIT_THREADS), 0, fs, N, S, (const double *)(d + oL), (const double *)(d + oR),
+  hipLaunchKernelGGL(k_tv_fit, dim3(1), dim3(TV_FIT_THREADS), 0, st.fs, N, S, (const double *)(d + oL), (const double *)(d + oR),
                      (const double *)(d + oE), (const float *)(d + oC), (double *)(d + oA), (unsigned char *)(d + oM),
                      (LfvioTwoViewOut *)(d + oO));
   HIPCHK(c, hipGetLastError());
-  const size_t down_end = E_all ? total : score_all ? oC + (size_t)S * 4 : oM + (size_t)N;
-  HIPCHK(c, hipMemcpyAsync(h + oO, d + oO, down_end - oO, hipMemcpyDeviceToHost, fs));
-  HIPCHK(c, hipStreamSynchronize(fs));
+  if (int rc = st.down(oO, E_all ? st.end : score_all ? oC + (size_t)S * 4 : oM + (size_t)N)) return rc;
   const LfvioTwoViewOut *o = (const LfvioTwoViewOut *)(h + oO);
   if (o->status == 0) {
     *out = *o;

@@ -1,11 +1,10 @@
 // vialign.inc — host side of lfvio_vi_align (include/lfvio.h): VisualIMUAlignment (initial/initial_aligment.cpp:3-216) on the
 // kernels of kernels_vialign.h and the existing k_preintegrate.  Included by lfvio_hip.hip inside its extern "C" block.
 //
-// One call: validate, pack [ImuJobs | noise | samples | R | T | tic, G] into the pinned feature staging block, one copy up,
+// One call: validate, pack [ImuJobs | noise | samples | R | T | tic, G] into the staging block of feat.inc, one copy up,
 //   k_preintegrate (the spans as passed) -> k_va_bias (delta_bg; writes ba = 0, bg = Bgs[0] + delta_bg into the jobs on the device)
 //   -> k_preintegrate (the same launch again) -> k_va_align (LinearAlignment + RefineGravity)
 // and one copy down of [LfvioViAlignOut | x | pre] as far as the caller asked.  No host round trip in between.
-// Stream: the feature stream, like lfvio_triangulate — an optimization in flight is not waited for.
 
 int lfvio_vi_align(lfvio_ctx *c, const LfvioViAlignIn *in, LfvioViAlignOut *out, double *x, LfvioPreintegration *pre) {
   if (!c || !in || !out || !x) return LFVIO_ERR_ARG;
@@ -29,53 +28,35 @@ int lfvio_vi_align(lfvio_ctx *c, const LfvioViAlignIn *in, LfvioViAlignOut *out,
     }
     S += (size_t)sp.num_samples;
   }
-  (void)hipSetDevice(c->device);
-  hipStream_t fs = c->fstream ? c->fstream : c->stream;  // not behind the tail of an optimization still in flight
+  FeatStage st(c);
   const size_t K = (size_t)F - 1;
-  const size_t oJ = 0, oN = align_up(K * sizeof(ImuJob), 256), oT = oN + 256, oA = align_up(oT + S * 8, 256), oG = align_up(oA + S * 24, 256),
-               oR = align_up(oG + S * 24, 256), oP = align_up(oR + (size_t)F * 72, 256), oV = align_up(oP + (size_t)F * 24, 256),
-               in_end = oV + sizeof(VaParams);
-  const size_t oO = align_up(in_end, 256), oX = oO + align_up(sizeof(LfvioViAlignOut), 256), oI = align_up(oX + (size_t)F * 24, 256),
-               total = oI + K * sizeof(LfvioPreintegration);
-  int rc = feat_reserve(c, total);
-  if (rc) return rc;
-  char *h = c->h_feat, *d = c->d_feat;
-  size_t off = 0;
-  for (int k = 1; k < F; k++) {
-    const LfvioImuInterval &sp = in->span[k];
-    ImuJob *jb = (ImuJob *)(h + oJ) + (k - 1);
-    const size_t n = (size_t)sp.num_samples;
-    jb->n = (int)n, jb->off = (int)off;
-    std::memcpy(jb->acc_0, sp.acc_0, 24), std::memcpy(jb->gyr_0, sp.gyr_0, 24);
-    std::memcpy(jb->ba, sp.linearized_ba, 24), std::memcpy(jb->bg, sp.linearized_bg, 24);
-    std::memcpy(h + oT + off * 8, sp.dt, n * 8);
-    std::memcpy(h + oA + off * 24, sp.acc, n * 24);
-    std::memcpy(h + oG + off * 24, sp.gyr, n * 24);
-    off += n;
-  }
-  std::memcpy(h + oN, in->noise, 32);
+  const ImuStage im = imu_take(st, K, S);
+  const size_t oR = st.take((size_t)F * 72), oP = st.take((size_t)F * 24), oV = st.take(sizeof(VaParams)), in_end = st.end;
+  const size_t oO = st.take(sizeof(LfvioViAlignOut)), oX = st.take((size_t)F * 24), oI = st.take(K * sizeof(LfvioPreintegration));
+  if (int rc = st.reserve()) return rc;
+  char *h = st.h, *d = st.d;
+  imu_pack(h, im, (int)K, in->span + 1, in->noise);
   std::memcpy(h + oR, in->R, (size_t)F * 72);
   std::memcpy(h + oP, in->T, (size_t)F * 24);
   VaParams prm;
   std::memcpy(prm.tic, in->tic, 24), prm.g_norm = in->g_norm;
   std::memcpy(h + oV, &prm, sizeof prm);
-  HIPCHK(c, hipMemcpyAsync(d, h, in_end, hipMemcpyHostToDevice, fs));
-  ImuJob *jobs = (ImuJob *)(d + oJ);
+  if (int rc = st.up(in_end)) return rc;
+  ImuJob *jobs = (ImuJob *)(d + im.jobs);
   LfvioPreintegration *dpre = (LfvioPreintegration *)(d + oI);
   LfvioViAlignOut *dout = (LfvioViAlignOut *)(d + oO);
   for (int pass = 0; pass < 2; pass++) {
-    hipLaunchKernelGGL(k_preintegrate, dim3((unsigned)K), dim3(PRE_THREADS), 0, fs, (const ImuJob *)jobs, (const double *)(d + oT),
-                       (const double *)(d + oA), (const double *)(d + oG), (const double *)(d + oN), dpre);
+    hipLaunchKernelGGL(k_preintegrate, dim3((unsigned)K), dim3(PRE_THREADS), 0, st.fs, (const ImuJob *)jobs, (const double *)(d + im.dt),
+                       (const double *)(d + im.acc), (const double *)(d + im.gyr), (const double *)(d + im.noise), dpre);
     HIPCHK(c, hipGetLastError());
     if (pass == 0)
-      hipLaunchKernelGGL(k_va_bias, dim3(1), dim3(VA_THREADS), 0, fs, F, (const double *)(d + oR), (const LfvioPreintegration *)dpre, jobs, dout);
+      hipLaunchKernelGGL(k_va_bias, dim3(1), dim3(VA_THREADS), 0, st.fs, F, (const double *)(d + oR), (const LfvioPreintegration *)dpre, jobs, dout);
     else
-      hipLaunchKernelGGL(k_va_align, dim3(1), dim3(VA_THREADS), 0, fs, F, (const double *)(d + oR), (const double *)(d + oP),
+      hipLaunchKernelGGL(k_va_align, dim3(1), dim3(VA_THREADS), 0, st.fs, F, (const double *)(d + oR), (const double *)(d + oP),
                          (const LfvioPreintegration *)dpre, (const VaParams *)(d + oV), dout, (double *)(d + oX));
     HIPCHK(c, hipGetLastError());
   }
-  HIPCHK(c, hipMemcpyAsync(h + oO, d + oO, (pre ? total : oI) - oO, hipMemcpyDeviceToHost, fs));
-  HIPCHK(c, hipStreamSynchronize(fs));
+  if (int rc = st.down(oO, pre ? st.end : oI)) return rc;
   const LfvioViAlignOut *o = (const LfvioViAlignOut *)(h + oO);
   if (o->status == 0) {
     *out = *o;
