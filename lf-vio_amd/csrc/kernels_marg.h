@@ -560,8 +560,9 @@ DEV int jacobi_small(double *Am, double *Vm, int n, int tid, int nthreads, doubl
 //   3. eigenvectors of T by the twisted factorization (Parlett & Dhillon; LAPACK dlar1v without the relatively robust
 //      representation): one thread per eigenvalue runs the stationary, another the progressive quotient-difference
 //      recurrence; they twist where |gamma| is smallest and each multiplies out on its side of the twist.  Eigenvalues
-//      closer than the rounding level give parallel vectors; that only happens in the block of noise eigenvalues
-//      (|lambda| ~ 1e-6 against ||A'|| ~ 1e6), whose rows contribute lambda v v^T ~ 1e-6 to J0^T J0 whatever v is.
+//      closer than the rounding level give parallel vectors.  What that costs is measured rather than assumed: `recon` of
+//      tests/test_marg_hp.py — ||J0^T J0 - A'||_2 beyond the largest dropped eigenvalue, held to 139 u ||A'||_2 on windows with
+//      up to 16 eigenvalues crowded around eps (per case in DESIGN.md, section 3a).
 //   4. V = Q Z: eight lanes per eigenvector push their column through the reflectors, last to first (four reflectors per
 //      step, only the rows they touch), and write
 //      J0 = sqrt(S) V^T,  r0 = sqrt(1/S) V^T b'  for the eigenvalues above eps, zero rows for the others.
@@ -769,7 +770,7 @@ DEV void bt_dispatch(const double *RV, const double *tau, int k, int n, int l8, 
 // |q| < pivmin -> +-pivmin (the sign of q): the quotient-difference recurrences divide by q.  max + sign insertion instead of
 // compare + select: a v_cmp_f64 -> SGPR mask -> v_cndmask round trip costs the chain several times what the arithmetic does.
 DEV double guard_pivot(double q, double pivmin) { return copysign(fmax(fabs(q), pivmin), q); }
-// A: n x n, row stride LDN, full symmetric (destroyed; receives Z, component i of vector m at [i * LDN + m]); b: n;
+// A: n x n, row stride LDN, symmetric by its lower triangle (destroyed; receives Z, component i of vector m at [i * LDN + m]); b: n;
 // RV: >= n * 76, DM: >= n * LDN, vec: >= 7 * 96, nn2: >= 2 * 96 doubles of LDS.  Writes out->linearized_jacobians / _residuals.
 // sp (a worker's launch, kernels_spec.h): thread MARG_THREADS - 1 — idle in phases 1 to 3 — polls whether the state this prior belongs
 // to has been overtaken; returns true (nothing written) when it has.
@@ -791,7 +792,8 @@ DEV bool eig_tridiag(double *A, const double *b, int n, int tid, double *RV, dou
   // twelve carry the per-thread overhead once per SIMD, and column k only touches the 16 x 16 register tiles that still
   // hold live rows and columns (tri_matvec / tri_update are instantiated per leading tile P = (k + 1) / 16: 25, 16, 9, 4, 1
   // tiles).  The 16 lanes that own row k + 1 form the NEXT reflector (dlarfg) right after they have updated that row,
-  // inside the update phase.  Only the lower triangle of the input is read, like Eigen's solver (and tred2) do.
+  // inside the update phase.  Only the lower triangle of the input is read, like Eigen's solver (and tred2) do: the matrix that is
+  // factored is the lower triangle mirrored, and that is the A' k_marg_solve reports (see there).
   const bool tri = tid < 256;
   const int r0 = (tid >> 4) & 15, c0 = tid & 15;
   double ar[5][5];
@@ -1204,7 +1206,8 @@ __global__ __launch_bounds__(MARG_THREADS) void k_marg_solve(char *base, size_t 
 #pragma unroll
     for (int k = 0; k < GR; k++) {
       const int e = tid + MARG_THREADS * k, ec = e < D * D ? e : 0;
-      const int r = perm[ec / D], c = perm[ec % D];
+      // D = 0 (no prior, IMU interval 0 skipped, no landmark anchored at frame 0: nothing takes part) maps no column: perm is unwritten
+      const int r = D ? perm[ec / max(D, 1)] : 0, c = D ? perm[ec % max(D, 1)] : 0;
       const int hi = max(r, c), lo = min(r, c);
       hv[k] = Hp[hi * (hi + 1) / 2 + lo];
       sv[k] = (sub && hi < KC) ? Sc[schur_index(lo, hi)] : 0.0;
@@ -1295,9 +1298,15 @@ __global__ __launch_bounds__(MARG_THREADS) void k_marg_solve(char *base, size_t 
     br[r] = bv[m15 + r] - s;
   }
   __syncthreads();
-  // keep A', b' for parity checks (global scratch after the gathered system)
+  // keep A', b' for parity checks (global scratch after the gathered system): the A' that is factored below, which is the lower
+  // triangle mirrored (marginalization_factor.cpp:283 hands A' to Eigen's solver, which reads that triangle).  The two triangles of
+  // A_rr - (A_rm A_mm^+) A_mr differ by the rounding of the product, 0.1 u ||H||_2 ~ 7e-7: a fiftieth of the rounding of A' itself, but
+  // thousands of u ||A'||_2 — the prior is the factor of the matrix reported here to u ||A'||_2 (tests/test_marg_hp.py), not of the other
   double *Aout = Ag + 92 * 92 + 96;
-  for (int e = tid; e < n * n; e += MARG_THREADS) Aout[e] = Ar[(e / n) * LDN + e % n];
+  for (int e = tid; e < n * n; e += MARG_THREADS) {
+    const int r = e / n, c = e % n;
+    Aout[e] = Ar[max(r, c) * LDN + min(r, c)];
+  }
   for (int r = tid; r < n; r += MARG_THREADS) Aout[n * n + r] = br[r];
   if (poller) spec_poll_take(sp);
   __syncthreads();

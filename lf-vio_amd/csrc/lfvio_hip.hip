@@ -1672,7 +1672,9 @@ int check_prior(lfvio_ctx *c, int slot, const Fetched &f, bool *pass) {
   *pass = hp->valid == -1;
   if (*pass) return LFVIO_OK;
   const int n = hp->n;
-  if (hp->valid != 1 || n <= 0 || n > LFVIO_MAX_PRIOR_DIM || n > info.marg_n) {
+  // (n = 0: a marginalization in which nothing takes part — no prior, IMU interval 0 skipped, no landmark anchored at frame 0 — leaves a
+  // valid prior with m = n = 0 and no blocks, as the oracle's statement of MarginalizationInfo::marginalize does)
+  if (hp->valid != 1 || n < 0 || n > LFVIO_MAX_PRIOR_DIM || n > info.marg_n) {
     c->err = "marginalization produced no prior";
     return LFVIO_ERR_DEVICE;
   }
@@ -2167,7 +2169,27 @@ int lfvio_debug_marg_system(lfvio_ctx *c, int n, double *A, double *b) {
   if (!c || !c->d_base) return LFVIO_ERR_ARG;
   (void)hipSetDevice(c->device);
   if (int rc = join_inflight(c)) return rc;
+  if (n < 0 || n > 76) return LFVIO_ERR_ARG;  // (k_marg_solve forms no larger system: see the upload)
+  if (n == 0) return LFVIO_OK;
   char *d = c->d_base + c->L.mscr;
+  if (c->shadow) {
+    // A prior that a worker delivered (kernels_spec.h) was formed in the worker's shadow slot, and so were its A', b': slot 0's
+    // scratch still holds those of an earlier marginalization.  The shadow slot whose prior is the one in slot 0, bit for bit, is
+    // where the system of that prior lies (a worker that lost the call to the loop's own tail holds the same bits or an older state's).
+    const size_t head = offsetof(LfvioPrior, linearized_jacobians), bytes = head + sizeof(double) * n * n;
+    std::vector<char> p0(bytes), pw(bytes);
+    HIPCHK(c, hipMemcpy(p0.data(), c->d_base + offsetof(Slot, prior_out), bytes, hipMemcpyDeviceToHost));
+    const LfvioPrior *h0 = (const LfvioPrior *)p0.data();
+    for (int wk = 0; wk < lfvio_ctx::WORKERS && h0->valid == 1 && h0->n == n; wk++) {
+      char *ds = c->d_base + (size_t)(c->batch + wk) * c->L.total;
+      HIPCHK(c, hipMemcpy(pw.data(), ds + offsetof(Slot, prior_out), bytes, hipMemcpyDeviceToHost));
+      const LfvioPrior *hw = (const LfvioPrior *)pw.data();
+      if (hw->valid == 1 && hw->n == n && std::memcmp(p0.data() + head, pw.data() + head, bytes - head) == 0) {
+        d = ds + c->L.mscr;
+        break;
+      }
+    }
+  }
   HIPCHK(c, hipMemcpy(A, d + sizeof(double) * (92 * 92 + 96), sizeof(double) * n * n, hipMemcpyDeviceToHost));
   HIPCHK(c, hipMemcpy(b, d + sizeof(double) * (92 * 92 + 96 + n * n), sizeof(double) * n, hipMemcpyDeviceToHost));
   return LFVIO_OK;
