@@ -156,6 +156,22 @@ struct TRState {
 // residuals are written), announced by the second flag word; words 2 and 3 carry Slot::passes_used and the iteration count of the call.
 constexpr size_t MAIL_X = 64, MAIL_TR = MAIL_X + 2 * sizeof(FrameState), MAIL_LAM = (MAIL_TR + sizeof(TRState) + 63) / 64 * 64,
                  MAIL_LAM_STRIDE = (size_t)MAIL_MAX_LM * 8, MAIL_PRIOR = MAIL_LAM + 2 * MAIL_LAM_STRIDE, MAIL_BYTES = MAIL_PRIOR + sizeof(LfvioPrior);
+// The int words at the head of the mailbox, in front of MAIL_X.  The two flags carry Slot::mail_seq of the window they speak of (the
+// host clears them to 0); each count is final when the flag behind which it is read is up.
+enum MailWord {
+  MAIL_STATE_FLAG = 0,    // the state is in the mailbox (publish_solution)
+  MAIL_PRIOR_FLAG = 1,    // ... and the prior (publish_prior)
+  MAIL_PRIOR_PASSES = 2,  // Slot::passes_used and the iteration count, written with the prior
+  MAIL_PRIOR_ITERS = 3,
+  MAIL_STATE_PASSES = 4,  // Slot::passes_used, written with the state
+  MAIL_CHAIN_ERR = 5,     // Slot::chain_err, written with the state
+  MAIL_TICKET = 6,        // host -> device: the ticket of the call whose workers were started (0: none; k_setup reads it, kernels_spec.h)
+  MAIL_ECHO = 7,          // the worker that delivered the prior echoes the ticket
+  MAIL_WORDS = 8
+};
+static_assert(MAIL_X >= MAIL_WORDS * sizeof(int), "the mailbox words lie in front of the state");
+// Slot::tail_state: the gated gauge fix + marginalization of this call (kernels_lin.h MODE_GATED, kernels_spec.h)
+enum TailState { TAIL_OPEN = 0, TAIL_DONE = 2, TAIL_WORKER = 3 };  // not run | finished | the loop has left the prior to a worker, which sets TAIL_DONE when it delivers
 
 // What the trust-region bookkeeping (k_decide) changes in the header.  In the passes of a graph that follow another pass the
 // bookkeeping rides in the prologue of k_lin (every workgroup repeats it, none of them may write the header the others
@@ -315,3 +331,14 @@ struct Slot {
   // marginalization outputs
   LfvioPrior prior_out;
 };
+
+// The pinned block the host reads between graph launches (lfvio_ctx::h_pending).  Its tail is ONE 16-byte copy out of the Slot of a
+// single window, whose four ints must lie in this order.
+struct PendingBlock {
+  int open, passes;  // k_pending: slots not done yet | the most passes any slot has used
+  int tail_state, passes_used, iters_done, chain_err;  // Slot::tail_state .. chain_err
+};
+static_assert(offsetof(Slot, passes_used) - offsetof(Slot, tail_state) == offsetof(PendingBlock, passes_used) - offsetof(PendingBlock, tail_state) &&
+                  offsetof(Slot, iters_done) - offsetof(Slot, tail_state) == offsetof(PendingBlock, iters_done) - offsetof(PendingBlock, tail_state) &&
+                  offsetof(Slot, chain_err) - offsetof(Slot, tail_state) == offsetof(PendingBlock, chain_err) - offsetof(PendingBlock, tail_state),
+              "PendingBlock mirrors Slot::tail_state .. chain_err");

@@ -21,7 +21,7 @@ constexpr int MODE_MARG = 1;        // MODE_MARG + flag: 1 = MARGIN_OLD, 2 = MAR
 constexpr int MODE_GATED = 16;
 constexpr int MODE_DECIDE = 64;   // the trust-region bookkeeping of the pass before rides in the prologue (see k_lin)
 constexpr int MODE_NOCOUNT = 32;  // k_lin launched role by role: only the first of the launches counts the pass
-DEV bool tail_gate(const Slot *S, int done) { return done && S->tail_state == 0; }
+DEV bool tail_gate(const Slot *S, int done) { return done && S->tail_state == TAIL_OPEN; }
 DEV bool is_marg(int mode) { return mode >= MODE_MARG; }
 DEV const MargPlan *marg_plan(const Slot *S, int mode) { return &S->marg[mode - MODE_MARG]; }
 
@@ -51,7 +51,7 @@ __global__ __launch_bounds__(256, 4) void k_setup(char *base, size_t stride, int
     if (tid == 0) {
       TRState *t = &S->tr;
       tr_init(t, S->init_radius, S->fn_tol);
-      S->tail_state = 0;
+      S->tail_state = TAIL_OPEN;
       S->passes_used = 0;
       S->dec_pending = 0;
       if (mode >= MODE_MARG) t->mu = 0.0;
@@ -1150,7 +1150,7 @@ DEV void sum_hpp_entry(Slot *S, const SumArgs &o, int mode_bits, int e) {
   SUM_KEEP(imu_v[0]);
   SUM_KEEP(imu_v[1]);
   if (mode_bits & MODE_GATED) {
-    if (!(fl.done && tail_state == 0)) return;
+    if (!(fl.done && tail_state == TAIL_OPEN)) return;
   } else if (fl.done | !fl.do_lin) return;
   if (!in) return;
   const bool act_r = is_marg(mode) || !((!est_ex && r >= off_ex() && r < off_ex() + 6) || (!est_td && r == off_td()));

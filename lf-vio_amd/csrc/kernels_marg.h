@@ -86,12 +86,12 @@ DEV void publish_solution(Slot *S) {
       for (int k = tid; k < N; k += nthr) ld[k] = ls[k];
     }
   }
-  if (tid == 0) ((int *)m)[4] = S->passes_used, ((int *)m)[5] = S->chain_err;  // (final: the loop is closed; k_prior_chain's verdict on the prior this window ran with)
+  if (tid == 0) ((int *)m)[MAIL_STATE_PASSES] = S->passes_used, ((int *)m)[MAIL_CHAIN_ERR] = S->chain_err;  // (final: the loop is closed; k_prior_chain's verdict on the prior this window ran with)
   __threadfence_system();
   __syncthreads();
   // (the flags carry the upload's sequence number, not 1: the marginalization of the window BEFORE may still be publishing its
   // prior when the host is already waiting for this window's — lfvio_batch_upload_chained_device)
-  if (tid == 0) __hip_atomic_store((int *)m, S->mail_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  if (tid == 0) __hip_atomic_store((int *)m + MAIL_STATE_FLAG, S->mail_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 // The prior the gated marginalization has just written (Slot::prior_out) into the mailbox, then the second flag.  Called by
 // every thread of k_marg_solve's workgroup at its end, behind a barrier that follows the last store to prior_out.
@@ -105,15 +105,15 @@ DEV void publish_prior(Slot *S) {
   copy_rounds((long long *)dst, (const long long *)src, (int)(offsetof(LfvioPrior, linearized_jacobians) / 8), tid, nthr);
   copy_rounds(dst->linearized_jacobians, src->linearized_jacobians, n * n, tid, nthr);
   copy_rounds(dst->linearized_residuals, src->linearized_residuals, n, tid, nthr);
-  if (tid == 0) ((int *)m)[2] = S->passes_used, ((int *)m)[3] = S->tr.iteration;  // (two words: max_num_iterations is the caller's, either count may pass 255)
+  if (tid == 0) ((int *)m)[MAIL_PRIOR_PASSES] = S->passes_used, ((int *)m)[MAIL_PRIOR_ITERS] = S->tr.iteration;  // (two words: max_num_iterations is the caller's, either count may pass 255)
   __threadfence_system();
   __syncthreads();
-  if (tid == 0) __hip_atomic_store((int *)m + 1, S->mail_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  if (tid == 0) __hip_atomic_store((int *)m + MAIL_PRIOR_FLAG, S->mail_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 // behind a k_gauge of several workgroups (windows too large for k_decide_gauge): the same gate, then the mailbox
 __global__ __launch_bounds__(256) void k_publish(char *base, size_t stride) {
   Slot *S = SLOT(base, stride);
-  if (!(S->tr.done && (S->tail_state == 0 || S->tail_state == 3))) return;  // (3: the prior of this state is a worker's — kernels_spec.h; the state is the loop's)
+  if (!(S->tr.done && (S->tail_state == TAIL_OPEN || S->tail_state == TAIL_WORKER))) return;  // (TAIL_WORKER: the prior of this state is a worker's — kernels_spec.h; the state is the loop's)
   publish_solution(S);
 }
 // k_prior_chain: grid 1 x 256, behind the upload of the NEXT window of the same estimator into a slot whose marginalization has
@@ -126,12 +126,12 @@ __global__ __launch_bounds__(256) void k_prior_chain(char *base, size_t stride) 
   const LfvioPrior *src = &S->prior_out;
   const int tid = threadIdx.x, n = S->prior_n, nb = S->prior_nb;
   // the marginalization in front of this window was a worker's on the second stream (kernels_spec.h): it ends by moving the prior
-  // here and setting tail_state to 2 — bounded wait (a worker the loop has committed holds a finished prior)
+  // here and setting tail_state to TAIL_DONE — bounded wait (a worker the loop has committed holds a finished prior)
   __shared__ int late;
   if (tid == 0) {
     late = 0;
     const long long t0 = wall_clock64();
-    while (spec_peek(&S->tail_state) == 3) {
+    while (spec_peek(&S->tail_state) == TAIL_WORKER) {
       if (wall_clock64() - t0 > 10 * SPEC_WAIT_TICKS) {
         late = 1;
         break;
@@ -268,7 +268,7 @@ __global__ __launch_bounds__(64) void k_spec_wait(char *base) {
   Slot *S = (Slot *)base;
   if (threadIdx.x != 0) return;
   const long long t0 = wall_clock64();
-  while (spec_peek(&S->tail_state) == 3 && wall_clock64() - t0 < 10 * SPEC_WAIT_TICKS) __builtin_amdgcn_s_sleep(8);
+  while (spec_peek(&S->tail_state) == TAIL_WORKER && wall_clock64() - t0 < 10 * SPEC_WAIT_TICKS) __builtin_amdgcn_s_sleep(8);
 }
 // k_spec_begin: grid 1 x 128 on a worker's stream — first launch of a round (kernels_spec.h).  base: the worker's SHADOW slot; back: its
 // distance from the slot being solved.  Waits for an accepted state newer than the last one it looked at, copies it, claims
@@ -368,7 +368,7 @@ __global__ __launch_bounds__(128) void k_spec_begin(char *base, size_t back) {
     }
     if (tid == 0) {
       S->shadow.word = w, S->shadow.ticket = S0->spec.ticket;
-      S->spec_on = 0, S->dec_pending = 0, S->tail_state = 0, S->chain_err = 0;
+      S->spec_on = 0, S->dec_pending = 0, S->tail_state = TAIL_OPEN, S->chain_err = 0;
       S->tr.cur = 0, S->tr.done = 1;
     }
     __syncthreads();
@@ -1086,7 +1086,7 @@ DEV bool eig_tridiag(double *A, const double *b, int n, int tid, double *RV, dou
 
 // End of a worker's k_marg_solve (kernels_spec.h): the prior of the state `my_word` lies finished in the shadow slot S.  Wait for
 // the loop of S0 to close (or for a newer accepted state); if this state is the final one the loop has committed the prior to us:
-// it moves into S0->prior_out, tail_state 3 -> 2, the caller's ticket is echoed (and the mailbox filled when the call hands its
+// it moves into S0->prior_out, tail_state TAIL_WORKER -> TAIL_DONE, the caller's ticket is echoed (and the mailbox filled when the call hands its
 // results over early).  Every thread of the workgroup comes here, behind a barrier that follows the last store to S->prior_out.
 DEV void spec_deliver(Slot *S, Slot *S0, int my_word, bool publish) {
   const int tid = threadIdx.x, nthr = blockDim.x;
@@ -1129,8 +1129,8 @@ DEV void spec_deliver(Slot *S, Slot *S0, int my_word, bool publish) {
   char *m = (char *)S0->mail;
   if (tid == 0) {
     __threadfence_system();
-    __hip_atomic_store(&S0->tail_state, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (m) __hip_atomic_store((int *)m + 7, S->shadow.ticket, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(&S0->tail_state, (int)TAIL_DONE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (m) __hip_atomic_store((int *)m + MAIL_ECHO, S->shadow.ticket, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }
 }
 
@@ -1164,7 +1164,7 @@ __global__ __launch_bounds__(MARG_THREADS) void k_marg_solve(char *base, size_t 
       spec_deliver(S, S0, sp.my_word, publish != 0);
       return;
     }
-    if (gated && tid == 0) S->iters_done = tr->iteration, S->tail_state = 2;
+    if (gated && tid == 0) S->iters_done = tr->iteration, S->tail_state = TAIL_DONE;
     if (gated && publish) {
       __syncthreads();
       publish_prior(S);
@@ -1338,7 +1338,7 @@ __global__ __launch_bounds__(MARG_THREADS) void k_marg_solve(char *base, size_t 
     out->m = m15 + (S->sharded ? (int)(S->xch[XOFF_C + XS_N0] + 0.5) : mp->N0);
     out->n = n;
     out->num_blocks = mp->nb;
-    if (gated && !worker) S->iters_done = tr->iteration, S->tail_state = 2;
+    if (gated && !worker) S->iters_done = tr->iteration, S->tail_state = TAIL_DONE;
   }
   if (worker) {
     __syncthreads();

@@ -1616,5 +1616,5 @@ __global__ __launch_bounds__(64) void k_decide(char *base, size_t stride) {
   Slot *S = SLOT(base, stride);
   decide_body(S);
   // the loop is closed and the gated gauge fix is the next kernel: no worker may claim this state from here on (kernels_spec.h)
-  if (S->spec_on && threadIdx.x == 0 && S->tr.done && S->tail_state == 0) spec_closing(S);
+  if (S->spec_on && threadIdx.x == 0 && S->tr.done && S->tail_state == TAIL_OPEN) spec_closing(S);
 }

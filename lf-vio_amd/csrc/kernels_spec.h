@@ -54,7 +54,7 @@ DEV void spec_arm(Slot *S) {
   spec_st(&S->spec.word, 0);
   for (int k = 0; k < SPEC_OWN; k++) S->spec.own[k] = SPEC_FREE;
   S->spec.ep = ep;
-  S->spec.ticket = S->mail ? __hip_atomic_load((const int *)S->mail + 6, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : 0;
+  S->spec.ticket = S->mail ? __hip_atomic_load((const int *)S->mail + MAIL_TICKET, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : 0;
   spec_st(&S->spec.fin, 0);
 }
 // k_lin, one thread of every pass, as soon as the accepted state the pass linearizes at is complete in x[cur] / lam[cur]: at once
@@ -69,7 +69,7 @@ DEV void spec_closing(Slot *S) {
   __hip_atomic_store(&S->spec.fin, S->spec.ep << 16 | FIN_CLOSING, __ATOMIC_SEQ_CST, __HIP_MEMORY_SCOPE_AGENT);
   __threadfence();
 }
-// ... and behind it (the state is out): who forms the prior.  Returns true when a worker owns it — tail_state 3, the gated
+// ... and behind it (the state is out): who forms the prior.  Returns true when a worker owns it — TAIL_WORKER, the gated
 // kernels that follow return.
 DEV bool spec_settle(Slot *S) {
   const int a = S->tr.num_succ;
@@ -79,7 +79,7 @@ DEV bool spec_settle(Slot *S) {
     if (was == SPEC_SIDE) side = spec_cas(&S->spec.own[a], SPEC_SIDE, SPEC_COMMIT) == SPEC_SIDE;
     if (was != SPEC_FREE && !side) spec_st(&S->spec.own[a], SPEC_MAIN);
   }
-  if (side) S->tail_state = 3, S->iters_done = S->tr.iteration;  // (what k_marg_solve leaves for the host's copy of {tail_state .. chain_err})
+  if (side) S->tail_state = TAIL_WORKER, S->iters_done = S->tr.iteration;  // (what k_marg_solve leaves for the host's copy of {tail_state .. chain_err})
   spec_st(&S->spec.fin, S->spec.ep << 16 | (a < SPEC_OWN ? a : 0) << 2 | (side ? FIN_SIDE : FIN_MAIN));
   return side;
 }

@@ -39,6 +39,7 @@ constexpr ncclDataType_t ncclDouble = 8;
 #include "kernels_feat.h"
 #include "kernels_linw.h"
 #include "linb_plan.h"
+#include "call_state.h"
 #include "kernels_stepw.h"
 #include "kernels_relo.h"
 #include "kernels_twoview.h"
@@ -221,60 +222,49 @@ struct lfvio_ctx {
   GraphKey graph_key;
   // cached graph of one chunk of passes (synchronous entry points: the loop is launched chunk by chunk)
   // [publish]: the variants whose gated gauge fix / marginalization also push state and prior into the caller's mailbox
-  // (lfvio_batch_optimize_begin) — a kernel argument, so the plain call pays nothing for the split one
-  bool publish = false;
+  // (CallPlan::publish)
   hipGraphExec_t chunk[2] = {}, tail[2][3] = {};  // chunk[speculation variant]
   hipGraphExec_t first[2][2][4][13] = {};  // [speculation variant: 0 three candidates (or none), 1 four][publish][0: solve only, 1 + flag: with the gated tail][passes in the first graph]
   int fixed_passes = 0;             // debug (lfvio_debug_configure "first_passes"): > 0 sizes every first graph with this many passes
   int recent_passes[4] = {0, 0, 0, 0}, recent_head = 0;  // passes of the last four synchronous calls (predict())
-  bool predicted_early = false;     // lfvio_batch_optimize_begin has fed this call's pass count to predict() already (the join / finish that follows must not again)
   int predict_passes = 4;           // passes the first graph of the next call carries: the most any of the last four calls needed (predict()); tail[flag]: force-done + gated gauge fix + marginalization
   double pass_seconds = 2e-4;       // measured duration of one pass of a continuation chunk (sizes the first graph of a call with a wall-clock cap)
   GraphKey chunk_key;  // of chunk, tail, first and the workers' graphs
-  int *d_pending = nullptr, *h_pending = nullptr;  // number of slots whose trust-region loop is not done
+  int *d_pending = nullptr;  // number of slots whose trust-region loop is not done
+  PendingBlock *h_pending = nullptr;
   // lfvio_batch_optimize_begin / _finish: the solution of slot 0 arrives in host memory the gated gauge fix writes directly
-  // (Slot::mail, dev_types.h MAIL_*) while the marginalization of the same graph is still running; `inflight` from the moment
-  // begin has returned on that flag until the stream has been synchronized again (join_inflight: every entry point that
-  // touches the slots or the stream starts with it).  The landmark-parallel steps either side of optimization()
+  // (Slot::mail, dev_types.h MAIL_*) while the marginalization of the same graph is still running.  What is in flight then, and what
+  // every entry point has to wait for, is `call` (call_state.h: the state table; join_inflight: every entry point that touches the
+  // slots or the stream starts with it).  The landmark-parallel steps either side of optimization()
   // (triangulate / shift_depth / preintegrate) have their own stream and scratch and do not wait for the tail.
+  CallState call;
   char *h_mail = nullptr, *d_mail = nullptr;
   hipStream_t fstream = nullptr;
   // The marginalization run ahead of the loop's end (kernels_spec.h): a SHADOW slot behind the last one (contexts of one small
   // window), workers on a stream of their own (lowest priority: a third pool of hardware queues), one graph of SIDE_ROUNDS rounds
-  // per marginalization flag and hand-over variant.  mail[6]: the ticket of the call in flight, echoed into mail[7] by the worker
+  // per marginalization flag and hand-over variant.  MAIL_TICKET: the ticket of the call in flight, echoed into MAIL_ECHO by the worker
   // that delivers its prior.
   static constexpr int WORKERS = 2;  // two, so that the newest accepted state never waits for the round of an older one to notice it is stale
   hipStream_t sstream[WORKERS] = {};
   bool shadow = false;          // the blob has batch + WORKERS slots, the last ones the shadows of slot 0
   bool marg_ahead = true;       // debug (lfvio_debug_configure): off = every call ends with the serial tail
   hipGraphExec_t side[WORKERS][2][2] = {};  // [worker][marg_flag][publish]
-  int side_ticket = 0;          // last ticket handed out
-  bool side_launched = false;   // workers were started for the call in flight (or just finished)
-  bool side_known = false;      // ... and h_pending[2] holds its tail_state (the first graph carried the tail)
   long long stat_ahead_calls = 0, stat_ahead_hits = 0;  // calls with workers | priors a worker delivered
-  bool inflight = false;
-  bool unsynced = false;        // finish() took the prior from the mailbox and left the last microseconds of the graph to the next join
-  // a prior collected on the caller's behalf because the slots had to be re-allocated while its call was in flight
-  // (reserve): lfvio_batch_optimize_finish / lfvio_batch_upload_chained hand it over
   // the copies out of h_stage are awaited by the NEXT user of the staging block, not by the upload that enqueued them
   hipEvent_t stage_event = nullptr;
   bool stage_busy = false;
   double up_us[4] = {0, 0, 0, 0};  // last upload: host packing | collecting the chained prior | prior + copies enqueued | final synchronization (lfvio_debug_query "upload_times")
+  // a prior collected on the caller's behalf because the slots had to be re-allocated while its call was in flight
+  // (reserve, CallState::HELD): lfvio_batch_optimize_finish / lfvio_batch_upload_chained hand it over
   std::unique_ptr<LfvioPrior> held;
-  bool has_held = false;
-  int inflight_flag = 0;        // marg_flag of the call in flight
-  bool pipelined = false;       // the window resident in slot 0 was uploaded behind a marginalization still running (lfvio_batch_upload_chained_device):
-                                // the stream holds work nobody has waited for; the next lfvio_batch_optimize_begin goes out behind it without a wait
   int mail_seq = 0;             // sequence number of the last upload (Slot::mail_seq)
   std::unique_ptr<LfvioPrior> chain_struct;  // the structure-only prior of a device-chained upload
-  bool chain_err_told = false;     // the call in flight ran without the prior it was promised and its begin() has said so
   // lfvio_solve_relo (relo.inc): the route's device blob and pinned staging blob (grow-only), the loop's `done` word read per pass
   char *d_relo = nullptr, *h_relo = nullptr;
   size_t relo_dev_cap = 0, relo_stage_cap = 0;
   int relo_done_word = 0;
   bool relo_force = false;  // lfvio_debug_configure "relo_route": the relo route even without a match
   bool debug_break_chain = false;  // lfvio_debug_configure "break_next_chain": the next device-chained upload promises a prior of another size than the device will find
-  bool inflight_first = false;  // the flag came out of the first graph: {tail_state, passes_used} land in h_pending[2..3] when it ends
   bool use_graph = true;
   int stat_chunks = 0;  // graph launches of the last synchronous solve loop (debug)
   int last_passes = 0;  // passes of the trust-region loop the last synchronous call used (slowest slot)
@@ -308,10 +298,7 @@ namespace {
 // dimensions, and a stream of windows changes those every few frames
 void destroy_graph(lfvio_ctx *c, bool keep_side = false) {
   // (a graph whose tail is still running behind an early state is not destroyed under it)
-  if (c->stream && (c->inflight || c->unsynced || c->pipelined)) {
-    (void)hipStreamSynchronize(c->stream);
-    c->unsynced = false, c->pipelined = false;
-  }
+  if (c->stream && c->call.graphs_dropped()) (void)hipStreamSynchronize(c->stream);
   if (c->graph) {
     (void)hipGraphExecDestroy(c->graph);
     c->graph = nullptr;
@@ -336,10 +323,6 @@ void destroy_graph(lfvio_ctx *c, bool keep_side = false) {
           if (t) (void)hipGraphExecDestroy(t), t = nullptr;
 }
 
-// The tail of a call whose solution went out early (lfvio_batch_optimize_begin) is still on the stream: wait for it and
-// take the bookkeeping its graph left in the pinned block.  First statement of everything that touches the slots.
-// pipelined_ok (lfvio_batch_optimize_begin only): a window uploaded behind a marginalization that is still running
-// (lfvio_batch_upload_chained_device) is optimized behind it too — everything is ordered by the stream, nothing is waited for.
 // The first graph of the next call is sized from the calls before it.  A pass the window does not need returns at once (~15 us of
 // launches for the four kernels); a pass it needs and the graph does not carry is a round trip to the host and another graph
 // launch (~60 us).  A resident window re-solved again and again needs the same number every time; the windows of a stream vary by
@@ -351,55 +334,53 @@ void predict(lfvio_ctx *c) {
   for (int k = 0; k < 4; k++) m = std::max(m, c->recent_passes[k]);
   c->predict_passes = m;
 }
-// The call whose loop has just ended on stream 0 left its prior to a worker on the second stream (tail_state 3, kernels_spec.h): wait
+// The counts of a call whose loop has ended (lfvio_debug_query "last_call"); act & FEED_PREDICTION: ... for the first time, so they
+// size the next call's first graph
+void record_call(lfvio_ctx *c, int passes, int iters, unsigned act) {
+  c->last_passes = std::max(passes, 1), c->last_iters = iters;
+  if (act & CallState::FEED_PREDICTION) predict(c);
+}
+volatile int *mail_word(lfvio_ctx *c, MailWord w) { return (volatile int *)c->h_mail + w; }
+// The call whose loop has just ended on stream 0 left its prior to a worker on the second stream (TAIL_WORKER, kernels_spec.h): wait
 // for the worker's echo of the call's ticket — it follows the prior's arrival in slot 0 (and in the mailbox) behind a system-scope
 // fence.  Stream 0 is idle when this is called.
 int wait_side(lfvio_ctx *c) {
-  if (!c->side_launched) return LFVIO_OK;
-  c->side_launched = false;
+  const CallState::Workers w = c->call.take_workers();
+  if (w == CallState::NO_WORKERS) return LFVIO_OK;
   int ts = 0;
-  if (c->side_known) ts = c->h_pending[2];
+  if (w == CallState::KNOWN) ts = c->h_pending->tail_state;
   else HIPCHK(c, hipMemcpy(&ts, c->d_base + offsetof(Slot, tail_state), sizeof ts, hipMemcpyDeviceToHost));  // (a tail graph of its own: rare)
-  const int *echo = (const int *)c->h_mail + 7;
-  if (ts == 3) {
+  const int *echo = (const int *)mail_word(c, MAIL_ECHO);
+  if (ts == TAIL_WORKER) {
     const auto t0 = std::chrono::steady_clock::now();
-    while (__atomic_load_n(echo, __ATOMIC_ACQUIRE) != c->side_ticket) {
+    while (__atomic_load_n(echo, __ATOMIC_ACQUIRE) != c->call.ticket) {
       if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 2.0) {
+        c->call.worker_wait_timed_out();
         c->err = "the marginalization handed to a worker stream did not arrive";
         return LFVIO_ERR_DEVICE;
       }
     }
   }
-  if (__atomic_load_n(echo, __ATOMIC_ACQUIRE) == c->side_ticket) c->stat_ahead_hits++;
-  ((volatile int *)c->h_mail)[6] = 0;  // (whatever runs k_setup on this slot next without workers of its own — a standalone marginalization, a debug sweep — publishes nothing)
+  if (__atomic_load_n(echo, __ATOMIC_ACQUIRE) == c->call.ticket) c->stat_ahead_hits++;
+  *mail_word(c, MAIL_TICKET) = 0;  // (whatever runs k_setup on this slot next without workers of its own — a standalone marginalization, a debug sweep — publishes nothing)
   return LFVIO_OK;
 }
 constexpr const char *CHAIN_ERR_TEXT = "the prior this window was to take over on the device was not there (the marginalization before it produced none): it ran without a prior";
-int join_inflight(lfvio_ctx *c, bool pipelined_ok = false) {
-  if (c->pipelined && !c->inflight && pipelined_ok) return LFVIO_OK;
-  if (c->unsynced || c->pipelined) {
-    c->unsynced = false, c->pipelined = false;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (!c->inflight)
-      if (int rc = wait_side(c)) return rc;
-  }
-  if (!c->inflight) return LFVIO_OK;
-  c->inflight = false;
+// The tail of a call whose solution went out early (lfvio_batch_optimize_begin) is still on the stream: wait for it and
+// take the bookkeeping its graph left in the pinned block.  First statement of everything that touches the slots.
+// OVERTAKE_PIPELINED (lfvio_batch_optimize_begin only): a window uploaded behind a marginalization that is still running
+// (lfvio_batch_upload_chained_device) is optimized behind it too — everything is ordered by the stream, nothing is waited for.
+// (the chain error of the call in flight is not looked at here: its begin() has reported it with the state, and once is enough)
+int join_inflight(lfvio_ctx *c, CallState::Overtake overtake = CallState::WAIT) {
+  const unsigned act = c->call.join(overtake);
+  if (!(act & CallState::DRAIN)) return LFVIO_OK;
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  const bool handed = c->side_launched && c->side_known && c->h_pending[2] == 3;  // the prior was a worker's (kernels_spec.h)
+  const bool handed = c->h_pending && c->call.handed_to_worker(c->h_pending->tail_state == TAIL_WORKER);  // the prior was a worker's (kernels_spec.h)
   if (int rc = wait_side(c)) return rc;
-  if (c->inflight_first) {
-    c->last_passes = std::max(c->h_pending[3], 1), c->last_iters = c->h_pending[4];
-    if (!c->predicted_early) predict(c);
-    c->predicted_early = false;
-    if (c->h_pending[2] != 2 && !handed) {
+  if (act & CallState::READ_FIRST_WORDS) {
+    record_call(c, c->h_pending->passes_used, c->h_pending->iters_done, act);
+    if (c->h_pending->tail_state != TAIL_DONE && !handed) {
       c->err = "the marginalization behind an early solution did not finish";
-      return LFVIO_ERR_DEVICE;
-    }
-    const bool told = c->chain_err_told;  // (lfvio_batch_optimize_begin has reported it with the state: once is enough)
-    c->chain_err_told = false;
-    if (c->h_pending[5] && !told) {
-      c->err = CHAIN_ERR_TEXT;
       return LFVIO_ERR_DEVICE;
     }
   }
@@ -411,7 +392,7 @@ int join_inflight(lfvio_ctx *c, bool pipelined_ok = false) {
 // (the flag is the sequence number of the resident window's upload: a window optimized behind the marginalization of the one
 // before must not take that one's late prior flag for its own)
 bool wait_early(lfvio_ctx *c) {
-  int *flag = (int *)c->h_mail;
+  int *flag = (int *)c->h_mail + MAIL_STATE_FLAG;
   const int want = c->info[0].mail_seq;
   for (;;) {
     if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == want) return true;
@@ -422,10 +403,10 @@ bool wait_early(lfvio_ctx *c) {
 constexpr int SHADOW_MAX_LM = 1024;  // capacity (with reserve()'s headroom) up to which a one-window context carries a shadow slot
 int reserve(lfvio_ctx *c, int batch, int maxN, int maxM) {
   if (c->d_base && batch <= c->batch && maxN <= c->L.maxN && maxM <= c->L.maxM) return LFVIO_OK;  // (the usual case: nothing to wait for)
-  if (c->inflight) {  // the slot that holds the prior of the call in flight is about to be freed: collect it first
+  if (c->call.early()) {  // the slot that holds the prior of the call in flight is about to be freed: collect it first
     if (!c->held) c->held.reset(new LfvioPrior);
     if (int rc = lfvio_batch_optimize_finish(c, c->held.get())) return rc;
-    c->has_held = true;
+    c->call.prior_held();
   }
   if (int rc = join_inflight(c)) return rc;
   batch = std::max(batch, c->batch);
@@ -618,11 +599,11 @@ int check_window(lfvio_ctx *c, const LfvioWindow *w) {
 // values k_prior_chain copies out of Slot::prior_out behind these copies, which the stream puts behind the marginalization.
 int upload_window(lfvio_ctx *c, int slot, const LfvioWindow *w, int sharded = 0, int pose_side = 1, LfvioPrior *chain = nullptr, bool device_chain = false) {
   if (device_chain) {
-    if (slot != 0 || sharded || !c->inflight || c->has_held || !c->info[0].resident) {
+    if (slot != 0 || sharded || !c->call.can_chain_on_device() || !c->info[0].resident) {
       c->err = "lfvio_batch_upload_chained_device: no call in flight on slot 0 (lfvio_batch_optimize_begin) whose prior could be taken over";
       return LFVIO_ERR_ARG;
     }
-    const SlotHostInfo::MargOut &mo = c->info[0].marg_out[c->inflight_flag];
+    const SlotHostInfo::MargOut &mo = c->info[0].marg_out[c->call.marg_flag];
     if (!mo.valid) {
       c->err = "lfvio_batch_upload_chained_device: the marginalization in flight passes its input prior through (MARGIN_SECOND_NEW without a "
                "prior on the newest pose) — use lfvio_batch_upload_chained";
@@ -636,7 +617,7 @@ int upload_window(lfvio_ctx *c, int slot, const LfvioWindow *w, int sharded = 0,
     for (int i = 0; i < mo.nb; i++) sp->blocks[i].kind = mo.kind[i], sp->blocks[i].frame = mo.frame[i], sp->block_idx[i] = mo.idx[i];
     chain = sp;
   }
-  const bool chained = !device_chain && chain && (c->inflight || c->has_held) && slot == 0;
+  const bool chained = !device_chain && chain && c->call.pending() && slot == 0;
   const auto t_up0 = std::chrono::steady_clock::now();
   auto lap = [&](int k, std::chrono::steady_clock::time_point from) {
     const auto now = std::chrono::steady_clock::now();
@@ -1015,7 +996,7 @@ int upload_window(lfvio_ctx *c, int slot, const LfvioWindow *w, int sharded = 0,
   info.linw_ok = linw;
   info.linb_ok = linb, info.linb_ng = linb_ng;
   // (an upload behind a call in flight whose prior a worker on the second stream may own: it reads this slot's inputs until it delivers)
-  if (slot == 0 && c->side_launched) hipLaunchKernelGGL(k_spec_wait, dim3(1), dim3(64), 0, c->stream, d);
+  if (slot == 0 && c->call.workers_outstanding()) hipLaunchKernelGGL(k_spec_wait, dim3(1), dim3(64), 0, c->stream, d);
   // header prefix + input arrays (two copies: the work-pointer part of the header is written once below)
   HIPCHK(c, hipMemcpyAsync(d, h, offsetof(Slot, x), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(d + L.in_begin, h + L.in_begin, (lists_cached ? L.sum_off : L.sum_items + (size_t)used_items * 4) - L.in_begin, hipMemcpyHostToDevice,
@@ -1024,7 +1005,7 @@ int upload_window(lfvio_ctx *c, int slot, const LfvioWindow *w, int sharded = 0,
   if (device_chain) {
     hipLaunchKernelGGL(k_prior_chain, dim3(1, 1), dim3(256), 0, c->stream, d, L.total);  // (the slot's own blob as base)
     // the call that was in flight is now only work on the stream in front of this window's: nothing of it is left to collect
-    c->inflight = false, c->pipelined = true;
+    c->call.chained_on_device();
   }
   if (linw) HIPCHK(c, hipMemcpyAsync(d + L.linw_begin, h + L.linw_begin, L.pm_pair + (size_t)std::max(M - N, 0) - L.linw_begin, hipMemcpyHostToDevice, c->stream));
   if (linb) HIPCHK(c, hipMemcpyAsync(d + L.linb_lm0, h + L.linb_lm0, L.linw_end - L.linb_lm0, hipMemcpyHostToDevice, c->stream));
@@ -1284,13 +1265,19 @@ void launch_solve(lfvio_ctx *c, int count, bool lw = false) {
     hipLaunchKernelGGL(k_solve_dense<false>, dim3(1, count), dim3(SOLVE_THREADS), SOLVE_LDS, c->stream, c->d_base, st, xo, io, po, (const int *)nullptr);
 }
 
-// speculate: small windows evaluate the steps for radius, radius / 2, radius / 4 in every pass (dev_types.h, SPEC_EXTRA)
-// first / last: position of the pass in the sequence being issued (a graph, or a plain run of passes).  For small windows
-// the trust-region bookkeeping of a pass rides in the prologue of the NEXT pass's k_lin (MODE_DECIDE, one launch less per
-// pass); k_decide itself is only launched behind the last pass, so that the header is final where the sequence ends.
-// gauge: the gated gauge fix follows this (last) pass — returns true if it went out with the bookkeeping (k_decide_gauge)
-// r: route_for(c, count, mode); offs: see with_offs
-bool launch_iteration(lfvio_ctx *c, const Route &r, int mode, bool speculate = false, bool first = true, bool last = true, bool gauge = false, bool offs = true) {
+// One pass of the loop (or the sweep of a marginalization), where it stands in the sequence being issued and what rides with it
+struct Pass {
+  bool speculate = false;          // small windows evaluate the steps for radius, radius / 2, radius / 4 in every pass (dev_types.h, SPEC_EXTRA)
+  // position of the pass in the sequence (a graph, or a plain run of passes).  For small windows
+  // the trust-region bookkeeping of a pass rides in the prologue of the NEXT pass's k_lin (MODE_DECIDE, one launch less per
+  // pass); k_decide itself is only launched behind the last pass, so that the header is final where the sequence ends.
+  bool first = true, last = true;
+  bool gauge = false;              // the gated gauge fix follows this (last) pass: launch_iteration returns true if it went out with the bookkeeping (k_decide_gauge)
+  bool publish = false;            // ... and hands the state over early (CallPlan::publish)
+  bool offs = true;                // see with_offs
+};
+// r: route_for(c, count, mode)
+bool launch_iteration(lfvio_ctx *c, const Route &r, int mode, const Pass &ps) {
   const int count = r.count;
   const Grid &g = r.g;
   const size_t st = c->L.total;
@@ -1299,12 +1286,12 @@ bool launch_iteration(lfvio_ctx *c, const Route &r, int mode, bool speculate = f
   // GPU than the launch it saves)
   const bool lw = r.sweep == Route::LINW, lb = r.sweep == Route::LINB;
   const bool merge = solve && !lw && g.lm <= DOGLEG_INLINE_BLOCKS && r.role_wgs <= LIN_SPLIT_WGS;
-  launch_sweep(c, r, mode, offs, merge && !first);
+  launch_sweep(c, r, mode, ps.offs, merge && !ps.first);
   if ((mode & (MODE_GATED - 1)) == MODE_SOLVE) {
     launch_solve(c, count, lw);  // (k_sumb leaves the complete matrix)
     // small windows: the landmark back-substitution rides inside k_dogleg (one launch less per pass)
     const bool inl = g.lm <= DOGLEG_INLINE_BLOCKS;
-    const int spec = speculate && inl ? c->spec_count : 1;
+    const int spec = ps.speculate && inl ? c->spec_count : 1;
     const int nb = g.lm + LFVIO_WINDOW_SIZE + 1;
     // few small windows: the step and the cost of its candidates in one launch (k_step)
     const bool split = r.split || lw;
@@ -1332,11 +1319,11 @@ bool launch_iteration(lfvio_ctx *c, const Route &r, int mode, bool speculate = f
       hipLaunchKernelGGL(k_cost_imu, dim3((count * LFVIO_WINDOW_SIZE + 63) / 64), dim3(64), 0, c->stream, c->d_base, st, count);
     } else
       hipLaunchKernelGGL(k_cost<1>, dim3(spec * nb, count), dim3(64), 0, c->stream, c->d_base, st, g.lm, spec);
-    if (merge && last && gauge) {
-      hipLaunchKernelGGL(k_decide_gauge, dim3(1, count), dim3(128), 0, c->stream, c->d_base, st, c->publish ? 1 : 0);
+    if (merge && ps.last && ps.gauge) {
+      hipLaunchKernelGGL(k_decide_gauge, dim3(1, count), dim3(128), 0, c->stream, c->d_base, st, ps.publish ? 1 : 0);
       return true;
     }
-    if (!merge || last) hipLaunchKernelGGL(k_decide, dim3(1, count), dim3(64), 0, c->stream, c->d_base, st);
+    if (!merge || ps.last) hipLaunchKernelGGL(k_decide, dim3(1, count), dim3(64), 0, c->stream, c->d_base, st);
   }
   return false;
 }
@@ -1347,7 +1334,7 @@ __global__ void k_pending(char *base, size_t stride, int count, int *out, int ta
   int n = 0, used = 0;
   for (int s = threadIdx.x; s < count; s += 64) {
     const Slot *S = (const Slot *)(base + (size_t)s * stride);
-    n += (tail ? S->tail_state == 2 : S->tr.done != 0) ? 0 : 1;
+    n += (tail ? S->tail_state == TAIL_DONE : S->tr.done != 0) ? 0 : 1;
     used = max(used, S->passes_used);
   }
   used = __reduce_max_sync(~0ull, used);
@@ -1362,20 +1349,226 @@ __global__ void k_force_done(char *base, size_t stride, int count) {
   if (s < count) {
     Slot *S = (Slot *)(base + (size_t)s * stride);
     if (!S->tr.done) S->tr.done = 1;
-    if (S->spec_on && S->tail_state == 0) spec_closing(S);  // (the gated gauge fix follows: kernels_spec.h)
+    if (S->spec_on && S->tail_state == TAIL_OPEN) spec_closing(S);  // (the gated gauge fix follows: kernels_spec.h)
   }
 }
 
-// Enqueue the trust-region loop for slots [0, count): max_iter Ceres iterations plus spare
+constexpr int SOLVE_CHUNK = 2, MAX_FIRST_PASSES = 12;  // continuation chunk; longest first graph
+constexpr int SIDE_ROUNDS = 4;  // rounds of the workers' graph (kernels_spec.h): accepted states a call can have a prior started for
+// STANDALONE: lfvio_marginalize — k_setup and a sweep at the uploaded state; AFTER_LOOP: behind the static loop and its gauge fix;
+// GATED: part of a graph of lfvio_batch_optimize*, per slot on `done` and tail_state
+enum MargKind { MARG_STANDALONE, MARG_AFTER_LOOP, MARG_GATED };
+int enqueue_marg(lfvio_ctx *c, const CallPlan &p, MargKind kind);
+
+// After a graph launch that may raise the state flag: clear both flags, launch, `behind` (what has to go out right behind the graph),
+// then *early = the solution is in the mailbox while the rest of the graph is still running (wait_early)
+template <class F>
+int launch_watched(lfvio_ctx *c, hipGraphExec_t graph, bool watch, bool *early, F &&behind) {
+  if (watch) __atomic_store_n((int *)c->h_mail + MAIL_PRIOR_FLAG, 0, __ATOMIC_RELAXED), __atomic_store_n((int *)c->h_mail + MAIL_STATE_FLAG, 0, __ATOMIC_RELEASE);
+  HIPCHK(c, hipGraphLaunch(graph, c->stream));
+  if (int rc = behind()) return rc;
+  *early = watch && wait_early(c);
+  return LFVIO_OK;
+}
+// the counts the state came with (publish_solution)
+void record_mailbox_call(lfvio_ctx *c, unsigned act) {
+  record_call(c, *mail_word(c, MAIL_STATE_PASSES), ((const TRState *)(c->h_mail + MAIL_TR))->iteration, act);
+}
+
+// The graphs of an adaptive call's loop: `first` — k_setup, first_passes passes and, fused, the gated gauge fix + marginalization — and
+// `chunk`, SOLVE_CHUNK passes for whatever is still open behind it.  Captured on first use, kept under chunk_key.
+struct LoopGraphs {
+  int first_passes = 0;
+  hipGraphExec_t first = nullptr, chunk = nullptr;
+};
+int loop_graphs(lfvio_ctx *c, const Route &r, const CallPlan &p, int passes, LoopGraphs *G) {
+  const int count = r.count;
+  const Grid &g = r.g;
+  const bool speculate = (size_t)count * (g.lm + LFVIO_WINDOW_SIZE + 1) <= 512;
+  // How many candidates a pass prepares follows the previous call (a stream of windows from one estimator is steady): where a
+  // pass covered two iterations or more — most steps rejected: the bench window's nine iterations take four passes with three
+  // candidates, three with four — the fourth candidate saves a pass; where nearly every step is accepted it would only be
+  // evaluated (measured with a fixed count: 0.532 / 0.511 ms resident with 3 / 4, 0.950 / 0.963 ms on the stream).
+  if (speculate && !c->fixed_spec) c->spec_count = (c->last_iters > 0 && c->last_iters >= 2 * c->last_passes) ? std::min(4, 1 + SPEC_EXTRA) : 3;
+  if (!c->d_pending) {
+    HIPCHK(c, hipMalloc((void **)&c->d_pending, 256));
+    HIPCHK(c, hipHostMalloc((void **)&c->h_pending, 256, hipHostMallocDefault));
+  }
+  const int offs = r.offs;
+  const GraphKey key = graph_key(r, (int)speculate, 0, true);
+  if (!(c->chunk_key == key)) {
+    destroy_graph(c, c->chunk_key.count == count && ((c->chunk_key.offs ^ offs) & 2) == 0);  // (the workers' graphs: per context, but for the fixed-extrinsic bit)
+    c->chunk_key = key;
+  }
+  const bool fuse = p.fused;
+  // The first graph carries as many passes as the previous call on this context needed (a stream of windows from one
+  // estimator is steady: the bench window takes 4, windows whose steps are mostly accepted 5 to 8), then — fused —
+  // the gated gauge fix + marginalization; whatever is still pending afterwards continues in chunks of SOLVE_CHUNK.
+  // With a cap the first graph is still the predicted one — a cap of SOLVER_TIME = 0.04 s (the shipped default) is a few
+  // hundred passes away and must not cost the call its single launch — unless the cap is so tight that the predicted
+  // graph could overrun it: then no more passes than fit (at the measured time per pass), down to a chunk of SOLVE_CHUNK.
+  int first_passes = std::min(std::max(c->fixed_passes > 0 ? c->fixed_passes : c->predict_passes, 1), std::min(passes, MAX_FIRST_PASSES));
+  if (p.max_seconds > 0.0) first_passes = std::max(std::min(SOLVE_CHUNK, passes), std::min(first_passes, (int)std::min(p.max_seconds / c->pass_seconds, 1e6)));
+  G->first_passes = first_passes;
+  const int sv = speculate && c->spec_count > 3 ? 1 : 0;  // (both variants stay captured: a stream may alternate)
+  hipGraphExec_t &first_graph = c->first[sv][p.publish ? 1 : 0][fuse ? 1 + p.marg_flag : 0][first_passes];
+  enum Head { PASSES_ONLY, SETUP_FIRST };
+  auto capture = [&](hipGraphExec_t *out, Head head, int npass, bool tail) {
+    const bool setup = head == SETUP_FIRST;
+    return capture_graph(c, c->stream, out, [&]() -> int {
+      if (setup) launch_setup(c, r, MODE_SOLVE);
+      bool gauged = false;
+      // (the sweep behind k_setup linearizes at the uploaded state: the only point of a call that can hold a quaternion off the unit sphere,
+      // a fixed extrinsic aside — slots_offs)
+      Pass ps;
+      ps.speculate = speculate, ps.gauge = tail, ps.publish = p.publish;
+      for (int it = 0; it < npass; it++) {
+        ps.first = it == 0, ps.last = it == npass - 1, ps.offs = (offs & 2) || (setup && it == 0 && (offs & 1));
+        gauged = launch_iteration(c, r, MODE_SOLVE, ps);
+      }
+      if (tail) {
+        if (!gauged) {
+          hipLaunchKernelGGL(k_gauge, dim3(1 + (g.lm + 1) / 2, count), dim3(128), 0, c->stream, c->d_base, c->L.total, 1);
+          if (p.publish) hipLaunchKernelGGL(k_publish, dim3(1), dim3(256), 0, c->stream, c->d_base, c->L.total);  // (k_decide_gauge does it itself)
+        }
+        if (int rc = enqueue_marg(c, p, MARG_GATED)) return rc;
+      }
+      if (tail && count == 1) {
+        // one window: its {tail_state .. chain_err} are the answer — copied as they are (PendingBlock), no k_pending launch
+        HIPCHK(c, hipMemcpyAsync(&c->h_pending->tail_state, c->d_base + offsetof(Slot, tail_state), 4 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+      } else {
+        hipLaunchKernelGGL(k_pending, dim3(1), dim3(64), 0, c->stream, c->d_base, c->L.total, count, c->d_pending, tail ? 1 : 0);
+        HIPCHK(c, hipMemcpyAsync(&c->h_pending->open, c->d_pending, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+      }
+      return LFVIO_OK;
+    });
+  };
+  if (!first_graph)
+    if (int rc = capture(&first_graph, SETUP_FIRST, first_passes, fuse)) return rc;
+  if (!c->chunk[sv])
+    if (int rc = capture(&c->chunk[sv], PASSES_ONLY, SOLVE_CHUNK, /*tail*/ false)) return rc;
+  G->first = first_graph, G->chunk = c->chunk[sv];
+  return LFVIO_OK;
+}
+
+// Workers for the marginalization run ahead (kernels_spec.h): SIDE_ROUNDS rounds of [k_spec_begin, k_lin, k_sum, k_marg_solve] on the shadow
+// slot, captured once per marginalization flag and hand-over variant; a round that finds nothing to do is four launches that return.
+int worker_graphs(lfvio_ctx *c, const Route &r, const CallPlan &p) {
+  for (int wk = 0; wk < lfvio_ctx::WORKERS; wk++) {
+    hipGraphExec_t *side_graph = &c->side[wk][p.marg_flag][p.publish ? 1 : 0];
+    if (*side_graph) continue;
+    hipStream_t ss = c->sstream[wk];
+    const size_t back = (size_t)(c->batch + wk) * c->L.total;
+    char *sh = c->d_base + back;
+    // launch dimensions for the largest window the merged sequence takes (spare workgroups test their index against the slot's own
+    // counts and return): one capture serves every window of the context
+    const Layout &L = c->L;
+    const int mode = (MODE_MARG + p.marg_flag) | MODE_GATED, gram_wgs = (L.capChunks + 3) / 4, lw_cap = 2 * DOGLEG_INLINE_BLOCKS;
+    // (the gather lists are inputs: the shadow's copies of those members lead back into slot 0, and so do these offsets;
+    // no k_presum: that is for windows of thousands of landmarks)
+    const SumArgs sa{(long long)L.sum_off - (long long)back, (long long)L.sum_end_marg - (long long)back, (long long)L.sum_items - (long long)back,
+                     (long long)L.gram_part, (long long)L.pairG, (long long)L.imu_out, (long long)L.prior_A - (long long)back};
+    const int rc = capture_graph(c, ss, side_graph, [&]() -> int {
+      for (int rd = 0; rd < SIDE_ROUNDS; rd++) {
+        hipLaunchKernelGGL(k_spec_begin, dim3(1), dim3(128), 0, ss, sh, back);
+        // (a re-anchored state: on the sphere but for a fixed extrinsic)
+        with_offs(r.offs & 2, [&](auto o) {
+          hipLaunchKernelGGL((k_lin<LIN_ROLE_ALL, decltype(o)::value>), dim3(lw_cap + gram_wgs + LFVIO_WINDOW_SIZE + 1, 1), dim3(LIN_THREADS), 0, ss, sh, back, mode,
+                             lw_cap, gram_wgs);
+        });
+        hipLaunchKernelGGL(k_sum, dim3(HPP_BLOCKS + SCHUR_LEN / 256 + 1, 1), dim3(256), 0, ss, sh, back, mode, 0, sa);
+        hipLaunchKernelGGL(k_marg_solve<true>, dim3(1, 1), dim3(MARG_THREADS), MARG_LDS, ss, sh, back,
+                           p.marg_flag | (c->force_eig ? 256 : 0) | 512 | (p.publish ? 1024 : 0));
+      }
+      return LFVIO_OK;
+    });
+    if (rc) return rc;
+  }
+  return LFVIO_OK;
+}
+
+// The adaptive loop: the first graph, then — while a slot is open, the passes last and the wall clock allows — chunks, the host
+// reading the PendingBlock in between.  *tail_done: the gated tail ran inside the first graph (or is running behind an early return)
+int adaptive_loop(lfvio_ctx *c, const Route &r, const CallPlan &p, int passes, bool *tail_done) {
+  const auto t_start = std::chrono::steady_clock::now();
+  LoopGraphs G;
+  if (int rc = loop_graphs(c, r, p, passes, &G)) return rc;
+  const int count = r.count;
+  const Grid &g = r.g;
+  const bool fuse = p.fused, capped = p.max_seconds > 0.0;
+  // Workers: one small window on the merged launch sequence (its loop ends in k_decide_gauge), with a shadow slot and a mailbox.
+  // (not behind a device-chained upload: there the marginalization already runs beside the host's packing of the next window, and the next
+  // window's upload would have to wait for a worker instead of following the stream)
+  const bool ahead = fuse && count == 1 && c->info[0].spec_on && c->shadow && c->marg_ahead && !c->shard_active && !c->call.pipelined() &&
+                     g.lm <= DOGLEG_INLINE_BLOCKS && g.ch_raw <= PRE_CHUNK_LIMIT && g.sc <= 4 * PRE_GROUP && r.sweep == Route::ROLES;
+  if (ahead)
+    if (int rc = worker_graphs(c, r, p)) return rc;
+  // (ticket 0: a call without workers — rounds left over from an earlier call must not take its states: spec_publish)
+  const int ticket = c->call.loop_started(ahead);
+  if (c->h_mail && count == 1) *mail_word(c, MAIL_TICKET) = ticket;
+  c->stat_chunks = 0;
+  for (int done_passes = 0; done_passes < passes;) {
+    c->stat_chunks++;
+    const auto t_launch = std::chrono::steady_clock::now();
+    const bool first = done_passes == 0;
+    if (first) {
+      bool early = false;
+      const int rc = launch_watched(c, G.first, p.early && fuse && p.publish, &early, [&]() -> int {
+        if (ahead) {  // (behind the loop's graph: on a shared hardware queue the workers would otherwise wait in front of it)
+          for (int wk = 0; wk < lfvio_ctx::WORKERS; wk++) HIPCHK(c, hipGraphLaunch(c->side[wk][p.marg_flag][p.publish ? 1 : 0], c->sstream[wk]));
+          c->call.workers_started(), c->stat_ahead_calls++;
+        }
+        if (c->call.pipelined()) c->up_us[1] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_launch).count() * 1e6;  // (debug: lfvio_debug_query "upload_times")
+        return LFVIO_OK;
+      });
+      if (rc) return rc;
+      if (early) {  // the window was done inside the first graph: its tail follows in the same graph.  The loop is closed: its counts size
+                    // the next call's first graph (a caller that pipelines never joins this graph)
+        record_mailbox_call(c, c->call.early_from_first());
+        *tail_done = true;
+        return LFVIO_OK;
+      }
+    } else
+      HIPCHK(c, hipGraphLaunch(G.chunk, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    PendingBlock &hp = *c->h_pending;
+    if (!first) {  // time per pass, for sizing a capped call's first graph (continuation chunks carry nothing but passes)
+      const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_launch).count() / SOLVE_CHUNK;
+      c->pass_seconds = 0.75 * c->pass_seconds + 0.25 * dt;
+    }
+    done_passes += first ? G.first_passes : SOLVE_CHUNK;
+    if (first && fuse && count == 1) hp.open = hp.tail_state >= TAIL_DONE ? 0 : 1, hp.passes = hp.passes_used, c->last_iters = hp.iters_done;  // (TAIL_WORKER: the prior is a worker's)
+    if (first && (c->call.first_graph_ended(fuse && count == 1, hp.open == 0) & CallState::CHECK_CHAIN_ERR) && hp.chain_err) {
+      c->err = CHAIN_ERR_TEXT;
+      return LFVIO_ERR_DEVICE;
+    }
+    if (hp.open == 0) {
+      if (fuse && first) *tail_done = true;
+      break;
+    }
+    if (capped && std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count() >= p.max_seconds) {
+      // "Maximum solver time reached": the open slots end where they are, termination stays NO_CONVERGENCE
+      hipLaunchKernelGGL(k_force_done, dim3((count + 63) / 64), dim3(64), 0, c->stream, c->d_base, c->L.total, count);
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      break;
+    }
+  }
+  record_call(c, c->h_pending->passes, c->last_iters, c->call.loop_ended());  // passes the slowest window has used
+  HIPCHK(c, hipGetLastError());
+  // (a call that ended inside its first graph: the prior may be on its way from a worker; one that continues with a tail graph
+  // is waited for by the join in front of whatever comes next)
+  if (*tail_done)
+    if (int rc = wait_side(c)) return rc;
+  return LFVIO_OK;
+}
+
+// Enqueue the trust-region loop for slots [0, p.count): max_iter Ceres iterations plus spare
 // passes for mu-retries (a failed Cholesky consumes a pass but not an iteration).
 //   adaptive = false: the whole loop as one static graph, nothing but enqueues (lfvio_batch_optimize_async).
 //   adaptive = true (synchronous entry points): the passes go out in chunks of SOLVE_CHUNK and the host reads the number
 //     of unfinished slots in between.  A pass costs its ~30 us of launches and first loads whether or not the loop is
 //     already done, and with the speculative candidates of small windows nine iterations are four passes, not twelve.
-constexpr int SOLVE_CHUNK = 2, MAX_FIRST_PASSES = 12;  // continuation chunk; longest first graph
-constexpr int SIDE_ROUNDS = 4;  // rounds of the workers' graph (kernels_spec.h): accepted states a call can have a prior started for
-int enqueue_marg(lfvio_ctx *c, int count, int flag, bool standalone, bool gated = false);
-// fused_flag >= 0 (adaptive only): gauge fix + marginalization ride in the graph of the first chunk, gated per slot on
+// fused (adaptive only): gauge fix + marginalization ride in the graph of the first chunk, gated per slot on
 // `done` — the common case (every window done within the first chunk) is ONE graph launch and one synchronization; *tail_done
 // tells the caller whether anything is left for the (gated) tail graph.
 // max_seconds > 0 (adaptive only): Ceres' max_solver_time_in_seconds (estimator.cpp:815-822) — TrustRegionMinimizer tests the
@@ -1383,172 +1576,21 @@ int enqueue_marg(lfvio_ctx *c, int count, int flag, bool standalone, bool gated 
 // (the only points where it sees the loop) and ends the open slots the same way (k_force_done).  The first graph is sized
 // from the previous call as without a cap, shortened only when the cap is tighter than that many passes would take.
 // early (adaptive, fused, one window with a mailbox): return as soon as the solution is in the mailbox — the rest of the graph
-// (the marginalization) is still running then and c->inflight says so.
-int enqueue_solve(lfvio_ctx *c, int count, int max_iter, bool adaptive, int fused_flag = -1, bool *tail_done = nullptr,
-                  double max_seconds = -1.0, bool early = false) {
-  if (int rc = join_inflight(c, early)) return rc;
-  const Route r = route_for(c, count, MODE_SOLVE);
-  const Grid &g = r.g;
-  const int passes = std::max(max_iter, 0) + 4;
-  if (adaptive && c->use_graph) {
-    const bool speculate = (size_t)count * (g.lm + LFVIO_WINDOW_SIZE + 1) <= 512;
-    // How many candidates a pass prepares follows the previous call (a stream of windows from one estimator is steady): where a
-    // pass covered two iterations or more — most steps rejected: the bench window's nine iterations take four passes with three
-    // candidates, three with four — the fourth candidate saves a pass; where nearly every step is accepted it would only be
-    // evaluated (measured with a fixed count: 0.532 / 0.511 ms resident with 3 / 4, 0.950 / 0.963 ms on the stream).
-    if (speculate && !c->fixed_spec) c->spec_count = (c->last_iters > 0 && c->last_iters >= 2 * c->last_passes) ? std::min(4, 1 + SPEC_EXTRA) : 3;
-    if (!c->d_pending) {
-      HIPCHK(c, hipMalloc((void **)&c->d_pending, 256));
-      HIPCHK(c, hipHostMalloc((void **)&c->h_pending, 256, hipHostMallocDefault));
-    }
-    const int offs = r.offs;
-    const GraphKey key = graph_key(r, (int)speculate, 0, true);
-    if (!(c->chunk_key == key)) {
-      destroy_graph(c, c->chunk_key.count == count && ((c->chunk_key.offs ^ offs) & 2) == 0);  // (the workers' graphs: per context, but for the fixed-extrinsic bit)
-      c->chunk_key = key;
-    }
-    if (tail_done) *tail_done = false;
-    const bool fuse = fused_flag >= 0 && fused_flag < 2;
-    // The first graph carries as many passes as the previous call on this context needed (a stream of windows from one
-    // estimator is steady: the bench window takes 4, windows whose steps are mostly accepted 5 to 8), then — fused —
-    // the gated gauge fix + marginalization; whatever is still pending afterwards continues in chunks of SOLVE_CHUNK.
-    const bool capped = max_seconds > 0.0;
-    const auto t_start = std::chrono::steady_clock::now();
-    // With a cap the first graph is still the predicted one — a cap of SOLVER_TIME = 0.04 s (the shipped default) is a few
-    // hundred passes away and must not cost the call its single launch — unless the cap is so tight that the predicted
-    // graph could overrun it: then no more passes than fit (at the measured time per pass), down to a chunk of SOLVE_CHUNK.
-    int first_passes = std::min(std::max(c->fixed_passes > 0 ? c->fixed_passes : c->predict_passes, 1), std::min(passes, MAX_FIRST_PASSES));
-    if (capped) first_passes = std::max(std::min(SOLVE_CHUNK, passes), std::min(first_passes, (int)std::min(max_seconds / c->pass_seconds, 1e6)));
-    const int sv = speculate && c->spec_count > 3 ? 1 : 0;  // (both variants stay captured: a stream may alternate)
-    hipGraphExec_t &first_graph = c->first[sv][c->publish ? 1 : 0][fuse ? 1 + fused_flag : 0][first_passes];
-    auto capture = [&](hipGraphExec_t *out, bool setup, int npass, int tail_flag) {
-      return capture_graph(c, c->stream, out, [&]() -> int {
-        if (setup) launch_setup(c, r, MODE_SOLVE);
-        bool gauged = false;
-        // (the sweep behind k_setup linearizes at the uploaded state: the only point of a call that can hold a quaternion off the unit sphere,
-        // a fixed extrinsic aside — slots_offs)
-        for (int it = 0; it < npass; it++)
-          gauged = launch_iteration(c, r, MODE_SOLVE, speculate, it == 0, it == npass - 1, tail_flag >= 0, (offs & 2) || (setup && it == 0 && (offs & 1)));
-        if (tail_flag >= 0) {
-          if (!gauged) {
-            hipLaunchKernelGGL(k_gauge, dim3(1 + (g.lm + 1) / 2, count), dim3(128), 0, c->stream, c->d_base, c->L.total, 1);
-            if (c->publish) hipLaunchKernelGGL(k_publish, dim3(1), dim3(256), 0, c->stream, c->d_base, c->L.total);  // (k_decide_gauge does it itself)
-          }
-          if (int rc = enqueue_marg(c, count, tail_flag, false, true)) return rc;
-        }
-        if (tail_flag >= 0 && count == 1) {
-          // one window: its {tail_state, passes_used} pair is the answer — copied as it is, no k_pending launch
-          HIPCHK(c, hipMemcpyAsync(c->h_pending + 2, c->d_base + offsetof(Slot, tail_state), 4 * sizeof(int), hipMemcpyDeviceToHost, c->stream));  // (.. chain_err)
-        } else {
-          hipLaunchKernelGGL(k_pending, dim3(1), dim3(64), 0, c->stream, c->d_base, c->L.total, count, c->d_pending, tail_flag >= 0 ? 1 : 0);
-          HIPCHK(c, hipMemcpyAsync(c->h_pending, c->d_pending, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        }
-        return LFVIO_OK;
-      });
-    };
-    if (!first_graph) {
-      const int rc = capture(&first_graph, true, first_passes, fuse ? fused_flag : -1);
-      if (rc) return rc;
-    }
-    if (!c->chunk[sv]) {
-      const int rc = capture(&c->chunk[sv], false, SOLVE_CHUNK, -1);
-      if (rc) return rc;
-    }
-    // Workers for the marginalization run ahead (kernels_spec.h): one small window on the merged launch sequence (its loop ends in
-    // k_decide_gauge), with a shadow slot and a mailbox.  SIDE_ROUNDS rounds of [k_spec_begin, k_lin, k_sum, k_marg_solve] on the shadow
-    // slot, captured once per marginalization flag and hand-over variant; a round that finds nothing to do is four launches that return.
-    // (not behind a device-chained upload: there the marginalization already runs beside the host's packing of the next window, and the next
-    // window's upload would have to wait for a worker instead of following the stream)
-    const bool ahead = fuse && count == 1 && c->info[0].spec_on && c->shadow && c->marg_ahead  && !c->shard_active && !c->pipelined &&
-                       g.lm <= DOGLEG_INLINE_BLOCKS && g.ch_raw <= PRE_CHUNK_LIMIT && g.sc <= 4 * PRE_GROUP && r.sweep == Route::ROLES;
-    for (int wk = 0; ahead && wk < lfvio_ctx::WORKERS; wk++) {
-      hipGraphExec_t *side_graph = &c->side[wk][fused_flag][c->publish ? 1 : 0];
-      if (*side_graph) continue;
-      hipStream_t ss = c->sstream[wk];
-      const size_t back = (size_t)(c->batch + wk) * c->L.total;
-      char *sh = c->d_base + back;
-      // launch dimensions for the largest window the merged sequence takes (spare workgroups test their index against the slot's own
-      // counts and return): one capture serves every window of the context
-      const Layout &L = c->L;
-      const int mode = (MODE_MARG + fused_flag) | MODE_GATED, gram_wgs = (L.capChunks + 3) / 4, lw_cap = 2 * DOGLEG_INLINE_BLOCKS;
-      // (the gather lists are inputs: the shadow's copies of those members lead back into slot 0, and so do these offsets;
-      // no k_presum: that is for windows of thousands of landmarks)
-      const SumArgs sa{(long long)L.sum_off - (long long)back, (long long)L.sum_end_marg - (long long)back, (long long)L.sum_items - (long long)back,
-                       (long long)L.gram_part, (long long)L.pairG, (long long)L.imu_out, (long long)L.prior_A - (long long)back};
-      const int rc = capture_graph(c, ss, side_graph, [&]() -> int {
-        for (int rd = 0; rd < SIDE_ROUNDS; rd++) {
-          hipLaunchKernelGGL(k_spec_begin, dim3(1), dim3(128), 0, ss, sh, back);
-          // (a re-anchored state: on the sphere but for a fixed extrinsic)
-          with_offs(offs & 2, [&](auto o) {
-            hipLaunchKernelGGL((k_lin<LIN_ROLE_ALL, decltype(o)::value>), dim3(lw_cap + gram_wgs + LFVIO_WINDOW_SIZE + 1, 1), dim3(LIN_THREADS), 0, ss, sh, back, mode,
-                               lw_cap, gram_wgs);
-          });
-          hipLaunchKernelGGL(k_sum, dim3(HPP_BLOCKS + SCHUR_LEN / 256 + 1, 1), dim3(256), 0, ss, sh, back, mode, 0, sa);
-          hipLaunchKernelGGL(k_marg_solve<true>, dim3(1, 1), dim3(MARG_THREADS), MARG_LDS, ss, sh, back,
-                             fused_flag | (c->force_eig ? 256 : 0) | 512 | (c->publish ? 1024 : 0));
-        }
-        return LFVIO_OK;
-      });
-      if (rc) return rc;
-    }
-    c->side_launched = false, c->side_known = false;
-    c->stat_chunks = 0;
-    for (int done_passes = 0; done_passes < passes;) {
-      c->stat_chunks++;
-      const auto t_launch = std::chrono::steady_clock::now();
-      const bool watch = early && done_passes == 0 && fuse && c->publish;
-      if (watch) __atomic_store_n((int *)c->h_mail + 1, 0, __ATOMIC_RELAXED), __atomic_store_n((int *)c->h_mail, 0, __ATOMIC_RELEASE);
-      // (ticket 0: a call without workers — rounds left over from an earlier call must not take its states: spec_publish)
-      if (done_passes == 0 && c->h_mail && count == 1) ((volatile int *)c->h_mail)[6] = ahead ? (c->side_ticket = (c->side_ticket == 0x7fffffff ? 1 : c->side_ticket + 1)) : 0;
-      HIPCHK(c, hipGraphLaunch(done_passes == 0 ? first_graph : c->chunk[sv], c->stream));
-      if (ahead && done_passes == 0) {  // (behind the loop's graph: on a shared hardware queue the workers would otherwise wait in front of it)
-        for (int wk = 0; wk < lfvio_ctx::WORKERS; wk++) HIPCHK(c, hipGraphLaunch(c->side[wk][fused_flag][c->publish ? 1 : 0], c->sstream[wk]));
-        c->side_launched = true, c->stat_ahead_calls++;
-      }
-      if (c->pipelined && done_passes == 0) c->up_us[1] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_launch).count() * 1e6;  // (debug: lfvio_debug_query "upload_times")
-      if (watch && wait_early(c)) {  // the window was done inside the first graph: its tail follows in the same graph
-        c->inflight = true, c->inflight_first = true;
-        c->side_known = c->side_launched;
-        if (tail_done) *tail_done = true;
-        return LFVIO_OK;
-      }
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      const bool first = done_passes == 0;
-      if (!first) {  // time per pass, for sizing a capped call's first graph (continuation chunks carry nothing but passes)
-        const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_launch).count() / SOLVE_CHUNK;
-        c->pass_seconds = 0.75 * c->pass_seconds + 0.25 * dt;
-      }
-      done_passes += first ? first_passes : SOLVE_CHUNK;
-      if (first && fuse && count == 1) c->h_pending[0] = c->h_pending[2] >= 2 ? 0 : 1, c->h_pending[1] = c->h_pending[3], c->last_iters = c->h_pending[4];  // (3: the prior is a worker's)
-      if (first && fuse && count == 1 && c->h_pending[0] == 0) c->side_known = c->side_launched;
-      if (first && fuse && count == 1 && c->h_pending[5]) {
-        c->err = CHAIN_ERR_TEXT;
-        return LFVIO_ERR_DEVICE;
-      }
-      if (c->h_pending[0] == 0) {
-        if (tail_done && fuse && first) *tail_done = true;
-        break;
-      }
-      if (capped && std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count() >= max_seconds) {
-        // "Maximum solver time reached": the open slots end where they are, termination stays NO_CONVERGENCE
-        hipLaunchKernelGGL(k_force_done, dim3((count + 63) / 64), dim3(64), 0, c->stream, c->d_base, c->L.total, count);
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        break;
-      }
-    }
-    c->last_passes = std::max(c->h_pending[1], 1);  // passes the slowest window has used
-    predict(c);
-    HIPCHK(c, hipGetLastError());
-    // (a call that ended inside its first graph: the prior may be on its way from a worker; one that continues with a tail graph
-    // is waited for by the join in front of whatever comes next)
-    if (tail_done && *tail_done)
-      if (int rc = wait_side(c)) return rc;
-    return LFVIO_OK;
-  }
+// (the marginalization) is still running then and c->call says so.
+int enqueue_solve(lfvio_ctx *c, const CallPlan &p, bool *tail_done) {
+  *tail_done = false;
+  if (int rc = join_inflight(c, p.early ? CallState::OVERTAKE_PIPELINED : CallState::WAIT)) return rc;
+  const Route r = route_for(c, p.count, MODE_SOLVE);
+  const int passes = std::max(p.max_iter, 0) + 4;
+  if (p.adaptive && c->use_graph) return adaptive_loop(c, r, p, passes, tail_done);
   launch_setup(c, r, MODE_SOLVE);
   // (the pass behind k_setup sweeps at the uploaded state: slots_offs)
   auto loop = [&]() {
-    for (int it = 0; it < passes; it++) launch_iteration(c, r, MODE_SOLVE, false, it == 0, it == passes - 1, false, (r.offs & 2) || (it == 0 && (r.offs & 1)));
+    Pass ps;
+    for (int it = 0; it < passes; it++) {
+      ps.first = it == 0, ps.last = it == passes - 1, ps.offs = (r.offs & 2) || (it == 0 && (r.offs & 1));
+      launch_iteration(c, r, MODE_SOLVE, ps);
+    }
     return LFVIO_OK;
   };
   if (c->use_graph) {
@@ -1566,15 +1608,18 @@ int enqueue_solve(lfvio_ctx *c, int count, int max_iter, bool adaptive, int fuse
   return LFVIO_OK;
 }
 
-int enqueue_marg(lfvio_ctx *c, int count, int flag, bool standalone, bool gated) {
-  if (int rc = join_inflight(c, gated)) return rc;  // (gated: part of a graph of lfvio_batch_optimize*, which has joined — or may go out behind a pipelined upload)
-  const int mode = (MODE_MARG + flag) | (gated ? MODE_GATED : 0);
-  const Route r = route_for(c, count, mode);
+int enqueue_marg(lfvio_ctx *c, const CallPlan &p, MargKind kind) {
+  const bool gated = kind == MARG_GATED, standalone = kind == MARG_STANDALONE;
+  if (int rc = join_inflight(c, gated ? CallState::OVERTAKE_PIPELINED : CallState::WAIT)) return rc;  // (gated: part of a graph of lfvio_batch_optimize*, which has joined — or may go out behind a pipelined upload)
+  const int flag = p.marg_flag, mode = (MODE_MARG + flag) | (gated ? MODE_GATED : 0);
+  const Route r = route_for(c, p.count, mode);
   if (standalone) launch_setup(c, r, mode);
   // (standalone: the sweep is at the uploaded state; gated: at the re-anchored solution, on the sphere but for a fixed extrinsic)
-  launch_iteration(c, r, mode, false, true, true, false, standalone ? r.offs != 0 : (r.offs & 2) != 0);
-  hipLaunchKernelGGL(k_marg_solve<false>, dim3(1, count), dim3(MARG_THREADS), MARG_LDS, c->stream, c->d_base, c->L.total,
-                     flag | (c->force_eig ? 256 : 0) | (gated ? 512 : 0) | (gated && c->publish ? 1024 : 0));
+  Pass ps;
+  ps.offs = standalone ? r.offs != 0 : (r.offs & 2) != 0;
+  launch_iteration(c, r, mode, ps);
+  hipLaunchKernelGGL(k_marg_solve<false>, dim3(1, p.count), dim3(MARG_THREADS), MARG_LDS, c->stream, c->d_base, c->L.total,
+                     flag | (c->force_eig ? 256 : 0) | (gated ? 512 : 0) | (gated && p.publish ? 1024 : 0));
   HIPCHK(c, hipGetLastError());
   return LFVIO_OK;
 }
@@ -1871,7 +1916,10 @@ int lfvio_solve(lfvio_ctx *c, const LfvioWindow *in, LfvioSolution *out) {
   int rc = reserve(c, 1, in->num_landmarks, in->num_observations);
   if (rc) return rc;
   if ((rc = upload_window(c, 0, in))) return rc;
-  if ((rc = enqueue_solve(c, 1, in->max_num_iterations, true, -1, nullptr, in->max_solver_time_in_seconds))) return rc;
+  CallPlan p;
+  p.max_iter = in->max_num_iterations, p.max_seconds = in->max_solver_time_in_seconds;
+  bool tail_done = false;
+  if ((rc = enqueue_solve(c, p, &tail_done))) return rc;
   return download_solution(c, 0, out);
 }
 
@@ -1881,7 +1929,9 @@ int lfvio_marginalize(lfvio_ctx *c, const LfvioWindow *in, int flag, LfvioPrior 
   int rc = reserve(c, 1, in->num_landmarks, in->num_observations);
   if (rc) return rc;
   if ((rc = upload_window(c, 0, in))) return rc;
-  if ((rc = enqueue_marg(c, 1, flag, true))) return rc;
+  CallPlan p;
+  p.marg_flag = flag;
+  if ((rc = enqueue_marg(c, p, MARG_STANDALONE))) return rc;
   return download_prior(c, 0, out);
 }
 
@@ -1921,67 +1971,62 @@ int lfvio_batch_upload_chained(lfvio_ctx *c, int slot, const LfvioWindow *in, Lf
   return upload_window(c, slot, in, 0, 1, prior_io);
 }
 
-static int batch_optimize_impl(lfvio_ctx *c, int count, int marg_flag, bool adaptive, bool early = false) {
+enum CallForm { CALL_STATIC, CALL_ADAPTIVE, CALL_EARLY };  // lfvio_batch_optimize_async | lfvio_batch_optimize | lfvio_batch_optimize_begin
+static int batch_optimize_impl(lfvio_ctx *c, int count, int marg_flag, CallForm form) {
   if (!c || count <= 0 || count > c->batch) return LFVIO_ERR_ARG;
   if (marg_flag != LFVIO_MARGIN_OLD && marg_flag != LFVIO_MARGIN_SECOND_NEW) {  // (the flag indexes the slot's two marginalization plans)
     c->err = "marg_flag is neither LFVIO_MARGIN_OLD nor LFVIO_MARGIN_SECOND_NEW";
     return LFVIO_ERR_ARG;
   }
   (void)hipSetDevice(c->device);
-  if (int rc = join_inflight(c, early && count == 1)) return rc;
-  c->has_held = false;  // (a prior nobody collected before the next optimization is dropped, like one left in the slot)
-  c->inflight_flag = marg_flag;
-  c->publish = early && adaptive && count == 1 && c->h_mail && c->info[0].resident && c->info[0].N <= MAIL_MAX_LM;
-  struct PublishOff {
-    lfvio_ctx *c;
-    ~PublishOff() { c->publish = false; }
-  } publish_off{c};
+  CallPlan p;
+  p.count = count, p.marg_flag = marg_flag, p.adaptive = form != CALL_STATIC, p.early = form == CALL_EARLY;
+  if (int rc = join_inflight(c, p.early && count == 1 ? CallState::OVERTAKE_PIPELINED : CallState::WAIT)) return rc;
+  c->call.optimize_started(marg_flag);
+  p.publish = p.early && count == 1 && c->h_mail && c->info[0].resident && c->info[0].N <= MAIL_MAX_LM;
   // every slot carries its own max_iter on the device; the pass count follows the largest, the wall-clock cap
   // (synchronous driver only) the smallest positive one
-  int max_iter = 0;
-  double max_seconds = -1.0;
   for (int s = 0; s < count; s++) {
     if (!c->info[s].resident) {
       c->err = "slot not uploaded";
       return LFVIO_ERR_ARG;
     }
-    max_iter = std::max(max_iter, c->info[s].max_iter);
+    p.max_iter = std::max(p.max_iter, c->info[s].max_iter);
     const double t = c->info[s].max_seconds;
-    if (t > 0.0 && (max_seconds <= 0.0 || t < max_seconds)) max_seconds = t;
+    if (t > 0.0 && (p.max_seconds <= 0.0 || t < p.max_seconds)) p.max_seconds = t;
   }
-  if (c->info[0].in_prior_device && (count != 1 || !adaptive || !c->use_graph)) {
+  if (c->info[0].in_prior_device && (count != 1 || !p.adaptive || !c->use_graph)) {
     // (k_prior_chain's verdict on the prior travels with the graph of ONE window's synchronous call: include/lfvio.h)
     c->err = "a window uploaded with lfvio_batch_upload_chained_device is optimized by lfvio_batch_optimize_begin or lfvio_batch_optimize(ctx, 1, flag)";
     return LFVIO_ERR_ARG;
   }
-  const bool fuse = adaptive && c->use_graph;
+  p.fused = p.adaptive && c->use_graph;
   bool tail_done = false;
-  int rc = enqueue_solve(c, count, max_iter, adaptive, fuse ? marg_flag : -1, &tail_done, max_seconds, early);
+  int rc = enqueue_solve(c, p, &tail_done);
   if (rc) return rc;
-  if (fuse) {
+  if (p.fused) {
     if (tail_done) return LFVIO_OK;  // the usual case: everything ran in the graph of the first chunk
     // some window needed more passes: gauge fix + marginalization for the slots that have not had theirs (gated)
-    hipGraphExec_t &tail_graph = c->tail[c->publish ? 1 : 0][marg_flag];
+    hipGraphExec_t &tail_graph = c->tail[p.publish ? 1 : 0][marg_flag];
     if (!tail_graph) {
       rc = capture_graph(c, c->stream, &tail_graph, [&]() {
         hipLaunchKernelGGL(k_force_done, dim3((count + 63) / 64), dim3(64), 0, c->stream, c->d_base, c->L.total, count);
         hipLaunchKernelGGL(k_gauge, dim3(1 + (grid_for(c, count).lm + 1) / 2, count), dim3(128), 0, c->stream, c->d_base, c->L.total, 1);
-        if (c->publish) hipLaunchKernelGGL(k_publish, dim3(1), dim3(256), 0, c->stream, c->d_base, c->L.total);
-        return enqueue_marg(c, count, marg_flag, false, true);
+        if (p.publish) hipLaunchKernelGGL(k_publish, dim3(1), dim3(256), 0, c->stream, c->d_base, c->L.total);
+        return enqueue_marg(c, p, MARG_GATED);
       });
       if (rc) return rc;
     }
-    const bool watch = c->publish;
-    if (watch) __atomic_store_n((int *)c->h_mail + 1, 0, __ATOMIC_RELAXED), __atomic_store_n((int *)c->h_mail, 0, __ATOMIC_RELEASE);
-    HIPCHK(c, hipGraphLaunch(tail_graph, c->stream));
-    if (watch && wait_early(c)) c->inflight = true, c->inflight_first = false;
+    bool early = false;
+    if ((rc = launch_watched(c, tail_graph, p.publish, &early, [] { return LFVIO_OK; }))) return rc;
+    if (early) record_mailbox_call(c, c->call.early_from_tail());
     return LFVIO_OK;
   }
   hipLaunchKernelGGL(k_gauge, dim3(1 + (grid_for(c, count).lm + 1) / 2, count), dim3(128), 0, c->stream, c->d_base, c->L.total, 0);
-  return enqueue_marg(c, count, marg_flag, false);
+  return enqueue_marg(c, p, MARG_AFTER_LOOP);
 }
 
-int lfvio_batch_optimize_async(lfvio_ctx *c, int count, int marg_flag) { return batch_optimize_impl(c, count, marg_flag, false); }
+int lfvio_batch_optimize_async(lfvio_ctx *c, int count, int marg_flag) { return batch_optimize_impl(c, count, marg_flag, CALL_STATIC); }
 
 int lfvio_batch_sync(lfvio_ctx *c) {
   if (!c) return LFVIO_ERR_ARG;
@@ -1991,7 +2036,7 @@ int lfvio_batch_sync(lfvio_ctx *c) {
 }
 
 int lfvio_batch_optimize(lfvio_ctx *c, int count, int marg_flag) {
-  int rc = batch_optimize_impl(c, count, marg_flag, true);
+  int rc = batch_optimize_impl(c, count, marg_flag, CALL_ADAPTIVE);
   if (rc) return rc;
   return lfvio_batch_sync(c);
 }
@@ -2011,18 +2056,13 @@ int lfvio_batch_download(lfvio_ctx *c, int slot, LfvioSolution *sol, LfvioPrior 
 // and windows that were not done within the first graph take the synchronous route inside begin().
 int lfvio_batch_optimize_begin(lfvio_ctx *c, int marg_flag, LfvioSolution *sol) {
   if (!c || !sol || c->batch < 1) return LFVIO_ERR_ARG;
-  int rc = batch_optimize_impl(c, 1, marg_flag, true, true);
+  int rc = batch_optimize_impl(c, 1, marg_flag, CALL_EARLY);
   if (rc) return rc;
-  if (!c->inflight) return download(c, 0, sol, nullptr);  // (synchronizes)
+  if (!c->call.early()) return download(c, 0, sol, nullptr);  // (synchronizes)
   Fetched f;
   char *m = c->h_mail;
-  // the loop is closed: its pass and iteration counts size the next call's first graph (a caller that pipelines — the next window
-  // uploaded behind this call's marginalization — never joins this graph)
-  c->last_passes = std::max(((const int *)m)[4], 1), c->last_iters = ((const TRState *)(m + MAIL_TR))->iteration;
-  if (c->inflight_first) predict(c), c->predicted_early = true;
-  if (((const int *)m)[5]) {
+  if (*mail_word(c, MAIL_CHAIN_ERR)) {  // (CHECK_CHAIN_ERR of the early return: said here, with the state, and by no join after it)
     c->err = CHAIN_ERR_TEXT;
-    c->chain_err_told = true;
     return LFVIO_ERR_DEVICE;
   }
   f.xs = (const FrameState *)(m + MAIL_X), f.tr = (const TRState *)(m + MAIL_TR);
@@ -2036,28 +2076,25 @@ int lfvio_batch_optimize_begin(lfvio_ctx *c, int marg_flag, LfvioSolution *sol) 
 int lfvio_batch_optimize_finish(lfvio_ctx *c, LfvioPrior *prior) {
   if (!c) return LFVIO_ERR_ARG;
   (void)hipSetDevice(c->device);
-  if (c->has_held) {
-    c->has_held = false;
+  if (c->call.held_handed_out()) {
     if (prior) copy_prior(prior, c->held.get());
     return LFVIO_OK;
   }
-  if (c->inflight && prior) {
+  if (c->call.early() && prior) {
     // the marginalization ends by pushing its prior into the mailbox (publish_prior): wait for that word, not for the stream
-    int *flag = (int *)c->h_mail + 1;
+    int *flag = (int *)c->h_mail + MAIL_PRIOR_FLAG;
     const int want = c->info[0].mail_seq;
     bool there = false;
     for (;;) {
       if ((there = __atomic_load_n(flag, __ATOMIC_ACQUIRE) == want)) break;
-      if (hipStreamQuery(c->stream) != hipErrorNotReady && !(c->side_launched && (hipStreamQuery(c->sstream[0]) == hipErrorNotReady || hipStreamQuery(c->sstream[1]) == hipErrorNotReady))) {
+      if (hipStreamQuery(c->stream) != hipErrorNotReady && !(c->call.workers_outstanding() && (hipStreamQuery(c->sstream[0]) == hipErrorNotReady || hipStreamQuery(c->sstream[1]) == hipErrorNotReady))) {
         there = __atomic_load_n(flag, __ATOMIC_ACQUIRE) == want;  // (a worker of kernels_spec.h may still be delivering when stream 0 is idle)
         break;
       }
     }
     if (there) {
-      c->inflight = false, c->unsynced = true;  // (what is left of the graph is a copy of two words: the next join waits for it)
-      c->last_passes = std::max(((const int *)c->h_mail)[2], 1), c->last_iters = ((const int *)c->h_mail)[3];
-      if (c->inflight_first && !c->predicted_early) predict(c);
-      c->predicted_early = false;
+      c->call.prior_from_mailbox();  // (what is left of the graph is a copy of two words: the next join waits for it)
+      record_call(c, *mail_word(c, MAIL_PRIOR_PASSES), *mail_word(c, MAIL_PRIOR_ITERS), CallState::NOTHING);
       Fetched f{};
       f.prior = (LfvioPrior *)(c->h_mail + MAIL_PRIOR);
       bool pass = false;
@@ -2074,7 +2111,7 @@ int lfvio_batch_optimize_finish(lfvio_ctx *c, LfvioPrior *prior) {
   return prior ? download(c, 0, nullptr, prior) : LFVIO_OK;
 }
 
-int lfvio_batch_optimize_pending(const lfvio_ctx *c) { return c && (c->inflight || c->has_held) ? 1 : 0; }
+int lfvio_batch_optimize_pending(const lfvio_ctx *c) { return c && c->call.pending() ? 1 : 0; }
 
 // ---- debug / parity hooks (include/lfvio_debug.h)
 int lfvio_debug_linearize(lfvio_ctx *c, const LfvioWindow *in, double *Hpp, double *gp, double *a, double *b, double *W,

@@ -276,6 +276,29 @@ def test_device_chained_upload_follows_the_stream():
     same_prior(prior6, ref[6][2])
 
 
+def test_resident_window_solved_again_behind_a_device_chained_upload():
+    """upload, begin, upload_chained_device, begin, finish — and then begin + finish AGAIN on the window that is resident: the context
+    still counts the stream as pipelined (call_state.h: the bit is sticky), so the second call goes out without a join and without
+    workers, behind work that has long ended.  Every state and prior is, bit for bit, that of the same windows through whole calls
+    with the serial tail; a plain upload and a whole call follow on the same context."""
+    (w0, s0, _), (w1, s1, p1), (w2, s2, p2) = stream_windows(serial(), 2, n_lm=150)
+    eng = Engine(0)
+    eng.batch_reserve(1, 400, 3000)
+    eng.batch_upload(0, w0)
+    same_solution(eng.optimize_begin(abi.MARGIN_OLD, w0.N), s0)
+    eng.batch_upload_chained_device(0, w1.copy(prior=None))
+    for again in range(2):
+        assert not eng.optimize_pending()
+        same_solution(eng.optimize_begin(abi.MARGIN_OLD, w1.N), s1)
+        assert eng.optimize_pending()
+        same_prior(eng.optimize_finish(), p1)
+    eng.batch_upload(0, w2)
+    eng.batch_optimize(1, abi.MARGIN_OLD)
+    sol, prior = eng.batch_download(0, w2.N)
+    same_solution(sol, s2)
+    same_prior(prior, p2)
+
+
 def test_device_chained_upload_needs_a_prior_in_flight():
     ref = stream_windows(serial(), 2)
     eng = Engine(0)
