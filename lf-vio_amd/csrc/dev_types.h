@@ -35,6 +35,7 @@ constexpr int SUM_ITEMS_CAP = PRE_CHUNK_LIMIT * 209 + 64;
 // Entries of H_pp / g_p that have a visual (Gram) part, i.e. a gather list: rows < KC — the packed prefix and g_p[0, KC).
 // The list bounds are stored by this compact index (0 .. SUM_VIS), not by the packed index: 11 KB per upload, not 60.
 constexpr int SUM_VIS_PACKED = 73 * 74 / 2, SUM_VIS = SUM_VIS_PACKED + 73;
+constexpr int LINB_LEN = SUM_VIS + SCHUR_LEN + 8;  // one group partial of k_linb (kernels_linw.h): [camera H_pp packed | camera gradient | Schur tiles | landmark scalars]
 constexpr int HPP_CAP = 16384;
 // exchange buffer of the landmark-sharded mode (one contiguous sum-all-reduce):
 //   [ H_pp packed | g_p | Schur sums (80x80 upper tiles) | 16 scalars ]

@@ -6,11 +6,24 @@
 //   k_sum     : deterministic fixed-order reduction of the per-workgroup partials
 #pragma once
 #include "dev_factors.h"
+#include "slot_args.h"
 #include "kernels_spec.h"
 #include "tr_decide.h"
 #include <type_traits>
 
 #define SLOT(base, stride) ((Slot *)((char *)(base) + (size_t)blockIdx.y * (stride)))
+// an array of the blob by its byte offset from the Slot — a kernel argument (SlotArgs, SumArgs): nothing is fetched to form the address
+template <class T>
+DEV T *blob_at(const Slot *S, long long off) { return (T *)((char *)S + off); }
+// the eight channels of observation o, addressed from the arguments (load_obs: through the header)
+DEV void load_obs(const Slot *S, const SlotArgs &A, int o, d3 &p, d3 &v, double &td, double &row) {
+  const char *c0 = (const char *)S + A.obs0;
+  auto ch = [&](int k) { return ((const double *)(c0 + k * A.obs_stride))[o]; };
+  p = mk3(ch(0), ch(1), ch(2));
+  v = mk3(ch(3), ch(4), ch(5));
+  td = ch(6);
+  row = ch(7);
+}
 
 constexpr int MODE_SOLVE = 0;
 constexpr int MODE_MARG = 1;        // MODE_MARG + flag: 1 = MARGIN_OLD, 2 = MARGIN_SECOND_NEW
@@ -442,8 +455,31 @@ DEV void lin_schur_only_role(Slot *S, const LinView &lv, int wg, double *lds, do
 // instead of 1 + q, 5 + q, 9 + q, and the workgroup's Schur SYRK is 8 steps instead of 16: the role is the latency chain of a single
 // window's k_lin (36 k cycles of which the observations 14 k and the SYRK 8 k), and a 300-landmark window has 246 CUs to spare.
 // OFFS: see k_lin.
+// What a workgroup of k_lin indexes its role's data with, requested at the top of the kernel with the header (addresses from the
+// arguments, indices clamped: SlotArgs) — in front of the bookkeeping of a MODE_DECIDE pass, which they then travel beside.
+constexpr int LIN_ROLE_LM = 1, LIN_ROLE_GRAM = 2, LIN_ROLE_POSE = 4, LIN_ROLE_ALL = 7;  // (see k_lin)
+struct LinFirst {
+  int st, cnt, obs0, woff;        // landmark role: the thread's landmark
+  int ch_pair, ch_begin, ch_end;  // Gram role: the wave's chunk
+};
+// half: Slot::lm_half, requested in the same round — the thread's landmark is asked for in both forms (4 | 8 lanes per track) and the
+// form's own kept
+template <int ROLES>
+DEV void lin_first(const Slot *S, const SlotArgs &A, int gLw, int gCh, int half, LinFirst &F) {
+  const int b = blockIdx.x, tid = threadIdx.x;
+  if ((ROLES & LIN_ROLE_LM) && b < gLw) {
+    const int *st = blob_at<int>(S, A.lm_start), *cnt = blob_at<int>(S, A.lm_cnt), *o0 = blob_at<int>(S, A.lm_obs0), *wo = blob_at<int>(S, A.lm_woff);
+    const int l4 = first_lm_in_index(A, b * LM_BLOCK + tid / 4), l8 = first_lm_in_index(A, b * (LM_BLOCK / 2) + tid / 8);
+    const int s4 = st[l4], c4 = cnt[l4], o4 = o0[l4], w4 = wo[l4], s8 = st[l8], c8 = cnt[l8], o8 = o0[l8], w8 = wo[l8];
+    F.st = half ? s8 : s4, F.cnt = half ? c8 : c4, F.obs0 = half ? o8 : o4, F.woff = half ? w8 : w4;
+  } else if ((ROLES & LIN_ROLE_GRAM) && b >= gLw && b - gLw < gCh) {
+    const int chunk = first_chunk_index(A, 4 * (b - gLw) + (tid >> 6));
+    F.ch_pair = blob_at<int>(S, A.chunk_pair)[chunk], F.ch_begin = blob_at<int>(S, A.chunk_begin)[chunk], F.ch_end = blob_at<int>(S, A.chunk_end)[chunk];
+  }
+}
+
 template <bool TIGHT, int LPT, bool OFFS>
-DEV void lin_landmark_role(Slot *S, const LinView &lv, int wg, int mode, double *lds, double *part) {
+DEV void lin_landmark_role(Slot *S, const SlotArgs &A, const LinFirst &F, const LinView &lv, int wg, int mode, double *lds, double *part) {
   constexpr int LMB = LIN_THREADS / LPT;  // landmarks of the workgroup
   double(*tile)[WLD + 1] = (double(*)[WLD + 1]) lds;
   double *red = lds + LM_BLOCK * (WLD + 1);
@@ -466,17 +502,17 @@ DEV void lin_landmark_role(Slot *S, const LinView &lv, int wg, int mode, double 
   d3 wPi = mk3(0, 0, 0), wTi = wPi, wTic = wPi, wTx = wPi;
   int i = 0, cnt_l = 0, woff_l = 0;
   if (valid) {
-    i = S->lm_start[l];
-    const int k = S->lm_cnt[l], o0 = S->lm_obs0[l];
-    cnt_l = k, woff_l = S->lm_woff[l];
+    i = F.st;  // (l < N: the clamp of lin_first left the index what it was)
+    const int k = F.cnt, o0 = F.obs0;
+    cnt_l = k, woff_l = F.woff;
     lam = lv.lam[l];
     ObsPair ob;
-    load_obs(S, o0, ob.pi, ob.vi, ob.tdi, ob.rowi);
+    load_obs(S, A, o0, ob.pi, ob.vi, ob.tdi, ob.rowi);
     const m33 ricT = ldm(T->ricT);
     const unsigned offm = OFFS ? tab_offmask(T) : 0u;
     for (int o = 1 + q; o < k; o += LPT) {
       const int j = i + o, pair = i * 11 + j;
-      load_obs(S, o0 + o, ob.pj, ob.vj, ob.tdj, ob.rowj);
+      load_obs(S, A, o0 + o, ob.pj, ob.vj, ob.tdj, ob.rowj);
       PairU u;
       if (OFFS) load_pair_uniform(T, pair, offm, u);
       else load_pair_uniform(T, pair, u);
@@ -610,7 +646,7 @@ DEV void lin_landmark_role(Slot *S, const LinView &lv, int wg, int mode, double 
 // reduction of the Gram entries is left.  LDS operations of one wave execute in program order, so between the phases
 // only the compiler has to be kept from moving them (wavefront-scope fences).
 template <bool OFFS>
-DEV void lin_gram_role(Slot *S, const LinView &lv, int wg, int mode, double *lds) {
+DEV void lin_gram_role(Slot *S, const SlotArgs &A, const LinFirst &F, const LinView &lv, int wg, int mode, double *lds) {
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int chunk = 4 * wg + wv;
   if (chunk >= S->nChunks) return;
@@ -621,9 +657,9 @@ DEV void lin_gram_role(Slot *S, const LinView &lv, int wg, int mode, double *lds
   double(*E)[20] = (double(*)[20])(my + 32 * 17 + 256);  // 14 x 20
   double(*T1)[20] = (double(*)[20]) my;
   const Tab *T = lv.tab;
-  const int pair = S->chunk_pair[chunk];
+  const int pair = F.ch_pair;  // (chunk < nChunks: the clamp of lin_first left the index what it was)
   const int j = pair % 11;
-  const int begin = S->chunk_begin[chunk], end = S->chunk_end[chunk];
+  const int begin = F.ch_begin, end = F.ch_end;
   const int est_td = S->est_td;
   const double td = lv.x->td;
   PairU u;
@@ -637,12 +673,12 @@ DEV void lin_gram_role(Slot *S, const LinView &lv, int wg, int mode, double *lds
 #pragma unroll
   for (int e = 0; e < 14; e++) c0[e] = c1[e] = 0.0;
   if (idx < end) {
-    const int oj = S->pm_obs[idx], l = S->pm_lm[idx];
-    const int oi = S->lm_obs0[l];
+    const int oj = blob_at<int>(S, A.pm_obs)[idx], l = blob_at<int>(S, A.pm_lm)[idx];
+    const int oi = blob_at<int>(S, A.lm_obs0)[l];
     const double lam = lv.lam[l];
     ObsPair ob;
-    load_obs(S, oi, ob.pi, ob.vi, ob.tdi, ob.rowi);
-    load_obs(S, oj, ob.pj, ob.vj, ob.tdj, ob.rowj);
+    load_obs(S, A, oi, ob.pi, ob.vi, ob.tdi, ob.rowi);
+    load_obs(S, A, oj, ob.pj, ob.vj, ob.tdj, ob.rowj);
     Basis B;
     visual_basis<OFFS>(ob, lam, td, est_td, S->tr_over_row, S->half_row, S->sqrt_info, u, B);
     c0[0] = B.red[0].x, c0[1] = B.red[0].y, c0[2] = B.red[0].z;
@@ -775,8 +811,12 @@ DEV void lin_imu_role(Slot *S, const LinView &lv, int f, int mode, double *lds) 
 // STAGED (the workspace holds LIN_LDS_PRIOR doubles: the all-roles launch of a single window): J0 comes into LDS with one batch of
 // coalesced loads while the block differences are formed — the two products then read LDS; from global memory every term of them was
 // a load the loop had to wait for, and the prior's workgroup was the longest of the launch (12.3 us against 8.9 for an IMU factor).
+// jfirst (STAGED): the thread's entries of J0 as requested at the top of k_lin — all LIN_PRIOR_PER rounds of them, whatever n is: they lie
+// inside the array (FIRST_PRIOR_J) and the ones past n * n are dropped here.
+constexpr int LIN_PRIOR_PER = (LIN_PRIOR_N * LIN_PRIOR_N + LIN_THREADS - 1) / LIN_THREADS;
+static_assert(LIN_PRIOR_PER * LIN_THREADS == FIRST_PRIOR_J, "the speculative rounds of J0 are the ones slot_args.h accounts for");
 template <bool STAGED>
-DEV void lin_prior_role(Slot *S, const LinView &lv, int mode, double *lds) {
+DEV void lin_prior_role(Slot *S, const double *Jg, const double *prior_r, const double *jfirst, const LinView &lv, int mode, double *lds) {
   const int n = S->prior_n;
   const bool staged = STAGED && n <= LIN_PRIOR_N;
   double *Js = lds, *dx = lds + (STAGED ? LIN_PRIOR_N * LIN_PRIOR_N : 0), *r = dx + KP, *part = r + KP;  // part: [2][KP]
@@ -785,12 +825,11 @@ DEV void lin_prior_role(Slot *S, const LinView &lv, int mode, double *lds) {
   for (int c = tid; c < KP + 4; c += LIN_THREADS) g[c] = 0.0;
   if (!S->prior_valid || (S->sharded && !S->pose_side)) return;
   const FrameState *x = lv.x;
-  const double *Jg = S->prior_J;
   if (staged) {
-    constexpr int PER = (LIN_PRIOR_N * LIN_PRIOR_N + LIN_THREADS - 1) / LIN_THREADS;
+    constexpr int PER = LIN_PRIOR_PER;
     double v[PER];
 #pragma unroll
-    for (int k = 0; k < PER; k++) v[k] = tid + LIN_THREADS * k < n * n ? Jg[tid + LIN_THREADS * k] : 0.0;
+    for (int k = 0; k < PER; k++) v[k] = tid + LIN_THREADS * k < n * n ? jfirst[k] : 0.0;
     if (tid < S->prior_nb) prior_block_dx(S, x, tid, dx);
 #pragma unroll
     for (int k = 0; k < PER; k++)
@@ -805,7 +844,7 @@ DEV void lin_prior_role(Slot *S, const LinView &lv, int mode, double *lds) {
     double s = 0;
     for (int c = tid & 3; c < n; c += 4) s = fma(J[row * n + c], dx[c], s);
     s = quad_sum(s);
-    if ((tid & 3) == 0) r[row] = S->prior_r[row] + s;
+    if ((tid & 3) == 0) r[row] = prior_r[row] + s;
   }
   __syncthreads();
   // g = J0^T r: column c, two halves of the rows
@@ -853,40 +892,65 @@ __global__ __launch_bounds__(64) void k_imu_raw(char *base, size_t stride, int c
 // batch goes out role by role (lfvio_hip.hip launch_lin), and each of those kernels is compiled for its role alone: a
 // third of the code in the instruction cache, and the Gram role — 14-wide basis rows and a 4-double accumulator — runs
 // three waves per SIMD where the landmark role needs the registers of two.
-constexpr int LIN_ROLE_LM = 1, LIN_ROLE_GRAM = 2, LIN_ROLE_POSE = 4, LIN_ROLE_ALL = 7;
 constexpr int LIN_ROLE_POSE_RAW = 8;  // the pose-side roles with the IMU factors evaluated beforehand by k_imu_raw
 constexpr int LIN_LDS_POSE = 1024;     // doubles: what the IMU (947) and the prior (688) roles carve out of the workspace
 // OFFS: the instantiation whose visual roles know the reference's two back-rotations of a quaternion off the unit sphere (struct Tab,
 // dev_types.h; it reads the table's mask and serves every table).  The host launches it where the point may hold such a quaternion —
 // the first pass of a call whose uploaded state has one, every pass of a window whose FIXED extrinsic has one (SlotHostInfo::offs_*)
 // — and the instantiation without that flavour everywhere else.
+// A: the arrays' byte offsets (slot_args.h).  Everything whose address is known at launch leaves in the FIRST round, with the flags: what the
+// role of this workgroup indexes with (lin_first), the prior role's J0 and — MODE_DECIDE — the header and the partial sums of every
+// candidate the bookkeeping adds up.  The flags are looked at afterwards.
 template <int ROLES, bool OFFS = true>
-__global__ __launch_bounds__(LIN_THREADS, ROLES == LIN_ROLE_GRAM ? 3 : (ROLES == LIN_ROLE_POSE_RAW ? 6 : 2)) void k_lin(char *base, size_t stride, int mode_bits, int gLw, int gCh) {
+__global__ __launch_bounds__(LIN_THREADS, ROLES == LIN_ROLE_GRAM ? 3 : (ROLES == LIN_ROLE_POSE_RAW ? 6 : 2)) void k_lin(char *base, size_t stride, int mode_bits, int gLw, int gCh, const SlotArgs A) {
   Slot *S = SLOT(base, stride);
   TRState *tr = &S->tr;
   const int mode = mode_bits & (MODE_GATED - 1);
   LSTAMP(21);
+  // ---- the round that waits for nothing
   const TRFlags fl = tr_flags(tr);
   int do_lin = fl.do_lin, do_schur = fl.do_schur, cur = fl.cur, acc_z = 0;
   double mu = tr->mu;
   int num_succ = tr->num_succ;
+  const int N = S->N, half = S->lm_half, tail_state = S->tail_state;
+  LinFirst F;
+  lin_first<ROLES>(S, A, gLw, gCh, half, F);
+  constexpr bool STAGED_PRIOR = ROLES == LIN_ROLE_ALL;
+  double jfirst[LIN_PRIOR_PER];
+  if (STAGED_PRIOR && (int)blockIdx.x == gLw + gCh + LFVIO_WINDOW_SIZE) {
+    const double *Jg = blob_at<double>(S, A.prior_J);
+#pragma unroll
+    for (int k = 0; k < LIN_PRIOR_PER; k++) jfirst[k] = Jg[threadIdx.x + LIN_THREADS * k];  // (< FIRST_PRIOR_J, whatever the prior's size)
+  }
+  // (the bookkeeping rides only in the launch that carries all roles: launch_iteration's `merge` excludes the role-by-role route)
+  const bool decide = ROLES == LIN_ROLE_ALL && (mode_bits & MODE_DECIDE) && !(mode_bits & MODE_GATED);
+  TRHead t;
+  DecideFirst df;
+  int nLmBlocks = 0, max_iter = 0, spec_on = 0;
+  if (decide) {
+    nLmBlocks = S->nLmBlocks, max_iter = S->max_iter, spec_on = S->spec_on;
+    if (threadIdx.x < 64) {
+      t = *reinterpret_cast<const TRHead *>(tr);
+      decide_first(S, threadIdx.x, blob_at<double>(S, A.cost_part), blob_at<double>(S, A.cost_partE), A.cap_blocks, df);
+    }
+  }
+  // ---- the flags
   if (mode_bits & MODE_GATED) {
-    if (!tail_gate(S, fl.done)) return;
+    if (!(fl.done && tail_state == TAIL_OPEN)) return;  // tail_gate(S, fl.done)
   } else {
     int done = fl.done;
     const bool owner = blockIdx.x == 0 && !(mode_bits & MODE_NOCOUNT);
-    if ((mode_bits & MODE_DECIDE) && !done) {
+    if (decide && !done) {
       // The bookkeeping of the pass before (what k_decide does when it is launched on its own), repeated by every
       // workgroup: none of them may write the header the others are still reading, so workgroup 0 leaves the outcome in
       // S->dec for k_sum and k_solve (which moves it into the header) and each workgroup goes on with its own copy.
       __shared__ TRDecision dsh;
       if (threadIdx.x < 64) {
-        TRHead t = *reinterpret_cast<const TRHead *>(tr);
         const int K = decide_candidates(t);
         DecideSums sm;
-        decide_sums(S, t, K, 0, S->nLmBlocks, threadIdx.x, sm);
+        decide_sums(S, t, K, 0, nLmBlocks, threadIdx.x, sm, blob_at<double>(S, A.cost_part), blob_at<double>(S, A.cost_partE), &df);
         if (threadIdx.x == 0) {
-          const int az = decide_walk(t, sm, K, 0, S->max_iter, owner ? tr : nullptr);
+          const int az = decide_walk(t, sm, K, 0, max_iter, owner ? tr : nullptr);
           decision_from(dsh, t, az);
           if (owner) S->dec = dsh, S->dec_pending = 1;
         }
@@ -898,13 +962,13 @@ __global__ __launch_bounds__(LIN_THREADS, ROLES == LIN_ROLE_GRAM ? 3 : (ROLES ==
       num_succ = __builtin_amdgcn_readfirstlane(dsh.num_succ);
       mu = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(dsh.mu)), __builtin_amdgcn_readfirstlane(__double2loint(dsh.mu)));
       if (acc_z > 0 && blockIdx.x == gridDim.x - 1 && !(mode_bits & MODE_NOCOUNT)) {
-        copy_accepted(S, acc_z, cur, S->N, threadIdx.x, LIN_THREADS);
-        if (S->spec_on) {  // the accepted state is complete in x[cur] / lam[cur] once this copy is: a worker may take it (kernels_spec.h)
+        copy_accepted(S, acc_z, cur, N, threadIdx.x, LIN_THREADS);
+        if (spec_on) {  // the accepted state is complete in x[cur] / lam[cur] once this copy is: a worker may take it (kernels_spec.h)
           __threadfence();
           __syncthreads();
           if (threadIdx.x == 0) spec_publish(S, num_succ, cur);
         }
-      } else if (acc_z == 0 && owner && threadIdx.x == 0 && S->spec_on) spec_publish(S, num_succ, cur);  // (candidate 0 was written where it lies by the pass before)
+      } else if (acc_z == 0 && owner && threadIdx.x == 0 && spec_on) spec_publish(S, num_succ, cur);  // (candidate 0 was written where it lies by the pass before)
     } else if (owner && threadIdx.x == 0 && mode == MODE_SOLVE && S->spec_on) spec_publish(S, num_succ, cur);  // (the header's own state: the first pass of a graph)
     // a pass that starts with the loop still open is a pass this slot needs (the synchronous drivers size the first
     // graph of the next call from this count)
@@ -924,15 +988,15 @@ __global__ __launch_bounds__(LIN_THREADS, ROLES == LIN_ROLE_GRAM ? 3 : (ROLES ==
     // LDS was built and measured at 100 000 landmarks: k_presum + k_sum 33.5 -> 25.3 us, but the loop around the sweep — nothing
     // is carried through it — costs it 50 spilled registers and the landmark role 64 -> 97 us.)
     if (ROLES & LIN_ROLE_LM) {
-      const int half = S->lm_half, lmb = half ? LM_BLOCK / 2 : LM_BLOCK;
-      const int nblk = ((is_marg(mode) ? marg_plan(S, mode)->N0 : S->N) + lmb - 1) / lmb;
+      const int lmb = half ? LM_BLOCK / 2 : LM_BLOCK;
+      const int nblk = ((is_marg(mode) ? marg_plan(S, mode)->N0 : N) + lmb - 1) / lmb;
       if (b >= nblk) return;
       double *part = S->schur_part + (size_t)b * SCHUR_LEN;
       if (half) {  // (wave-uniform)
-        if (do_lin) lin_landmark_role<ROLES == LIN_ROLE_ALL, 8, OFFS>(S, lv, b, mode, lds, part);
+        if (do_lin) lin_landmark_role<ROLES == LIN_ROLE_ALL, 8, OFFS>(S, A, F, lv, b, mode, lds, part);
         else lin_schur_only_role<8>(S, lv, b, lds, part);
       } else {
-        if (do_lin) lin_landmark_role<ROLES == LIN_ROLE_ALL, 4, OFFS>(S, lv, b, mode, lds, part);
+        if (do_lin) lin_landmark_role<ROLES == LIN_ROLE_ALL, 4, OFFS>(S, A, F, lv, b, mode, lds, part);
         else lin_schur_only_role<4>(S, lv, b, lds, part);
       }
     }
@@ -941,7 +1005,7 @@ __global__ __launch_bounds__(LIN_THREADS, ROLES == LIN_ROLE_GRAM ? 3 : (ROLES ==
   if (!do_lin) return;
   b -= gLw;
   if (b < gCh) {  // gCh workgroups of 4 chunks
-    if (ROLES & LIN_ROLE_GRAM) lin_gram_role<OFFS>(S, lv, b, mode, lds);
+    if (ROLES & LIN_ROLE_GRAM) lin_gram_role<OFFS>(S, A, F, lv, b, mode, lds);
     return;
   }
   b -= gCh;
@@ -951,7 +1015,7 @@ __global__ __launch_bounds__(LIN_THREADS, ROLES == LIN_ROLE_GRAM ? 3 : (ROLES ==
       else lin_imu_role<false>(S, lv, b, mode, lds);
       return;
     }
-    lin_prior_role<ROLES == LIN_ROLE_ALL>(S, lv, mode, lds);
+    lin_prior_role<STAGED_PRIOR>(S, STAGED_PRIOR ? blob_at<double>(S, A.prior_J) : (double *)S->prior_J, S->prior_r, jfirst, lv, mode, lds);
   }
 }
 
@@ -1092,8 +1156,6 @@ __global__ __launch_bounds__(256) void k_presum(char *base, size_t stride, int m
 struct SumArgs {
   long long sum_off, sum_end_marg, sum_items, gram_part, pairG, imu_out, prior_A;
 };
-template <class T>
-DEV T *blob_at(const Slot *S, long long off) { return (T *)((char *)S + off); }
 #define SUM_KEEP(v) asm volatile("" ::"v"(v))
 
 // One entry e of the packed H_pp (e < PACKED) or of g_p: Gram partials of the frame pairs touching it, the (at most two)

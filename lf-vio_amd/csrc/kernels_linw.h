@@ -526,7 +526,7 @@ DEV void linw_prior(Slot *S, const LinView &lv, double *lw) {
   const int tid = threadIdx.x;
   const int n = S->prior_n;
   if (!S->prior_valid || (S->sharded && !S->pose_side) || n > LW_PRIOR_MAXN) {
-    lin_prior_role<false>(S, lv, MODE_SOLVE, lw);  // (zeroes prior_g when there is no prior)
+    lin_prior_role<false>(S, S->prior_J, S->prior_r, nullptr, lv, MODE_SOLVE, lw);  // (zeroes prior_g when there is no prior)
     __syncthreads();
     return;
   }
@@ -898,7 +898,6 @@ __global__ __launch_bounds__(LW_THREADS, 2) void k_linw(char *base, size_t strid
 // rest (LB_OFF); nothing zero-fills a large window's Wt, so a strip writes every entry of its span (a shorter track's zeros
 // too) and the Schur phase takes from a block only the pairs its longest track reaches.
 // ---------------------------------------------------------------------------
-constexpr int LINB_LEN = SUM_VIS + SCHUR_LEN + 8;
 // k_linb_gather: grid (ceil(max(N, NV) / 256), batch) x 256, once per upload of a large window — the copies of the observations in
 // the orders the strips read them (anchors by landmark, the others pair-major with their frame pair), made on the device from the
 // arrays the upload carries anyway: 36 MB less over PCIe and no host loop over half a million observations at 100 000 landmarks.

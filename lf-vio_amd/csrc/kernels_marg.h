@@ -275,7 +275,10 @@ __global__ __launch_bounds__(64) void k_spec_wait(char *base) {
 // its prior (the other worker may be faster: then it goes back to waiting) and re-anchors the copy like the gated gauge fix
 // re-anchors the original (the same gauge_poses on the same numbers).
 // Leaves tr.done = 0 in the shadow when there is nothing to do: the round's three gated launches return.
-__global__ __launch_bounds__(128) void k_spec_begin(char *base, size_t back) {
+// A: the arrays' offsets from a slot's own header (slot_args.h; lam lies at the same offset in slot 0 and in the shadow): the accepted
+// state's inverse depths are addressed from `cur` of the published word alone, their loads — indices clamped to the array — leave with
+// the state's and the header's, and N decides afterwards what is stored.
+__global__ __launch_bounds__(128) void k_spec_begin(char *base, size_t back, const SlotArgs A) {
   Slot *S = (Slot *)base;
   Slot *S0 = (Slot *)(base - back);
   const int tid = threadIdx.x;
@@ -331,8 +334,8 @@ __global__ __launch_bounds__(128) void k_spec_begin(char *base, size_t back) {
       static_assert(TW <= 128, "the trust-region header in one trip");
       const double *xs = (const double *)&S0->x[cur];
       double *xd = (double *)&S->x[0];
-      const double *ls = S0->lam[cur];
-      double *ld = S->lam[0];
+      const double *ls = blob_at<const double>(S0, cur ? A.lam[1] : A.lam[0]);
+      double *ld = blob_at<double>(S, A.lam[0]);
       const int N = S0->N;
       const long long *ts = (const long long *)&S0->tr;
       long long *td = (long long *)&S->tr;
@@ -340,7 +343,7 @@ __global__ __launch_bounds__(128) void k_spec_begin(char *base, size_t back) {
 #pragma unroll
       for (int k = 0; k < XT; k++) xv[k] = xs[tid + 128 * k < XW ? tid + 128 * k : 0];
 #pragma unroll
-      for (int k = 0; k < LT; k++) lv[k] = ls[tid + 128 * k < N ? tid + 128 * k : 0];
+      for (int k = 0; k < LT; k++) lv[k] = ls[first_lm_index(A, tid + 128 * k)];
       const long long tv = ts[tid < TW ? tid : 0];
 #pragma unroll
       for (int k = 0; k < XT; k++)

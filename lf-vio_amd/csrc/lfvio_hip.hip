@@ -57,77 +57,7 @@ constexpr ncclDataType_t ncclDouble = 8;
 
 namespace {
 
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-struct Layout {  // byte offsets inside one slot blob, by capacity
-  int maxN = 0, maxM = 0;
-  int capLmBlocks = 0, capChunks = 0, capSchurParts = 0;
-  size_t in_begin = 0, in_end = 0, total = 0;
-  size_t anc[8], pmo[8], pm_pair, linb_lm0, linb_ns, linw_begin = 0, linw_end = 0;  // k_linw's copies of the observations (behind the regular inputs: uploaded on their own, resident batches only)
-  size_t lm_start, lm_cnt, lm_obs0, lm_perm, lm_woff, lam0, obs[8], pm_obs, pm_lm, chunk_pair, chunk_begin, chunk_end, sum_off, sum_end_marg, sum_items, prior_J,
-      prior_r;
-  size_t lam[2], lamE[SPEC_EXTRA], cost_partE, prior_A, a, b, W, Wt, scale_l, grad_l, gn_l, diag_l, einv_l, d1, d2, gram_part, pairG, schur_part,
-      xch, lm_part, cost_part, imu_out, imu_raw, mscr, eig_aux;
-};
-
-Layout make_layout(int maxN, int maxM) {
-  Layout L;
-  L.maxN = maxN;
-  L.maxM = maxM;
-  L.capLmBlocks = std::max(1, (maxN + LM_BLOCK - 1) / LM_BLOCK);
-  L.capChunks = 64 + maxM / CHUNK_MAX;
-  // (one part per landmark workgroup of k_lin: 64 landmarks each, or 32 for windows of at most SPEC_MAX_LM landmarks — Slot::lm_half)
-  L.capSchurParts = std::max(L.capLmBlocks + 1, 2 * ((std::min(maxN, SPEC_MAX_LM) + LM_BLOCK - 1) / LM_BLOCK));
-  static_assert(LINB_LEN >= SCHUR_LEN, "the Schur partials of k_lin share the array of k_linb's group partials, which are the larger");
-  size_t o = align_up(sizeof(Slot), 256);
-  auto take = [&](size_t bytes) {
-    size_t r = o;
-    o = align_up(o + bytes, 256);
-    return r;
-  };
-  const size_t N = std::max(maxN, 1), M = std::max(maxM, 1), LB = (size_t)L.capLmBlocks * LM_BLOCK;
-  L.in_begin = o;
-  L.lm_start = take(N * 4), L.lm_cnt = take(N * 4), L.lm_obs0 = take(N * 4), L.lm_perm = take(N * 4);
-  L.lm_woff = take((N + 1) * 4);
-  L.lam0 = take(N * 8);
-  for (int k = 0; k < 8; k++) L.obs[k] = take(M * 8);
-  L.pm_obs = take(M * 4), L.pm_lm = take(M * 4);
-  L.chunk_pair = take((size_t)L.capChunks * 4), L.chunk_begin = take((size_t)L.capChunks * 4),
-  L.chunk_end = take((size_t)L.capChunks * 4);
-  // (the two arrays whose used part varies most come last, so that an upload copies [in_begin, used end of sum_items)
-  // and the n x n the prior really has — 0.2 MB instead of 0.7 MB at 300 landmarks)
-  L.prior_r = take(LFVIO_MAX_PRIOR_DIM * 8);
-  L.sum_off = take((size_t)(SUM_VIS + 1) * 4), L.sum_end_marg = take((size_t)SUM_VIS * 4);
-  L.sum_items = take((size_t)SUM_ITEMS_CAP * 4);
-  L.prior_J = take((size_t)LFVIO_MAX_PRIOR_DIM * LFVIO_MAX_PRIOR_DIM * 8);
-  L.in_end = o;
-  L.linw_begin = o;
-  for (int k = 0; k < 8; k++) L.anc[k] = take(N * 8);
-  for (int k = 0; k < 8; k++) L.pmo[k] = take(M * 8);
-  L.pm_pair = take(M);
-  L.linb_lm0 = take(((size_t)L.capLmBlocks + LFVIO_NUM_FRAMES + 1) * 4), L.linb_ns = take(((size_t)L.capLmBlocks + LFVIO_NUM_FRAMES + 1) * 4);  // (at most a group per strip)
-  L.linw_end = o;
-  L.lam[0] = take(LB * 8), L.lam[1] = take(LB * 8);
-  for (int k = 0; k < SPEC_EXTRA; k++) L.lamE[k] = take((size_t)SPEC_MAX_LM * 8);
-  L.cost_partE = take((size_t)SPEC_EXTRA * (SPEC_MAX_LM / 64) * LMS * 8);
-  L.prior_A = take((size_t)LFVIO_MAX_PRIOR_DIM * LFVIO_MAX_PRIOR_DIM * 8);
-  L.a = take(LB * 8), L.b = take(LB * 8), L.W = take(LB * WLD * 8);
-  L.Wt = take((size_t)WT_PAIRS * std::max((size_t)SPEC_MAX_LM, LB) * 16);  // (a large window's rows are LB apart: k_linb)
-  L.scale_l = take(LB * 8), L.grad_l = take(LB * 8), L.gn_l = take(LB * 8), L.diag_l = take(LB * 8);
-  L.einv_l = take(LB * 8), L.d1 = take(LB * 8), L.d2 = take(LB * 8);
-  L.gram_part = take((size_t)L.capChunks * NGP * 8);
-  L.pairG = take((size_t)NPAIR * NGP * 8);
-  L.schur_part = take((size_t)L.capSchurParts * LINB_LEN * 8);  // (k_linb's partials live there too: LINB_LEN > SCHUR_LEN doubles per group, at most a group per strip)
-  L.xch = take((size_t)XCH_ALLOC * 8);
-  L.lm_part = take((size_t)L.capLmBlocks * LMS * 8);
-  L.cost_part = take((size_t)L.capLmBlocks * LMS * 8);
-  L.imu_out = take((size_t)LFVIO_WINDOW_SIZE * IMU_OUT * 8);
-  L.imu_raw = take((size_t)LFVIO_WINDOW_SIZE * IMU_RAW * 8);
-  L.mscr = take((size_t)HPP_CAP * 8);
-  L.eig_aux = take(4096);
-  L.total = align_up(o, 4096);
-  return L;
-}
+// (Layout, make_layout and the kernels' SlotArgs: slot_args.h)
 
 size_t down_bytes(int maxN) { return sizeof(FrameState) * 2 + sizeof(TRState) + 2 * ((size_t)maxN * 8 + 128) + sizeof(LfvioPrior) + 4096; }
 
@@ -1188,24 +1118,25 @@ void with_offs(bool offs, F &&launch) {
 void launch_lin(lfvio_ctx *c, const Route &r, int mode, bool offs) {
   const int count = r.count, lw = r.g.lw, gram_wgs = (r.g.ch + 3) / 4;  // one chunk per wave
   const size_t st = c->L.total;
+  const SlotArgs sa = slot_args(c->L);  // (baked into a captured graph like SumArgs: whatever changes the Layout — reserve() — drops the graphs)
   with_offs(offs, [&](auto o) {
     if (!r.split) {
       hipLaunchKernelGGL((k_lin<LIN_ROLE_ALL, decltype(o)::value>), dim3(lw + gram_wgs + LFVIO_WINDOW_SIZE + 1, count), dim3(LIN_THREADS), 0, c->stream, c->d_base, st,
-                         mode, lw, gram_wgs);
+                         mode, lw, gram_wgs, sa);
       return;
     }
     // A resident batch: the roles go out as separate launches, each of a kernel compiled for that role alone.  Measured at 512 windows of 300 landmarks:
     // landmark role 115 us + Gram role 175 us + IMU / prior roles 104 us on their own, 679 us as ONE grid — workgroups of four
     // different code paths side by side on every CU (the sweep is ~30 KB of straight-line code per role) do not share an
     // instruction cache well; two more launches cost 9 us.
-    hipLaunchKernelGGL((k_lin<LIN_ROLE_LM, decltype(o)::value>), dim3(lw, count), dim3(LIN_THREADS), 0, c->stream, c->d_base, st, mode, lw, 0);
-    hipLaunchKernelGGL((k_lin<LIN_ROLE_GRAM, decltype(o)::value>), dim3(gram_wgs, count), dim3(LIN_THREADS), 0, c->stream, c->d_base, st, mode | MODE_NOCOUNT, 0, gram_wgs);
+    hipLaunchKernelGGL((k_lin<LIN_ROLE_LM, decltype(o)::value>), dim3(lw, count), dim3(LIN_THREADS), 0, c->stream, c->d_base, st, mode, lw, 0, sa);
+    hipLaunchKernelGGL((k_lin<LIN_ROLE_GRAM, decltype(o)::value>), dim3(gram_wgs, count), dim3(LIN_THREADS), 0, c->stream, c->d_base, st, mode | MODE_NOCOUNT, 0, gram_wgs, sa);
   });
   if (!r.split) return;
   const bool raw = (mode & (MODE_GATED - 1)) == MODE_SOLVE && !(mode & (MODE_GATED | MODE_DECIDE));
   if (raw) hipLaunchKernelGGL(k_imu_raw, dim3((count * LFVIO_WINDOW_SIZE + 63) / 64), dim3(64), 0, c->stream, c->d_base, st, count);
-  if (raw) hipLaunchKernelGGL((k_lin<LIN_ROLE_POSE_RAW, false>), dim3(LFVIO_WINDOW_SIZE + 1, count), dim3(LIN_THREADS), 0, c->stream, c->d_base, st, mode | MODE_NOCOUNT, 0, 0);
-  else hipLaunchKernelGGL((k_lin<LIN_ROLE_POSE, false>), dim3(LFVIO_WINDOW_SIZE + 1, count), dim3(LIN_THREADS), 0, c->stream, c->d_base, st, mode | MODE_NOCOUNT, 0, 0);
+  if (raw) hipLaunchKernelGGL((k_lin<LIN_ROLE_POSE_RAW, false>), dim3(LFVIO_WINDOW_SIZE + 1, count), dim3(LIN_THREADS), 0, c->stream, c->d_base, st, mode | MODE_NOCOUNT, 0, 0, sa);
+  else hipLaunchKernelGGL((k_lin<LIN_ROLE_POSE, false>), dim3(LFVIO_WINDOW_SIZE + 1, count), dim3(LIN_THREADS), 0, c->stream, c->d_base, st, mode | MODE_NOCOUNT, 0, 0, sa);
 }
 
 // fixed-order reduction of the partials; two levels once a single k_sum thread would have to walk hundreds of them
@@ -1470,11 +1401,11 @@ int worker_graphs(lfvio_ctx *c, const Route &r, const CallPlan &p) {
                      (long long)L.gram_part, (long long)L.pairG, (long long)L.imu_out, (long long)L.prior_A - (long long)back};
     const int rc = capture_graph(c, ss, side_graph, [&]() -> int {
       for (int rd = 0; rd < SIDE_ROUNDS; rd++) {
-        hipLaunchKernelGGL(k_spec_begin, dim3(1), dim3(128), 0, ss, sh, back);
+        hipLaunchKernelGGL(k_spec_begin, dim3(1), dim3(128), 0, ss, sh, back, slot_args(L));
         // (a re-anchored state: on the sphere but for a fixed extrinsic)
         with_offs(r.offs & 2, [&](auto o) {
           hipLaunchKernelGGL((k_lin<LIN_ROLE_ALL, decltype(o)::value>), dim3(lw_cap + gram_wgs + LFVIO_WINDOW_SIZE + 1, 1), dim3(LIN_THREADS), 0, ss, sh, back, mode,
-                             lw_cap, gram_wgs);
+                             lw_cap, gram_wgs, slot_args(L, back));  // (the shadow's variant: its input offsets lead back into slot 0)
         });
         hipLaunchKernelGGL(k_sum, dim3(HPP_BLOCKS + SCHUR_LEN / 256 + 1, 1), dim3(256), 0, ss, sh, back, mode, 0, sa);
         hipLaunchKernelGGL(k_marg_solve<true>, dim3(1, 1), dim3(MARG_THREADS), MARG_LDS, ss, sh, back,
@@ -2284,7 +2215,7 @@ int lfvio_debug_time_kernel(lfvio_ctx *c, int which, int count, int reps, double
         const int gram_wgs = (g.ch + 3) / 4;
         const int gx = which == 8 ? g.lw : which == 9 ? gram_wgs : which == 18 ? LFVIO_WINDOW_SIZE : LFVIO_WINDOW_SIZE + 1;
         hipLaunchKernelGGL((k_lin<LIN_ROLE_ALL, false>), dim3(gx, count), dim3(LIN_THREADS), 0, c->stream, c->d_base, st, MODE_SOLVE, which == 8 ? g.lw : 0,
-                           which == 9 ? gram_wgs : 0);
+                           which == 9 ? gram_wgs : 0, slot_args(c->L));
       } break;
       case 4: case 5: case 6: case 7: {  // k_setup by role: state + table | + IMU sqrt_info | + prior J0^T J0 | + inverse depths
         const SetupLaunch sl = setup_launch(c, count, g.lm, false);  // (the grid the product launches: compact for a resident batch)

@@ -3,6 +3,7 @@
 #pragma once
 #include "dev_math.h"
 #include "dev_types.h"
+#include "slot_args.h"
 
 // candidate z's number: slot 0 is the regular field, slots 1.. the *E arrays (compare-and-select: a run-time index into
 // these small arrays would put them, and the header copy around them, in scratch memory)
@@ -58,21 +59,42 @@ DEV int decide_candidates(const TRHead &t) { return t.chol_fail ? 1 : (t.spec_n 
 // The 64 lanes of one wave: cost and model terms of every candidate slot from the per-block partials.  The partial sums
 // of EVERY slot are requested at once, whatever K says (a slot that was not evaluated holds stale numbers, which are
 // dropped): behind `z < K` each slot's loads would be a memory round trip of their own.
-DEV void decide_sums(const Slot *S, const TRHead &t, int K, int sharded, int nLmBlocks, int lane, DecideSums &o) {
-  const double *cp0 = S->cost_part, *cpE = S->cost_partE, *pc0 = S->pose_cost;
+// decide_first: the round of loads that waits for nothing — every lane's FIRST block of every slot and its pose-side cost.
+// cp0 / cpE: Slot::cost_part / cost_partE, from the header or from a kernel argument (SlotArgs); in the second case the loads leave
+// before nLmBlocks is known, so the block index is clamped to the `cap` blocks the arrays are known to have (>= 1; a caller that
+// goes through the header passes the window's own count).  A lane past the window's blocks then adds +0.0, which leaves its zero a zero.
+struct DecideFirst {
+  double f[1 + SPEC_EXTRA][5], pc[1 + SPEC_EXTRA];
+};
+DEV void decide_first(const Slot *S, int lane, const double *cp0, const double *cpE, int cap, DecideFirst &o) {
+#pragma unroll
+  for (int z = 0; z < 1 + SPEC_EXTRA; z++) {
+    const double *cp = z == 0 ? cp0 : cpE + (size_t)(z > 0 ? z - 1 : 0) * (SPEC_MAX_LM / 64) * LMS;
+    const double *pcz = z == 0 ? (const double *)S->pose_cost : (const double *)S->pose_costE[z > 0 ? z - 1 : 0];
+    const double *p = cp + (size_t)(z == 0 ? first_block_index(cap, lane) : first_blockE_index(cap, lane)) * LMS;
+#pragma unroll
+    for (int e = 0; e < 5; e++) o.f[z][e] = p[e];
+    o.pc[z] = pcz[lane < 11 ? lane : 0];
+  }
+}
+// first: the lanes' first blocks as decide_first requested them ahead of the header (k_lin's prologue), or nullptr: everything is
+// requested here (the kernels off the call's chain, where the early round only costs registers).
+DEV void decide_sums(const Slot *S, const TRHead &t, int K, int sharded, int nLmBlocks, int lane, DecideSums &o, const double *cp0, const double *cpE, const DecideFirst *first) {
   double c[1 + SPEC_EXTRA], l[1 + SPEC_EXTRA], q[1 + SPEC_EXTRA], d[1 + SPEC_EXTRA], x[1 + SPEC_EXTRA];
 #pragma unroll
   for (int z = 0; z < 1 + SPEC_EXTRA; z++) {
     const double *cp = z == 0 ? cp0 : cpE + (size_t)(z > 0 ? z - 1 : 0) * (SPEC_MAX_LM / 64) * LMS;
-    const double *pcz = z == 0 ? pc0 : (const double *)S->pose_costE[z > 0 ? z - 1 : 0];
     const int nbz = z == 0 ? nLmBlocks : min(nLmBlocks, SPEC_MAX_LM / 64);
+    const double *pcz = z == 0 ? (const double *)S->pose_cost : (const double *)S->pose_costE[z > 0 ? z - 1 : 0];
+    const bool in = lane < nbz;
     c[z] = l[z] = q[z] = d[z] = x[z] = 0.0;
+    if (first) c[z] += in ? first->f[z][0] : 0.0, l[z] += in ? first->f[z][1] : 0.0, q[z] += in ? first->f[z][2] : 0.0, d[z] += in ? first->f[z][3] : 0.0, x[z] += in ? first->f[z][4] : 0.0;
 #pragma unroll 8
-    for (int k = lane; k < nbz; k += 64) {  // (unrolled: the partials of eight blocks are requested together)
+    for (int k = first ? lane + 64 : lane; k < nbz; k += 64) {  // (unrolled: the partials of eight blocks are requested together)
       const double *p = cp + (size_t)k * LMS;
       c[z] += p[0], l[z] += p[1], q[z] += p[2], d[z] += p[3], x[z] += p[4];
     }
-    if (lane < 11) c[z] += pcz[lane];
+    if (lane < 11) c[z] += first ? first->pc[z] : pcz[lane];
   }
 #pragma unroll
   for (int z = 0; z < 1 + SPEC_EXTRA; z++) {
@@ -84,6 +106,11 @@ DEV void decide_sums(const Slot *S, const TRHead &t, int K, int sharded, int nLm
     const double *sc = S->xch + XOFF_C;
     o.cost[0] = sc[XS_CCOST], o.mlin[0] = sc[XS_MLIN], o.mquad[0] = sc[XS_MQUAD], o.dn[0] = sc[XS_DN], o.xn[0] = sc[XS_XN];
   }
+}
+
+// the kernels off the call's chain (decide_body): everything through the header, requested here
+DEV void decide_sums(const Slot *S, const TRHead &t, int K, int sharded, int nLmBlocks, int lane, DecideSums &o) {
+  decide_sums(S, t, K, sharded, nLmBlocks, lane, o, S->cost_part, S->cost_partE, nullptr);
 }
 
 // ONE lane: one iteration per evaluated candidate.  The pass holds K of them (the steps for radius, radius / 2, radius / 4),
