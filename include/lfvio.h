@@ -453,6 +453,61 @@ typedef struct {
 } LfvioPnpOut;
 int lfvio_pnp(lfvio_ctx *ctx, const LfvioPnpIn *in, LfvioPnpOut *out /* [F] */);
 
+/* lfvio_sfm_ba: the "full BA" that ends GlobalSFM::construct (vins_estimator/src/initial/initial_sfm.cpp:233-309) — the second of the
+ * reference's two ceres::Solve calls.  The incremental part of construct() (:155-218) and relativePose() stay with the caller: their
+ * outputs are this call's inputs.
+ *   :237-257  parameter blocks c_rotation[i] (4, w x y z, world to camera, QuaternionParameterization) and c_translation[i] (3);
+ *             the rotation of frame l constant (:249-252), the translations of frames l and frame_num - 1 constant (:253-256);
+ *   :259-275  one ReprojectionError3D (initial_sfm.h:25-63) per observation of every sfm_f entry with state == true, no loss:
+ *             r = p / |p| - bearing, p = R(q / |q|) X + t (ceres::QuaternionRotatePoint normalises), the bearing as stored (not
+ *             renormalised; z <= 0 is an ordinary input); the caller lists only those entries, in sfm_f order, as a CSR;
+ *   :276-281  DENSE_SCHUR, every other option Ceres' default: TrustRegionMinimizer with the Levenberg-Marquardt strategy (initial
+ *             radius 1e4; the diagonal sqrt(clamp(diag J^T J, 1e-6, 1e32) / radius) on every column; on success radius <- min(1e16,
+ *             radius / max(1/3, 1 - (2 rho - 1)^3)), on rejection radius <- radius / factor, factor <- 2 factor), Jacobi scaling fixed
+ *             at iteration 0, min_relative_decrease 1e-3, the three tolerance tests, five consecutive invalid steps -> LFVIO_FAILURE;
+ *             DESIGN.md §3h lists every row of that policy and where it comes from — parity with Ceres itself is not pinned;
+ *   :283      accepted = termination == LFVIO_CONVERGENCE || final_cost < 5e-3 (the caller returns false when it is 0);
+ *   :295-309  Q[i] = the inverse of c_rotation[i] (conjugate / squared norm), T[i] = -(Q[i] * c_translation[i]).
+ * c_rotation [F][4], c_translation [F][3] and position [P][3] (sfm_f[j].position of the listed entries) are read and, on LFVIO_OK,
+ * written as Ceres leaves them (:240-246, :273); the constant blocks come back bit for bit.  x [+] delta = [cos|delta|, sin|delta| /
+ * |delta| delta] (x) x with no renormalisation afterwards: a rotation keeps the norm it came with.  The trace holds iteration 0 too,
+ * as LfvioSolution has it; the entry of a step that was not successful has gradient_max_norm 0.
+ * Options: a tolerance <= 0 takes Ceres' default (1e-6, 1e-10, 1e-8); max_num_iterations < 0 takes 50, 0 is iteration 0 alone (the
+ * evaluation at the start, as in Ceres), at most LFVIO_MAX_TRACE - 1.  The fields exist so that a test can force convergence.
+ * Deviations from the reference:
+ *   1. max_solver_time_in_seconds = 0.2 (:279) is NOT honoured: the loop runs on the device without a host round trip and ends on
+ *      its tolerances or its iteration cap;
+ *   2. a non-finite initial cost returns LFVIO_ERR_NONFINITE with every output untouched (Ceres would report FAILURE);
+ *   3. every sum runs in the device's own fixed order (no atomics): a repeated call returns the same bits.
+ * LFVIO_ERR_ARG (outputs untouched): null pointers, num_frames outside [2, LFVIO_NUM_FRAMES], ref_frame outside [0, F - 2], num_points
+ * outside [1, 4096], obs_offset[0] != 0, a point with no observation or more than F (which covers an offset array that is not
+ * ascending), an obs_frame outside [0, F), a frame listed twice for one point, max_num_iterations > LFVIO_MAX_TRACE - 1.
+ * A frame may have no observation at all: its blocks do not move.  One upload, one launch (one workgroup), one download; runs on the
+ * feature stream like lfvio_pnp: it does not wait for an optimization in flight. */
+typedef struct {
+  int num_frames;            /* F = frame_num, in [2, LFVIO_NUM_FRAMES] */
+  int ref_frame;             /* l, in [0, F - 2] */
+  int num_points;            /* P in [1, 4096] */
+  const int *obs_offset;     /* [P + 1] obs_offset[0] = 0, 1 <= obs_offset[j + 1] - obs_offset[j] <= F */
+  const int *obs_frame;      /* [M] observation.first, M = obs_offset[P] */
+  const double *obs_bearing; /* [M][3] observation.second, as stored */
+  int max_num_iterations;    /* < 0: 50 */
+  double function_tolerance, gradient_tolerance, parameter_tolerance; /* <= 0: 1e-6, 1e-10, 1e-8 */
+} LfvioSfmBaIn;
+typedef struct {
+  int termination;           /* LFVIO_CONVERGENCE / LFVIO_NO_CONVERGENCE / LFVIO_FAILURE */
+  int num_iterations;        /* iteration 0 included */
+  int num_successful_steps, num_unsuccessful_steps;
+  int accepted;              /* :283 */
+  int pad_;
+  double initial_cost, final_cost; /* 1/2 sum r^2, as summary.final_cost */
+  double Q[LFVIO_NUM_FRAMES][4];   /* w x y z; rows >= F untouched */
+  double T[LFVIO_NUM_FRAMES][3];
+  LfvioIterationSummary trace[LFVIO_MAX_TRACE];
+} LfvioSfmBaOut;
+int lfvio_sfm_ba(lfvio_ctx *ctx, const LfvioSfmBaIn *in, double *c_rotation /* [F][4] */, double *c_translation /* [F][3] */,
+                 double *position /* [P][3] */, LfvioSfmBaOut *out);
+
 /* ---- landmark-sharded API (multi-GPU) ------------------------
  * Every rank passes the same window but linearizes only landmarks [lm_begin, lm_end) (caller order);
  * IMU factors and the prior are added on the rank(s) with add_pose_side != 0 — exactly one rank.

@@ -45,6 +45,7 @@ constexpr ncclDataType_t ncclDouble = 8;
 #include "kernels_twoview.h"
 #include "kernels_vialign.h"
 #include "kernels_pnp.h"
+#include "kernels_sfmba.h"
 
 #define HIPCHK(ctx, call)                                                                      \
   do {                                                                                         \
@@ -2361,6 +2362,8 @@ int lfvio_debug_query(lfvio_ctx *c, const char *key, double *out, int n) {
 #include "vialign.inc"
 
 #include "pnp.inc"
+
+#include "sfmba.inc"
 // ---- landmark-sharded API: declared in lfvio.h, implemented in shard.inc
 #include "shard.inc"
 // ---- multi-GPU groups (RCCL): declared in lfvio.h, implemented in group.inc

@@ -464,6 +464,50 @@ class PnpOutC(C.Structure):
 
 PNP_MIN_POINTS, PNP_MAX_POINTS = 6, 4096
 
+
+class SfmBaInC(C.Structure):
+    """LfvioSfmBaIn (include/lfvio.h)."""
+    _fields_ = [
+        ("num_frames", C.c_int),
+        ("ref_frame", C.c_int),
+        ("num_points", C.c_int),
+        ("obs_offset", C.POINTER(C.c_int)),
+        ("obs_frame", C.POINTER(C.c_int)),
+        ("obs_bearing", C.POINTER(C.c_double)),
+        ("max_num_iterations", C.c_int),
+        ("function_tolerance", C.c_double),
+        ("gradient_tolerance", C.c_double),
+        ("parameter_tolerance", C.c_double),
+    ]
+
+
+class SfmBaOutC(C.Structure):
+    """LfvioSfmBaOut (include/lfvio.h)."""
+    _fields_ = [
+        ("termination", C.c_int),
+        ("num_iterations", C.c_int),
+        ("num_successful_steps", C.c_int),
+        ("num_unsuccessful_steps", C.c_int),
+        ("accepted", C.c_int),
+        ("pad_", C.c_int),
+        ("initial_cost", C.c_double),
+        ("final_cost", C.c_double),
+        ("Q", (C.c_double * 4) * NUM_FRAMES),
+        ("T", (C.c_double * 3) * NUM_FRAMES),
+        ("trace", IterationSummary * MAX_TRACE),
+    ]
+
+    def as_dict(self, F=NUM_FRAMES):
+        n = min(int(self.num_iterations), MAX_TRACE)
+        trace = [{k: getattr(self.trace[i], k) for k, _ in IterationSummary._fields_} for i in range(max(n, 0))]
+        return dict(termination=int(self.termination), num_iterations=int(self.num_iterations), num_successful_steps=int(self.num_successful_steps),
+                    num_unsuccessful_steps=int(self.num_unsuccessful_steps), accepted=int(self.accepted), initial_cost=float(self.initial_cost),
+                    final_cost=float(self.final_cost), Q=np.array([list(r) for r in self.Q], dtype=np.float64)[:F],
+                    T=np.array([list(r) for r in self.T], dtype=np.float64)[:F], trace=trace)
+
+
+SFMBA_MAX_POINTS = 4096
+
 HIP_SYMBOLS = [
     "lfvio_create", "lfvio_destroy", "lfvio_last_error", "lfvio_version", "lfvio_solve", "lfvio_solve_relo", "lfvio_marginalize",
     "lfvio_batch_reserve", "lfvio_batch_upload", "lfvio_batch_optimize", "lfvio_batch_optimize_async",
@@ -472,7 +516,7 @@ HIP_SYMBOLS = [
     "lfvio_shard_begin", "lfvio_shard_exchange_len", "lfvio_shard_scalar_offset", "lfvio_shard_exchange_ptr", "lfvio_shard_linearize",
     "lfvio_shard_solve", "lfvio_shard_candidate", "lfvio_shard_decide", "lfvio_shard_marg_linearize", "lfvio_shard_marg_finish",
     "lfvio_shard_finish", "lfvio_shard_restart", "lfvio_shard_enqueue", "lfvio_shard_poll", "lfvio_triangulate", "lfvio_shift_depth", "lfvio_preintegrate",
-    "lfvio_two_view", "lfvio_vi_align", "lfvio_pnp",
+    "lfvio_two_view", "lfvio_vi_align", "lfvio_pnp", "lfvio_sfm_ba",
     "lfvio_group_create", "lfvio_group_unique_id", "lfvio_group_create_rank", "lfvio_group_create_local", "lfvio_group_destroy",
     "lfvio_group_last_error", "lfvio_group_size", "lfvio_group_local", "lfvio_group_rank", "lfvio_group_ctx", "lfvio_group_backend",
     "lfvio_group_solve", "lfvio_group_upload", "lfvio_group_optimize", "lfvio_group_download", "lfvio_group_range",
@@ -541,6 +585,8 @@ def load_hip_library(path=None):
         lib.lfvio_vi_align.argtypes = [C.c_void_p, C.POINTER(ViAlignInC), C.POINTER(ViAlignOutC), _dp, C.POINTER(Preintegration)]
     if hasattr(lib, "lfvio_pnp"):
         lib.lfvio_pnp.argtypes = [C.c_void_p, C.POINTER(PnpInC), C.POINTER(PnpOutC)]
+    if hasattr(lib, "lfvio_sfm_ba"):
+        lib.lfvio_sfm_ba.argtypes = [C.c_void_p, C.POINTER(SfmBaInC), _dp, _dp, _dp, C.POINTER(SfmBaOutC)]
     lib.lfvio_shard_marg_linearize.argtypes = [C.c_void_p, C.c_int]
     lib.lfvio_shard_marg_finish.argtypes = [C.c_void_p, C.c_int, C.POINTER(Prior)]
     # multi-GPU groups (RCCL inside the library)

@@ -327,6 +327,31 @@ class Engine:
             return res
         return rc, res
 
+    def sfm_ba(self, ref_frame, obs_offset, obs_frame, obs_bearing, c_rotation, c_translation, position, max_num_iterations=-1,
+               function_tolerance=0.0, gradient_tolerance=0.0, parameter_tolerance=0.0, out=None, check=True):
+        """lfvio_sfm_ba: the full BA of GlobalSFM::construct — a CSR over the points' observations (obs_offset [P + 1], obs_frame [M],
+        obs_bearing [M, 3]), c_rotation [F, 4] (w x y z), c_translation [F, 3], position [P, 3].  The caller's arrays are not written:
+        returns a dict with the fields of LfvioSfmBaOut (Q [F, 4], T [F, 3], trace a list of dicts) plus c_rotation, c_translation,
+        position as the call left its own copies, and rc.  out: an abi.SfmBaOutC to be written (a test of what a failed call leaves alone
+        passes its own); check=False returns the error code under `rc` instead of raising."""
+        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32).reshape(-1)
+        off, frm = i32(obs_offset), i32(obs_frame)
+        us = np.ascontiguousarray(obs_bearing, dtype=np.float64).reshape(-1, 3)
+        q, t, X = (np.array(a, dtype=np.float64, order="C").reshape(-1, k) for a, k in ((c_rotation, 4), (c_translation, 3), (position, 3)))
+        bin_ = abi.SfmBaInC()
+        bin_.num_frames, bin_.ref_frame, bin_.num_points = len(q), int(ref_frame), len(off) - 1
+        ip = C.POINTER(C.c_int)
+        bin_.obs_offset, bin_.obs_frame, bin_.obs_bearing = off.ctypes.data_as(ip), frm.ctypes.data_as(ip), _p(us)
+        bin_.max_num_iterations = int(max_num_iterations)
+        bin_.function_tolerance, bin_.gradient_tolerance, bin_.parameter_tolerance = float(function_tolerance), float(gradient_tolerance), float(parameter_tolerance)
+        out = abi.SfmBaOutC() if out is None else out
+        rc = self.lib.lfvio_sfm_ba(self.ctx, C.byref(bin_), _p(q), _p(t), _p(X), C.byref(out))
+        if check:
+            self._check(rc, "lfvio_sfm_ba")
+        res = out.as_dict(len(q))
+        res.update(rc=rc, c_rotation=q, c_translation=t, position=X)
+        return res
+
     def time_kernel(self, which, count, reps):
         ms = np.zeros(1)
         self._check(self.lib.lfvio_debug_time_kernel(self.ctx, which, count, reps, _p(ms)), "time_kernel")
