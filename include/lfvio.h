@@ -454,8 +454,8 @@ typedef struct {
 int lfvio_pnp(lfvio_ctx *ctx, const LfvioPnpIn *in, LfvioPnpOut *out /* [F] */);
 
 /* lfvio_sfm_ba: the "full BA" that ends GlobalSFM::construct (vins_estimator/src/initial/initial_sfm.cpp:233-309) — the second of the
- * reference's two ceres::Solve calls.  The incremental part of construct() (:155-218) and relativePose() stay with the caller: their
- * outputs are this call's inputs.
+ * reference's two ceres::Solve calls.  The incremental part of construct() (:121-218) is lfvio_sfm_construct below and relativePose()
+ * stays with the caller: their outputs are this call's inputs.
  *   :237-257  parameter blocks c_rotation[i] (4, w x y z, world to camera, QuaternionParameterization) and c_translation[i] (3);
  *             the rotation of frame l constant (:249-252), the translations of frames l and frame_num - 1 constant (:253-256);
  *   :259-275  one ReprojectionError3D (initial_sfm.h:25-63) per observation of every sfm_f entry with state == true, no loss:
@@ -507,6 +507,66 @@ typedef struct {
 } LfvioSfmBaOut;
 int lfvio_sfm_ba(lfvio_ctx *ctx, const LfvioSfmBaIn *in, double *c_rotation /* [F][4] */, double *c_translation /* [F][3] */,
                  double *position /* [P][3] */, LfvioSfmBaOut *out);
+
+/* lfvio_sfm_construct: the incremental part of GlobalSFM::construct (vins_estimator/src/initial/initial_sfm.cpp:121-218) — from the
+ * relative pose of frames l and frame_num - 1 (what relativePose() returns; it stays with the caller) to a pose per keyframe and a
+ * position per point, which are lfvio_sfm_ba's in/out arrays.  The schedule, literally; an "op" is one step of it, numbered from 0:
+ *   :125-153  q[l] = 1, T[l] = 0, q[F - 1] = q[l] * Quaterniond(relative_R), T[F - 1] = relative_T; for both, c_Quat = q.inverse()
+ *             (conjugate / squared norm), c_Rotation = c_Quat.toRotationMatrix(), c_Translation = -1 * (c_Rotation * T).  Eigen's
+ *             matrix to quaternion conversion with its four branches (trace > 0, else the largest diagonal entry);
+ *   :157-175  for i = l .. F - 2: if i > l, solveFrameByPnP(i) [one op]; triangulateTwoFrames(i, F - 1) [one op];
+ *   :177-178  for i = l + 1 .. F - 2: triangulateTwoFrames(l, i) [one op each];
+ *   :181-195  for i = l - 1 .. 0: solveFrameByPnP(i) [one op]; triangulateTwoFrames(i, l) [one op];
+ *   :197-218  the closing loop [ONE op]: every point still untriangulated with >= 2 observations, from its first and last one.
+ * 3 F - 4 - l ops in all.  solveFrameByPnP (:23-71) takes the points with state == true that have an observation in frame i, in
+ * ascending j, and is lfvio_pnp's compute_pose on them (same kernel code, same bits); fewer than 10 returns false (:51-52).  Its
+ * result is the frame's c_Rotation, c_Translation; c_Quat[i] = c_Rotation[i] (:168, :190) is the same matrix to quaternion
+ * conversion, applied even when compute_pose returned a reflection.  triangulateTwoFrames (:73-110) takes every point with
+ * state == false seen in both frames; triangulatePoint (:6-21) takes the right singular vector of the smallest singular value of the
+ * 4 x 4 design matrix and divides by its fourth entry, with IEEE semantics: a zero fourth entry gives inf / NaN in that position and
+ * the chain goes on.  A position is written once and never changes.
+ * Outputs: c_rotation[i] = c_Quat[i] (w x y z), c_translation[i] = c_Translation[i] as :240-246 hand them to Ceres; position[j]
+ * (0, 0, 0 for a point that stays untriangulated); tri_op[j] = the op that set state = true for point j, or -1.  position compacted
+ * to the points with tri_op >= 0, with their observations, is what :259-275 hand to Ceres: with c_rotation and c_translation these
+ * are exactly lfvio_sfm_ba's arrays.
+ * Deviations from the reference:
+ *   1. where the finiteness gate of the PnP trips (lfvio_pnp, deviation 1) the chain stops with status 2; the reference would carry
+ *      the NaN on.  out->pnp[f] of that frame holds status 1 and the non-finite record as computed;
+ *   2. on status 1 or 2 the outputs hold what the chain had when it stopped: rows of c_rotation, c_translation of frames not yet
+ *      posed are left as the caller had them, position and tri_op are written for every point (the reference returns false and its
+ *      caller drops everything);
+ *   3. a frame listed twice for one point is LFVIO_ERR_ARG, as in lfvio_sfm_ba (the two scans of the reference, :34-46 and :87-99,
+ *      disagree on which of two duplicates they take);
+ *   4. the signs an SVD gives its vectors are lfvio_pnp's (its deviation 2: the principal axes pinned by this project's rule); a
+ *      triangulated point does not depend on the sign of its singular vector;
+ *   5. every sum runs in the device's own fixed order (no atomics): a repeated call returns the same bits.
+ * LFVIO_ERR_ARG (outputs untouched): null pointers, num_frames outside [2, LFVIO_NUM_FRAMES], ref_frame outside [0, F - 2], num_points
+ * outside [1, 4096], obs_offset[0] != 0, a point with no observation or more than F (which covers an offset array that is not
+ * ascending), an obs_frame outside [0, F), a frame listed twice for one point.
+ * One upload, one launch (one workgroup), one download; runs on the feature stream like lfvio_sfm_ba: it does not wait for an
+ * optimization in flight. */
+typedef struct {
+  int num_frames;            /* F = frame_num, in [2, LFVIO_NUM_FRAMES] */
+  int ref_frame;             /* l, in [0, F - 2] */
+  int num_points;            /* P in [1, 4096]: ALL of sfm_f, in sfm_f order */
+  const int *obs_offset;     /* [P + 1] obs_offset[0] = 0, 1 <= obs_offset[j + 1] - obs_offset[j] <= F */
+  const int *obs_frame;      /* [M] observation.first, M = obs_offset[P] */
+  const double *obs_bearing; /* [M][3] observation.second, as stored */
+  double relative_R[9];      /* row-major */
+  double relative_T[3];
+} LfvioSfmConstructIn;
+typedef struct {
+  int status;        /* 0 chain complete; 1 solveFrameByPnP returned false (< 10 correspondences, :51-52); 2 a PnP with a non-finite result */
+  int failed_frame;  /* the frame of status 1 / 2, else -1 */
+  int num_triangulated;
+  int pad_;
+  int pnp_op[LFVIO_NUM_FRAMES];    /* op index of the frame's PnP, -1 for l, F - 1 and frames not reached */
+  int pnp_count[LFVIO_NUM_FRAMES]; /* correspondences it was given (0 where pnp_op is -1) */
+  LfvioPnpOut pnp[LFVIO_NUM_FRAMES]; /* compute_pose's record of the frame (zeros where pnp_op is -1 or the count was below 10) */
+} LfvioSfmConstructOut;
+int lfvio_sfm_construct(lfvio_ctx *ctx, const LfvioSfmConstructIn *in, double *c_rotation /* [F][4] w x y z */,
+                        double *c_translation /* [F][3] */, double *position /* [P][3] */, int *tri_op /* [P] */,
+                        LfvioSfmConstructOut *out);
 
 /* ---- landmark-sharded API (multi-GPU) ------------------------
  * Every rank passes the same window but linearizes only landmarks [lm_begin, lm_end) (caller order);

@@ -198,15 +198,12 @@ DEV d3 pnp_pin_axis(d3 v) {
   return lead < 0.0 ? -v : v;
 }
 
-// alphas: device array of 4 doubles per correspondence, written and read by the same thread (plus row 0 by everybody,
-// behind a barrier).
-__global__ __launch_bounds__(PNP_THREADS) void k_pnp(const int *offset, const double *pw_all, const double *us_all, double *alpha_all,
-                                                     PnpRecord *out_all) {
+// compute_pose for the n correspondences (pw, us) of one frame, by the PNP_THREADS threads of one workgroup: steps 1 - 6 of
+// the list above.  al: device array of 4 doubles per correspondence, written and read by the same thread (plus row 0 by
+// everybody, behind a barrier).  red [40 * PNP_THREADS / 64], ut and sbeta are LDS blocks of the caller; thread 0 writes *out.
+// k_pnp calls it once per workgroup, k_sfm_chain (kernels_sfmchain.h) once per solveFrameByPnP of its schedule.
+DEV void pnp_pose(int n, const double *pw, const double *us, double *al, PnpRecord *out, double *red, double (*ut)[12], double (*sbeta)[4], int tid) {
   constexpr int NT = PNP_THREADS;
-  __shared__ double red[40 * NT / 64], ut[4][12], sbeta[3][4];
-  const int tid = threadIdx.x, f = blockIdx.x, o = offset[f], n = offset[f + 1] - o;
-  const double *pw = pw_all + 3 * (size_t)o, *us = us_all + 3 * (size_t)o;
-  double *al = alpha_all + 4 * (size_t)o;
   const double dn = (double)n;
 
   // 1 ---- choose_control_points
@@ -462,7 +459,6 @@ __global__ __launch_bounds__(PNP_THREADS) void k_pnp(const int *offset, const do
     const bool one = e1 < e0;
     const bool two = e2 < (one ? e1 : e0);
     const int N = two ? 2 : one ? 1 : 0;
-    PnpRecord *out = out_all + f;
     bool finite = isfinite(e0) && isfinite(e1) && isfinite(e2);
 #pragma unroll
     for (int j = 0; j < 9; j++) {
@@ -476,4 +472,11 @@ __global__ __launch_bounds__(PNP_THREADS) void k_pnp(const int *offset, const do
     out->err[0] = e0, out->err[1] = e1, out->err[2] = e2;
     out->chosen = N, out->status = finite ? 0 : 1;
   }
+}
+
+__global__ __launch_bounds__(PNP_THREADS) void k_pnp(const int *offset, const double *pw_all, const double *us_all, double *alpha_all,
+                                                     PnpRecord *out_all) {
+  __shared__ double red[40 * PNP_THREADS / 64], ut[4][12], sbeta[3][4];
+  const int f = blockIdx.x, o = offset[f], n = offset[f + 1] - o;
+  pnp_pose(n, pw_all + 3 * (size_t)o, us_all + 3 * (size_t)o, alpha_all + 4 * (size_t)o, out_all + f, red, ut, sbeta, threadIdx.x);
 }

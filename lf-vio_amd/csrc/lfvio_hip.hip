@@ -46,6 +46,7 @@ constexpr ncclDataType_t ncclDouble = 8;
 #include "kernels_vialign.h"
 #include "kernels_pnp.h"
 #include "kernels_sfmba.h"
+#include "kernels_sfmchain.h"
 
 #define HIPCHK(ctx, call)                                                                      \
   do {                                                                                         \
@@ -2364,6 +2365,8 @@ int lfvio_debug_query(lfvio_ctx *c, const char *key, double *out, int n) {
 #include "pnp.inc"
 
 #include "sfmba.inc"
+
+#include "sfmchain.inc"
 // ---- landmark-sharded API: declared in lfvio.h, implemented in shard.inc
 #include "shard.inc"
 // ---- multi-GPU groups (RCCL): declared in lfvio.h, implemented in group.inc

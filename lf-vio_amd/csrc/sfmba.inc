@@ -5,6 +5,25 @@
 // into the staging block of feat.inc, one copy up, one launch (one workgroup runs the whole loop), one copy down of the state and
 // the record.  The kernel's per-point and per-observation blocks live behind the record and never cross the bus.
 
+// The CSR checks that lfvio_sfm_ba and lfvio_sfm_construct (sfmchain.inc) share, and the (point, frame) -> observation table both
+// kernels walk.  Returns 0, or the check that failed: 1 obs_offset[0] != 0; 2 a point with no observation or more than F (which covers
+// an offset array that is not ascending); 3 an obs_frame outside [0, F) or a frame listed twice for one point.
+static int sfm_obs_table(int F, int P, const int *obs_offset, const int *obs_frame, std::vector<int> &slot) {
+  if (obs_offset[0] != 0) return 1;
+  for (int i = 0; i < P; i++) {
+    const long long k = (long long)obs_offset[i + 1] - obs_offset[i];
+    if (k < 1 || k > F) return 2;
+  }
+  slot.assign((size_t)P * F, -1);
+  for (int i = 0; i < P; i++)
+    for (int o = obs_offset[i]; o < obs_offset[i + 1]; o++) {
+      const int f = obs_frame[o];
+      if (f < 0 || f >= F || slot[(size_t)i * F + f] >= 0) return 3;
+      slot[(size_t)i * F + f] = o;
+    }
+  return 0;
+}
+
 int lfvio_sfm_ba(lfvio_ctx *c, const LfvioSfmBaIn *in, double *c_rotation, double *c_translation, double *position, LfvioSfmBaOut *out) {
   if (!c || !in || !out || !c_rotation || !c_translation || !position) return LFVIO_ERR_ARG;
   const int F = in->num_frames, l = in->ref_frame, P = in->num_points;
@@ -13,28 +32,14 @@ int lfvio_sfm_ba(lfvio_ctx *c, const LfvioSfmBaIn *in, double *c_rotation, doubl
     c->err = "lfvio_sfm_ba: num_frames outside [2, LFVIO_NUM_FRAMES], ref_frame outside [0, F - 2], num_points outside [1, 4096], null arrays or more than LFVIO_MAX_TRACE - 1 iterations";
     return LFVIO_ERR_ARG;
   }
-  if (in->obs_offset[0] != 0) {
-    c->err = "lfvio_sfm_ba: obs_offset[0] != 0";
+  std::vector<int> slot;
+  if (const int bad = sfm_obs_table(F, P, in->obs_offset, in->obs_frame, slot)) {
+    c->err = bad == 1   ? "lfvio_sfm_ba: obs_offset[0] != 0"
+             : bad == 2 ? "lfvio_sfm_ba: a point with no observation or more than num_frames (or obs_offset not ascending)"
+                        : "lfvio_sfm_ba: an obs_frame outside [0, num_frames) or a frame listed twice for one point";
     return LFVIO_ERR_ARG;
   }
-  for (int i = 0; i < P; i++) {
-    const long long k = (long long)in->obs_offset[i + 1] - in->obs_offset[i];
-    if (k < 1 || k > F) {
-      c->err = "lfvio_sfm_ba: a point with no observation or more than num_frames (or obs_offset not ascending)";
-      return LFVIO_ERR_ARG;
-    }
-  }
   const size_t M = (size_t)in->obs_offset[P];
-  std::vector<int> slot((size_t)P * F, -1);
-  for (int i = 0; i < P; i++)
-    for (int o = in->obs_offset[i]; o < in->obs_offset[i + 1]; o++) {
-      const int f = in->obs_frame[o];
-      if (f < 0 || f >= F || slot[(size_t)i * F + f] >= 0) {
-        c->err = "lfvio_sfm_ba: an obs_frame outside [0, num_frames) or a frame listed twice for one point";
-        return LFVIO_ERR_ARG;
-      }
-      slot[(size_t)i * F + f] = o;
-    }
   SfmBaHead hd;
   std::memset(&hd, 0, sizeof hd);
   hd.F = F, hd.P = P;

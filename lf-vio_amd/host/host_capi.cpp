@@ -423,6 +423,54 @@ void lfvio_host_set_sfm_structure(void *h, int K, const double *stamps, const do
   s.ids.assign(ids, ids + P), s.xyz.assign(xyz, xyz + 3 * (size_t)P);
   s.valid = true;
 }
+// RelativePose (what relativePose() returns): l, R[9] row-major, T[3]; used by the next full-window image when no bootstrap record, SfM
+// result or SfM structure is set: the estimator runs GlobalSFM::construct() on the device (WindowEstimator::constructSfm), then the PnP
+// loop and the alignment
+void lfvio_host_set_relative_pose(void *h, int l, const double *R, const double *T) {
+  WindowEstimator::RelativePose &r = E(h)->relative;
+  r.l = l;
+  std::memcpy(r.R, R, sizeof r.R), std::memcpy(r.T, T, sizeof r.T);
+  r.valid = true;
+}
+// the SfM structure as the estimator holds it (after constructSfm(), or as set): counts[2] = {K, P}; any array may be null and takes at
+// most cap_kf / cap_pts entries: stamps[K], Q[K][4], T[K][3], ids[P], xyz[P][3]
+void lfvio_host_get_sfm_structure(void *h, int cap_kf, int cap_pts, int *counts, double *stamps, double *Q, double *T, int *ids, double *xyz) {
+  const WindowEstimator::SfmStructure &s = E(h)->structure;
+  counts[0] = (int)s.stamps.size(), counts[1] = (int)s.ids.size();
+  const size_t k = std::min(s.stamps.size(), (size_t)std::max(cap_kf, 0)), p = std::min(s.ids.size(), (size_t)std::max(cap_pts, 0));
+  if (stamps && k) std::memcpy(stamps, s.stamps.data(), k * 8);
+  if (Q && k && s.Q.size() >= 4 * k) std::memcpy(Q, s.Q.data(), k * 32);
+  if (T && k && s.T.size() >= 3 * k) std::memcpy(T, s.T.data(), k * 24);
+  if (ids && p) std::memcpy(ids, s.ids.data(), p * 4);
+  if (xyz && p && s.xyz.size() >= 3 * p) std::memcpy(xyz, s.xyz.data(), p * 24);
+}
+// What the last attempt handed to lfvio_sfm_construct / lfvio_sfm_ba and got back.  info[8] = {frames F, l, points P, observations M,
+// construct call made, its return code, BA call made, its return code}; the arrays (any may be null) take at most cap_points points /
+// cap_obs observations: ids[P], offset[P + 1], frame[M], bearing[M][3], rel[12] = relative_R, relative_T, and as lfvio_sfm_construct left
+// them c_rotation[F][4], c_translation[F][3], position[P][3], tri_op[P]; out, ba.  Returns the number of lfvio_sfm_construct calls so far.
+long long lfvio_host_last_construct(void *h, int cap_points, int cap_obs, int *info, int *ids, int *offset, int *frame, double *bearing, double *rel,
+                                    double *c_rotation, double *c_translation, double *position, int *tri_op, LfvioSfmConstructOut *out, LfvioSfmBaOut *ba) {
+  const WindowEstimator::LastConstruct &v = E(h)->last_construct;
+  const int P = (int)v.ids.size(), M = (int)v.frame.size();
+  info[0] = v.F, info[1] = v.l, info[2] = P, info[3] = M, info[4] = v.called ? 1 : 0, info[5] = v.rc, info[6] = v.ba_called ? 1 : 0, info[7] = v.ba_rc;
+  const bool fits = P <= cap_points && M <= cap_obs;
+  if (fits && P) {
+    if (ids) std::memcpy(ids, v.ids.data(), (size_t)P * 4);
+    if (offset) std::memcpy(offset, v.offset.data(), ((size_t)P + 1) * 4);
+    if (frame && M) std::memcpy(frame, v.frame.data(), (size_t)M * 4);
+    if (bearing && M) std::memcpy(bearing, v.bearing.data(), (size_t)M * 24);
+    if (position && v.position.size() == 3 * (size_t)P) std::memcpy(position, v.position.data(), (size_t)P * 24);
+    if (tri_op && v.tri_op.size() == (size_t)P) std::memcpy(tri_op, v.tri_op.data(), (size_t)P * 4);
+  }
+  if (rel) std::memcpy(rel, v.R, 72), std::memcpy(rel + 9, v.T, 24);
+  if (c_rotation && !v.c_rotation.empty()) std::memcpy(c_rotation, v.c_rotation.data(), v.c_rotation.size() * 8);
+  if (c_translation && !v.c_translation.empty()) std::memcpy(c_translation, v.c_translation.data(), v.c_translation.size() * 8);
+  if (out) *out = v.out;
+  if (ba) *ba = v.ba;
+  return E(h)->construct_calls;
+}
+// out[2] = {attempts that reached lfvio_sfm_construct, attempts that filled the SfM structure}
+void lfvio_host_construct_counts(void *h, long long *out) { out[0] = E(h)->construct_calls, out[1] = E(h)->construct_ok; }
 // ImageFrame::points of entry k of all_image_frame: ids[cap], pts[cap][3]; returns their number, -1: no such entry
 int lfvio_host_image_frame_points(void *h, int k, int cap, int *ids, double *pts) {
   const std::vector<WindowEstimator::ImageFrame> &l = E(h)->image_frames;

@@ -133,6 +133,21 @@ bool Trace::load(const char *path) {
       s.st.valid = true;
       s.at_image = images.size();
       structures.push_back(std::move(s));
+    } else if (head[0] == 9) {
+      if (head[1] != 8 + 4 + 12 * sizeof(double)) {
+        error = "relative pose record with a wrong length";
+        std::fclose(f);
+        return false;
+      }
+      TraceRelative r;
+      int32_t l;
+      double v[12];
+      std::memcpy(&r.stamp, buf.data(), 8), std::memcpy(&l, buf.data() + 8, 4), std::memcpy(v, buf.data() + 12, sizeof v);
+      r.rel.l = l;
+      std::memcpy(r.rel.R, v, 72), std::memcpy(r.rel.T, v + 9, 24);
+      r.rel.valid = true;
+      r.at_image = images.size();
+      relatives.push_back(std::move(r));
     }
   }
   std::fclose(f);
@@ -178,7 +193,7 @@ int replay(WindowEstimator &est, const Trace &trace, const char *traj_path, int 
       for (int j = 0; j < 3; j++) est.ric(i, j) = trace.ric[3 * i + j];
     est.td = trace.td;
   }
-  size_t next_boot = 0, next_restart = 0, image_index = 0, next_relo = 0, next_sfm = 0, next_structure = 0;
+  size_t next_boot = 0, next_restart = 0, image_index = 0, next_relo = 0, next_sfm = 0, next_structure = 0, next_relative = 0;
   const int relo_solves0 = est.relo_solves;
   const std::vector<TraceImu> &imu = trace.imu;
   size_t front = 0;         // head of the IMU queue
@@ -217,6 +232,10 @@ int replay(WindowEstimator &est, const Trace &trace, const char *traj_path, int 
       while (next_structure < trace.structures.size() && trace.structures[next_structure].stamp < msg.t - 1e-6) next_structure++;
       if (next_structure < trace.structures.size() && !(trace.structures[next_structure].stamp > msg.t + 1e-6))
         est.structure = trace.structures[next_structure++].st;
+      // ... and the next relative pose record (an SfM structure for the same image wins inside the estimator)
+      while (next_relative < trace.relatives.size() && trace.relatives[next_relative].stamp < msg.t - 1e-6) next_relative++;
+      if (next_relative < trace.relatives.size() && !(trace.relatives[next_relative].stamp > msg.t + 1e-6))
+        est.relative = trace.relatives[next_relative++].rel;
     }
     // getMeasurements(), estimator_node.cpp:96-134, against the CURRENT time-offset estimate
     const double img_t = msg.t + est.td;

@@ -34,6 +34,12 @@
 //                                     WindowEstimator::solvePnpFrames) and then the same alignment.  A bootstrap record or an
 //                                     SfM result for the same image wins.
 //
+//   type 9 = relative pose            f64 stamp (Headers[WINDOW_SIZE] when relativePose() had returned true), i32 l, f64 R[9] (row-major),
+//                                     f64 T[3]: relative_R, relative_T and l as relativePose() returns them (estimator.cpp:270-277).
+//                                     Handed over as type 8 is; the estimator runs GlobalSFM::construct() on the device
+//                                     (WindowEstimator::constructSfm), then the PnP loop and the same alignment.  A bootstrap
+//                                     record, an SfM result or an SfM structure for the same image wins.
+//
 // Unknown record types are skipped, so a recorder can add its own.
 #pragma once
 #include <cstdint>
@@ -76,7 +82,13 @@ struct TraceStructure {  // record type 8
   WindowEstimator::SfmStructure st;
   size_t at_image;  // images recorded before it
 };
+struct TraceRelative {  // record type 9
+  double stamp;
+  WindowEstimator::RelativePose rel;
+  size_t at_image;  // images recorded before it
+};
 struct Trace {
+  std::vector<TraceRelative> relatives;  // in file order
   std::vector<TraceSfm> sfms;         // in file order
   std::vector<TraceStructure> structures;  // in file order
   std::vector<TraceRelo> relos;       // in file order

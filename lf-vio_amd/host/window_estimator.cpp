@@ -8,6 +8,8 @@
 #pragma weak lfvio_two_view
 #pragma weak lfvio_vi_align
 #pragma weak lfvio_pnp
+#pragma weak lfvio_sfm_construct
+#pragma weak lfvio_sfm_ba
 
 #include <algorithm>
 #include <cmath>
@@ -301,6 +303,7 @@ void WindowEstimator::reset() {
   bootstrap.depth_ids.clear(), bootstrap.depths.clear();
   sfm.valid = false;
   structure.valid = false;
+  relative.valid = false;
   image_frames.clear();  // clearState(): all_image_frame.clear(), tmp_pre_integration = nullptr (estimator.cpp:60-66)
   pending_ = ImageFrame();
 }
@@ -378,6 +381,84 @@ Matrix3d g2R(const Vector3d &g) {  // Utility::g2R (utility.cpp:3-13): FromTwoVe
   return fromYawPitchRollDeg(Vector3d(-yaw, 0, 0)) * R0;
 }
 }  // namespace
+
+bool WindowEstimator::constructSfm() {  // estimator.cpp:250-286
+  LastConstruct &lc = last_construct;
+  lc.called = lc.ba_called = false, lc.rc = lc.ba_rc = LFVIO_OK;
+  lc.ids.clear(), lc.offset.assign(1, 0), lc.frame.clear(), lc.bearing.clear();
+  lc.c_rotation.clear(), lc.c_translation.clear(), lc.position.clear(), lc.tri_op.clear();
+  std::memset(&lc.out, 0, sizeof lc.out), std::memset(&lc.ba, 0, sizeof lc.ba);
+  structure.valid = false;
+  const int F = frame_count + 1, l = relative.l;
+  lc.F = F, lc.l = l;
+  std::memcpy(lc.R, relative.R, sizeof lc.R), std::memcpy(lc.T, relative.T, sizeof lc.T);
+  if (F < 2 || F > LFVIO_NUM_FRAMES || l < 0 || l > F - 2) return false;
+  for (int s : tracks.order()) {  // :255-269
+    const int start = tracks.start(s), n = tracks.count(s);
+    if (n < 1 || start < 0 || start + n > F) return false;
+    lc.ids.push_back(tracks.id(s));
+    for (int k = 0; k < n; k++) {
+      lc.frame.push_back(start + k);
+      const double *o = tracks.obs(s, k);
+      lc.bearing.insert(lc.bearing.end(), o, o + 3);
+    }
+    lc.offset.push_back((int)lc.frame.size());
+  }
+  const int P = (int)lc.ids.size();
+  if (P < 1 || P > 4096) return false;  // (4096: the device entries' limit)
+  if (!lfvio_sfm_construct || !lfvio_sfm_ba || !device()) {  // no fallback: over an ABI without the entries the attempt fails
+    status = LFVIO_ERR_DEVICE;
+    lc.rc = LFVIO_ERR_DEVICE;
+    return false;
+  }
+  lc.c_rotation.assign(4 * (size_t)F, 0.0), lc.c_translation.assign(3 * (size_t)F, 0.0), lc.position.assign(3 * (size_t)P, 0.0), lc.tri_op.assign(P, -1);
+  LfvioSfmConstructIn in;
+  in.num_frames = F, in.ref_frame = l, in.num_points = P;
+  in.obs_offset = lc.offset.data(), in.obs_frame = lc.frame.data(), in.obs_bearing = lc.bearing.data();
+  std::memcpy(in.relative_R, relative.R, sizeof in.relative_R), std::memcpy(in.relative_T, relative.T, sizeof in.relative_T);
+  lc.rc = lfvio_sfm_construct(gpu, &in, lc.c_rotation.data(), lc.c_translation.data(), lc.position.data(), lc.tri_op.data(), &lc.out);
+  lc.called = true;
+  construct_calls++;
+  if (lc.rc != LFVIO_OK) {
+    status = lc.rc;
+    return false;
+  }
+  if (lc.out.status != 0 || lc.out.num_triangulated < 1) return false;
+  // :259-275: the entries with state == true, in sfm_f order
+  std::vector<int> keep, off(1, 0), frm;
+  std::vector<double> us, X, q = lc.c_rotation, t = lc.c_translation;
+  for (int j = 0; j < P; j++) {
+    if (lc.tri_op[j] < 0) continue;
+    keep.push_back(j);
+    frm.insert(frm.end(), lc.frame.begin() + lc.offset[j], lc.frame.begin() + lc.offset[j + 1]);
+    us.insert(us.end(), lc.bearing.begin() + 3 * (size_t)lc.offset[j], lc.bearing.begin() + 3 * (size_t)lc.offset[j + 1]);
+    X.insert(X.end(), &lc.position[3 * (size_t)j], &lc.position[3 * (size_t)j] + 3);
+    off.push_back((int)frm.size());
+  }
+  LfvioSfmBaIn bin;
+  bin.num_frames = F, bin.ref_frame = l, bin.num_points = (int)keep.size();
+  bin.obs_offset = off.data(), bin.obs_frame = frm.data(), bin.obs_bearing = us.data();
+  bin.max_num_iterations = -1, bin.function_tolerance = bin.gradient_tolerance = bin.parameter_tolerance = 0.0;  // Ceres' defaults (:276-281)
+  lc.ba_rc = lfvio_sfm_ba(gpu, &bin, q.data(), t.data(), X.data(), &lc.ba);
+  lc.ba_called = true;
+  if (lc.ba_rc != LFVIO_OK) {
+    status = lc.ba_rc;
+    return false;
+  }
+  if (!lc.ba.accepted) return false;  // :283-294
+  SfmStructure &st = structure;  // :295-314
+  st.stamps.resize(F), st.Q.resize(4 * (size_t)F), st.T.resize(3 * (size_t)F);
+  for (int i = 0; i < F; i++) {
+    st.stamps[i] = kf(i).stamp;
+    std::memcpy(&st.Q[4 * (size_t)i], lc.ba.Q[i], 32), std::memcpy(&st.T[3 * (size_t)i], lc.ba.T[i], 24);
+  }
+  st.ids.resize(keep.size());
+  for (size_t k = 0; k < keep.size(); k++) st.ids[k] = lc.ids[keep[k]];
+  st.xyz = X;
+  st.valid = true;
+  construct_ok++;
+  return true;
+}
 
 bool WindowEstimator::solvePnpFrames() {  // estimator.cpp:288-357
   const Config &c = config();
@@ -798,9 +879,15 @@ void WindowEstimator::advanceWindow(double stamp) {  // estimator.cpp:161-220
       } else if (structure.valid) {  // the PnP loop first, then the same path
         aligned = solvePnpFrames() && visualInitialAlign();
         from_sfm = aligned;
+      } else if (relative.valid) {  // GlobalSFM::construct() first, then the same path; a failed construct() slides MARGIN_OLD (:284)
+        const bool built = constructSfm();
+        if (!built) marg_flag = LFVIO_MARGIN_OLD;
+        aligned = built && solvePnpFrames() && visualInitialAlign();
+        from_sfm = aligned;
       }
       sfm.valid = false;
       structure.valid = false;
+      relative.valid = false;
       if (from_sfm && stop_after_align) return;
       initial_timestamp = stamp;
     }

@@ -311,6 +311,33 @@ class WindowEstimator {
     std::vector<LfvioPnpOut> out;
   } last_pnp;
   long long pnp_calls = 0;
+  // What relativePose() returns (estimator.cpp:270-277, :445-473): the rotation and unit-norm position of the newest camera in the frame
+  // of camera l, and l.  It is the one input of initialStructure() still taken from outside (solveRelativeRT as shipped returns values
+  // computed from uninitialised locals); used by the next full-window image when no bootstrap record, SfM result or SfM structure is set.
+  struct RelativePose {
+    bool valid = false;
+    int l = 0;
+    double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, T[3] = {0, 0, 0};  // row-major
+  } relative;
+  // estimator.cpp:250-286 on `relative`: sfm_f from the track table (every track, in f_manager.feature order, its frames start_frame ...,
+  // the bearings as stored), lfvio_sfm_construct (the incremental part of GlobalSFM::construct), the triangulated points compacted into
+  // lfvio_sfm_ba (its full BA, :283 applied through `accepted`), then Q, T and sfm_tracked_points (:295-314) into `structure`.  Returns
+  // true with `structure` filled; false (the attempt fails and the slide is MARGIN_OLD, :284) when the chain's status is not 0,
+  // accepted == 0, a return code is negative, there are no tracks or more than 4096, l is outside [0, frame_count - 1] or either device
+  // entry is missing.  There is no CPU fallback.
+  bool constructSfm();
+  struct LastConstruct {  // what the last attempt passed to lfvio_sfm_construct / lfvio_sfm_ba and got back (tests, tools)
+    bool called = false, ba_called = false;
+    int rc = LFVIO_OK, ba_rc = LFVIO_OK, F = 0, l = 0;
+    double R[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, T[3] = {0, 0, 0};
+    std::vector<int> ids, offset, frame;  // sfm_f: feature ids [P], CSR [P + 1], observation.first [M]
+    std::vector<double> bearing;          // observation.second [M][3]
+    std::vector<double> c_rotation, c_translation, position;  // as lfvio_sfm_construct left them: [F][4], [F][3], [P][3]
+    std::vector<int> tri_op;
+    LfvioSfmConstructOut out;
+    LfvioSfmBaOut ba;
+  } last_construct;
+  long long construct_calls = 0, construct_ok = 0;  // attempts that reached lfvio_sfm_construct; attempts that filled `structure`
   struct LastViAlign {  // what the last attempt passed to lfvio_vi_align and got back (tests, tools)
     bool called = false;
     int rc = LFVIO_OK;

@@ -508,6 +508,41 @@ class SfmBaOutC(C.Structure):
 
 SFMBA_MAX_POINTS = 4096
 
+
+class SfmConstructInC(C.Structure):
+    """LfvioSfmConstructIn (include/lfvio.h)."""
+    _fields_ = [
+        ("num_frames", C.c_int),
+        ("ref_frame", C.c_int),
+        ("num_points", C.c_int),
+        ("obs_offset", C.POINTER(C.c_int)),
+        ("obs_frame", C.POINTER(C.c_int)),
+        ("obs_bearing", C.POINTER(C.c_double)),
+        ("relative_R", C.c_double * 9),
+        ("relative_T", C.c_double * 3),
+    ]
+
+
+class SfmConstructOutC(C.Structure):
+    """LfvioSfmConstructOut (include/lfvio.h)."""
+    _fields_ = [
+        ("status", C.c_int),
+        ("failed_frame", C.c_int),
+        ("num_triangulated", C.c_int),
+        ("pad_", C.c_int),
+        ("pnp_op", C.c_int * NUM_FRAMES),
+        ("pnp_count", C.c_int * NUM_FRAMES),
+        ("pnp", PnpOutC * NUM_FRAMES),
+    ]
+
+    def as_dict(self, F=NUM_FRAMES):
+        return dict(status=int(self.status), failed_frame=int(self.failed_frame), num_triangulated=int(self.num_triangulated),
+                    pnp_op=np.array(self.pnp_op, dtype=np.int32)[:F], pnp_count=np.array(self.pnp_count, dtype=np.int32)[:F],
+                    pnp=[self.pnp[f].as_dict() for f in range(F)])
+
+
+SFM_MIN_PNP = 10  # solveFrameByPnP returns false below it (initial_sfm.cpp:51-52)
+
 HIP_SYMBOLS = [
     "lfvio_create", "lfvio_destroy", "lfvio_last_error", "lfvio_version", "lfvio_solve", "lfvio_solve_relo", "lfvio_marginalize",
     "lfvio_batch_reserve", "lfvio_batch_upload", "lfvio_batch_optimize", "lfvio_batch_optimize_async",
@@ -516,7 +551,7 @@ HIP_SYMBOLS = [
     "lfvio_shard_begin", "lfvio_shard_exchange_len", "lfvio_shard_scalar_offset", "lfvio_shard_exchange_ptr", "lfvio_shard_linearize",
     "lfvio_shard_solve", "lfvio_shard_candidate", "lfvio_shard_decide", "lfvio_shard_marg_linearize", "lfvio_shard_marg_finish",
     "lfvio_shard_finish", "lfvio_shard_restart", "lfvio_shard_enqueue", "lfvio_shard_poll", "lfvio_triangulate", "lfvio_shift_depth", "lfvio_preintegrate",
-    "lfvio_two_view", "lfvio_vi_align", "lfvio_pnp", "lfvio_sfm_ba",
+    "lfvio_two_view", "lfvio_vi_align", "lfvio_pnp", "lfvio_sfm_ba", "lfvio_sfm_construct",
     "lfvio_group_create", "lfvio_group_unique_id", "lfvio_group_create_rank", "lfvio_group_create_local", "lfvio_group_destroy",
     "lfvio_group_last_error", "lfvio_group_size", "lfvio_group_local", "lfvio_group_rank", "lfvio_group_ctx", "lfvio_group_backend",
     "lfvio_group_solve", "lfvio_group_upload", "lfvio_group_optimize", "lfvio_group_download", "lfvio_group_range",
@@ -587,6 +622,8 @@ def load_hip_library(path=None):
         lib.lfvio_pnp.argtypes = [C.c_void_p, C.POINTER(PnpInC), C.POINTER(PnpOutC)]
     if hasattr(lib, "lfvio_sfm_ba"):
         lib.lfvio_sfm_ba.argtypes = [C.c_void_p, C.POINTER(SfmBaInC), _dp, _dp, _dp, C.POINTER(SfmBaOutC)]
+    if hasattr(lib, "lfvio_sfm_construct"):
+        lib.lfvio_sfm_construct.argtypes = [C.c_void_p, C.POINTER(SfmConstructInC), _dp, _dp, _dp, C.POINTER(C.c_int), C.POINTER(SfmConstructOutC)]
     lib.lfvio_shard_marg_linearize.argtypes = [C.c_void_p, C.c_int]
     lib.lfvio_shard_marg_finish.argtypes = [C.c_void_p, C.c_int, C.POINTER(Prior)]
     # multi-GPU groups (RCCL inside the library)

@@ -352,6 +352,36 @@ class Engine:
         res.update(rc=rc, c_rotation=q, c_translation=t, position=X)
         return res
 
+    def sfm_construct(self, num_frames, ref_frame, obs_offset, obs_frame, obs_bearing, relative_R, relative_T, c_rotation=None, c_translation=None,
+                      position=None, tri_op=None, out=None, check=True):
+        """lfvio_sfm_construct: the incremental part of GlobalSFM::construct — a CSR over ALL points' observations (obs_offset [P + 1],
+        obs_frame [M], obs_bearing [M, 3]) and the relative pose of frames l and F - 1 (relative_R [3, 3], relative_T [3]).  Returns a dict
+        with the fields of LfvioSfmConstructOut (pnp a list of F dicts as Engine.pnp returns them) plus c_rotation [F, 4] (w x y z),
+        c_translation [F, 3], position [P, 3], tri_op [P] and rc.  The four arrays, and out (an abi.SfmConstructOutC), may be passed in to
+        be written (a test of what a failed call or a chain that stops leaves alone passes its own; they are used as they are and must be
+        C-contiguous float64 / int32); check=False returns the error code under `rc` instead of raising."""
+        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32).reshape(-1)
+        off, frm = i32(obs_offset), i32(obs_frame)
+        us = np.ascontiguousarray(obs_bearing, dtype=np.float64).reshape(-1, 3)
+        F, P = int(num_frames), len(off) - 1
+        q = np.zeros((max(F, 1), 4)) if c_rotation is None else c_rotation
+        t = np.zeros((max(F, 1), 3)) if c_translation is None else c_translation
+        X = np.zeros((max(P, 1), 3)) if position is None else position
+        ops = np.full(max(P, 1), -1, dtype=np.int32) if tri_op is None else tri_op
+        cin = abi.SfmConstructInC()
+        cin.num_frames, cin.ref_frame, cin.num_points = F, int(ref_frame), P
+        ip = C.POINTER(C.c_int)
+        cin.obs_offset, cin.obs_frame, cin.obs_bearing = off.ctypes.data_as(ip), frm.ctypes.data_as(ip), _p(us)
+        cin.relative_R = (C.c_double * 9)(*[float(v) for v in np.asarray(relative_R, dtype=np.float64).reshape(-1)])
+        cin.relative_T = (C.c_double * 3)(*[float(v) for v in np.asarray(relative_T, dtype=np.float64).reshape(-1)])
+        out = abi.SfmConstructOutC() if out is None else out
+        rc = self.lib.lfvio_sfm_construct(self.ctx, C.byref(cin), _p(q), _p(t), _p(X), ops.ctypes.data_as(ip), C.byref(out))
+        if check:
+            self._check(rc, "lfvio_sfm_construct")
+        res = out.as_dict(min(max(F, 0), abi.NUM_FRAMES))
+        res.update(rc=rc, c_rotation=q[:max(F, 0)], c_translation=t[:max(F, 0)], position=X[:max(P, 0)], tri_op=ops[:max(P, 0)])
+        return res
+
     def time_kernel(self, which, count, reps):
         ms = np.zeros(1)
         self._check(self.lib.lfvio_debug_time_kernel(self.ctx, which, count, reps, _p(ms)), "time_kernel")

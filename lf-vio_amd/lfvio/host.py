@@ -367,6 +367,53 @@ class HostEstimator:
         self.L.lfvio_host_set_sfm_structure.restype = None
         self.L.lfvio_host_set_sfm_structure(self.h, len(st), _p(st), _p(Q), _p(T), len(ids), ids.ctypes.data_as(ip), _p(xyz))
 
+    def set_relative_pose(self, l, R, T):
+        """What relativePose() returns, for the next full-window image: l, relative_R [3, 3], relative_T [3].  The estimator runs
+        GlobalSFM::construct() on the device (lfvio_sfm_construct, lfvio_sfm_ba), then the PnP loop and the alignment."""
+        R, T = _f(R).reshape(9), _f(T).reshape(3)
+        self.L.lfvio_host_set_relative_pose.argtypes = [C.c_void_p, C.c_int, _dp, _dp]
+        self.L.lfvio_host_set_relative_pose.restype = None
+        self.L.lfvio_host_set_relative_pose(self.h, int(l), _p(R), _p(T))
+
+    def sfm_structure(self, cap_kf=16, cap_pts=4096):
+        """The SfM structure the estimator holds (what constructSfm() filled, or what was set): dict(stamps, Q [K, 4], T [K, 3], ids, xyz)."""
+        cnt, ids = np.zeros(2, dtype=np.int32), np.zeros(cap_pts, dtype=np.int32)
+        st, Q, T, xyz = np.zeros(cap_kf), np.zeros((cap_kf, 4)), np.zeros((cap_kf, 3)), np.zeros((cap_pts, 3))
+        ip = C.POINTER(C.c_int)
+        self.L.lfvio_host_get_sfm_structure.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, _dp, _dp, _dp, ip, _dp]
+        self.L.lfvio_host_get_sfm_structure.restype = None
+        self.L.lfvio_host_get_sfm_structure(self.h, cap_kf, cap_pts, cnt.ctypes.data_as(ip), _p(st), _p(Q), _p(T), ids.ctypes.data_as(ip), _p(xyz))
+        K, P = min(int(cnt[0]), cap_kf), min(int(cnt[1]), cap_pts)
+        return dict(stamps=st[:K].copy(), Q=Q[:K].copy(), T=T[:K].copy(), ids=ids[:P].copy(), xyz=xyz[:P].copy())
+
+    def last_construct(self, cap_points=4096, cap_obs=4096 * 11):
+        """What the last attempt passed to lfvio_sfm_construct / lfvio_sfm_ba and got back: dict(F, l, ids, offset, frame, bearing,
+        relative_R, relative_T, c_rotation, c_translation, position, tri_op (as lfvio_sfm_construct left them), out (the fields of
+        LfvioSfmConstructOut), ba (those of LfvioSfmBaOut), called, rc, ba_called, ba_rc, calls)."""
+        info = np.zeros(8, dtype=np.int32)
+        ids, off, frm, ops = (np.zeros(n, dtype=np.int32) for n in (cap_points, cap_points + 1, cap_obs, cap_points))
+        us, rel, q, t, X = np.zeros((cap_obs, 3)), np.zeros(12), np.zeros((abi.NUM_FRAMES, 4)), np.zeros((abi.NUM_FRAMES, 3)), np.zeros((cap_points, 3))
+        out, ba = abi.SfmConstructOutC(), abi.SfmBaOutC()
+        ip = C.POINTER(C.c_int)
+        i_ = lambda a: a.ctypes.data_as(ip)
+        self.L.lfvio_host_last_construct.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, ip, ip, ip, _dp, _dp, _dp, _dp, _dp, ip,
+                                                     C.POINTER(abi.SfmConstructOutC), C.POINTER(abi.SfmBaOutC)]
+        self.L.lfvio_host_last_construct.restype = C.c_longlong
+        calls = self.L.lfvio_host_last_construct(self.h, cap_points, cap_obs, i_(info), i_(ids), i_(off), i_(frm), _p(us), _p(rel), _p(q), _p(t), _p(X), i_(ops),
+                                                 C.byref(out), C.byref(ba))
+        F, l, P, M = (int(v) for v in info[:4])
+        return dict(F=F, l=l, ids=ids[:P].copy(), offset=off[:P + 1].copy(), frame=frm[:M].copy(), bearing=us[:M].copy(), relative_R=rel[:9].reshape(3, 3).copy(),
+                    relative_T=rel[9:].copy(), c_rotation=q[:F].copy(), c_translation=t[:F].copy(), position=X[:P].copy(), tri_op=ops[:P].copy(),
+                    out=out.as_dict(min(F, abi.NUM_FRAMES)) if info[4] else None, ba=ba.as_dict(min(F, abi.NUM_FRAMES)) if info[6] else None,
+                    called=bool(info[4]), rc=int(info[5]), ba_called=bool(info[6]), ba_rc=int(info[7]), calls=int(calls))
+
+    def construct_counts(self):
+        """(attempts that reached lfvio_sfm_construct, attempts that filled the SfM structure)."""
+        o = np.zeros(2, dtype=np.int64)
+        self.L.lfvio_host_construct_counts.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
+        self.L.lfvio_host_construct_counts(self.h, o.ctypes.data_as(C.POINTER(C.c_longlong)))
+        return int(o[0]), int(o[1])
+
     def sfm(self, cap=1024):
         """The SfM result the estimator holds (after the PnP loop: every frame of all_image_frame): (stamps, R [n, 3, 3], T [n, 3])."""
         st, R, T = np.zeros(cap), np.zeros((cap, 9)), np.zeros((cap, 3))

@@ -10,7 +10,7 @@ import numpy as np
 from . import abi, synth
 
 MAGIC = b"LFVT"
-REC_IMU, REC_FEATURES, REC_BOOTSTRAP, REC_TRUTH, REC_RESTART, REC_RELO, REC_SFM, REC_STRUCTURE = 1, 2, 3, 4, 5, 6, 7, 8
+REC_IMU, REC_FEATURES, REC_BOOTSTRAP, REC_TRUTH, REC_RESTART, REC_RELO, REC_SFM, REC_STRUCTURE, REC_RELATIVE = 1, 2, 3, 4, 5, 6, 7, 8, 9
 
 
 class TraceWriter:
@@ -76,6 +76,11 @@ class TraceWriter:
         pt = np.concatenate([ids[:, None], xyz], axis=1).astype("<f8")
         self._rec(REC_STRUCTURE, struct.pack("<dII", stamp, len(stamps), len(ids)) + kf.tobytes() + pt.tobytes())
 
+    def relative_pose(self, stamp, l, R, T):
+        """A relative pose (type 9): stamp of the image it belongs to (Headers[WINDOW_SIZE]), then what relativePose() returns: l,
+        relative_R [3, 3] and relative_T [3] (the rotation and unit-norm position of the newest camera in the frame of camera l)."""
+        self._rec(REC_RELATIVE, struct.pack("<di", stamp, int(l)) + np.concatenate([np.ravel(R), np.ravel(T)]).astype("<f8").tobytes())
+
     def truth(self, t, p, q_xyzw):
         self._rec(REC_TRUTH, struct.pack("<8d", t, *p, *q_xyzw))
 
@@ -85,7 +90,7 @@ class TraceWriter:
 
 def read_trace(path):
     """-> dict(imu [n,7], images [(t, array[n,9] float32)], bootstrap array or None, truth [n,8])"""
-    out = dict(imu=[], images=[], bootstrap=None, bootstraps=[], restarts=[], truth=[], relos=[], sfms=[], structures=[], order=[])
+    out = dict(imu=[], images=[], bootstrap=None, bootstraps=[], restarts=[], truth=[], relos=[], sfms=[], structures=[], relatives=[], order=[])
     with open(path, "rb") as f:
         head = f.read(8)
         assert head[:4] == MAGIC and struct.unpack("<I", head[4:])[0] == 1
@@ -122,6 +127,10 @@ def read_trace(path):
                 pt = np.frombuffer(p[16 + 64 * K:], dtype="<f8").reshape(P, 4)
                 out["structures"].append(dict(at_image=len(out["images"]), stamp=stamp, stamps=kf[:, 0].copy(), Q=kf[:, 1:5].copy(), T=kf[:, 5:8].copy(),
                                               ids=pt[:, 0].astype(np.int64), xyz=pt[:, 1:4].copy()))
+            elif kind == REC_RELATIVE:
+                stamp, l = struct.unpack("<di", p[:12])
+                d = np.frombuffer(p[12:], dtype="<f8")
+                out["relatives"].append(dict(at_image=len(out["images"]), stamp=stamp, l=l, R=d[:9].reshape(3, 3).copy(), T=d[9:12].copy()))
             elif kind == REC_TRUTH:
                 out["truth"].append(struct.unpack("<8d", p))
     out["imu"] = np.array(out["imu"]).reshape(-1, 7)
@@ -351,6 +360,17 @@ def structure_from_truth(stamps, Ps, Rs, ids, Xw, keyframe=0, scale=1.0, rot_noi
     if point_noise > 0:
         xyz = xyz * (1.0 + point_noise * rng.standard_normal(xyz.shape))
     return np.asarray(stamps, float), Q, T, np.asarray(ids, np.int64), xyz
+
+
+def relative_pose_from_truth(Ps, Rs, l, tic=None, ric=None):
+    """What relativePose() is meant to return, made from true body poses Ps [K, 3], Rs [K, 3, 3] of the window's keyframes: the rotation
+    of the newest camera in the frame of camera l and its position there scaled to unit norm.  -> (relative_R [3, 3], relative_T [3])."""
+    tic = synth.TIC if tic is None else np.asarray(tic, float)
+    ric = synth.RIC if ric is None else np.asarray(ric, float)
+    Ps, Rs = np.asarray(Ps, float).reshape(-1, 3), np.asarray(Rs, float).reshape(-1, 3, 3)
+    R_wcl, p_cl = Rs[l] @ ric, Ps[l] + Rs[l] @ tic
+    T = R_wcl.T @ (Ps[-1] + Rs[-1] @ tic - p_cl)
+    return R_wcl.T @ Rs[-1] @ ric, T / np.linalg.norm(T)
 
 
 def bootstraps_to_structure(src, dst, made, keyframe=0, scale=1.0, rot_noise_deg=0.0, pos_noise=0.0, point_noise=0.0, seed=0, repeat=2,
