@@ -47,6 +47,7 @@ constexpr ncclDataType_t ncclDouble = 8;
 #include "kernels_pnp.h"
 #include "kernels_sfmba.h"
 #include "kernels_sfmchain.h"
+#include "window_pack.h"
 
 #define HIPCHK(ctx, call)                                                                      \
   do {                                                                                         \
@@ -93,14 +94,15 @@ struct SlotHostInfo {
   } marg_out[2];
   int mail_seq = 0;  // Slot::mail_seq of the resident window: what its mailbox flags are set to
   // k_sum's gather lists on the device are a function of the chunks per frame pair alone: kept from one upload of the slot
-  // to the next while that table stays the same (consecutive windows of one estimator: nearly always)
+  // to the next while that table stays the same (consecutive windows of one estimator: nearly always).  WindowPacker::gather_lists
+  // (window_pack.h) compares and replaces the key; upload_window sets list_items once the lists' copy is enqueued
   std::vector<int> list_key;  // pair_chunk0[0 .. NPAIR], pre_gram
   int list_items = -1;
 };
 
 struct Grid {
   int lm, ch, sc, lw;
-  int ch_raw;  // largest chunk count of a slot before the rounding of `ch` (what decides the two-level sums: upload_window's pre_gram)
+  int ch_raw;  // largest chunk count of a slot before the rounding of `ch` (what decides the two-level sums: Slot::pre_gram, window_pack.h)
 };
 
 // k_setup's launch: grid.x and the bits of its last argument.  A resident batch is bound by the number of workgroups the launch
@@ -148,7 +150,7 @@ struct lfvio_ctx {
   char *h_down = nullptr;   // pinned download buffer
   size_t h_down_bytes = 0;
   std::vector<SlotHostInfo> info;
-  std::vector<int> perm_build;  // upload_window builds the next permutation here and swaps it in at its commit point
+  std::vector<int> perm_build;  // pack_window (window_pack.h) builds the next permutation here; commit_slot_info swaps it in
   // cached graph of the solve loop
   hipGraphExec_t graph = nullptr;
   GraphKey graph_key;
@@ -367,88 +369,7 @@ int reserve(lfvio_ctx *c, int batch, int maxN, int maxM) {
   return LFVIO_OK;
 }
 
-inline int local_size(int kind) {
-  return (kind == LFVIO_BLOCK_POSE || kind == LFVIO_BLOCK_EX_POSE) ? 6 : (kind == LFVIO_BLOCK_SPEEDBIAS ? 9 : 1);
-}
-inline int tangent_off(int kind, int frame) {
-  return kind == LFVIO_BLOCK_POSE ? off_pose(frame)
-         : kind == LFVIO_BLOCK_SPEEDBIAS ? off_sb(frame)
-         : kind == LFVIO_BLOCK_EX_POSE ? off_ex()
-                                       : off_td();
-}
-
-// Structure of MarginalizationInfo for this window (estimator.cpp:833-1005): which blocks
-// take part, which are dropped, canonical column order (dropped first, then poses / speed-bias
-// by frame, ex pose, td) and the addr_shift of the kept blocks.
-// N0 / nChunks0: what THIS slot sweeps; any0 / kmax0: whether the WINDOW has landmarks anchored at frame 0 and their longest track —
-// the same thing unless the slot holds a rank's share of a landmark-sharded window, whose block structure is the whole window's
-void plan_marg(const LfvioWindow *w, const LfvioPrior *pr, int flag, int N0, bool any0, int kmax0, int nChunks0, bool imu0_ok, MargPlan *mp) {
-  std::memset(mp, 0, sizeof *mp);
-  for (int c = 0; c < KP; c++) mp->col[c] = -1;
-  bool present[4][LFVIO_NUM_FRAMES] = {}, dropped[4][LFVIO_NUM_FRAMES] = {};
-  auto touch = [&](int kind, int frame, bool drop) {
-    present[kind][frame] = true;
-    if (drop) dropped[kind][frame] = true;
-  };
-  if (flag == LFVIO_MARGIN_OLD) {
-    if (pr)
-      for (int i = 0; i < pr->num_blocks; i++) {
-        const int k = pr->blocks[i].kind, f = pr->blocks[i].frame;
-        touch(k, f, (k == LFVIO_BLOCK_POSE || k == LFVIO_BLOCK_SPEEDBIAS) && f == 0);
-      }
-    mp->use_imu0 = (w->imu[0].sum_dt < 10.0) && imu0_ok;
-    if (w->imu[0].sum_dt < 10.0) {
-      touch(LFVIO_BLOCK_POSE, 0, true), touch(LFVIO_BLOCK_SPEEDBIAS, 0, true);
-      touch(LFVIO_BLOCK_POSE, 1, false), touch(LFVIO_BLOCK_SPEEDBIAS, 1, false);
-    }
-    if (any0) {
-      touch(LFVIO_BLOCK_POSE, 0, true);
-      for (int j = 1; j < kmax0; j++) touch(LFVIO_BLOCK_POSE, j, false);
-      touch(LFVIO_BLOCK_EX_POSE, 0, false);
-      if (w->estimate_td) touch(LFVIO_BLOCK_TD, 0, false);
-    }
-    mp->N0 = N0;
-    mp->nChunks0 = nChunks0;
-    mp->use_visual = N0 > 0;
-    mp->valid = 1;
-  } else {
-    bool touches = false;
-    if (pr)
-      for (int i = 0; i < pr->num_blocks; i++)
-        if (pr->blocks[i].kind == LFVIO_BLOCK_POSE && pr->blocks[i].frame == LFVIO_WINDOW_SIZE - 1) touches = true;
-    if (!touches) return;  // valid = 0
-    for (int i = 0; i < pr->num_blocks; i++) {
-      const int k = pr->blocks[i].kind, f = pr->blocks[i].frame;
-      touch(k, f, k == LFVIO_BLOCK_POSE && f == LFVIO_WINDOW_SIZE - 1);
-    }
-    mp->valid = 1;
-  }
-  int pos = 0;
-  for (int k = 0; k < 4; k++)
-    for (int f = 0; f < LFVIO_NUM_FRAMES; f++)
-      if (present[k][f] && dropped[k][f]) {
-        const int o = tangent_off(k, f);
-        for (int e = 0; e < local_size(k); e++) mp->col[o + e] = pos++;
-      }
-  mp->m15 = pos;
-  int nb = 0;
-  for (int k = 0; k < 4; k++)
-    for (int f = 0; f < LFVIO_NUM_FRAMES; f++)
-      if (present[k][f] && !dropped[k][f]) {
-        const int o = tangent_off(k, f);
-        mp->kind[nb] = k, mp->frame[nb] = f, mp->idx[nb] = pos - mp->m15;
-        int sf = f;
-        if (k == LFVIO_BLOCK_POSE || k == LFVIO_BLOCK_SPEEDBIAS) {
-          if (flag == LFVIO_MARGIN_OLD) sf = f - 1;
-          else if (f == LFVIO_WINDOW_SIZE) sf = LFVIO_WINDOW_SIZE - 1;
-        }
-        mp->shifted_frame[nb] = sf;
-        nb++;
-        for (int e = 0; e < local_size(k); e++) mp->col[o + e] = pos++;
-      }
-  mp->nb = nb;
-  mp->n = pos - mp->m15;
-}
+// (local_size, tangent_off, plan_marg: window_pack.h)
 
 // a prior carries n x n of its 172 x 172 Jacobian slots: copy what is there (46 KB instead of 240 KB for n = 76)
 void copy_prior(LfvioPrior *dst, const LfvioPrior *src) {
@@ -521,7 +442,7 @@ int check_window(lfvio_ctx *c, const LfvioWindow *w) {
   return LFVIO_OK;
 }
 
-// Pack one window into the pinned staging blob and upload it to slot `slot`.
+// What an upload is asked for beyond the window and its slot.
 // chain (lfvio_batch_upload_chained): the window's prior is *chain, and if a call is still in flight on the context (the
 // marginalization behind an early state), it is THAT call's prior: the landmark tables and gather lists of the new window —
 // nine tenths of the host work of an upload — are packed while the device finishes it, then the prior is taken from the
@@ -529,380 +450,63 @@ int check_window(lfvio_ctx *c, const LfvioWindow *w) {
 // device_chain (lfvio_batch_upload_chained_device): the prior of the call in flight STAYS on the device — nothing is waited for or
 // collected; the new window's prior has the structure the host planned for that marginalization (SlotHostInfo::marg_out) and the
 // values k_prior_chain copies out of Slot::prior_out behind these copies, which the stream puts behind the marginalization.
-int upload_window(lfvio_ctx *c, int slot, const LfvioWindow *w, int sharded = 0, int pose_side = 1, LfvioPrior *chain = nullptr, bool device_chain = false) {
-  if (device_chain) {
-    if (slot != 0 || sharded || !c->call.can_chain_on_device() || !c->info[0].resident) {
-      c->err = "lfvio_batch_upload_chained_device: no call in flight on slot 0 (lfvio_batch_optimize_begin) whose prior could be taken over";
-      return LFVIO_ERR_ARG;
-    }
-    const SlotHostInfo::MargOut &mo = c->info[0].marg_out[c->call.marg_flag];
-    if (!mo.valid) {
-      c->err = "lfvio_batch_upload_chained_device: the marginalization in flight passes its input prior through (MARGIN_SECOND_NEW without a "
-               "prior on the newest pose) — use lfvio_batch_upload_chained";
-      return LFVIO_ERR_ARG;
-    }
-    if (!c->chain_struct) c->chain_struct.reset(new LfvioPrior);
-    LfvioPrior *sp = c->chain_struct.get();
-    std::memset(sp, 0, offsetof(LfvioPrior, linearized_jacobians));
-    sp->valid = 1, sp->n = mo.n, sp->m = mo.m, sp->num_blocks = mo.nb;
-    if (c->debug_break_chain) sp->n = mo.n + 1, c->debug_break_chain = false;  // (k_prior_chain finds a prior of mo.n rows: the failure path, end to end)
-    for (int i = 0; i < mo.nb; i++) sp->blocks[i].kind = mo.kind[i], sp->blocks[i].frame = mo.frame[i], sp->block_idx[i] = mo.idx[i];
-    chain = sp;
+struct UploadMode {
+  int sharded = 0;    // Slot::sharded: the slot holds a rank's share of the window (lfvio_shard_begin; 2: driven by an lfvio_group)
+  int pose_side = 1;  // Slot::pose_side
+  LfvioPrior *chain = nullptr;
+  bool device_chain = false;
+};
+
+// The structure-only prior of a device-chained upload (lfvio_ctx::chain_struct), from what the host planned for the marginalization in flight
+int device_chain_prior(lfvio_ctx *c, int slot, const UploadMode &mode) {
+  if (slot != 0 || mode.sharded || !c->call.can_chain_on_device() || !c->info[0].resident) {
+    c->err = "lfvio_batch_upload_chained_device: no call in flight on slot 0 (lfvio_batch_optimize_begin) whose prior could be taken over";
+    return LFVIO_ERR_ARG;
   }
-  const bool chained = !device_chain && chain && c->call.pending() && slot == 0;
-  const auto t_up0 = std::chrono::steady_clock::now();
-  auto lap = [&](int k, std::chrono::steady_clock::time_point from) {
-    const auto now = std::chrono::steady_clock::now();
-    c->up_us[k] = std::chrono::duration<double>(now - from).count() * 1e6;
-    return now;
-  };
-  if (!chained && !device_chain)
-    if (int rc = join_inflight(c)) return rc;
-  if (int rc = check_window(c, w)) return rc;
-  const int N = w->num_landmarks, M = w->num_observations;
-  const LfvioPrior *given = chain ? chain : w->prior;
-  const LfvioPrior *pr = (given && given->valid) ? given : nullptr;  // (chained: not known before the prior section below)
-  if (!chained)
-    if (int rc = check_input_prior(c, pr)) return rc;
-  const Layout &L = c->L;
-  char *h = c->h_stage;
-  char *d = c->d_base + (size_t)slot * L.total;
-  Slot *S = (Slot *)h;
-  if (c->stage_busy) {  // the previous upload's copies out of the staging block (long done, unless uploads come back to back)
-    c->stage_busy = false;
-    HIPCHK(c, hipEventSynchronize(c->stage_event));
+  const SlotHostInfo::MargOut &mo = c->info[0].marg_out[c->call.marg_flag];
+  if (!mo.valid) {
+    c->err = "lfvio_batch_upload_chained_device: the marginalization in flight passes its input prior through (MARGIN_SECOND_NEW without a "
+             "prior on the newest pose) — use lfvio_batch_upload_chained";
+    return LFVIO_ERR_ARG;
   }
-  std::memset(S, 0, offsetof(Slot, x));
-  S->N = N, S->M = M, S->NV = M - N;
-  S->est_ex = w->estimate_extrinsic != 0, S->est_td = w->estimate_td != 0;
-  S->max_iter = w->max_num_iterations;
-  S->sharded = sharded, S->pose_side = pose_side;
-  S->mail = (slot == 0 && !sharded && c->d_mail && w->num_landmarks <= MAIL_MAX_LM) ? (long long)(uintptr_t)c->d_mail : 0;
-  // (the loop's side of kernels_spec.h costs a store per pass and a compare-and-swap at its end; whether workers are started is
-  // decided per call, enqueue_solve)
-  S->spec_on = (slot == 0 && c->shadow && c->marg_ahead && !sharded && S->mail && N <= SPEC_MAX_LM) ? 1 : 0;
-  const int seq = c->mail_seq == 0x7fffffff ? 1 : c->mail_seq + 1;  // (never 0: the host clears the flags to 0)
-  S->mail_seq = seq;
-  for (int k = 0; k < 3; k++) S->g[k] = w->g[k];
-  S->tr_over_row = w->row > 0.0 ? w->tr / w->row : 0.0;  // only the td factor reads it (row > 0 checked above)
-  S->half_row = w->row / 2;
-  S->sqrt_info = w->sqrt_info;
-  S->fn_tol = c->fn_tol;
-  S->init_radius = c->init_radius;
-  std::memcpy(S->x0.pose, w->para_pose, sizeof S->x0.pose);
-  std::memcpy(S->x0.sb, w->para_speed_bias, sizeof S->x0.sb);
-  std::memcpy(S->x0.ex, w->para_ex_pose, sizeof S->x0.ex);
-  S->x0.td = w->para_td;
-  for (int i = 0; i < LFVIO_WINDOW_SIZE; i++) {
-    S->imu[i] = w->imu[i];
-    S->imu_active[i] = !(w->imu[i].sum_dt > 10.0);  // estimator.cpp:720
-  }
-  // ---- landmarks: stable bucket sort by (start_frame, track length)
-  // What the host keeps about the slot (sizes, permutation, grid) is built beside it and committed where the copies are
-  // enqueued: an upload refused on the way — or a chained one, which collects the prior of the window still resident in
-  // between — leaves the slot's description matching what the device holds.
+  if (!c->chain_struct) c->chain_struct.reset(new LfvioPrior);
+  LfvioPrior *sp = c->chain_struct.get();
+  std::memset(sp, 0, offsetof(LfvioPrior, linearized_jacobians));
+  sp->valid = 1, sp->n = mo.n, sp->m = mo.m, sp->num_blocks = mo.nb;
+  if (c->debug_break_chain) sp->n = mo.n + 1, c->debug_break_chain = false;  // (k_prior_chain finds a prior of mo.n rows: the failure path, end to end)
+  for (int i = 0; i < mo.nb; i++) sp->blocks[i].kind = mo.kind[i], sp->blocks[i].frame = mo.frame[i], sp->block_idx[i] = mo.idx[i];
+  return LFVIO_OK;
+}
+
+// What pack_window (window_pack.h) takes from the context
+PackOptions pack_options(const lfvio_ctx *c, int slot, const LfvioWindow *w, const UploadMode &mode) {
+  const int N = w->num_landmarks;
+  PackOptions o;
+  o.slot = slot, o.sharded = mode.sharded, o.pose_side = mode.pose_side;
+  o.mail = (long long)(uintptr_t)c->d_mail;
+  o.shadow = c->shadow, o.marg_ahead = c->marg_ahead;
+  o.lm_half = c->lm_half;
+  o.want_linw = c->linw_mode != 0 && !mode.sharded && N <= SPEC_MAX_LM && (c->batch >= LIN_SPLIT_MIN_BATCH || c->linw_mode == 2);
+  // a large single window: the same strips as groups of one start frame, one workgroup each (k_linb)
+  o.want_linb = c->linw_mode != 0 && !o.want_linw && N >= (c->linw_mode == 2 ? SPEC_MAX_LM + 1 : LINB_MIN_LM);  // (a rank's share of a sharded window too)
+  o.linb_max_groups = LINB_MAX_GROUPS;
+  o.fn_tol = c->fn_tol, o.init_radius = c->init_radius;
+  o.seq = c->mail_seq == 0x7fffffff ? 1 : c->mail_seq + 1;  // (never 0: the host clears the flags to 0)
+  return o;
+}
+
+// Everything the host believes about the slot, from the staging block S and pack_window's result.  Written where the copies are
+// enqueued: an upload refused on the way — or a chained one, which collects the prior of the window still resident in between —
+// leaves the slot's description matching what the device holds.  From here on the device copy changes (resident = false until the
+// copies are enqueued).
+void commit_slot_info(lfvio_ctx *c, int slot, const LfvioWindow *w, const Slot *S, const LfvioPrior *pr, bool device_chain, const PackResult &r, int seq) {
   SlotHostInfo &info = c->info[slot];
-  std::vector<int> &perm = c->perm_build;
-  perm.resize(N);
-  {
-    int count[16 * 16 + 1] = {0};
-    for (int l = 0; l < N; l++) count[w->start_frame[l] * 16 + (w->obs_offset[l + 1] - w->obs_offset[l]) + 1]++;
-    for (int k = 0; k < 256; k++) count[k + 1] += count[k];
-    for (int l = 0; l < N; l++) perm[count[w->start_frame[l] * 16 + (w->obs_offset[l + 1] - w->obs_offset[l])]++] = l;
-  }
-  int *lm_start = (int *)(h + L.lm_start), *lm_cnt = (int *)(h + L.lm_cnt), *lm_obs0 = (int *)(h + L.lm_obs0);
-  int *lm_perm = (int *)(h + L.lm_perm), *lm_woff = (int *)(h + L.lm_woff);
-  double *lam0 = (double *)(h + L.lam0);
-  double *obs[8];
-  for (int k = 0; k < 8; k++) obs[k] = (double *)(h + L.obs[k]);
-  int o = 0, N0 = 0, kmax0 = 0;
-  int pair_count[NPAIR + 1] = {0};
-  for (int dl = 0; dl < N; dl++) {
-    const int l = perm[dl];
-    const int s = w->start_frame[l], k = w->obs_offset[l + 1] - w->obs_offset[l], o0 = w->obs_offset[l];
-    lm_start[dl] = s, lm_cnt[dl] = k, lm_obs0[dl] = o, lm_perm[dl] = l;
-    lm_woff[dl] = dl == 0 ? 0 : lm_woff[dl - 1] + w_row_len(lm_cnt[dl - 1]);
-    lam0[dl] = w->inv_depth[l];
-    if (s == 0) N0++, kmax0 = std::max(kmax0, k);
-    for (int q = 0; q < k; q++, o++) {
-      const int src = o0 + q;
-      obs[0][o] = w->obs_point[3 * src], obs[1][o] = w->obs_point[3 * src + 1], obs[2][o] = w->obs_point[3 * src + 2];
-      obs[3][o] = w->obs_velocity[3 * src], obs[4][o] = w->obs_velocity[3 * src + 1], obs[5][o] = w->obs_velocity[3 * src + 2];
-      obs[6][o] = w->obs_cur_td[src];
-      obs[7][o] = w->obs_uv_y[src];
-      if (q > 0) pair_count[s * 11 + s + q + 1]++;
-    }
-  }
-  // ---- pair-major list of the non-anchor observations + chunk table
-  for (int p = 0; p < NPAIR; p++) pair_count[p + 1] += pair_count[p];
-  int *pm_obs = (int *)(h + L.pm_obs), *pm_lm = (int *)(h + L.pm_lm);
-  {
-    int cursor[NPAIR];
-    for (int p = 0; p < NPAIR; p++) cursor[p] = pair_count[p];
-    for (int dl = 0; dl < N; dl++) {
-      const int s = lm_start[dl], k = lm_cnt[dl];
-      for (int q = 1; q < k; q++) {
-        const int p = s * 11 + s + q;
-        pm_obs[cursor[p]] = lm_obs0[dl] + q;
-        pm_lm[cursor[p]] = dl;
-        cursor[p]++;
-      }
-    }
-  }
-  int *chunk_pair = (int *)(h + L.chunk_pair), *chunk_begin = (int *)(h + L.chunk_begin), *chunk_end = (int *)(h + L.chunk_end);
-  int nChunks = 0;
-  for (int p = 0; p < NPAIR; p++) {
-    S->pair_chunk0[p] = nChunks;
-    for (int b = pair_count[p]; b < pair_count[p + 1]; b += CHUNK_MAX) {
-      if (nChunks >= L.capChunks) {
-        c->err = "chunk table overflow";
-        return LFVIO_ERR_ARG;
-      }
-      chunk_pair[nChunks] = p, chunk_begin[nChunks] = b, chunk_end[nChunks] = std::min(b + CHUNK_MAX, pair_count[p + 1]);
-      nChunks++;
-    }
-  }
-  S->pair_chunk0[NPAIR] = nChunks;
-  S->nChunks = nChunks;
-  lm_woff[N] = N == 0 ? 0 : lm_woff[N - 1] + w_row_len(lm_cnt[N - 1]);
-  S->nLmBlocks = (N + LM_BLOCK - 1) / LM_BLOCK;
-  // one part per landmark workgroup of k_lin, which forms it from its LDS tile: 64 landmarks, or 32 in the 8-lanes-per-track form
-  S->lm_half = (N <= SPEC_MAX_LM && c->lm_half) ? 1 : 0;
-  S->schur_lm = S->lm_half ? SCHUR_LM / 2 : SCHUR_LM;
-  S->nSchurParts = S->lm_half ? (N + SCHUR_LM / 2 - 1) / (SCHUR_LM / 2) : S->nLmBlocks;
-  // ---- k_linw (kernels_linw.h): strips of <= 64 landmarks of one start frame, dealt to the four waves of the window's
-  //      workgroup (all strips of a start frame on one wave: it is the one writer of that frame's pair blocks), and the
-  //      observations once more in the orders its lanes read them — anchors by landmark, the others pair-major.
-  bool linw = c->linw_mode != 0 && !sharded && N <= SPEC_MAX_LM && (c->batch >= LIN_SPLIT_MIN_BATCH || c->linw_mode == 2);
-  // a large single window: the same strips as groups of four of one start frame, one workgroup each (k_linb)
-  bool linb = c->linw_mode != 0 && !linw && N >= (c->linw_mode == 2 ? SPEC_MAX_LM + 1 : LINB_MIN_LM);  // (a rank's share of a sharded window too)
-  int linb_ng = 0;
-  if (linw || linb) {
-    LinwPlan &P = S->linw;
-    int begin_s[LFVIO_NUM_FRAMES + 1];
-    {
-      int dl = 0;
-      for (int s = 0; s <= LFVIO_NUM_FRAMES; s++) {
-        while (dl < N && lm_start[dl] < s) dl++;
-        begin_s[s] = dl;
-      }
-    }
-    struct Strip {
-      int lm0, nlm, start, kmax;
-    };
-    std::vector<Strip> by_start[LFVIO_NUM_FRAMES];
-    int cost[LFVIO_NUM_FRAMES] = {0}, n_strips = 0;
-    for (int s = 0; s < LFVIO_NUM_FRAMES; s++) {
-      {
-        int f = begin_s[s];  // (ascending track length inside a start frame)
-        for (int o2 = 0; o2 < 12; o2++) {
-          while (f < begin_s[s + 1] && lm_cnt[f] <= o2) f++;
-          P.firstl[s][o2] = f;
-        }
-      }
-      for (int l0 = begin_s[s]; l0 < begin_s[s + 1] && !linb; l0 += 64) {
-        const int n = std::min(64, begin_s[s + 1] - l0);
-        by_start[s].push_back(Strip{l0, n, s, lm_cnt[l0 + n - 1]});  // (ascending track length inside a start frame: the last one is the longest)
-        cost[s] += lm_cnt[l0 + n - 1] - 1;
-        n_strips++;
-      }
-    }
-    auto observation_copies = [&] {
-      for (int p = 0; p <= NPAIR; p++) P.pair_obs0[p] = pair_count[p];
-      double *anc[8], *pmo[8];
-      for (int k = 0; k < 8; k++) anc[k] = (double *)(h + L.anc[k]), pmo[k] = (double *)(h + L.pmo[k]);
-      for (int dl = 0; dl < N; dl++)
-        for (int k = 0; k < 8; k++) anc[k][dl] = obs[k][lm_obs0[dl]];
-      for (int q = 0; q < M - N; q++)
-        for (int k = 0; k < 8; k++) pmo[k][q] = obs[k][pm_obs[q]];
-      unsigned char *pm_pair = (unsigned char *)(h + L.pm_pair);
-      for (int p = 0; p < NPAIR; p++)
-        for (int q = pair_count[p]; q < pair_count[p + 1]; q++) pm_pair[q] = (unsigned char)p;
-    };
-    if (linb) {
-      // the groups of k_linb: consecutive strips of one start frame sized by a cost model, the most expensive first (linb_plan.h)
-      const std::vector<LinbGroup> groups = linb_plan_groups(begin_s, LFVIO_NUM_FRAMES, lm_cnt, LM_BLOCK, LINB_MAX_GROUPS);
-      int *g_lm0 = (int *)(h + L.linb_lm0), *g_ns = (int *)(h + L.linb_ns);
-      linb_ng = (int)groups.size();
-      if (linb_ng > L.capSchurParts) linb = false, linb_ng = 0;  // (the partials live in the Schur partials' space)
-      else {
-        for (int g2 = 0; g2 < linb_ng; g2++) g_lm0[g2] = groups[g2].lm0, g_ns[g2] = groups[g2].n | (groups[g2].s << 16);
-        P.big = 1, P.ng = linb_ng, P.wt_ld = L.capLmBlocks * LM_BLOCK;
-        for (int p = 0; p <= NPAIR; p++) P.pair_obs0[p] = pair_count[p];  // (the observations' copies are made on the device: k_linb_gather)
-      }
-    } else if (n_strips > LINW_MAX_STRIPS) linw = false;
-    else {
-      // longest-processing-time first over the start frames
-      int order[LFVIO_NUM_FRAMES], load[LINW_WAVES] = {0};
-      for (int s = 0; s < LFVIO_NUM_FRAMES; s++) order[s] = s;
-      std::stable_sort(order, order + LFVIO_NUM_FRAMES, [&](int a, int b) { return cost[a] > cost[b]; });
-      std::vector<Strip> per_wave[LINW_WAVES];
-      for (int k = 0; k < LFVIO_NUM_FRAMES; k++) {
-        const int s = order[k];
-        if (by_start[s].empty()) continue;
-        int w = 0;
-        for (int q = 1; q < LINW_WAVES; q++)
-          if (load[q] < load[w]) w = q;
-        load[w] += cost[s];
-        per_wave[w].insert(per_wave[w].end(), by_start[s].begin(), by_start[s].end());
-      }
-      int t = 0;
-      for (int w = 0; w < LINW_WAVES; w++) {
-        P.wave_first[w] = t;
-        for (const Strip &st : per_wave[w]) P.lm0[t] = (short)st.lm0, P.nlm[t] = (short)st.nlm, P.start[t] = (short)st.start, P.kmax[t] = (short)st.kmax, t++;
-      }
-      P.wave_first[LINW_WAVES] = t;
-      P.n_strips = t;
-      observation_copies();
-    }
-    P.ok = (linw || linb) ? 1 : 0;
-  }
-  int used_items = 0;
-  bool lists_cached = false;
-  // ---- gather lists of k_sum: which Gram entries (chunk or, for large windows, frame pair; local index of the
-  //      20 x 20 block [Pi th_i Pj th_j tic th_ic td | r]) add up to each packed H_pp / g_p entry.  Units ascend, so the
-  //      marginalization's subset (pairs (0, j)) is a prefix of every list.
-  {
-    S->pre_gram = nChunks > PRE_CHUNK_LIMIT ? 1 : 0;
-    auto col = [](int l, int i, int j) { return l < 6 ? 6 * i + l : l < 12 ? 6 * j + (l - 6) : l < 18 ? 66 + (l - 12) : 72; };
-    const int units = S->pre_gram ? NPAIR : nChunks;
-    int *sum_off = (int *)(h + L.sum_off), *sum_end_marg = (int *)(h + L.sum_end_marg), *sum_items = (int *)(h + L.sum_items);
-    const int marg_units = S->pre_gram ? 11 : S->pair_chunk0[11];  // pairs (0, j) / their chunks
-    // Which (frame pair, local entry) pairs feed an H_pp / g_p entry is the same for every window: a table built once.
-    // Only the visual entries have a list (rows < KC: the packed prefix [0, KC (KC + 1) / 2) and g_p[0, KC)); k_sum reads
-    // the bounds of the others but never uses them.  Per upload the lists are ONE pass over those 2 774 entries — the
-    // pairs of the entry in ascending order, each with its chunks in ascending order, so units ascend as before.
-    struct PairLocal {
-      short pair, local;
-    };
-    struct EntryTable {
-      std::vector<int> first;       // [VIS + 1] into items
-      std::vector<PairLocal> items;
-    };
-    constexpr int VIS_PACKED = SUM_VIS_PACKED, VIS = SUM_VIS;  // visual entries: packed prefix, then g_p
-    static_assert(SUM_VIS_PACKED == KC * (KC + 1) / 2 && SUM_VIS == SUM_VIS_PACKED + KC, "compact gather index");
-    static const EntryTable table = [&] {
-      EntryTable t;
-      std::vector<std::vector<PairLocal>> per(VIS);
-      for (int pp = 0; pp < NPAIR; pp++) {
-        const int i = pp / 11, j = pp % 11;
-        if (i >= j) continue;
-        for (int lp = 0; lp < 19; lp++) {
-          const int cp = col(lp, i, j);
-          for (int lq = lp; lq < 20; lq++) {
-            const int e = lq == 19 ? VIS_PACKED + cp : col(lq, i, j) * (col(lq, i, j) + 1) / 2 + cp;
-            per[e].push_back(PairLocal{(short)pp, (short)(lp * 20 - (lp * (lp - 1)) / 2 + (lq - lp))});
-          }
-        }
-      }
-      t.first.assign(VIS + 1, 0);
-      for (int e = 0; e < VIS; e++) {
-        t.first[e + 1] = t.first[e] + (int)per[e].size();
-        t.items.insert(t.items.end(), per[e].begin(), per[e].end());
-      }
-      return t;
-    }();
-    int n_items = 0;
-    bool overflow = false;
-    {
-      // the lists depend on nothing but this table: the ones the device holds from the last upload of the slot still stand
-      // if it has not changed (the pass below over ~11 500 items is the largest single part of an upload)
-      std::vector<int> key(S->pair_chunk0, S->pair_chunk0 + NPAIR + 1);
-      key.push_back(S->pre_gram);
-      lists_cached = info.uploaded && info.list_items >= 0 && key == info.list_key;
-      if (!lists_cached) info.list_key.swap(key), info.list_items = -1;
-    }
-    if (lists_cached) n_items = info.list_items;
-    for (int v = 0; v < VIS && !overflow && !lists_cached; v++) {
-      const int e = v;  // the bounds are stored by the compact index
-      sum_off[e] = n_items;
-      int marg_end = n_items;
-      for (int k = table.first[v]; k < table.first[v + 1]; k++) {
-        const int pp = table.items[k].pair, local = table.items[k].local;
-        const int c0 = S->pair_chunk0[pp], c1 = S->pair_chunk0[pp + 1];
-        if (c1 == c0) continue;
-        if (n_items + (c1 - c0) > SUM_ITEMS_CAP) {
-          overflow = true;
-          break;
-        }
-        if (S->pre_gram) {
-          sum_items[n_items++] = pp * NGP + local;
-        } else {
-          for (int ch = c0; ch < c1; ch++) sum_items[n_items++] = ch * NGP + local;
-        }
-        if (pp < 11) marg_end = n_items;  // pairs (0, j): the marginalization's subset, a prefix of the list
-      }
-      sum_end_marg[e] = marg_end;
-    }
-    if (!lists_cached) sum_off[VIS] = n_items;
-    used_items = n_items;
-    if (overflow) {
-      c->err = "gather list overflow";
-      return LFVIO_ERR_ARG;
-    }
-    (void)units;
-    (void)marg_units;
-  }
-  // ---- prior
-  auto t_up1 = lap(0, t_up0);
-  c->up_us[1] = 0.0;
-  if (chained) {
-    // everything above was host work on the staging block; the prior of the call in flight is needed from here on
-    // (c->info[0] still describes THAT window's prior: marg_n, the input prior a pass-through hands back)
-    if (int rc = lfvio_batch_optimize_finish(c, chain)) return rc;
-    pr = chain->valid ? chain : nullptr;
-    if (int rc = check_input_prior(c, pr)) return rc;
-    t_up1 = lap(1, t_up1);
-  }
-  for (int c2 = 0; c2 < KP; c2++) S->prior_inv[c2] = -1;
-  if (pr) {
-    S->prior_valid = 1, S->prior_n = pr->n, S->prior_nb = pr->num_blocks;
-    for (int i = 0; i < pr->num_blocks; i++) {
-      S->prior_kind[i] = pr->blocks[i].kind, S->prior_frame[i] = pr->blocks[i].frame, S->prior_idx[i] = pr->block_idx[i];
-      if (!device_chain) std::memcpy(S->prior_x0[i], pr->block_x0[i], sizeof(double) * 9);  // (device_chain: k_prior_chain fills them)
-      const int to = tangent_off(pr->blocks[i].kind, pr->blocks[i].frame);
-      for (int e = 0; e < local_size(pr->blocks[i].kind); e++) {
-        S->prior_cmap[pr->block_idx[i] + e] = to + e;
-        S->prior_inv[to + e] = pr->block_idx[i] + e;
-      }
-    }
-    if (!device_chain) {
-      std::memcpy(h + L.prior_J, pr->linearized_jacobians, sizeof(double) * pr->n * pr->n);
-      std::memcpy(h + L.prior_r, pr->linearized_residuals, sizeof(double) * pr->n);
-    }
-  }
-  {
-    // (a rank's share of a sharded window: the other ranks' frame-0 landmarks shape the prior's blocks too — lfvio_shard_begin)
-    const bool whole = sharded && c->shard_kmax0 >= 0;
-    plan_marg(w, pr, LFVIO_MARGIN_OLD, N0, whole ? c->shard_kmax0 > 0 : N0 > 0, whole ? c->shard_kmax0 : kmax0, S->pair_chunk0[11], true, &S->marg[0]);
-  }
-  plan_marg(w, pr, LFVIO_MARGIN_SECOND_NEW, 0, false, 0, 0, true, &S->marg[1]);
-  for (int f = 0; f < 2; f++)
-    if (S->marg[f].valid && (S->marg[f].n > 76 || S->marg[f].m15 + S->marg[f].n > 92)) {
-      // k_marg_solve keeps the dense system in LDS: sized for what the reference's own marginalization produces
-      // (10 poses + ex + td + one speed/bias = 76 kept, 15 dropped), not for an arbitrary hand-made prior
-      c->err = "prior keeps more than 76 tangent dimensions";
-      return LFVIO_ERR_ARG;
-    }
-  // ---- device pointers
-  S->lm_start.set(S, L.lm_start), S->lm_cnt.set(S, L.lm_cnt), S->lm_obs0.set(S, L.lm_obs0), S->lm_perm.set(S, L.lm_perm);
-  S->lm_woff.set(S, L.lm_woff);
-  S->lam0.set(S, L.lam0);
-  for (int k = 0; k < 8; k++) S->obs[k].set(S, L.obs[k]);
-  S->pm_obs.set(S, L.pm_obs), S->pm_lm.set(S, L.pm_lm);
-  for (int k = 0; k < 8; k++) S->anc[k].set(S, L.anc[k]), S->pmo[k].set(S, L.pmo[k]);
-  S->pm_pair.set(S, L.pm_pair);
-  S->linb_lm0.set(S, L.linb_lm0), S->linb_ns.set(S, L.linb_ns);
-  S->chunk_pair.set(S, L.chunk_pair), S->chunk_begin.set(S, L.chunk_begin), S->chunk_end.set(S, L.chunk_end);
-  S->prior_J.set(S, L.prior_J), S->prior_r.set(S, L.prior_r);
-  S->sum_off.set(S, L.sum_off), S->sum_end_marg.set(S, L.sum_end_marg), S->sum_items.set(S, L.sum_items);
-  // ---- commit: from here on the device copy changes, and the slot's description with it
   info.resident = false;
-  info.N = N, info.M = M;
+  info.N = r.N, info.M = r.M;
   info.prior_n = S->prior_valid ? S->prior_n : 0;
   info.max_iter = w->max_num_iterations, info.max_seconds = w->max_solver_time_in_seconds;
-  info.perm.swap(perm);
-  info.gLm = S->nLmBlocks, info.gLw = S->nSchurParts, info.gCh = nChunks, info.gSc = S->nSchurParts;
+  info.perm.swap(c->perm_build);
+  info.gLm = S->nLmBlocks, info.gLw = S->nSchurParts, info.gCh = r.nChunks, info.gSc = S->nSchurParts;
   info.has_in_prior = pr != nullptr;
   info.in_prior_device = pr && device_chain;
   if (pr && device_chain) std::memcpy(&info.in_prior, pr, offsetof(LfvioPrior, linearized_jacobians));  // (structure; the values are the device's)
@@ -915,23 +519,21 @@ int upload_window(lfvio_ctx *c, int slot, const LfvioWindow *w, int sharded = 0,
   }
   info.mail_seq = c->mail_seq = seq;
   info.spec_on = S->spec_on != 0;
-  {
-    // (a little below the device's own threshold: a "yes" too many costs a few percent of one sweep, a "no" too many would put a
-    // table with the residual chain's flavour in front of a kernel that does not look for it)
-    auto off = [](const double *q) { return std::fabs((q[3] * q[3] + q[0] * q[0] + q[1] * q[1] + q[2] * q[2]) - 1.0) > 0.5 * TAB_OFF_SPHERE; };
-    bool any = false;
-    for (int f = 0; f < LFVIO_NUM_FRAMES; f++) any = any || off(w->para_pose[f] + 3);
-    const bool ex = off(w->para_ex_pose + 3);
-    info.offs_first = any || ex, info.offs_all = ex && !w->estimate_extrinsic;
-  }
+  info.offs_first = r.offs_first, info.offs_all = r.offs_all;
   info.marg_n = std::max(S->marg[0].valid ? S->marg[0].n : 0, S->marg[1].valid ? S->marg[1].n : 0);
-  info.linw_ok = linw;
-  info.linb_ok = linb, info.linb_ng = linb_ng;
+  info.linw_ok = r.linw;
+  info.linb_ok = r.linb, info.linb_ng = r.linb_ng;
+}
+
+// The staging block's way to the slot
+int enqueue_window_copies(lfvio_ctx *c, int slot, const LfvioPrior *pr, bool device_chain, const PackResult &r) {
+  const Layout &L = c->L;
+  char *h = c->h_stage, *d = c->d_base + (size_t)slot * L.total;
   // (an upload behind a call in flight whose prior a worker on the second stream may own: it reads this slot's inputs until it delivers)
   if (slot == 0 && c->call.workers_outstanding()) hipLaunchKernelGGL(k_spec_wait, dim3(1), dim3(64), 0, c->stream, d);
-  // header prefix + input arrays (two copies: the work-pointer part of the header is written once below)
+  // header prefix + input arrays (two copies: the work-pointer part of the header is written once, put_work_pointers)
   HIPCHK(c, hipMemcpyAsync(d, h, offsetof(Slot, x), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d + L.in_begin, h + L.in_begin, (lists_cached ? L.sum_off : L.sum_items + (size_t)used_items * 4) - L.in_begin, hipMemcpyHostToDevice,
+  HIPCHK(c, hipMemcpyAsync(d + L.in_begin, h + L.in_begin, (r.lists_cached ? L.sum_off : L.sum_items + (size_t)r.used_items * 4) - L.in_begin, hipMemcpyHostToDevice,
                            c->stream));
   if (pr && !device_chain) HIPCHK(c, hipMemcpyAsync(d + L.prior_J, h + L.prior_J, sizeof(double) * pr->n * pr->n, hipMemcpyHostToDevice, c->stream));
   if (device_chain) {
@@ -939,57 +541,114 @@ int upload_window(lfvio_ctx *c, int slot, const LfvioWindow *w, int sharded = 0,
     // the call that was in flight is now only work on the stream in front of this window's: nothing of it is left to collect
     c->call.chained_on_device();
   }
-  if (linw) HIPCHK(c, hipMemcpyAsync(d + L.linw_begin, h + L.linw_begin, L.pm_pair + (size_t)std::max(M - N, 0) - L.linw_begin, hipMemcpyHostToDevice, c->stream));
-  if (linb) HIPCHK(c, hipMemcpyAsync(d + L.linb_lm0, h + L.linb_lm0, L.linw_end - L.linb_lm0, hipMemcpyHostToDevice, c->stream));
-  info.list_items = used_items;  // (only now: an upload refused half-way leaves the key without lists on the device)
+  if (r.linw) HIPCHK(c, hipMemcpyAsync(d + L.linw_begin, h + L.linw_begin, L.pm_pair + (size_t)std::max(r.M - r.N, 0) - L.linw_begin, hipMemcpyHostToDevice, c->stream));
+  if (r.linb) HIPCHK(c, hipMemcpyAsync(d + L.linb_lm0, h + L.linb_lm0, L.linw_end - L.linb_lm0, hipMemcpyHostToDevice, c->stream));
+  return LFVIO_OK;
+}
+
+// The pointer members of Slot that lead to its work arrays, all but prior_A: fixed per slot until the next reserve()
+#define SLOT_WORK_POINTERS(X)                                                                                                     \
+  X(lam) X(lamE) X(cost_partE)                                                                                                    \
+  X(a) X(b) X(W) X(Wt) X(scale_l) X(grad_l) X(gn_l) X(diag_l) X(einv_l) X(d1) X(d2)                                                \
+  X(gram_part) X(pairG) X(schur_part) X(schur_sum) X(xch) X(gp) X(lm_part) X(cost_part) X(imu_out) X(imu_raw)                      \
+  X(Hpp) X(mscr) X(eig_aux)
+
+// Written once per slot, and with slot 0 of a context that keeps them into its shadow slots: a shadow's work arrays are its own, laid
+// out like every slot's (the members are self-relative: the same bytes) — but J0^T J0 of the input prior, which k_setup forms once
+// per call, is read from slot 0: a shadow's prior_A leads back there.
+int put_work_pointers(lfvio_ctx *c, int slot) {
+  const Layout &L = c->L;
+  Slot W;
+  std::memset(&W, 0, sizeof W);
+  W.lam[0].set(&W, L.lam[0]), W.lam[1].set(&W, L.lam[1]);
+  for (int k = 0; k < SPEC_EXTRA; k++) W.lamE[k].set(&W, L.lamE[k]);
+  W.cost_partE.set(&W, L.cost_partE);
+  W.prior_A.set(&W, L.prior_A);
+  W.a.set(&W, L.a), W.b.set(&W, L.b), W.W.set(&W, L.W), W.Wt.set(&W, L.Wt);
+  W.scale_l.set(&W, L.scale_l), W.grad_l.set(&W, L.grad_l), W.gn_l.set(&W, L.gn_l);
+  W.diag_l.set(&W, L.diag_l), W.einv_l.set(&W, L.einv_l), W.d1.set(&W, L.d1), W.d2.set(&W, L.d2);
+  W.gram_part.set(&W, L.gram_part), W.pairG.set(&W, L.pairG);
+  W.schur_part.set(&W, L.schur_part);
+  W.xch.set(&W, L.xch);
+  W.schur_sum.set(&W, L.xch + (size_t)XOFF_S * 8), W.gp.set(&W, L.xch + (size_t)XOFF_G * 8), W.Hpp.set(&W, L.xch + (size_t)XOFF_H * 8);
+  W.lm_part.set(&W, L.lm_part), W.cost_part.set(&W, L.cost_part), W.imu_out.set(&W, L.imu_out), W.imu_raw.set(&W, L.imu_raw);
+  W.mscr.set(&W, L.mscr);
+  W.eig_aux.set(&W, L.eig_aux);
+  const int shadows = (c->shadow && slot == 0) ? lfvio_ctx::WORKERS : 0;
+  GP<double> prior_A[1 + lfvio_ctx::WORKERS];
+  for (int k = 0; k <= shadows; k++) {
+    const size_t target = k == 0 ? (size_t)slot : (size_t)(c->batch + k - 1);
+    char *ds = c->d_base + target * L.total;
+    // field by field so that only pointer members are touched
+#define PUT(field) HIPCHK(c, hipMemcpyAsync(ds + offsetof(Slot, field), &W.field, sizeof W.field, hipMemcpyHostToDevice, c->stream));
+    SLOT_WORK_POINTERS(PUT)
+#undef PUT
+    prior_A[k].off = W.prior_A.off - (long long)((target - (size_t)slot) * L.total);
+    HIPCHK(c, hipMemcpyAsync(ds + offsetof(Slot, prior_A), &prior_A[k], sizeof prior_A[k], hipMemcpyHostToDevice, c->stream));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));  // W is on the stack
+  return LFVIO_OK;
+}
+#undef SLOT_WORK_POINTERS
+
+// Pack one window into the pinned staging block (window_pack.h) and upload it to slot `slot`.
+int upload_window(lfvio_ctx *c, int slot, const LfvioWindow *w, const UploadMode &mode = UploadMode()) {
+  const bool device_chain = mode.device_chain;
+  LfvioPrior *chain = mode.chain;
+  if (device_chain) {
+    if (int rc = device_chain_prior(c, slot, mode)) return rc;
+    chain = c->chain_struct.get();
+  }
+  const bool chained = !device_chain && chain && c->call.pending() && slot == 0;
+  const auto t_up0 = std::chrono::steady_clock::now();
+  auto lap = [&](int k, std::chrono::steady_clock::time_point from) {
+    const auto now = std::chrono::steady_clock::now();
+    c->up_us[k] = std::chrono::duration<double>(now - from).count() * 1e6;
+    return now;
+  };
+  if (!chained && !device_chain)
+    if (int rc = join_inflight(c)) return rc;
+  if (int rc = check_window(c, w)) return rc;
+  const LfvioPrior *given = chain ? chain : w->prior;
+  const LfvioPrior *pr = (given && given->valid) ? given : nullptr;  // (chained: not known before the call in flight has finished)
+  if (!chained)
+    if (int rc = check_input_prior(c, pr)) return rc;
+  const Layout &L = c->L;
+  char *h = c->h_stage;
+  if (c->stage_busy) {  // the previous upload's copies out of the staging block (long done, unless uploads come back to back)
+    c->stage_busy = false;
+    HIPCHK(c, hipEventSynchronize(c->stage_event));
+  }
+  SlotHostInfo &info = c->info[slot];
+  const PackOptions opt = pack_options(c, slot, w, mode);
+  PackResult r;
+  if (const char *text = pack_window(w, L, h, opt, c->perm_build, info.list_key, info.list_items, info.uploaded, &r)) {
+    c->err = text;
+    return LFVIO_ERR_ARG;
+  }
+  auto t_up1 = lap(0, t_up0);
+  c->up_us[1] = 0.0;
+  if (chained) {
+    // everything above was host work on the staging block; the prior of the call in flight is needed from here on
+    // (c->info[0] still describes THAT window's prior: marg_n, the input prior a pass-through hands back)
+    if (int rc = lfvio_batch_optimize_finish(c, chain)) return rc;
+    pr = chain->valid ? chain : nullptr;
+    if (int rc = check_input_prior(c, pr)) return rc;
+    t_up1 = lap(1, t_up1);
+  }
+  if (const char *text = pack_prior(w, pr, device_chain, L, h, r, mode.sharded, c->shard_kmax0)) {
+    c->err = text;
+    return LFVIO_ERR_ARG;
+  }
+  commit_slot_info(c, slot, w, (const Slot *)h, pr, device_chain, r, opt.seq);
+  if (int rc = enqueue_window_copies(c, slot, pr, device_chain, r)) return rc;
+  info.list_items = r.used_items;  // (only now: an upload refused half-way leaves the key without lists on the device)
   if (!info.uploaded) {
-    // work-array pointers: fixed per slot until the next reserve()
-    Slot W;
-    std::memset(&W, 0, sizeof W);
-    W.lam[0].set(&W, L.lam[0]), W.lam[1].set(&W, L.lam[1]);
-    for (int k = 0; k < SPEC_EXTRA; k++) W.lamE[k].set(&W, L.lamE[k]);
-    W.cost_partE.set(&W, L.cost_partE);
-    W.prior_A.set(&W, L.prior_A);
-    W.a.set(&W, L.a), W.b.set(&W, L.b), W.W.set(&W, L.W), W.Wt.set(&W, L.Wt);
-    W.scale_l.set(&W, L.scale_l), W.grad_l.set(&W, L.grad_l), W.gn_l.set(&W, L.gn_l);
-    W.diag_l.set(&W, L.diag_l), W.einv_l.set(&W, L.einv_l), W.d1.set(&W, L.d1), W.d2.set(&W, L.d2);
-    W.gram_part.set(&W, L.gram_part), W.pairG.set(&W, L.pairG);
-    W.schur_part.set(&W, L.schur_part);
-    W.xch.set(&W, L.xch);
-    W.schur_sum.set(&W, L.xch + (size_t)XOFF_S * 8), W.gp.set(&W, L.xch + (size_t)XOFF_G * 8), W.Hpp.set(&W, L.xch + (size_t)XOFF_H * 8);
-    W.lm_part.set(&W, L.lm_part), W.cost_part.set(&W, L.cost_part), W.imu_out.set(&W, L.imu_out), W.imu_raw.set(&W, L.imu_raw);
-    W.mscr.set(&W, L.mscr);
-    W.eig_aux.set(&W, L.eig_aux);
-    // field-by-field so that only pointer members are touched
-#define PUTP(field) HIPCHK(c, hipMemcpyAsync(d + offsetof(Slot, field), &W.field, sizeof W.field, hipMemcpyHostToDevice, c->stream))
-    PUTP(lam); PUTP(lamE); PUTP(cost_partE);
-    PUTP(prior_A);
-    PUTP(a); PUTP(b); PUTP(W); PUTP(Wt); PUTP(scale_l); PUTP(grad_l); PUTP(gn_l); PUTP(diag_l); PUTP(einv_l); PUTP(d1); PUTP(d2);
-    PUTP(gram_part); PUTP(pairG); PUTP(schur_part); PUTP(schur_sum); PUTP(xch); PUTP(gp); PUTP(lm_part); PUTP(cost_part); PUTP(imu_out); PUTP(imu_raw);
-    PUTP(Hpp);
-    PUTP(mscr); PUTP(eig_aux);
-#undef PUTP
-    if (c->shadow && slot == 0) {
-      // a shadow slot's work arrays are its own, laid out like every slot's (the members are self-relative: the same bytes) —
-      // but J0^T J0 of the input prior, which k_setup forms once per call, is read from slot 0
-      GP<double> prior_A[lfvio_ctx::WORKERS];
-      for (int wk = 0; wk < lfvio_ctx::WORKERS; wk++) {
-        char *ds = c->d_base + (size_t)(c->batch + wk) * L.total;
-#define PUTS(field) HIPCHK(c, hipMemcpyAsync(ds + offsetof(Slot, field), &W.field, sizeof W.field, hipMemcpyHostToDevice, c->stream))
-        PUTS(lam); PUTS(lamE); PUTS(cost_partE);
-        PUTS(a); PUTS(b); PUTS(W); PUTS(Wt); PUTS(scale_l); PUTS(grad_l); PUTS(gn_l); PUTS(diag_l); PUTS(einv_l); PUTS(d1); PUTS(d2);
-        PUTS(gram_part); PUTS(pairG); PUTS(schur_part); PUTS(schur_sum); PUTS(xch); PUTS(gp); PUTS(lm_part); PUTS(cost_part); PUTS(imu_out); PUTS(imu_raw);
-        PUTS(Hpp);
-        PUTS(mscr); PUTS(eig_aux);
-#undef PUTS
-        prior_A[wk].off = W.prior_A.off - (long long)((size_t)(c->batch + wk) * L.total);
-        HIPCHK(c, hipMemcpyAsync(ds + offsetof(Slot, prior_A), &prior_A[wk], sizeof prior_A[wk], hipMemcpyHostToDevice, c->stream));
-      }
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));  // W is on the stack
+    if (int rc = put_work_pointers(c, slot)) return rc;
     info.uploaded = true;
   }
-  if (linb) hipLaunchKernelGGL(k_linb_gather, dim3((std::max(N, M - N) + 255) / 256, 1), dim3(256), 0, c->stream, d, L.total);  // (the slot's own blob as base)
+  if (r.linb)  // (the slot's own blob as base)
+    hipLaunchKernelGGL(k_linb_gather, dim3((std::max(r.N, r.M - r.N) + 255) / 256, 1), dim3(256), 0, c->stream, c->d_base + (size_t)slot * L.total, L.total);
   // The staging block is reused by the next upload: that one waits for these copies (an event), this one does not — what
   // follows an upload is an optimization on the same stream, and a round trip to the device saved here is ~30 us of the call.
   const auto t_up2 = lap(2, t_up1);
@@ -1891,7 +1550,9 @@ int lfvio_batch_upload_chained_device(lfvio_ctx *c, int slot, const LfvioWindow 
     return LFVIO_ERR_ARG;
   }
   (void)hipSetDevice(c->device);
-  return upload_window(c, slot, in, 0, 1, nullptr, true);
+  UploadMode mode;
+  mode.device_chain = true;
+  return upload_window(c, slot, in, mode);
 }
 
 int lfvio_batch_upload_chained(lfvio_ctx *c, int slot, const LfvioWindow *in, LfvioPrior *prior_io) {
@@ -1901,7 +1562,9 @@ int lfvio_batch_upload_chained(lfvio_ctx *c, int slot, const LfvioWindow *in, Lf
     return LFVIO_ERR_ARG;
   }
   (void)hipSetDevice(c->device);
-  return upload_window(c, slot, in, 0, 1, prior_io);
+  UploadMode mode;
+  mode.chain = prior_io;
+  return upload_window(c, slot, in, mode);
 }
 
 enum CallForm { CALL_STATIC, CALL_ADAPTIVE, CALL_EARLY };  // lfvio_batch_optimize_async | lfvio_batch_optimize | lfvio_batch_optimize_begin
@@ -2146,15 +1809,23 @@ int lfvio_debug_marg_system(lfvio_ctx *c, int n, double *A, double *b) {
     // A prior that a worker delivered (kernels_spec.h) was formed in the worker's shadow slot, and so were its A', b': slot 0's
     // scratch still holds those of an earlier marginalization.  The shadow slot whose prior is the one in slot 0, bit for bit, is
     // where the system of that prior lies (a worker that lost the call to the loop's own tail holds the same bits or an older state's).
+    // The round that formed it worked on the state the call ended with — x[0] of the shadow after k_spec_begin's gauge fix is x[cur] of
+    // slot 0 after the loop's, the same function on the same numbers: a shadow that still holds the same prior from an EARLIER call on
+    // the same window, and has begun a round on another state since, has other scratch.
     const size_t head = offsetof(LfvioPrior, linearized_jacobians), bytes = head + sizeof(double) * n * n;
     std::vector<char> p0(bytes), pw(bytes);
     HIPCHK(c, hipMemcpy(p0.data(), c->d_base + offsetof(Slot, prior_out), bytes, hipMemcpyDeviceToHost));
     const LfvioPrior *h0 = (const LfvioPrior *)p0.data();
+    int cur = 0;
+    FrameState x0, xw;
+    HIPCHK(c, hipMemcpy(&cur, c->d_base + offsetof(Slot, tr) + offsetof(TRState, cur), sizeof cur, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(&x0, c->d_base + offsetof(Slot, x) + sizeof(FrameState) * (cur & 1), sizeof x0, hipMemcpyDeviceToHost));
     for (int wk = 0; wk < lfvio_ctx::WORKERS && h0->valid == 1 && h0->n == n; wk++) {
       char *ds = c->d_base + (size_t)(c->batch + wk) * c->L.total;
       HIPCHK(c, hipMemcpy(pw.data(), ds + offsetof(Slot, prior_out), bytes, hipMemcpyDeviceToHost));
+      HIPCHK(c, hipMemcpy(&xw, ds + offsetof(Slot, x), sizeof xw, hipMemcpyDeviceToHost));
       const LfvioPrior *hw = (const LfvioPrior *)pw.data();
-      if (hw->valid == 1 && hw->n == n && std::memcmp(p0.data() + head, pw.data() + head, bytes - head) == 0) {
+      if (std::memcmp(&x0, &xw, sizeof x0) == 0 && hw->valid == 1 && hw->n == n && std::memcmp(p0.data() + head, pw.data() + head, bytes - head) == 0) {
         d = ds + c->L.mscr;
         break;
       }

@@ -1,8 +1,8 @@
 // linb_plan.h — host side of k_linb (kernels_linw.h): the GROUPS of a large window.  Plain C++ (no HIP): lfvio_hip.hip builds
 // the plan at upload, tests/test_linb_plan.py compiles this file alone and checks its properties on the CPU.
 //
-// The landmarks arrive in device order: ascending start frame, ascending track length inside a start frame (upload_window's
-// bucket sort).  A strip is up to 64 consecutive landmarks of one start frame; a group is one to eight consecutive strips of one
+// The landmarks arrive in device order: ascending start frame, ascending track length inside a start frame (the bucket
+// sort of window_pack.h).  A strip is up to 64 consecutive landmarks of one start frame; a group is one to eight consecutive strips of one
 // start frame, the work of one workgroup:
 //   1 strip   four waves share its steps (steps 1, 5, 9 / 2, 6, 10 / ...)
 //   2 strips  two waves per strip

@@ -58,7 +58,10 @@ int lfvio_shard_begin(lfvio_ctx *c, const LfvioWindow *in, int lm_begin, int lm_
     if (in->start_frame[l] == 0) c->shard_kmax0 = std::max(c->shard_kmax0, in->obs_offset[l + 1] - in->obs_offset[l]);
   int rc = reserve(c, 1, n, o1 - o0);
   if (rc) return rc;
-  if ((rc = upload_window(c, 0, &sub, (add_pose_side & 4) ? 2 : 1, (add_pose_side & 3) == 2 ? 2 : (add_pose_side & 3) ? 1 : 0))) return rc;
+  UploadMode mode;
+  mode.sharded = (add_pose_side & 4) ? 2 : 1;
+  mode.pose_side = (add_pose_side & 3) == 2 ? 2 : (add_pose_side & 3) ? 1 : 0;
+  if ((rc = upload_window(c, 0, &sub, mode))) return rc;
   launch_setup(c, route_for(c, 1, MODE_SOLVE), MODE_SOLVE);  // (no Wt clear: a rank's share carries no LinwPlan)
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));
