@@ -455,7 +455,7 @@ int lfvio_pnp(lfvio_ctx *ctx, const LfvioPnpIn *in, LfvioPnpOut *out /* [F] */);
 
 /* lfvio_sfm_ba: the "full BA" that ends GlobalSFM::construct (vins_estimator/src/initial/initial_sfm.cpp:233-309) — the second of the
  * reference's two ceres::Solve calls.  The incremental part of construct() (:121-218) is lfvio_sfm_construct below and relativePose()
- * stays with the caller: their outputs are this call's inputs.
+ * is lfvio_relative_pose: their outputs are this call's inputs.
  *   :237-257  parameter blocks c_rotation[i] (4, w x y z, world to camera, QuaternionParameterization) and c_translation[i] (3);
  *             the rotation of frame l constant (:249-252), the translations of frames l and frame_num - 1 constant (:253-256);
  *   :259-275  one ReprojectionError3D (initial_sfm.h:25-63) per observation of every sfm_f entry with state == true, no loss:
@@ -509,7 +509,7 @@ int lfvio_sfm_ba(lfvio_ctx *ctx, const LfvioSfmBaIn *in, double *c_rotation /* [
                  double *position /* [P][3] */, LfvioSfmBaOut *out);
 
 /* lfvio_sfm_construct: the incremental part of GlobalSFM::construct (vins_estimator/src/initial/initial_sfm.cpp:121-218) — from the
- * relative pose of frames l and frame_num - 1 (what relativePose() returns; it stays with the caller) to a pose per keyframe and a
+ * relative pose of frames l and frame_num - 1 (what relativePose() returns: lfvio_relative_pose below) to a pose per keyframe and a
  * position per point, which are lfvio_sfm_ba's in/out arrays.  The schedule, literally; an "op" is one step of it, numbered from 0:
  *   :125-153  q[l] = 1, T[l] = 0, q[F - 1] = q[l] * Quaterniond(relative_R), T[F - 1] = relative_T; for both, c_Quat = q.inverse()
  *             (conjugate / squared norm), c_Rotation = c_Quat.toRotationMatrix(), c_Translation = -1 * (c_Rotation * T).  Eigen's
@@ -567,6 +567,76 @@ typedef struct {
 int lfvio_sfm_construct(lfvio_ctx *ctx, const LfvioSfmConstructIn *in, double *c_rotation /* [F][4] w x y z */,
                         double *c_translation /* [F][3] */, double *position /* [P][3] */, int *tri_op /* [P] */,
                         LfvioSfmConstructOut *out);
+
+/* lfvio_relative_pose: Estimator::relativePose (vins_estimator/src/estimator.cpp:445-473) — the candidate loop over the pairs
+ * (frame p, newest frame), p = 0 .. P - 1, with MotionEstimator::solveRelativeRT (initial/solve_5pts.cpp:536-576) behind it, ALL
+ * pairs in one call.  Its l, relative_R, relative_T are lfvio_sfm_construct's inputs: with this call initialStructure() takes
+ * nothing from outside.  Pair p owns the matches match_offset[p] .. match_offset[p + 1] (a CSR): getCorresponding(p, WINDOW_SIZE),
+ * FeaturePerFrame::point as stored (not renormalised; z < 0 is an ordinary input).  Per pair, literally where the reference is
+ * defined:
+ *   :452      N <= 20: the pair is skipped (gate 1; this implies the >= 15 of solve_5pts.cpp:538);
+ *   :454-463  average_parallax: per match |(x_l/z_l, y_l/z_l) - (x_r/z_r, y_r/z_r)| in double, summed in match order into one
+ *             double, divided by N.  IEEE semantics kept: a ray with z == 0 gives inf or NaN;
+ *   :464      !(average_parallax * 160 > 30): the pair is skipped (gate 2; 160, not 460: this tree's value; NaN > 30 is false);
+ *   solve_5pts.cpp:275-335  myfindFundamentalMat: the 8-point RANSAC on bearings, the refit over the winner's inliers and its mask.
+ *             compute_E_21 (:201-230) and check_inliers (:231-273) are those of initial_ex_rotation.cpp: this is lfvio_two_view's
+ *             arithmetic, bit for bit on the same matches and sample sets (best_sample, best_score, num_inliers, the mask, E,
+ *             R_cand, t_cand).  The threshold 0.3 / 460, the confidence and cv::findFundamentalMat of :554-558 have no effect and
+ *             are not restated.  The sample sets are an INPUT, as for lfvio_two_view, local to the pair;
+ *   :395-535  recoverPose over ALL N matches (_mask is not a filter here, unlike OpenCV's): for each of (R1,t) (R2,t) (R1,-t)
+ *             (R2,-t) the point is triangulatePoint's 4 x 4 null vector divided by its fourth entry (:364-379), and it counts
+ *             when b_l . Q / |Q| > 0 && b_r . Q' / |Q'| > 0 (:436-440; the divisions by the norms are kept, so a non-finite
+ *             point does not count); the choice is the >= chain of :507-534, in that order.  Which rotation is called R1
+ *             follows the signs an SVD gives its vectors and is not pinned (lfvio_two_view);
+ *   :570      ok = inlier_cnt > 12.
+ * l is the first pair with gate == 0 && ok; relative_R / relative_T are that pair's rotation / translation.
+ * Deviations from the reference:
+ *   1. the OUTPUT.  As shipped, recoverPose takes _R, _t and _mask BY VALUE (:395-396) and solveRelativeRT forms Rotation and
+ *      Translation from uninitialised locals R, T (:566-569): there is no behaviour to restate.  The intent is unambiguous and is
+ *      what is returned: rotation = rot^T, translation = -rot^T trans with (rot, trans) the candidate recoverPose chose — the
+ *      rotation and unit-norm position of the newest camera in the frame of camera p, which is what lfvio_sfm_construct takes;
+ *   2. where no hypothesis scores above 0, or the winner has fewer than 8 inliers, the reference reads an uninitialised matrix
+ *      or refits an under-determined system (lfvio_two_view's status 1): the pair gets gate 3, with best_sample, num_inliers and
+ *      best_score as lfvio_two_view reports them, and is passed over;
+ *   3. ALL pairs are evaluated and reported, not only those up to l (the reference stops at the first success).  That changes
+ *      nothing in l, relative_R, relative_T;
+ *   4. every sum runs in a fixed order (the integer counts alone are added atomically): a repeated call returns the same bits.
+ * A pair that did not run (gate 1 or 2) has best_sample = chosen = -1 and zeros in the fields behind average_parallax; a pair with
+ * gate 3 has chosen = -1 and zeros behind best_score.  inlier (when not NULL) receives the refit mask of every pair with gate 0;
+ * the slices of the other pairs stay as the caller had them.
+ * LFVIO_ERR_ARG (outputs untouched): null pointers, num_pairs outside [1, LFVIO_WINDOW_SIZE], num_samples outside [1, 1024],
+ * match_offset[0] != 0, a descending offset, a pair with more than 4096 matches, a sample index outside [0, N_p) for a pair with
+ * N_p > 20 (the sample slots of a pair with N_p <= 20 are never read).
+ * One upload, two launches (k_rp_hyp: a wave per (hypothesis, pair) and one per pair's parallax; k_rp_fit: a workgroup per pair),
+ * one download; runs on the feature stream like lfvio_two_view: it does not wait for an optimization in flight. */
+typedef struct {
+  int num_pairs;             /* P in [1, LFVIO_WINDOW_SIZE]: pair p = getCorresponding(p, WINDOW_SIZE), in the reference's order */
+  const int *match_offset;   /* [P + 1] CSR over the pairs' matches, match_offset[0] = 0, 0 <= N_p <= 4096 */
+  const double *bearing_l;   /* [M][3] FeaturePerFrame::point of frame p, as stored */
+  const double *bearing_r;   /* [M][3] ... of the newest frame */
+  int num_samples;           /* S in [1, 1024]; the reference: 100 */
+  const int *samples;        /* [P][S][8] indices LOCAL to the pair; read (and validated) only for pairs with N_p > 20 */
+} LfvioRelativePoseIn;
+typedef struct {
+  int gate;                  /* 0 ran; 1 N <= 20 (:452); 2 !(average_parallax * 160 > 30) (:464); 3 no model (lfvio_two_view's status 1) */
+  int num_matches, best_sample, num_inliers;   /* as LfvioTwoViewOut; num_inliers after the refit */
+  double average_parallax;   /* :454-463, unscaled */
+  double best_score;
+  double E[9], R_cand[2][9], t_cand[3];        /* as LfvioTwoViewOut */
+  int good[4];               /* recoverPose's good1..good4: (R1,t) (R2,t) (R1,-t) (R2,-t) — NOT front[]'s order */
+  int chosen, inlier_cnt;    /* :507-534 with its >= chain; inlier_cnt = good[chosen] */
+  int ok, pad_;              /* inlier_cnt > 12 (:570) */
+  double rot[9], trans[3];   /* the chosen candidate */
+  double rotation[9], translation[3];          /* rot^T, -rot^T trans (deviation 1) */
+} LfvioRelativePosePair;
+typedef struct {
+  int l;                     /* first p with gate == 0 && ok, else -1 (relativePose() returned false) */
+  int pad_;
+  double relative_R[9], relative_T[3];         /* pair l's rotation / translation; untouched when l == -1 */
+  LfvioRelativePosePair pair[LFVIO_WINDOW_SIZE]; /* entries >= P untouched */
+} LfvioRelativePoseOut;
+int lfvio_relative_pose(lfvio_ctx *ctx, const LfvioRelativePoseIn *in, unsigned char *inlier /* [M] refit masks, or NULL */,
+                        LfvioRelativePoseOut *out);
 
 /* ---- landmark-sharded API (multi-GPU) ------------------------
  * Every rank passes the same window but linearizes only landmarks [lm_begin, lm_end) (caller order);

@@ -14,6 +14,8 @@
 // needed.
 // The score is the reference's: a FLOAT accumulator taking double terms match by match, in match order, against the FLOAT
 // threshold — one lane walks the terms the others left in LDS.
+// The bodies are device functions (tv_hyp_body, tv_fit_body): solve_5pts.cpp restates the same steps for relativePose(), and
+// kernels_relpose.h runs them per candidate pair.
 #pragma once
 #include "dev_smallmat.h"
 
@@ -95,15 +97,13 @@ DEV bool tv_residual(const double (&E)[9], d3 bl, d3 br, double &c2, double &c1)
   return true;
 }
 
-// grid S x 64: hypothesis k on the matches samples[8 k .. 8 k + 8).  Every lane runs the same 8-point solve (a wave
-// issues it once either way); the residuals are lanes-parallel, a chunk of matches at a time.
-__global__ __launch_bounds__(TV_HYP_THREADS) void k_tv_hyp(int N, const double *bl, const double *br, const int *samples, double *E_all,
-                                                           float *score_all) {
-  __shared__ double s2[TV_CHUNK], s1[TV_CHUNK];
-  const int k = blockIdx.x, lane = threadIdx.x;
+// Hypothesis on the matches idx8[0 .. 8) of bl / br [N][3]: E to E_out[9], the score to *score_out.  One wave; s2 / s1: TV_CHUNK
+// doubles of LDS each.  Every lane runs the same 8-point solve (a wave issues it once either way); the residuals are
+// lanes-parallel, a chunk of matches at a time.  Shared by k_tv_hyp and k_rp_hyp (kernels_relpose.h).
+DEV void tv_hyp_body(int N, const double *bl, const double *br, const int *idx8, double *E_out, float *score_out, double *s2, double *s1, int lane) {
   int idx[8];
 #pragma unroll
-  for (int j = 0; j < 8; j++) idx[j] = samples[8 * k + j];
+  for (int j = 0; j < 8; j++) idx[j] = idx8[j];
   d3 pl[8], pr[8];
 #pragma unroll
   for (int j = 0; j < 8; j++) pl[j] = ld3(bl + 3 * (size_t)idx[j]), pr[j] = ld3(br + 3 * (size_t)idx[j]);
@@ -120,7 +120,7 @@ __global__ __launch_bounds__(TV_HYP_THREADS) void k_tv_hyp(int N, const double *
     double e = E[0];
 #pragma unroll
     for (int j = 1; j < 9; j++) e = lane == j ? E[j] : e;
-    E_all[9 * (size_t)k + lane] = e;
+    E_out[lane] = e;
   }
   float score = 0.0f;
   for (int base = 0; base < N; base += TV_CHUNK) {
@@ -141,7 +141,15 @@ __global__ __launch_bounds__(TV_HYP_THREADS) void k_tv_hyp(int N, const double *
       }
     __syncthreads();
   }
-  if (lane == 0) score_all[k] = score;
+  if (lane == 0) *score_out = score;
+}
+
+// grid S x 64: hypothesis k on the matches samples[8 k .. 8 k + 8).
+__global__ __launch_bounds__(TV_HYP_THREADS) void k_tv_hyp(int N, const double *bl, const double *br, const int *samples, double *E_all,
+                                                           float *score_all) {
+  __shared__ double s2[TV_CHUNK], s1[TV_CHUNK];
+  const int k = blockIdx.x;
+  tv_hyp_body(N, bl, br, samples + 8 * (size_t)k, E_all + 9 * (size_t)k, score_all + k, s2, s1, threadIdx.x);
 }
 
 // Step K of the Householder QR of A (NR x 9, rows striped over the NT threads): column K below the diagonal to zero.
@@ -180,13 +188,31 @@ DEV void tv_qr_step(double *A, int NR, double *red, int tid) {
   if (tid == K % NT) A[9 * (size_t)K + K] = alpha;
 }
 
-// One workgroup.  A: scratch of max(N, 9) x 9 doubles.  out is written on every path; mask only when status == 0.
-__global__ __launch_bounds__(TV_FIT_THREADS) void k_tv_fit(int N, int S, const double *bl, const double *br, const double *E_all,
-                                                           const float *score_all, double *A, unsigned char *mask, LfvioTwoViewOut *out) {
+// The LDS of tv_fit_body, and what it leaves in every thread's registers.
+struct TvFitLds {
+  float sc[TV_MAX_SAMPLES];
+  double red[8 * TV_FIT_THREADS / 64], sv[9];
+  int sbest, cnt[4];  // cnt: the four candidates' counts in testTriangulation's order (R1,t) (R1,-t) (R2,t) (R2,-t)
+};
+struct TvFit {
+  int best, n_in;  // the winning hypothesis (-1: none scored > 0); its inliers before the refit (status 1) or after it (status 0)
+  double best_score, E[9];
+  m33 R1, R2;
+  d3 u3;
+};
+
+// One workgroup of TV_FIT_THREADS: selection, refit, mask, decomposition and the 4 x N triangulations.  A: scratch of max(N, 9) x 9
+// doubles.  Returns lfvio_two_view's status, the same in every thread; with 0 the mask and lds.cnt are written and f is complete,
+// with 1 only f.best, f.n_in and f.best_score are.  UNIT: a match counts when both dot products DIVIDED BY THE NORMS of the
+// triangulated point are > 0 (recoverPose, solve_5pts.cpp:436-440: a non-finite point does not count) instead of the plain dot
+// products of testTriangulation (initial_ex_rotation.cpp:310-311).  Shared by k_tv_fit and k_rp_fit (kernels_relpose.h).
+template <bool UNIT>
+DEV int tv_fit_body(int N, int S, const double *bl, const double *br, const double *E_all, const float *score_all, double *A, unsigned char *mask,
+                    TvFitLds &lds, TvFit &f) {
   constexpr int NT = TV_FIT_THREADS;
-  __shared__ float sc[TV_MAX_SAMPLES];
-  __shared__ double red[8 * NT / 64], sv[9];
-  __shared__ int sbest, cnt[4];
+  float *sc = lds.sc;
+  double *red = lds.red, *sv = lds.sv;
+  int &sbest = lds.sbest, *cnt = lds.cnt;
   const int tid = threadIdx.x, NR = max(N, 9);
   for (int k = tid; k < S; k += NT) sc[k] = score_all[k];
   if (tid < 4) cnt[tid] = 0;
@@ -200,11 +226,10 @@ __global__ __launch_bounds__(TV_FIT_THREADS) void k_tv_fit(int N, int S, const d
   }
   __syncthreads();
   const int best = sbest;
-  if (best < 0) {
-    if (tid == 0) out->status = 1, out->best_sample = -1, out->num_inliers = 0, out->best_score = 0.0;
-    return;
-  }
-  double E[9];
+  f.best = best, f.n_in = 0, f.best_score = 0.0;
+  if (best < 0) return 1;
+  f.best_score = (double)sc[best];
+  double (&E)[9] = f.E;
 #pragma unroll
   for (int j = 0; j < 9; j++) E[j] = E_all[9 * (size_t)best + j];
   // the winner's inliers (the same arithmetic on the same bits as in k_tv_hyp) and the rows of the refit system
@@ -225,10 +250,8 @@ __global__ __launch_bounds__(TV_FIT_THREADS) void k_tv_fit(int N, int S, const d
     a[6] = w * (r.z * l.x), a[7] = w * (r.z * l.y), a[8] = w * (r.z * l.z);
   }
   n_in = block_sum<NT>(n_in, red, tid);
-  if (n_in < 8.0) {
-    if (tid == 0) out->status = 1, out->best_sample = best, out->num_inliers = (int)n_in, out->best_score = (double)sc[best];
-    return;
-  }
+  f.n_in = (int)n_in;
+  if (n_in < 8.0) return 1;
   // Householder QR of A down to a 9 x 9 triangle
   tv_qr_step<NT, 0>(A, NR, red, tid), tv_qr_step<NT, 1>(A, NR, red, tid), tv_qr_step<NT, 2>(A, NR, red, tid);
   tv_qr_step<NT, 3>(A, NR, red, tid), tv_qr_step<NT, 4>(A, NR, red, tid), tv_qr_step<NT, 5>(A, NR, red, tid);
@@ -260,6 +283,7 @@ __global__ __launch_bounds__(TV_FIT_THREADS) void k_tv_fit(int N, int S, const d
     n_in += in ? 1.0 : 0.0;
   }
   n_in = block_sum<NT>(n_in, red, tid);
+  f.n_in = (int)n_in;
   // decomposeE (:321-336) from the SVD the projection already holds: E = sigma_1 u_1 v_1^T + sigma_2 u_2 v_2^T.  u_3 and
   // v_3 are the cross products, so det U = det V = +1 and both candidates are proper rotations.
   d3 u1, u2, u3;
@@ -267,7 +291,7 @@ __global__ __launch_bounds__(TV_FIT_THREADS) void k_tv_fit(int N, int S, const d
   const d3 v1 = mk3(V[0][0], V[1][0], V[2][0]), v2 = mk3(V[0][1], V[1][1], V[2][1]), v3 = cross(v1, v2);
   const double U1[3] = {u1.x, u1.y, u1.z}, U2[3] = {u2.x, u2.y, u2.z}, U3[3] = {u3.x, u3.y, u3.z};
   const double V1[3] = {v1.x, v1.y, v1.z}, V2[3] = {v2.x, v2.y, v2.z}, V3[3] = {v3.x, v3.y, v3.z};
-  m33 R1, R2;  // U W V^T and U W^T V^T
+  m33 &R1 = f.R1, &R2 = f.R2;  // U W V^T and U W^T V^T
 #pragma unroll
   for (int i = 0; i < 3; i++)
 #pragma unroll
@@ -305,22 +329,38 @@ __global__ __launch_bounds__(TV_FIT_THREADS) void k_tv_fit(int N, int S, const d
       const d3 Xr = mk3(R.a[0] * X.x + R.a[1] * X.y + R.a[2] * X.z + t.x, R.a[3] * X.x + R.a[4] * X.y + R.a[5] * X.z + t.y,
                         R.a[6] * X.x + R.a[7] * X.y + R.a[8] * X.z + t.z);
       const double dl = l.x * X.x + l.y * X.y + l.z * X.z, dr = r.x * Xr.x + r.y * Xr.y + r.z * Xr.z;  // :310-311
-      if (dl > 0 && dr > 0) front++;
+      if constexpr (UNIT) {
+        const double nl = sqrt(X.x * X.x + X.y * X.y + X.z * X.z), nr = sqrt(Xr.x * Xr.x + Xr.y * Xr.y + Xr.z * Xr.z);
+        if (dl / nl > 0 && dr / nr > 0) front++;
+      } else {
+        if (dl > 0 && dr > 0) front++;
+      }
     }
     atomicAdd(&cnt[cand], front);  // integers: the order does not matter
   }
   __syncthreads();
-  if (tid == 0) {
-    out->status = 0, out->best_sample = best, out->num_inliers = (int)n_in, out->best_score = (double)sc[best];
-    double f[4];
+  f.u3 = u3;
+  return 0;
+}
+
+// One workgroup.  out is written on every path; mask only when status == 0.
+__global__ __launch_bounds__(TV_FIT_THREADS) void k_tv_fit(int N, int S, const double *bl, const double *br, const double *E_all,
+                                                           const float *score_all, double *A, unsigned char *mask, LfvioTwoViewOut *out) {
+  __shared__ TvFitLds lds;
+  TvFit f;
+  const int status = tv_fit_body<false>(N, S, bl, br, E_all, score_all, A, mask, lds, f);
+  if (threadIdx.x != 0) return;
+  out->status = status, out->best_sample = f.best, out->num_inliers = f.n_in, out->best_score = f.best_score;
+  if (status == 0) {
+    double fr[4];
 #pragma unroll
-    for (int j = 0; j < 9; j++) out->E[j] = E[j], out->R_cand[0][j] = R1.a[j], out->R_cand[1][j] = R2.a[j];
-    out->t_cand[0] = u3.x, out->t_cand[1] = u3.y, out->t_cand[2] = u3.z;
+    for (int j = 0; j < 9; j++) out->E[j] = f.E[j], out->R_cand[0][j] = f.R1.a[j], out->R_cand[1][j] = f.R2.a[j];
+    out->t_cand[0] = f.u3.x, out->t_cand[1] = f.u3.y, out->t_cand[2] = f.u3.z;
 #pragma unroll
-    for (int j = 0; j < 4; j++) f[j] = 1.0 * cnt[j] / N, out->front[j] = f[j];
-    const double ratio1 = fmax(f[0], f[1]), ratio2 = fmax(f[2], f[3]);  // :276-278
-    const bool first = ratio1 > ratio2;                                 // :280-284: transposed
+    for (int j = 0; j < 4; j++) fr[j] = 1.0 * lds.cnt[j] / N, out->front[j] = fr[j];
+    const double ratio1 = fmax(fr[0], fr[1]), ratio2 = fmax(fr[2], fr[3]);  // :276-278
+    const bool first = ratio1 > ratio2;                                     // :280-284: transposed
 #pragma unroll
-    for (int j = 0; j < 9; j++) out->R_rel[j] = first ? R1.a[3 * (j % 3) + j / 3] : R2.a[3 * (j % 3) + j / 3];
+    for (int j = 0; j < 9; j++) out->R_rel[j] = first ? f.R1.a[3 * (j % 3) + j / 3] : f.R2.a[3 * (j % 3) + j / 3];
   }
 }

@@ -43,6 +43,7 @@ constexpr ncclDataType_t ncclDouble = 8;
 #include "kernels_stepw.h"
 #include "kernels_relo.h"
 #include "kernels_twoview.h"
+#include "kernels_relpose.h"
 #include "kernels_vialign.h"
 #include "kernels_pnp.h"
 #include "kernels_sfmba.h"
@@ -2030,6 +2031,7 @@ int lfvio_debug_query(lfvio_ctx *c, const char *key, double *out, int n) {
 #include "feat.inc"
 
 #include "twoview.inc"
+#include "relpose.inc"
 
 #include "vialign.inc"
 

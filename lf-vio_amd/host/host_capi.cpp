@@ -471,6 +471,37 @@ long long lfvio_host_last_construct(void *h, int cap_points, int cap_obs, int *i
 }
 // out[2] = {attempts that reached lfvio_sfm_construct, attempts that filled the SfM structure}
 void lfvio_host_construct_counts(void *h, long long *out) { out[0] = E(h)->construct_calls, out[1] = E(h)->construct_ok; }
+// Config::self_relative_pose: a full-window image without any record runs relativePose() on the device (process-wide, like the mode)
+void lfvio_host_set_self_relative_pose(int on) { config().self_relative_pose = on != 0; }
+// What the last attempt handed to lfvio_relative_pose and got back.  info[4] = {matches M, sample sets per pair S, call made, its return
+// code}; the arrays (any may be null) take at most cap_matches matches / cap_samples sets per pair: offset[WINDOW_SIZE + 1], bl[M][3],
+// br[M][3], samples[WINDOW_SIZE][S][8]; out.  Returns the number of lfvio_relative_pose calls so far.
+long long lfvio_host_last_relative(void *h, int cap_matches, int cap_samples, int *info, int *offset, double *bl, double *br, int *samples,
+                                   LfvioRelativePoseOut *out) {
+  const WindowEstimator::LastRelative &v = E(h)->last_relative;
+  const int M = v.offset.empty() ? 0 : v.offset.back(), S = v.num_samples;
+  info[0] = M, info[1] = S, info[2] = v.called ? 1 : 0, info[3] = v.rc;
+  if (offset)
+    for (size_t k = 0; k < v.offset.size() && k <= (size_t)WINDOW_SIZE; k++) offset[k] = v.offset[k];
+  if (M <= cap_matches) {
+    if (bl) std::memcpy(bl, v.bl.data(), v.bl.size() * sizeof(double));
+    if (br) std::memcpy(br, v.br.data(), v.br.size() * sizeof(double));
+  }
+  if (samples && S <= cap_samples) std::memcpy(samples, v.samples.data(), v.samples.size() * sizeof(int));
+  if (out) *out = v.out;
+  return E(h)->relative_calls;
+}
+// out[2] = {attempts that reached lfvio_relative_pose, attempts that filled the relative pose}
+void lfvio_host_relative_counts(void *h, long long *out) { out[0] = E(h)->relative_calls, out[1] = E(h)->relative_ok; }
+// the sample sets relativePose() draws from std::mt19937(seed) for pairs of n[0 .. pairs) matches: `count` sets per pair with n > 20, pair
+// order, then set order; out[pairs][count][8], zeros for the other pairs
+void lfvio_host_draw_pair_samples(unsigned seed, int pairs, const int *n, int count, int *out) {
+  std::mt19937 rng(seed);
+  std::memset(out, 0, (size_t)pairs * count * 8 * sizeof(int));
+  for (int p = 0; p < pairs; p++)
+    if (n[p] > 20)
+      for (int k = 0; k < count; k++) drawSampleSet(rng, n[p], out + ((size_t)p * count + k) * 8);
+}
 // ImageFrame::points of entry k of all_image_frame: ids[cap], pts[cap][3]; returns their number, -1: no such entry
 int lfvio_host_image_frame_points(void *h, int k, int cap, int *ids, double *pts) {
   const std::vector<WindowEstimator::ImageFrame> &l = E(h)->image_frames;

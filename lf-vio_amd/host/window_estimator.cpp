@@ -10,6 +10,7 @@
 #pragma weak lfvio_pnp
 #pragma weak lfvio_sfm_construct
 #pragma weak lfvio_sfm_ba
+#pragma weak lfvio_relative_pose
 
 #include <algorithm>
 #include <cmath>
@@ -381,6 +382,54 @@ Matrix3d g2R(const Vector3d &g) {  // Utility::g2R (utility.cpp:3-13): FromTwoVe
   return fromYawPitchRollDeg(Vector3d(-yaw, 0, 0)) * R0;
 }
 }  // namespace
+
+bool WindowEstimator::relativePose() {  // estimator.cpp:445-473
+  LastRelative &lr = last_relative;
+  lr.called = false, lr.rc = LFVIO_OK;
+  lr.offset.assign(1, 0), lr.bl.clear(), lr.br.clear();
+  std::memset(&lr.out, 0, sizeof lr.out);
+  lr.out.l = -1;
+  relative.valid = false;
+  const int S = std::max(1, config().ransac_iterations);
+  lr.num_samples = S;
+  lr.samples.assign((size_t)WINDOW_SIZE * S * 8, 0);
+  std::vector<double> bl, br;
+  bool fits = true;
+  for (int i = 0; i < WINDOW_SIZE; i++) {  // :448-451
+    const int N = tracks.corresponding(i, WINDOW_SIZE, &bl, &br);
+    lr.bl.insert(lr.bl.end(), bl.begin(), bl.end()), lr.br.insert(lr.br.end(), br.begin(), br.end());
+    lr.offset.push_back(lr.offset.back() + N);
+    fits = fits && N <= 4096;  // (the device entry's limit)
+  }
+  if (!fits || lr.offset.back() == 0) return false;  // (no match at all: every pair is skipped, :452)
+  if (!lfvio_relative_pose || !device()) {  // no fallback: over an ABI without the entry the attempt fails
+    status = LFVIO_ERR_DEVICE;
+    lr.rc = LFVIO_ERR_DEVICE;
+    return false;
+  }
+  seedRansac();
+  for (int i = 0; i < WINDOW_SIZE; i++) {  // util::create_random_array per iteration of myfindFundamentalMat (solve_5pts.cpp:300)
+    const int N = lr.offset[i + 1] - lr.offset[i];
+    if (N <= 20) continue;  // :452
+    for (int k = 0; k < S; k++) drawSampleSet(ransac_rng_, N, &lr.samples[((size_t)i * S + k) * 8]);
+  }
+  LfvioRelativePoseIn in;
+  in.num_pairs = WINDOW_SIZE, in.match_offset = lr.offset.data(), in.bearing_l = lr.bl.data(), in.bearing_r = lr.br.data();
+  in.num_samples = S, in.samples = lr.samples.data();
+  lr.rc = lfvio_relative_pose(gpu, &in, nullptr, &lr.out);
+  lr.called = true;
+  relative_calls++;
+  if (lr.rc != LFVIO_OK) {
+    status = lr.rc;
+    return false;
+  }
+  if (lr.out.l < 0) return false;  // :472
+  relative.l = lr.out.l;
+  std::memcpy(relative.R, lr.out.relative_R, sizeof relative.R), std::memcpy(relative.T, lr.out.relative_T, sizeof relative.T);
+  relative.valid = true;
+  relative_ok++;
+  return true;
+}
 
 bool WindowEstimator::constructSfm() {  // estimator.cpp:250-286
   LastConstruct &lc = last_construct;
@@ -780,6 +829,21 @@ void drawSampleSet(std::mt19937 &rng, int n, int out[8]) {
   std::copy(v.begin(), v.end(), out);
 }
 
+void WindowEstimator::seedRansac() {
+  const Config &c = config();
+  if (ransac_seeded_ && ransac_seed_used_ == c.ransac_seed) return;
+  if (c.ransac_seed != 0) {
+    ransac_rng_.seed(c.ransac_seed);
+  } else {  // random_array.cc:12-19
+    std::random_device rd;
+    std::vector<std::uint_least32_t> v(10);
+    std::generate(v.begin(), v.end(), std::ref(rd));
+    std::seed_seq seq(v.begin(), v.end());
+    ransac_rng_.seed(seq);
+  }
+  ransac_seeded_ = true, ransac_seed_used_ = c.ransac_seed;
+}
+
 int WindowEstimator::calibrateExtrinsicRotation() {  // estimator.cpp:142-159
   Config &c = config();
   status = LFVIO_OK;
@@ -793,18 +857,7 @@ int WindowEstimator::calibrateExtrinsicRotation() {  // estimator.cpp:142-159
   Matrix3d Rc = Matrix3d::Identity();  // fewer than 9 matches (initial_ex_rotation.cpp:223, :286)
   if (N >= 9) {
     if (!lfvio_two_view || !device()) return LFVIO_ERR_DEVICE;  // no fallback: without the device entry the mode cannot run
-    if (!ransac_seeded_ || ransac_seed_used_ != c.ransac_seed) {
-      if (c.ransac_seed != 0) {
-        ransac_rng_.seed(c.ransac_seed);
-      } else {  // random_array.cc:12-19
-        std::random_device rd;
-        std::vector<std::uint_least32_t> v(10);
-        std::generate(v.begin(), v.end(), std::ref(rd));
-        std::seed_seq seq(v.begin(), v.end());
-        ransac_rng_.seed(seq);
-      }
-      ransac_seeded_ = true, ransac_seed_used_ = c.ransac_seed;
-    }
+    seedRansac();
     const int S = std::max(1, c.ransac_iterations);
     tv.samples.resize((size_t)S * 8);
     for (int k = 0; k < S; k++) drawSampleSet(ransac_rng_, N, &tv.samples[(size_t)8 * k]);
@@ -879,7 +932,10 @@ void WindowEstimator::advanceWindow(double stamp) {  // estimator.cpp:161-220
       } else if (structure.valid) {  // the PnP loop first, then the same path
         aligned = solvePnpFrames() && visualInitialAlign();
         from_sfm = aligned;
-      } else if (relative.valid) {  // GlobalSFM::construct() first, then the same path; a failed construct() slides MARGIN_OLD (:284)
+      } else if (relative.valid || (config().self_relative_pose && relativePose())) {
+        // a record wins; without one and with Config::self_relative_pose, relativePose() on the device fills `relative` (false: no pair
+        // passed and the window slides with the flag the parallax test set).  GlobalSFM::construct() first, then the same path; a failed
+        // construct() slides MARGIN_OLD (:284)
         const bool built = constructSfm();
         if (!built) marg_flag = LFVIO_MARGIN_OLD;
         aligned = built && solvePnpFrames() && visualInitialAlign();

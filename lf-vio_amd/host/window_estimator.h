@@ -62,6 +62,10 @@ struct Config {
   // (random_array.cc:12-19); any other value makes the draws, and with them the calibration, reproducible.
   int ransac_iterations = 100;
   unsigned ransac_seed = 0;
+  // initialStructure() without any record from outside: a full-window image for which no bootstrap record, SfM result, SfM structure
+  // or relative pose was set runs relativePose() on the device (WindowEstimator::relativePose) and goes on from its result.  false:
+  // such an image slides the window, as it always did.
+  bool self_relative_pose = false;
 };
 Config &config();
 
@@ -312,13 +316,29 @@ class WindowEstimator {
   } last_pnp;
   long long pnp_calls = 0;
   // What relativePose() returns (estimator.cpp:270-277, :445-473): the rotation and unit-norm position of the newest camera in the frame
-  // of camera l, and l.  It is the one input of initialStructure() still taken from outside (solveRelativeRT as shipped returns values
-  // computed from uninitialised locals); used by the next full-window image when no bootstrap record, SfM result or SfM structure is set.
+  // of camera l, and l.  Set from outside (a record wins), or by relativePose() below with Config::self_relative_pose; used by the next
+  // full-window image when no bootstrap record, SfM result or SfM structure is set.
   struct RelativePose {
     bool valid = false;
     int l = 0;
     double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, T[3] = {0, 0, 0};  // row-major
   } relative;
+  // estimator.cpp:445-473: getCorresponding(i, WINDOW_SIZE) for i = 0 .. WINDOW_SIZE - 1 as one CSR, Config::ransac_iterations sample sets
+  // for every pair with more than 20 matches (ransac_rng_ / drawSampleSet, seeded as in calibrateExtrinsicRotation(); pair order, then
+  // set order), ONE lfvio_relative_pose call.  Returns true with `relative` filled (l and the INTENDED output of solveRelativeRT,
+  // include/lfvio.h deviation 1); false when no pair passes (the reference returns false from initialStructure() without touching
+  // marginalization_flag: the window slides with the flag of the parallax test), a pair has more than 4096 matches, the return code is
+  // negative or the device entry is missing (status is set then, as in constructSfm()).  There is no CPU fallback.
+  bool relativePose();
+  struct LastRelative {  // what the last attempt passed to lfvio_relative_pose and got back (tests, tools)
+    bool called = false;
+    int rc = LFVIO_OK, num_samples = 0;
+    std::vector<int> offset;     // CSR over the pairs [WINDOW_SIZE + 1]
+    std::vector<double> bl, br;  // [M][3]
+    std::vector<int> samples;    // [WINDOW_SIZE][S][8], zeros for a pair with <= 20 matches
+    LfvioRelativePoseOut out;
+  } last_relative;
+  long long relative_calls = 0, relative_ok = 0;  // attempts that reached lfvio_relative_pose; attempts that filled `relative`
   // estimator.cpp:250-286 on `relative`: sfm_f from the track table (every track, in f_manager.feature order, its frames start_frame ...,
   // the bearings as stored), lfvio_sfm_construct (the incremental part of GlobalSFM::construct), the triangulated points compacted into
   // lfvio_sfm_ba (its full BA, :283 applied through `accepted`), then Q, T and sfm_tracked_points (:295-314) into `structure`.  Returns
@@ -377,6 +397,7 @@ class WindowEstimator {
   ImageFrame pending_;  // tmp_pre_integration: the samples since the last image
   void advanceWindow(double stamp);  // processImage() behind the keyframe test and the calibration (estimator.cpp:161-220)
   std::mt19937 ransac_rng_;
+  void seedRansac();  // on first use and whenever Config::ransac_seed changed
   bool ransac_seeded_ = false;
   unsigned ransac_seed_used_ = 0;
   void optimizationRelo();  // optimization() with relocalization_info set: lfvio_solve_relo, double2vector(), lfvio_marginalize

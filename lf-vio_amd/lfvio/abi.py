@@ -543,6 +543,68 @@ class SfmConstructOutC(C.Structure):
 
 SFM_MIN_PNP = 10  # solveFrameByPnP returns false below it (initial_sfm.cpp:51-52)
 
+
+class RelativePoseInC(C.Structure):
+    """LfvioRelativePoseIn (include/lfvio.h)."""
+    _fields_ = [
+        ("num_pairs", C.c_int),
+        ("match_offset", C.POINTER(C.c_int)),
+        ("bearing_l", C.POINTER(C.c_double)),
+        ("bearing_r", C.POINTER(C.c_double)),
+        ("num_samples", C.c_int),
+        ("samples", C.POINTER(C.c_int)),
+    ]
+
+
+class RelativePosePairC(C.Structure):
+    """LfvioRelativePosePair (include/lfvio.h)."""
+    _fields_ = [
+        ("gate", C.c_int),
+        ("num_matches", C.c_int),
+        ("best_sample", C.c_int),
+        ("num_inliers", C.c_int),
+        ("average_parallax", C.c_double),
+        ("best_score", C.c_double),
+        ("E", C.c_double * 9),
+        ("R_cand", (C.c_double * 9) * 2),
+        ("t_cand", C.c_double * 3),
+        ("good", C.c_int * 4),
+        ("chosen", C.c_int),
+        ("inlier_cnt", C.c_int),
+        ("ok", C.c_int),
+        ("pad_", C.c_int),
+        ("rot", C.c_double * 9),
+        ("trans", C.c_double * 3),
+        ("rotation", C.c_double * 9),
+        ("translation", C.c_double * 3),
+    ]
+
+    def as_dict(self):
+        a = lambda x: np.array(x, dtype=np.float64)
+        return dict(gate=int(self.gate), num_matches=int(self.num_matches), best_sample=int(self.best_sample), num_inliers=int(self.num_inliers),
+                    average_parallax=float(self.average_parallax), best_score=float(self.best_score), E=a(self.E),
+                    R_cand=np.array([list(self.R_cand[0]), list(self.R_cand[1])]).reshape(2, 3, 3), t_cand=a(self.t_cand),
+                    good=np.array(self.good, dtype=np.int32), chosen=int(self.chosen), inlier_cnt=int(self.inlier_cnt), ok=int(self.ok),
+                    rot=a(self.rot).reshape(3, 3), trans=a(self.trans), rotation=a(self.rotation).reshape(3, 3), translation=a(self.translation))
+
+
+class RelativePoseOutC(C.Structure):
+    """LfvioRelativePoseOut (include/lfvio.h)."""
+    _fields_ = [
+        ("l", C.c_int),
+        ("pad_", C.c_int),
+        ("relative_R", C.c_double * 9),
+        ("relative_T", C.c_double * 3),
+        ("pair", RelativePosePairC * WINDOW_SIZE),
+    ]
+
+    def as_dict(self, P=WINDOW_SIZE):
+        return dict(l=int(self.l), relative_R=np.array(self.relative_R, dtype=np.float64).reshape(3, 3), relative_T=np.array(self.relative_T, dtype=np.float64),
+                    pair=[self.pair[p].as_dict() for p in range(P)])
+
+
+RELPOSE_MIN_MATCHES = 20  # a pair runs when N > 20 (estimator.cpp:452)
+
 HIP_SYMBOLS = [
     "lfvio_create", "lfvio_destroy", "lfvio_last_error", "lfvio_version", "lfvio_solve", "lfvio_solve_relo", "lfvio_marginalize",
     "lfvio_batch_reserve", "lfvio_batch_upload", "lfvio_batch_optimize", "lfvio_batch_optimize_async",
@@ -551,7 +613,7 @@ HIP_SYMBOLS = [
     "lfvio_shard_begin", "lfvio_shard_exchange_len", "lfvio_shard_scalar_offset", "lfvio_shard_exchange_ptr", "lfvio_shard_linearize",
     "lfvio_shard_solve", "lfvio_shard_candidate", "lfvio_shard_decide", "lfvio_shard_marg_linearize", "lfvio_shard_marg_finish",
     "lfvio_shard_finish", "lfvio_shard_restart", "lfvio_shard_enqueue", "lfvio_shard_poll", "lfvio_triangulate", "lfvio_shift_depth", "lfvio_preintegrate",
-    "lfvio_two_view", "lfvio_vi_align", "lfvio_pnp", "lfvio_sfm_ba", "lfvio_sfm_construct",
+    "lfvio_two_view", "lfvio_vi_align", "lfvio_pnp", "lfvio_sfm_ba", "lfvio_sfm_construct", "lfvio_relative_pose",
     "lfvio_group_create", "lfvio_group_unique_id", "lfvio_group_create_rank", "lfvio_group_create_local", "lfvio_group_destroy",
     "lfvio_group_last_error", "lfvio_group_size", "lfvio_group_local", "lfvio_group_rank", "lfvio_group_ctx", "lfvio_group_backend",
     "lfvio_group_solve", "lfvio_group_upload", "lfvio_group_optimize", "lfvio_group_download", "lfvio_group_range",
@@ -624,6 +686,8 @@ def load_hip_library(path=None):
         lib.lfvio_sfm_ba.argtypes = [C.c_void_p, C.POINTER(SfmBaInC), _dp, _dp, _dp, C.POINTER(SfmBaOutC)]
     if hasattr(lib, "lfvio_sfm_construct"):
         lib.lfvio_sfm_construct.argtypes = [C.c_void_p, C.POINTER(SfmConstructInC), _dp, _dp, _dp, C.POINTER(C.c_int), C.POINTER(SfmConstructOutC)]
+    if hasattr(lib, "lfvio_relative_pose"):
+        lib.lfvio_relative_pose.argtypes = [C.c_void_p, C.POINTER(RelativePoseInC), C.POINTER(C.c_ubyte), C.POINTER(RelativePoseOutC)]
     lib.lfvio_shard_marg_linearize.argtypes = [C.c_void_p, C.c_int]
     lib.lfvio_shard_marg_finish.argtypes = [C.c_void_p, C.c_int, C.POINTER(Prior)]
     # multi-GPU groups (RCCL inside the library)

@@ -382,6 +382,30 @@ class Engine:
         res.update(rc=rc, c_rotation=q[:max(F, 0)], c_translation=t[:max(F, 0)], position=X[:max(P, 0)], tri_op=ops[:max(P, 0)])
         return res
 
+    def relative_pose(self, offsets, bl, br, samples, out=None, inlier=None, check=True):
+        """lfvio_relative_pose: Estimator::relativePose over every candidate pair at once — offsets [P + 1] (a CSR over the pairs'
+        matches), bl, br [M, 3] and samples [P, S, 8] (indices local to the pair).  Returns a dict with l, relative_R [3, 3],
+        relative_T, pair (a list of P dicts with the fields of LfvioRelativePosePair), mask [M] (the refit masks of the pairs that ran)
+        and rc.  out / inlier: an abi.RelativePoseOutC / uint8 array to be written (a test of what a failed call leaves alone passes
+        its own); check=False returns the error code under `rc` instead of raising."""
+        off = np.ascontiguousarray(offsets, dtype=np.int32).reshape(-1)
+        bl = np.ascontiguousarray(bl, dtype=np.float64).reshape(-1, 3)
+        br = np.ascontiguousarray(br, dtype=np.float64).reshape(-1, 3)
+        sm = np.ascontiguousarray(samples, dtype=np.int32)
+        P = len(off) - 1
+        rin = abi.RelativePoseInC()
+        rin.num_pairs, rin.num_samples = P, sm.size // (8 * P) if P > 0 else 0
+        ip = C.POINTER(C.c_int)
+        rin.match_offset, rin.bearing_l, rin.bearing_r, rin.samples = off.ctypes.data_as(ip), _p(bl), _p(br), sm.ctypes.data_as(ip)
+        out = abi.RelativePoseOutC() if out is None else out
+        mask = np.zeros(max(len(bl), 1), dtype=np.uint8) if inlier is None else inlier
+        rc = self.lib.lfvio_relative_pose(self.ctx, C.byref(rin), mask.ctypes.data_as(C.POINTER(C.c_ubyte)), C.byref(out))
+        if check:
+            self._check(rc, "lfvio_relative_pose")
+        res = out.as_dict(min(max(P, 0), abi.WINDOW_SIZE))
+        res.update(rc=rc, mask=mask[:len(bl)])
+        return res
+
     def time_kernel(self, which, count, reps):
         ms = np.zeros(1)
         self._check(self.lib.lfvio_debug_time_kernel(self.ctx, which, count, reps, _p(ms)), "time_kernel")

@@ -414,6 +414,47 @@ class HostEstimator:
         self.L.lfvio_host_construct_counts(self.h, o.ctypes.data_as(C.POINTER(C.c_longlong)))
         return int(o[0]), int(o[1])
 
+    def set_self_relative_pose(self, on):
+        """Config::self_relative_pose (process-wide): a full-window image for which no record of any kind was set runs relativePose()
+        on the device (lfvio_relative_pose) and initializes from its own measurements."""
+        self.L.lfvio_host_set_self_relative_pose.argtypes = [C.c_int]
+        self.L.lfvio_host_set_self_relative_pose.restype = None
+        self.L.lfvio_host_set_self_relative_pose(int(bool(on)))
+
+    def last_relative(self):
+        """What the last attempt passed to lfvio_relative_pose and got back: dict(offset [P + 1], bl, br [M, 3], samples [P, S, 8], out
+        (the fields of LfvioRelativePoseOut, None without a device call), called, rc, calls)."""
+        P = abi.WINDOW_SIZE
+        info, off = np.zeros(4, dtype=np.int32), np.zeros(P + 1, dtype=np.int32)
+        ip = C.POINTER(C.c_int)
+        i_ = lambda a: a.ctypes.data_as(ip)
+        self.L.lfvio_host_last_relative.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, ip, _dp, _dp, ip, C.POINTER(abi.RelativePoseOutC)]
+        self.L.lfvio_host_last_relative.restype = C.c_longlong
+        self.L.lfvio_host_last_relative(self.h, 0, 0, i_(info), i_(off), None, None, None, None)  # the sizes first
+        M, S = int(info[0]), int(info[1])
+        bl, br, sm, out = np.zeros((max(M, 1), 3)), np.zeros((max(M, 1), 3)), np.zeros((P, max(S, 1), 8), dtype=np.int32), abi.RelativePoseOutC()
+        calls = self.L.lfvio_host_last_relative(self.h, max(M, 1), max(S, 1), i_(info), i_(off), _p(bl), _p(br), i_(sm), C.byref(out))
+        return dict(offset=off, bl=bl[:M].copy(), br=br[:M].copy(), samples=sm[:, :S].copy(), out=out.as_dict() if info[2] else None,
+                    called=bool(info[2]), rc=int(info[3]), calls=int(calls))
+
+    def relative_counts(self):
+        """(attempts that reached lfvio_relative_pose, attempts that filled the relative pose)."""
+        o = np.zeros(2, dtype=np.int64)
+        self.L.lfvio_host_relative_counts.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
+        self.L.lfvio_host_relative_counts(self.h, o.ctypes.data_as(C.POINTER(C.c_longlong)))
+        return int(o[0]), int(o[1])
+
+    def draw_pair_samples(self, seed, counts, num_sets):
+        """The sample sets relativePose() draws from std::mt19937(seed) for pairs of counts[p] matches: num_sets per pair with more than
+        20 matches, pair order, then set order -> [P, num_sets, 8] (zeros for the other pairs)."""
+        n = np.ascontiguousarray(counts, dtype=np.int32)
+        o = np.zeros((len(n), num_sets, 8), dtype=np.int32)
+        ip = C.POINTER(C.c_int)
+        self.L.lfvio_host_draw_pair_samples.argtypes = [C.c_uint, C.c_int, ip, C.c_int, ip]
+        self.L.lfvio_host_draw_pair_samples.restype = None
+        self.L.lfvio_host_draw_pair_samples(int(seed), len(n), n.ctypes.data_as(ip), int(num_sets), o.ctypes.data_as(ip))
+        return o
+
     def sfm(self, cap=1024):
         """The SfM result the estimator holds (after the PnP loop: every frame of all_image_frame): (stamps, R [n, 3, 3], T [n, 3])."""
         st, R, T = np.zeros(cap), np.zeros((cap, 9)), np.zeros((cap, 3))
