@@ -638,6 +638,58 @@ typedef struct {
 int lfvio_relative_pose(lfvio_ctx *ctx, const LfvioRelativePoseIn *in, unsigned char *inlier /* [M] refit masks, or NULL */,
                         LfvioRelativePoseOut *out);
 
+/* lfvio_klt_track: the optical flow of FeatureTracker::readImage — cv::calcOpticalFlowPyrLK(cur_img, forw_img, cur_pts, forw_pts,
+ * status, err, cv::Size(41, 41), 3) at feature_tracker/src/feature_tracker.cpp:127 and the inBorder test of :6-12, :129-131.  The
+ * rest of feature_tracker/ (goodFeaturesToTrack, setMask, CLAHE, rejectWithF, undistortedPoints) stays the caller's.
+ * One call uploads `image`, builds its pyramid, tracks the N points from the pyramid of the PREVIOUS call's image (resident in the
+ * context: cur_img = forw_img, :180) into the new one, and makes the new pyramid the resident one.  A context with no resident image —
+ * after lfvio_create, after lfvio_klt_reset, or when width or height differ from the resident image's — treats `image` as both
+ * images (:111-114).
+ *   levels    level k + 1 is pyrDown of level k: separable [1 4 6 4 1] / 16, reflect-101 borders, even pixels, size ((w + 1) / 2,
+ *             (h + 1) / 2), integer sums rounded (s + 128) >> 8.  Building stops before the first level whose width or height is
+ *             <= win_size; levels_used is the last level built, capped by max_level.
+ *   gradients Scharr 3 / 10 / 3 over 32 on the uint8 level, reflect-101 neighbours at the edge.  Outside a level the image continues
+ *             by (repeated) reflect-101 and both gradients are 0.
+ *   a point   for level L = levels_used .. 0: prev = p / 2^L; the guess is prev at the top level and twice the level above's result
+ *             below it, and is the level's result until an iteration replaces it; the window's corner is prev - (win_size - 1) / 2
+ *             with integer part ip; ip.x < -win_size, ip.x >= cols, ip.y < -win_size or ip.y >= rows skips the level (status 0 at
+ *             level 0); A = sum g g^T / 1024 over the bilinear win x win patch, minEig = (A11 + A22 - sqrt((A11 - A22)^2 +
+ *             4 A12^2)) / (2 win^2); minEig < min_eig_threshold or det A < FLT_EPSILON skips the level (status 0 at level 0);
+ *             otherwise at most max_iterations times: the same bounds test on the guess's corner (failing it ends the level, status
+ *             0 at level 0), b = sum (J - I) g / 1024, delta = ((A12 b2 - A22 b1) / det, (A12 b1 - A11 b2) / det), guess += delta;
+ *             stop when delta . delta <= epsilon^2; from the second iteration on, when both components of |delta + previous delta|
+ *             are < 0.01, take back delta / 2 and stop.
+ *   after level 0: the border test; next_pts (rounded to float) is written for EVERY point, status 0 included.
+ * tests/klt_ref.py restates this in numpy and is the specification.  Deviations from OpenCV: its fixed-point
+ * interpolation (14-bit weights, 5 fractional bits in the patch) is plain floating point here; `err` is not produced — the tracker
+ * never reads it.
+ * LFVIO_ERR_ARG (every output and the resident image untouched): null ctx / in / image / next_pts / status / out, prev_pts null with
+ * N > 0, or a field outside the range noted beside it.  Runs on the feature stream like lfvio_two_view: it does not wait for an
+ * optimization in flight.  The pyramids live in device memory of their own, not in the feature calls' staging block. */
+#define LFVIO_KLT_MAX_POINTS 4096
+#define LFVIO_KLT_MAX_LEVEL 5
+typedef struct {
+  int width, height;           /* 8-bit grey image, rows contiguous; 16 <= width, height <= 8192 */
+  const unsigned char *image;  /* forw_img */
+  int num_points;              /* N, 0 <= N <= 4096: cur_pts */
+  const float *prev_pts;       /* [N][2] x, y in the image of the PREVIOUS call (cv::Point2f) */
+  int win_size;                /* odd, 5..41; the reference: 41 */
+  int max_level;               /* 0..5; the reference: 3 */
+  int max_iterations;          /* 1..100; OpenCV's default criteria: 30 */
+  double epsilon;              /* > 0; default criteria: 0.01 (compared squared, as OpenCV does) */
+  double min_eig_threshold;    /* >= 0; default 1e-4 */
+  int border;                  /* inBorder() of :6-12 and :129-131: status 0 where the point, rounded half to even
+                                  like cvRound, is outside [border, width-border) x [border, height-border);
+                                  negative: no test; the reference: 1 */
+} LfvioKltIn;
+typedef struct { int levels_used; int num_tracked; } LfvioKltOut;
+int lfvio_klt_track(lfvio_ctx *ctx, const LfvioKltIn *in, float *next_pts /* [N][2] */, unsigned char *status /* [N] */,
+                    int *iterations /* [N][max_level+1], level 0 first, or NULL */, LfvioKltOut *out);
+int lfvio_klt_reset(lfvio_ctx *ctx);   /* forget the resident image */
+/* A level of the resident pyramid (0 .. the last level a call has built of it): its size and, where pixels is not NULL, its
+ * width * height bytes.  LFVIO_ERR_ARG without a resident image or for a level that is not built. */
+int lfvio_klt_level(lfvio_ctx *ctx, int level, int *width, int *height, unsigned char *pixels /* or NULL */);
+
 /* ---- landmark-sharded API (multi-GPU) ------------------------
  * Every rank passes the same window but linearizes only landmarks [lm_begin, lm_end) (caller order);
  * IMU factors and the prior are added on the rank(s) with add_pose_side != 0 — exactly one rank.

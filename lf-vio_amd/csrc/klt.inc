@@ -1,0 +1,103 @@
+// klt.inc — host side of lfvio_klt_track / lfvio_klt_reset / lfvio_klt_level (include/lfvio.h): the optical flow of
+// FeatureTracker::readImage (feature_tracker/src/feature_tracker.cpp:111-131) on the kernels of kernels_klt.h.  Included by
+// lfvio_hip.hip inside its extern "C" block.
+//
+// One call: validate and plan (klt_plan.h), pack [points | image] into the staging block of feat.inc, one copy up, the image into the
+// context's other pyramid buffer, k_klt_down per level, k_klt_track (grid N) from the resident pyramid into the new one, one copy
+// down of [next | status | iterations]; then the new pyramid is the resident one.  The pyramid buffers are the context's own: the
+// staging block is freed when it grows and overwritten by every feature call.
+
+// levels from + 1 .. to of the pyramid at `pyr` (offsets and sizes of `full`, which covers every level of this image size)
+static int klt_build(lfvio_ctx *c, hipStream_t fs, unsigned char *pyr, const KltPlan &full, int from, int to) {
+  for (int k = from + 1; k <= to; k++) {
+    hipLaunchKernelGGL(k_klt_down, dim3((full.w[k] + 63) / 64, (full.h[k] + 3) / 4), dim3(256), 0, fs, (const unsigned char *)(pyr + full.off[k - 1]),
+                       full.w[k - 1], full.h[k - 1], pyr + full.off[k], full.w[k], full.h[k]);
+    HIPCHK(c, hipGetLastError());
+  }
+  return LFVIO_OK;
+}
+
+int lfvio_klt_track(lfvio_ctx *c, const LfvioKltIn *in, float *next_pts, unsigned char *status, int *iterations, LfvioKltOut *out) {
+  if (!c || !in || !next_pts || !status || !out) return LFVIO_ERR_ARG;
+  if (const char *why = klt_check(in)) {
+    c->err = why;
+    return LFVIO_ERR_ARG;
+  }
+  const int N = in->num_points, W = in->width, H = in->height, ML = in->max_level;
+  const KltPlan p = klt_plan(W, H, in->win_size, ML), full = klt_plan(W, H, 0, LFVIO_KLT_MAX_LEVEL);
+  const int LU = p.levels_used;
+  lfvio_ctx::KltState &k = c->klt;
+  FeatStage st(c);
+  const size_t nI = (size_t)W * H, nT = (size_t)N * (ML + 1) * 4;
+  const size_t oP = st.take((size_t)N * 8), oI = st.take(nI), in_end = st.end;
+  const size_t oN = st.take((size_t)N * 8), oS = st.take((size_t)N), oT = st.take(nT);
+  if (int rc = st.reserve()) return rc;
+  const int nb = 1 - k.cur;  // (every earlier call on the feature stream has been waited for: nobody reads this buffer)
+  if (k.cap[nb] < full.bytes) {
+    if (k.d[nb]) (void)hipFree(k.d[nb]);
+    k.d[nb] = nullptr, k.cap[nb] = 0;
+    if (hipMalloc((void **)&k.d[nb], full.bytes) != hipSuccess) {
+      c->err = "out of memory (image pyramid)";
+      return LFVIO_ERR_DEVICE;
+    }
+    k.cap[nb] = full.bytes;
+  }
+  char *d = st.d, *h = st.h;
+  if (N) std::memcpy(h + oP, in->prev_pts, (size_t)N * 8);
+  std::memcpy(h + oI, in->image, nI);
+  if (int rc = st.up(in_end)) return rc;
+  unsigned char *fresh = k.d[nb];
+  HIPCHK(c, hipMemcpyAsync(fresh, d + oI, nI, hipMemcpyDeviceToDevice, st.fs));
+  if (int rc = klt_build(c, st.fs, fresh, full, 0, LU)) return rc;
+  const bool same = k.valid && k.w == W && k.h == H;  // otherwise the new image is both images (:111-114)
+  if (same && k.built < LU) {  // (an earlier call asked for fewer levels: a level is a function of the one below)
+    if (int rc = klt_build(c, st.fs, k.d[k.cur], full, k.built, LU)) return rc;
+    k.built = LU;
+  }
+  if (N) {
+    KltArgs a;
+    a.win = in->win_size, a.levels_used = LU, a.max_level = ML, a.max_iter = in->max_iterations, a.border = in->border;
+    a.eps2 = in->epsilon * in->epsilon, a.min_eig = in->min_eig_threshold;
+    for (int l = 0; l < KLT_LEVELS; l++) a.w[l] = full.w[l], a.h[l] = full.h[l], a.off[l] = (long long)full.off[l];
+    hipLaunchKernelGGL(k_klt_track, dim3(N), dim3(KLT_THREADS), 0, st.fs, a, N, (const unsigned char *)(same ? k.d[k.cur] : fresh),
+                       (const unsigned char *)fresh, (const float *)(d + oP), (float *)(d + oN), (unsigned char *)(d + oS),
+                       iterations ? (int *)(d + oT) : (int *)nullptr);
+    HIPCHK(c, hipGetLastError());
+    if (int rc = st.down(oN, iterations ? st.end : oS + (size_t)N)) return rc;
+  } else {
+    HIPCHK(c, hipStreamSynchronize(st.fs));
+  }
+  int tracked = 0;
+  if (N) {
+    std::memcpy(next_pts, h + oN, (size_t)N * 8);
+    std::memcpy(status, h + oS, (size_t)N);
+    if (iterations) std::memcpy(iterations, h + oT, nT);
+    for (int i = 0; i < N; i++) tracked += status[i] != 0;
+  }
+  out->levels_used = LU, out->num_tracked = tracked;
+  k.cur = nb, k.w = W, k.h = H, k.built = LU, k.valid = true;
+  return LFVIO_OK;
+}
+
+int lfvio_klt_reset(lfvio_ctx *c) {
+  if (!c) return LFVIO_ERR_ARG;
+  c->klt.valid = false;
+  return LFVIO_OK;
+}
+
+int lfvio_klt_level(lfvio_ctx *c, int level, int *width, int *height, unsigned char *pixels) {
+  if (!c || !width || !height) return LFVIO_ERR_ARG;
+  const lfvio_ctx::KltState &k = c->klt;
+  if (!k.valid || level < 0 || level > k.built) {
+    c->err = "lfvio_klt_level: no resident image, or a level that is not built";
+    return LFVIO_ERR_ARG;
+  }
+  const KltPlan full = klt_plan(k.w, k.h, 0, LFVIO_KLT_MAX_LEVEL);
+  if (pixels) {
+    FeatStage st(c);
+    HIPCHK(c, hipMemcpyAsync(pixels, k.d[k.cur] + full.off[level], (size_t)full.w[level] * full.h[level], hipMemcpyDeviceToHost, st.fs));
+    HIPCHK(c, hipStreamSynchronize(st.fs));
+  }
+  *width = full.w[level], *height = full.h[level];
+  return LFVIO_OK;
+}

@@ -48,6 +48,7 @@ constexpr ncclDataType_t ncclDouble = 8;
 #include "kernels_pnp.h"
 #include "kernels_sfmba.h"
 #include "kernels_sfmchain.h"
+#include "kernels_klt.h"
 #include "window_pack.h"
 
 #define HIPCHK(ctx, call)                                                                      \
@@ -143,6 +144,13 @@ struct lfvio_ctx {
   char *d_feat = nullptr;  // scratch of lfvio_triangulate / lfvio_shift_depth (grow-only)
   size_t feat_bytes = 0;
   char *h_feat = nullptr;  // pinned mirror of d_feat: the inputs of a feature step go up as ONE copy, its outputs come down as one
+  // lfvio_klt_track (klt.inc): two pyramid buffers of their own (grow-only); `cur` holds the resident image's levels 0 .. built
+  struct KltState {
+    unsigned char *d[2] = {nullptr, nullptr};
+    size_t cap[2] = {0, 0};
+    int cur = 0, w = 0, h = 0, built = 0;
+    bool valid = false;
+  } klt;
   std::string err;
   int batch = 0;
   Layout L;
@@ -1479,6 +1487,8 @@ void lfvio_destroy(lfvio_ctx *c) {
   if (c->d_base) (void)hipFree(c->d_base);
   if (c->d_feat) (void)hipFree(c->d_feat);
   if (c->h_feat) (void)hipHostFree(c->h_feat);
+  for (auto &p : c->klt.d)
+    if (p) (void)hipFree(p);
   if (c->h_stage) (void)hipHostFree(c->h_stage);
   if (c->h_down) (void)hipHostFree(c->h_down);
   if (c->d_asm) (void)hipFree(c->d_asm);
@@ -2040,6 +2050,8 @@ int lfvio_debug_query(lfvio_ctx *c, const char *key, double *out, int n) {
 #include "sfmba.inc"
 
 #include "sfmchain.inc"
+
+#include "klt.inc"
 // ---- landmark-sharded API: declared in lfvio.h, implemented in shard.inc
 #include "shard.inc"
 // ---- multi-GPU groups (RCCL): declared in lfvio.h, implemented in group.inc

@@ -603,6 +603,30 @@ class RelativePoseOutC(C.Structure):
                     pair=[self.pair[p].as_dict() for p in range(P)])
 
 
+class KltInC(C.Structure):
+    """LfvioKltIn (include/lfvio.h)."""
+    _fields_ = [
+        ("width", C.c_int),
+        ("height", C.c_int),
+        ("image", C.POINTER(C.c_ubyte)),
+        ("num_points", C.c_int),
+        ("prev_pts", C.POINTER(C.c_float)),
+        ("win_size", C.c_int),
+        ("max_level", C.c_int),
+        ("max_iterations", C.c_int),
+        ("epsilon", C.c_double),
+        ("min_eig_threshold", C.c_double),
+        ("border", C.c_int),
+    ]
+
+
+class KltOutC(C.Structure):
+    """LfvioKltOut (include/lfvio.h)."""
+    _fields_ = [("levels_used", C.c_int), ("num_tracked", C.c_int)]
+
+
+KLT_MAX_POINTS, KLT_MAX_LEVEL = 4096, 5  # LFVIO_KLT_MAX_POINTS, LFVIO_KLT_MAX_LEVEL
+
 RELPOSE_MIN_MATCHES = 20  # a pair runs when N > 20 (estimator.cpp:452)
 
 HIP_SYMBOLS = [
@@ -614,6 +638,7 @@ HIP_SYMBOLS = [
     "lfvio_shard_solve", "lfvio_shard_candidate", "lfvio_shard_decide", "lfvio_shard_marg_linearize", "lfvio_shard_marg_finish",
     "lfvio_shard_finish", "lfvio_shard_restart", "lfvio_shard_enqueue", "lfvio_shard_poll", "lfvio_triangulate", "lfvio_shift_depth", "lfvio_preintegrate",
     "lfvio_two_view", "lfvio_vi_align", "lfvio_pnp", "lfvio_sfm_ba", "lfvio_sfm_construct", "lfvio_relative_pose",
+    "lfvio_klt_track", "lfvio_klt_reset", "lfvio_klt_level",
     "lfvio_group_create", "lfvio_group_unique_id", "lfvio_group_create_rank", "lfvio_group_create_local", "lfvio_group_destroy",
     "lfvio_group_last_error", "lfvio_group_size", "lfvio_group_local", "lfvio_group_rank", "lfvio_group_ctx", "lfvio_group_backend",
     "lfvio_group_solve", "lfvio_group_upload", "lfvio_group_optimize", "lfvio_group_download", "lfvio_group_range",
@@ -688,6 +713,10 @@ def load_hip_library(path=None):
         lib.lfvio_sfm_construct.argtypes = [C.c_void_p, C.POINTER(SfmConstructInC), _dp, _dp, _dp, C.POINTER(C.c_int), C.POINTER(SfmConstructOutC)]
     if hasattr(lib, "lfvio_relative_pose"):
         lib.lfvio_relative_pose.argtypes = [C.c_void_p, C.POINTER(RelativePoseInC), C.POINTER(C.c_ubyte), C.POINTER(RelativePoseOutC)]
+    if hasattr(lib, "lfvio_klt_track"):
+        lib.lfvio_klt_track.argtypes = [C.c_void_p, C.POINTER(KltInC), C.POINTER(C.c_float), C.POINTER(C.c_ubyte), C.POINTER(C.c_int), C.POINTER(KltOutC)]
+        lib.lfvio_klt_reset.argtypes = [C.c_void_p]
+        lib.lfvio_klt_level.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_ubyte)]
     lib.lfvio_shard_marg_linearize.argtypes = [C.c_void_p, C.c_int]
     lib.lfvio_shard_marg_finish.argtypes = [C.c_void_p, C.c_int, C.POINTER(Prior)]
     # multi-GPU groups (RCCL inside the library)

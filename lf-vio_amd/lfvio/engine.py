@@ -406,6 +406,52 @@ class Engine:
         res.update(rc=rc, mask=mask[:len(bl)])
         return res
 
+    def klt_track(self, image, prev_pts, win_size=41, max_level=3, max_iterations=30, epsilon=0.01, min_eig_threshold=1e-4, border=1,
+                  next=None, status=None, size=None, num_points=None, want_iterations=True, check=True):
+        """lfvio_klt_track: pyramidal Lucas-Kanade of the points prev_pts [N, 2] (float32, in the image of the previous call) into
+        `image` [height, width] uint8, which then becomes the resident image.  Returns a dict with next [N, 2] float32, status [N]
+        uint8, iterations [N, max_level + 1] (None without want_iterations), levels_used, num_tracked and rc.  next / status: arrays
+        to be written, size = (width, height) / num_points: the struct's fields whatever the arrays say, image / prev_pts None: null
+        pointers (tests of what a refused call leaves alone); check=False returns the error code under `rc` instead of raising."""
+        img = None if image is None else np.ascontiguousarray(image, dtype=np.uint8)
+        pts = None if prev_pts is None else np.ascontiguousarray(prev_pts, dtype=np.float32).reshape(-1, 2)
+        N = (0 if pts is None else len(pts)) if num_points is None else num_points
+        kin = abi.KltInC()
+        kin.width, kin.height = size if size is not None else (img.shape[1], img.shape[0])
+        kin.image = None if img is None else img.ctypes.data_as(C.POINTER(C.c_ubyte))
+        kin.num_points = N
+        kin.prev_pts = None if pts is None else pts.ctypes.data_as(C.POINTER(C.c_float))
+        kin.win_size, kin.max_level, kin.max_iterations, kin.border = win_size, max_level, max_iterations, border
+        kin.epsilon, kin.min_eig_threshold = epsilon, min_eig_threshold
+        cap = min(max(N, 1), abi.KLT_MAX_POINTS)
+        nxt = np.zeros((cap, 2), dtype=np.float32) if next is None else next
+        stat = np.zeros(cap, dtype=np.uint8) if status is None else status
+        its = np.zeros((cap, min(max(max_level, 0), abi.KLT_MAX_LEVEL) + 1), dtype=np.int32) if want_iterations else None
+        out = abi.KltOutC(-1, -1)
+        rc = self.lib.lfvio_klt_track(self.ctx, C.byref(kin), nxt.ctypes.data_as(C.POINTER(C.c_float)), stat.ctypes.data_as(C.POINTER(C.c_ubyte)),
+                                      its.ctypes.data_as(C.POINTER(C.c_int)) if want_iterations else None, C.byref(out))
+        if check:
+            self._check(rc, "lfvio_klt_track")
+        n = min(max(N, 0), len(stat))
+        return dict(next=nxt[:n], status=stat[:n], iterations=its[:n] if want_iterations else None, levels_used=int(out.levels_used),
+                    num_tracked=int(out.num_tracked), rc=rc)
+
+    def klt_reset(self):
+        """lfvio_klt_reset: forget the resident image; the next klt_track tracks its image against itself."""
+        self._check(self.lib.lfvio_klt_reset(self.ctx), "lfvio_klt_reset")
+
+    def klt_level(self, level, check=True):
+        """lfvio_klt_level: level `level` of the resident pyramid as a [height, width] uint8 array (None, with check=False, where the
+        call is refused: no resident image, or a level no call has built)."""
+        w, h = C.c_int(0), C.c_int(0)
+        rc = self.lib.lfvio_klt_level(self.ctx, level, C.byref(w), C.byref(h), None)
+        if rc != 0 and not check:
+            return None
+        self._check(rc, "lfvio_klt_level")
+        px = np.zeros((h.value, w.value), dtype=np.uint8)
+        self._check(self.lib.lfvio_klt_level(self.ctx, level, C.byref(w), C.byref(h), px.ctypes.data_as(C.POINTER(C.c_ubyte))), "lfvio_klt_level")
+        return px
+
     def time_kernel(self, which, count, reps):
         ms = np.zeros(1)
         self._check(self.lib.lfvio_debug_time_kernel(self.ctx, which, count, reps, _p(ms)), "time_kernel")
