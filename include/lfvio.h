@@ -640,7 +640,8 @@ int lfvio_relative_pose(lfvio_ctx *ctx, const LfvioRelativePoseIn *in, unsigned 
 
 /* lfvio_klt_track: the optical flow of FeatureTracker::readImage — cv::calcOpticalFlowPyrLK(cur_img, forw_img, cur_pts, forw_pts,
  * status, err, cv::Size(41, 41), 3) at feature_tracker/src/feature_tracker.cpp:127 and the inBorder test of :6-12, :129-131.  The
- * rest of feature_tracker/ (goodFeaturesToTrack, setMask, CLAHE, rejectWithF, undistortedPoints) stays the caller's.
+ * goodFeaturesToTrack and setMask are lfvio_gft_detect below; the rest of feature_tracker/ (CLAHE, rejectWithF, undistortedPoints)
+ * stays the caller's.
  * One call uploads `image`, builds its pyramid, tracks the N points from the pyramid of the PREVIOUS call's image (resident in the
  * context: cur_img = forw_img, :180) into the new one, and makes the new pyramid the resident one.  A context with no resident image —
  * after lfvio_create, after lfvio_klt_reset, or when width or height differ from the resident image's — treats `image` as both
@@ -689,6 +690,50 @@ int lfvio_klt_reset(lfvio_ctx *ctx);   /* forget the resident image */
 /* A level of the resident pyramid (0 .. the last level a call has built of it): its size and, where pixels is not NULL, its
  * width * height bytes.  LFVIO_ERR_ARG without a resident image or for a level that is not built. */
 int lfvio_klt_level(lfvio_ctx *ctx, int level, int *width, int *height, unsigned char *pixels /* or NULL */);
+
+/* lfvio_gft_detect: the other half of FeatureTracker::readImage — setMask() (feature_tracker/src/feature_tracker.cpp:46-83) and
+ * cv::goodFeaturesToTrack(forw_img, n_pts, MAX_CNT - forw_pts.size(), 0.01, MIN_DIST, mask) (:147-176) on the image that
+ * lfvio_klt_track left resident: level 0 of its pyramid (a call with N = 0 makes an image resident without tracking).  Tracked
+ * points and counts go up, kept indices and new corners come down; the image does not move.
+ *   response  Shi-Tomasi, block 3, Sobel 3: dx, dy = the 3 x 3 Sobel responses of the image continued by reflect-101; a, b, c = the
+ *             3 x 3 box sums of dx^2, dx dy, dy^2, THESE maps continued by reflect-101 (not the gradients of the reflected image);
+ *             S = a + c, D = (a - c)^2 + 4 b^2 as integers; lambda = 0.5 * (double(S) - sqrt(double(D))) >= 0.  OpenCV's value is
+ *             lambda / (12 * 255)^2: only ratios are used, the factor is not applied.
+ *   thinning  the points in order of descending track_cnt, equal counts by ascending index; (px, py) = the coordinates rounded half
+ *             to even (cvRound); a point is dropped when a coordinate is NaN or the pixel is outside the image, when the base mask
+ *             is not 255 there, or when an already kept point q has (px - qx)^2 + (py - qy)^2 <= mask_radius^2; otherwise it is
+ *             kept.  The final mask is the base mask with zeros in every kept point's disc <= mask_radius^2.
+ *   detection budget = max_count - num_kept; budget <= 0: no corners (num_candidates 0, max_response 0).  max_response = the
+ *             largest lambda where the final mask is not 0, border rows included; 0 or no such pixel: no corners.  thr =
+ *             quality_level * max_response.  A candidate: 1 <= x <= w - 2, 1 <= y <= h - 2, lambda > thr, lambda >= the lambda of
+ *             each of its 8 neighbours (these NOT masked), final mask not 0.  Order: descending lambda, equal lambda by descending
+ *             y * w + x.  Greedy: accepted when every accepted (x', y') has (x - x')^2 + (y - y')^2 >= min_distance^2; stops at
+ *             `budget` accepted; corners are (float) x, (float) y in acceptance order.
+ * tests/gft_ref.py restates this in numpy and is the specification; the device gives its bits.  Stated deviations
+ * from the reference: equal counts are ordered by index (std::sort leaves them unspecified), discs are Euclidean (cv::circle differs
+ * in a few rim pixels), a point outside the image is dropped (the reference reads out of bounds).
+ * The base mask (fisheye_mask, or the annulus of :53-56) is device memory of the context: lfvio_gft_set_mask uploads it once, it
+ * survives lfvio_klt_reset and every other call, and it is all 255 until set (pixels = NULL: all 255 again, width and height
+ * ignored).  lfvio_gft_response gives lambda of the resident image, [height][width] doubles.
+ * LFVIO_ERR_ARG (every output, the resident image and the base mask untouched): null ctx / in / corners / out / response, kept, pts
+ * or track_cnt null with N > 0, a field outside the range noted beside it, no resident image, a base mask whose size is not the
+ * resident image's (for lfvio_gft_set_mask: outside [16, 8192], or not the size of an image that is resident).  The calls run on
+ * the feature stream like lfvio_klt_track: they do not wait for an optimization in flight. */
+#define LFVIO_GFT_MAX_CORNERS 4096
+typedef struct {
+  int num_points;          /* N, 0 .. LFVIO_KLT_MAX_POINTS */
+  const float *pts;        /* [N][2], forw_pts after the flow and rejectWithF; may be NULL when N = 0 */
+  const int *track_cnt;    /* [N] */
+  int max_count;           /* MAX_CNT, 1 .. LFVIO_GFT_MAX_CORNERS */
+  double quality_level;    /* the reference: 0.01; in (0, 1] */
+  int min_distance;        /* MIN_DIST for the new corners, 0 .. 1024 */
+  int mask_radius;         /* MIN_DIST for the discs of setMask, 0 .. 1024 */
+} LfvioGftIn;
+typedef struct { int num_kept, num_corners, num_candidates; double max_response; } LfvioGftOut;
+int lfvio_gft_detect(lfvio_ctx *ctx, const LfvioGftIn *in, int *kept /* [N] indices in kept order; num_kept written */,
+                     float *corners /* [max_count][2]; num_corners written */, LfvioGftOut *out);
+int lfvio_gft_set_mask(lfvio_ctx *ctx, int width, int height, const unsigned char *pixels /* NULL: all 255 */);
+int lfvio_gft_response(lfvio_ctx *ctx, double *response /* [h][w] of the resident image */);
 
 /* ---- landmark-sharded API (multi-GPU) ------------------------
  * Every rank passes the same window but linearizes only landmarks [lm_begin, lm_end) (caller order);

@@ -1,0 +1,156 @@
+// gft.inc — host side of lfvio_gft_detect / lfvio_gft_set_mask / lfvio_gft_response (include/lfvio.h): setMask and
+// goodFeaturesToTrack of FeatureTracker::readImage (feature_tracker/src/feature_tracker.cpp:46-83, :147-176) on the kernels of
+// kernels_gft.h.  Included by lfvio_hip.hip inside its extern "C" block.
+//
+// One call: validate (gft_plan.h), pack [points | counts] into the staging block of feat.inc, one copy up, k_gft_thin, k_gft_response,
+// k_gft_cand, the sort network, k_gft_pick, one copy down of [kept | corners | LfvioGftOut].  The image is level 0 of the resident
+// pyramid of klt.inc and is only read.  The base mask and the work arrays (lambda, final mask, candidates) are device memory of the
+// context's own, grow-only: no allocation once they have reached the image's size.
+
+struct GftWork {  // offsets in lfvio_ctx::GftState::work for one image size
+  size_t lam, keys, idx, mask, kxy, st, bytes, capacity;
+};
+static GftWork gft_work(int W, int H) {
+  GftWork o;
+  const size_t px = (size_t)W * H;
+  o.capacity = gft_capacity(W, H);
+  size_t end = 0;
+  auto take = [&](size_t bytes) {
+    const size_t at = end;
+    end = align_up(end + bytes, 256);
+    return at;
+  };
+  o.lam = take(px * 8), o.keys = take(o.capacity * 8), o.idx = take(o.capacity * 4), o.mask = take(px), o.kxy = take((size_t)GFT_LIST * 4);
+  o.st = take(sizeof(GftDev)), o.bytes = end;
+  return o;
+}
+
+static int gft_reserve(lfvio_ctx *c, const GftWork &wk) {
+  lfvio_ctx::GftState &g = c->gft;
+  if (g.work_cap >= wk.bytes) return LFVIO_OK;
+  if (g.work) (void)hipFree(g.work);
+  g.work = nullptr, g.work_cap = 0;
+  if (hipMalloc((void **)&g.work, wk.bytes) != hipSuccess) {
+    c->err = "out of memory (corner detection)";
+    return LFVIO_ERR_DEVICE;
+  }
+  g.work_cap = wk.bytes;
+  return LFVIO_OK;
+}
+
+static int gft_launch_response(lfvio_ctx *c, hipStream_t fs, const GftWork &wk, const unsigned char *base, int r, int max_count) {
+  const lfvio_ctx::KltState &k = c->klt;
+  char *w = c->gft.work;
+  hipLaunchKernelGGL(k_gft_response, dim3((k.w + GFT_TX - 1) / GFT_TX, (k.h + GFT_TY - 1) / GFT_TY), dim3(GFT_THREADS), 0, fs,
+                     (const unsigned char *)k.d[k.cur], k.w, k.h, base, (const int *)(w + wk.kxy), r, max_count, (GftDev *)(w + wk.st),
+                     (double *)(w + wk.lam), (unsigned char *)(w + wk.mask));
+  HIPCHK(c, hipGetLastError());
+  return LFVIO_OK;
+}
+
+int lfvio_gft_detect(lfvio_ctx *c, const LfvioGftIn *in, int *kept, float *corners, LfvioGftOut *out) {
+  if (!c || !in || !corners || !out) return LFVIO_ERR_ARG;
+  if (const char *why = gft_check(in)) {
+    c->err = why;
+    return LFVIO_ERR_ARG;
+  }
+  const lfvio_ctx::KltState &k = c->klt;
+  lfvio_ctx::GftState &g = c->gft;
+  const int N = in->num_points, MC = in->max_count;
+  if ((N > 0 && !kept) || !k.valid || (g.mask_set && (g.mw != k.w || g.mh != k.h))) {
+    c->err = "lfvio_gft_detect: null kept, no resident image, or a base mask that is not the resident image's size";
+    return LFVIO_ERR_ARG;
+  }
+  const int W = k.w, H = k.h;
+  const GftWork wk = gft_work(W, H);
+  FeatStage st(c);
+  const size_t oP = st.take((size_t)N * 8), oC = st.take((size_t)N * 4), in_end = st.end;
+  const size_t oK = st.take((size_t)N * 4), oX = st.take((size_t)MC * 8), oO = st.take(sizeof(LfvioGftOut));
+  if (int rc = st.reserve()) return rc;
+  if (int rc = gft_reserve(c, wk)) return rc;
+  char *d = st.d, *h = st.h, *w = g.work;
+  if (N) {
+    std::memcpy(h + oP, in->pts, (size_t)N * 8);
+    std::memcpy(h + oC, in->track_cnt, (size_t)N * 4);
+    if (int rc = st.up(in_end)) return rc;
+  }
+  const unsigned char *base = g.mask_set ? g.mask : nullptr;
+  GftDev *dev = (GftDev *)(w + wk.st);
+  unsigned long long *ck = (unsigned long long *)(w + wk.keys);
+  unsigned *ci = (unsigned *)(w + wk.idx);
+  hipLaunchKernelGGL(k_gft_thin, dim3(1), dim3(GFT_THREADS), 0, st.fs, N, (const float *)(d + oP), (const int *)(d + oC), base, W, H, in->mask_radius, dev,
+                     (int *)(d + oK), (int *)(w + wk.kxy));
+  HIPCHK(c, hipGetLastError());
+  if (int rc = gft_launch_response(c, st.fs, wk, base, in->mask_radius, MC)) return rc;
+  hipLaunchKernelGGL(k_gft_cand, dim3((W + GFT_THREADS - 1) / GFT_THREADS, (H + GFT_CAND_ROWS - 1) / GFT_CAND_ROWS), dim3(GFT_THREADS), 0, st.fs, (const double *)(w + wk.lam),
+                     (const unsigned char *)(w + wk.mask), W, H, in->quality_level, MC, dev, ck, ci);
+  HIPCHK(c, hipGetLastError());
+  // the network of the arrays' capacity: the candidate count stays on the device, a stage beyond it returns at once (gft_plan.h)
+  const unsigned chunks = (unsigned)std::min<size_t>(wk.capacity / GFT_CHUNK, GFT_SORT_GRID), halves = (unsigned)std::min<size_t>(wk.capacity / 2 / GFT_THREADS, GFT_SORT_GRID);
+  hipLaunchKernelGGL(k_gft_sort_local, dim3(chunks), dim3(GFT_SORT_THREADS), 0, st.fs, (const GftDev *)dev, ck, ci, 0u);
+  for (size_t kk = 2 * (size_t)GFT_CHUNK; kk <= wk.capacity; kk *= 2) {
+    for (size_t j = kk / 2; j >= (size_t)GFT_CHUNK; j /= 2)
+      hipLaunchKernelGGL(k_gft_sort_global, dim3(halves), dim3(GFT_THREADS), 0, st.fs, (const GftDev *)dev, ck, ci, (unsigned)kk, (unsigned)j);
+    hipLaunchKernelGGL(k_gft_sort_local, dim3(chunks), dim3(GFT_SORT_THREADS), 0, st.fs, (const GftDev *)dev, ck, ci, (unsigned)kk);
+  }
+  HIPCHK(c, hipGetLastError());
+  hipLaunchKernelGGL(k_gft_pick, dim3(1), dim3(GFT_THREADS), 0, st.fs, (const GftDev *)dev, (const unsigned *)ci, W, in->min_distance, MC, (float *)(d + oX),
+                     (LfvioGftOut *)(d + oO));
+  HIPCHK(c, hipGetLastError());
+  if (int rc = st.down(oK, st.end)) return rc;
+  LfvioGftOut o;
+  std::memcpy(&o, h + oO, sizeof o);
+  if (o.num_kept) std::memcpy(kept, h + oK, (size_t)o.num_kept * 4);
+  if (o.num_corners) std::memcpy(corners, h + oX, (size_t)o.num_corners * 8);
+  *out = o;
+  return LFVIO_OK;
+}
+
+int lfvio_gft_set_mask(lfvio_ctx *c, int width, int height, const unsigned char *pixels) {
+  if (!c) return LFVIO_ERR_ARG;
+  lfvio_ctx::GftState &g = c->gft;
+  if (!pixels) {
+    g.mask_set = false;
+    return LFVIO_OK;
+  }
+  if (const char *why = gft_mask_check(width, height, c->klt.valid ? c->klt.w : 0, c->klt.h)) {
+    c->err = why;
+    return LFVIO_ERR_ARG;
+  }
+  const size_t n = (size_t)width * height;
+  FeatStage st(c);
+  const size_t oM = st.take(n);
+  if (int rc = st.reserve()) return rc;
+  if (g.mask_cap < n) {
+    unsigned char *fresh = nullptr;
+    if (hipMalloc((void **)&fresh, n) != hipSuccess) {
+      c->err = "out of memory (base mask)";
+      return LFVIO_ERR_DEVICE;
+    }
+    HIPCHK(c, hipStreamSynchronize(st.fs));
+    if (g.mask) (void)hipFree(g.mask);
+    g.mask = fresh, g.mask_cap = n, g.mask_set = false;
+  }
+  std::memcpy(st.h + oM, pixels, n);
+  if (int rc = st.up(st.end)) return rc;
+  HIPCHK(c, hipMemcpyAsync(g.mask, st.d + oM, n, hipMemcpyDeviceToDevice, st.fs));
+  HIPCHK(c, hipStreamSynchronize(st.fs));
+  g.mw = width, g.mh = height, g.mask_set = true;
+  return LFVIO_OK;
+}
+
+int lfvio_gft_response(lfvio_ctx *c, double *response) {
+  if (!c || !response) return LFVIO_ERR_ARG;
+  if (!c->klt.valid) {
+    c->err = "lfvio_gft_response: no resident image";
+    return LFVIO_ERR_ARG;
+  }
+  const GftWork wk = gft_work(c->klt.w, c->klt.h);
+  FeatStage st(c);
+  if (int rc = gft_reserve(c, wk)) return rc;
+  HIPCHK(c, hipMemsetAsync(c->gft.work + wk.st, 0, sizeof(GftDev), st.fs));  // no kept points
+  if (int rc = gft_launch_response(c, st.fs, wk, nullptr, 0, 1)) return rc;
+  HIPCHK(c, hipMemcpyAsync(response, c->gft.work + wk.lam, (size_t)c->klt.w * c->klt.h * 8, hipMemcpyDeviceToHost, st.fs));
+  HIPCHK(c, hipStreamSynchronize(st.fs));
+  return LFVIO_OK;
+}

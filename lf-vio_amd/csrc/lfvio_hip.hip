@@ -49,6 +49,7 @@ constexpr ncclDataType_t ncclDouble = 8;
 #include "kernels_sfmba.h"
 #include "kernels_sfmchain.h"
 #include "kernels_klt.h"
+#include "kernels_gft.h"
 #include "window_pack.h"
 
 #define HIPCHK(ctx, call)                                                                      \
@@ -151,6 +152,16 @@ struct lfvio_ctx {
     int cur = 0, w = 0, h = 0, built = 0;
     bool valid = false;
   } klt;
+  // lfvio_gft_detect (gft.inc): the base mask (all 255 until lfvio_gft_set_mask; survives lfvio_klt_reset) and the work arrays of one
+  // image size (lambda, final mask, candidates, kept pixels, GftDev), both grow-only
+  struct GftState {
+    unsigned char *mask = nullptr;
+    size_t mask_cap = 0;
+    int mw = 0, mh = 0;
+    bool mask_set = false;
+    char *work = nullptr;
+    size_t work_cap = 0;
+  } gft;
   std::string err;
   int batch = 0;
   Layout L;
@@ -1489,6 +1500,8 @@ void lfvio_destroy(lfvio_ctx *c) {
   if (c->h_feat) (void)hipHostFree(c->h_feat);
   for (auto &p : c->klt.d)
     if (p) (void)hipFree(p);
+  if (c->gft.mask) (void)hipFree(c->gft.mask);
+  if (c->gft.work) (void)hipFree(c->gft.work);
   if (c->h_stage) (void)hipHostFree(c->h_stage);
   if (c->h_down) (void)hipHostFree(c->h_down);
   if (c->d_asm) (void)hipFree(c->d_asm);
@@ -2052,6 +2065,8 @@ int lfvio_debug_query(lfvio_ctx *c, const char *key, double *out, int n) {
 #include "sfmchain.inc"
 
 #include "klt.inc"
+
+#include "gft.inc"
 // ---- landmark-sharded API: declared in lfvio.h, implemented in shard.inc
 #include "shard.inc"
 // ---- multi-GPU groups (RCCL): declared in lfvio.h, implemented in group.inc

@@ -627,6 +627,27 @@ class KltOutC(C.Structure):
 
 KLT_MAX_POINTS, KLT_MAX_LEVEL = 4096, 5  # LFVIO_KLT_MAX_POINTS, LFVIO_KLT_MAX_LEVEL
 
+
+class GftInC(C.Structure):
+    """LfvioGftIn (include/lfvio.h)."""
+    _fields_ = [
+        ("num_points", C.c_int),
+        ("pts", C.POINTER(C.c_float)),
+        ("track_cnt", C.POINTER(C.c_int)),
+        ("max_count", C.c_int),
+        ("quality_level", C.c_double),
+        ("min_distance", C.c_int),
+        ("mask_radius", C.c_int),
+    ]
+
+
+class GftOutC(C.Structure):
+    """LfvioGftOut (include/lfvio.h)."""
+    _fields_ = [("num_kept", C.c_int), ("num_corners", C.c_int), ("num_candidates", C.c_int), ("max_response", C.c_double)]
+
+
+GFT_MAX_CORNERS = 4096  # LFVIO_GFT_MAX_CORNERS
+
 RELPOSE_MIN_MATCHES = 20  # a pair runs when N > 20 (estimator.cpp:452)
 
 HIP_SYMBOLS = [
@@ -638,7 +659,7 @@ HIP_SYMBOLS = [
     "lfvio_shard_solve", "lfvio_shard_candidate", "lfvio_shard_decide", "lfvio_shard_marg_linearize", "lfvio_shard_marg_finish",
     "lfvio_shard_finish", "lfvio_shard_restart", "lfvio_shard_enqueue", "lfvio_shard_poll", "lfvio_triangulate", "lfvio_shift_depth", "lfvio_preintegrate",
     "lfvio_two_view", "lfvio_vi_align", "lfvio_pnp", "lfvio_sfm_ba", "lfvio_sfm_construct", "lfvio_relative_pose",
-    "lfvio_klt_track", "lfvio_klt_reset", "lfvio_klt_level",
+    "lfvio_klt_track", "lfvio_klt_reset", "lfvio_klt_level", "lfvio_gft_detect", "lfvio_gft_set_mask", "lfvio_gft_response",
     "lfvio_group_create", "lfvio_group_unique_id", "lfvio_group_create_rank", "lfvio_group_create_local", "lfvio_group_destroy",
     "lfvio_group_last_error", "lfvio_group_size", "lfvio_group_local", "lfvio_group_rank", "lfvio_group_ctx", "lfvio_group_backend",
     "lfvio_group_solve", "lfvio_group_upload", "lfvio_group_optimize", "lfvio_group_download", "lfvio_group_range",
@@ -717,6 +738,10 @@ def load_hip_library(path=None):
         lib.lfvio_klt_track.argtypes = [C.c_void_p, C.POINTER(KltInC), C.POINTER(C.c_float), C.POINTER(C.c_ubyte), C.POINTER(C.c_int), C.POINTER(KltOutC)]
         lib.lfvio_klt_reset.argtypes = [C.c_void_p]
         lib.lfvio_klt_level.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_ubyte)]
+    if hasattr(lib, "lfvio_gft_detect"):
+        lib.lfvio_gft_detect.argtypes = [C.c_void_p, C.POINTER(GftInC), C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(GftOutC)]
+        lib.lfvio_gft_set_mask.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_ubyte)]
+        lib.lfvio_gft_response.argtypes = [C.c_void_p, _dp]
     lib.lfvio_shard_marg_linearize.argtypes = [C.c_void_p, C.c_int]
     lib.lfvio_shard_marg_finish.argtypes = [C.c_void_p, C.c_int, C.POINTER(Prior)]
     # multi-GPU groups (RCCL inside the library)

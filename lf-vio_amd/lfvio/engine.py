@@ -12,6 +12,14 @@ def _p(a):
     return a.ctypes.data_as(_dp)
 
 
+def annulus_mask(w, h, cx, cy, max_r, min_r):
+    """The base mask of feature_tracker.cpp:53-56 as a [h, w] uint8 array for Engine.gft_set_mask: 255 where min_r^2 < (x - cx)^2 +
+    (y - cy)^2 <= max_r^2, 0 elsewhere.  Euclidean discs: cv::circle rasterises its own, which differ in a few rim pixels."""
+    yy, xx = np.mgrid[0:h, 0:w]
+    d2 = (xx - cx) ** 2 + (yy - cy) ** 2
+    return np.where((d2 <= max_r * max_r) & (d2 > min_r * min_r), 255, 0).astype(np.uint8)
+
+
 class Engine:
     def __init__(self, device=0, lib_path=None):
         self.lib = abi.load_hip_library(lib_path)
@@ -451,6 +459,55 @@ class Engine:
         px = np.zeros((h.value, w.value), dtype=np.uint8)
         self._check(self.lib.lfvio_klt_level(self.ctx, level, C.byref(w), C.byref(h), px.ctypes.data_as(C.POINTER(C.c_ubyte))), "lfvio_klt_level")
         return px
+
+    def gft_set_mask(self, mask, size=None, check=True):
+        """lfvio_gft_set_mask: the base mask [height, width] uint8 of gft_detect (fisheye_mask, or annulus_mask()); None: all 255
+        again.  size = (width, height): the call's fields whatever the array says.  Returns the error code."""
+        if mask is None:
+            rc = self.lib.lfvio_gft_set_mask(self.ctx, 0, 0, None)
+        else:
+            m = np.ascontiguousarray(mask, dtype=np.uint8)
+            w, h = size if size is not None else (m.shape[1], m.shape[0])
+            rc = self.lib.lfvio_gft_set_mask(self.ctx, w, h, m.ctypes.data_as(C.POINTER(C.c_ubyte)))
+        if check:
+            self._check(rc, "lfvio_gft_set_mask")
+        return rc
+
+    def gft_detect(self, pts, track_cnt, max_count=150, quality_level=0.01, min_distance=30, mask_radius=30, kept=None, corners=None,
+                   num_points=None, check=True):
+        """lfvio_gft_detect on the resident image of klt_track: setMask over the tracked points pts [N, 2] float32 with their
+        track_cnt [N] int32, then goodFeaturesToTrack for max_count - (number kept) new corners.  Returns a dict with kept (indices
+        into pts in kept order), corners [K, 2] float32 in acceptance order, num_candidates, max_response and rc.  kept / corners:
+        arrays to be written, num_points: the struct's field whatever the arrays say, pts / track_cnt None: null pointers (tests of
+        what a refused call leaves alone); check=False returns the error code under `rc` instead of raising."""
+        p = None if pts is None else np.ascontiguousarray(pts, dtype=np.float32).reshape(-1, 2)
+        t = None if track_cnt is None else np.ascontiguousarray(track_cnt, dtype=np.int32).reshape(-1)
+        N = (0 if p is None else len(p)) if num_points is None else num_points
+        gin = abi.GftInC()
+        gin.num_points = N
+        gin.pts = None if p is None else p.ctypes.data_as(C.POINTER(C.c_float))
+        gin.track_cnt = None if t is None else t.ctypes.data_as(C.POINTER(C.c_int))
+        gin.max_count, gin.quality_level, gin.min_distance, gin.mask_radius = max_count, quality_level, min_distance, mask_radius
+        kp = np.zeros(min(max(N, 1), abi.KLT_MAX_POINTS), dtype=np.int32) if kept is None else kept
+        cr = np.zeros((min(max(max_count, 1), abi.GFT_MAX_CORNERS), 2), dtype=np.float32) if corners is None else corners
+        out = abi.GftOutC(-1, -1, -1, -1.0)
+        rc = self.lib.lfvio_gft_detect(self.ctx, C.byref(gin), kp.ctypes.data_as(C.POINTER(C.c_int)), cr.ctypes.data_as(C.POINTER(C.c_float)), C.byref(out))
+        if check:
+            self._check(rc, "lfvio_gft_detect")
+        return dict(kept=kp[:max(out.num_kept, 0)], corners=cr[:max(out.num_corners, 0)], num_candidates=int(out.num_candidates),
+                    max_response=float(out.max_response), rc=rc)
+
+    def gft_response(self, check=True):
+        """lfvio_gft_response: the Shi-Tomasi response lambda of the resident image, [height, width] float64 (None, with check=False,
+        where the call is refused: no resident image)."""
+        w, h = C.c_int(0), C.c_int(0)
+        rc = self.lib.lfvio_klt_level(self.ctx, 0, C.byref(w), C.byref(h), None)
+        if rc != 0 and not check:
+            return None
+        self._check(rc, "lfvio_gft_response")
+        out = np.zeros((h.value, w.value), dtype=np.float64)
+        self._check(self.lib.lfvio_gft_response(self.ctx, _p(out)), "lfvio_gft_response")
+        return out
 
     def time_kernel(self, which, count, reps):
         ms = np.zeros(1)
