@@ -640,8 +640,8 @@ int lfvio_relative_pose(lfvio_ctx *ctx, const LfvioRelativePoseIn *in, unsigned 
 
 /* lfvio_klt_track: the optical flow of FeatureTracker::readImage — cv::calcOpticalFlowPyrLK(cur_img, forw_img, cur_pts, forw_pts,
  * status, err, cv::Size(41, 41), 3) at feature_tracker/src/feature_tracker.cpp:127 and the inBorder test of :6-12, :129-131.  The
- * goodFeaturesToTrack and setMask are lfvio_gft_detect below; the rest of feature_tracker/ (CLAHE, rejectWithF, undistortedPoints)
- * stays the caller's.
+ * goodFeaturesToTrack and setMask are lfvio_gft_detect below, the CLAHE of :101-107 is lfvio_clahe_set below them; the rest of
+ * feature_tracker/ (rejectWithF, undistortedPoints) stays the caller's.
  * One call uploads `image`, builds its pyramid, tracks the N points from the pyramid of the PREVIOUS call's image (resident in the
  * context: cur_img = forw_img, :180) into the new one, and makes the new pyramid the resident one.  A context with no resident image —
  * after lfvio_create, after lfvio_klt_reset, or when width or height differ from the resident image's — treats `image` as both
@@ -734,6 +734,39 @@ int lfvio_gft_detect(lfvio_ctx *ctx, const LfvioGftIn *in, int *kept /* [N] indi
                      float *corners /* [max_count][2]; num_corners written */, LfvioGftOut *out);
 int lfvio_gft_set_mask(lfvio_ctx *ctx, int width, int height, const unsigned char *pixels /* NULL: all 255 */);
 int lfvio_gft_response(lfvio_ctx *ctx, double *response /* [h][w] of the resident image */);
+
+/* lfvio_clahe_set / lfvio_clahe_apply: the equalize step of FeatureTracker::readImage — cv::createCLAHE(3.0, cv::Size(8, 8))->
+ * apply(_img, img) at feature_tracker/src/feature_tracker.cpp:101-107 (EQUALIZE = 1), on 8 bits.
+ *   extent    width % tiles_x == 0 and height % tiles_y == 0: the image itself.  Otherwise the image continued right and down by
+ *             (repeated) reflect-101 to (width + tiles_x - width % tiles_x) x (height + tiles_y - height % tiles_y): a side that does
+ *             divide grows by a whole tiles_x (tiles_y), as in OpenCV.  tw, th = extent / tiles; area = tw th.
+ *   clip      0 when clip_limit == 0, otherwise max((int)(clip_limit * area / 256), 1), in double.
+ *   a tile    its 256-bin histogram in the extended image; with clip > 0: clipped = sum max(hist - clip, 0), hist = min(hist, clip),
+ *             every bin += clipped / 256, and with rest = clipped % 256 != 0 and step = max(256 / rest, 1) the bins 0, step, 2 step,
+ *             ... take one more each until `rest` are handed out.  lut[i] = saturate(round half even((float)(sum of hist[0 .. i]) *
+ *             (255.0f / (float)area))).
+ *   a pixel   (x, y) of the original width x height with value v: txf = (float)x * (1.0f / (float)tw) - 0.5f, tx1 = floor(txf),
+ *             xa = txf - tx1, xa1 = 1.0f - xa, then tx2 = min(tx1 + 1, tiles_x - 1), tx1 = max(tx1, 0); the same in y; out =
+ *             saturate(round half even((L[ty1][tx1][v] xa1 + L[ty1][tx2][v] xa) ya1 + (L[ty2][tx1][v] xa1 + L[ty2][tx2][v] xa) ya))
+ *             in float, EVERY operation rounded on its own: a fused multiply-add gives other bytes.
+ * tests/clahe_ref.py restates this in numpy and is the specification; the device gives its bits.
+ * lfvio_clahe_set: cfg != NULL: every later lfvio_klt_track equalizes its image before the pyramid is built, so the resident image
+ * is the equalized one (forw_img): lfvio_klt_level(ctx, 0, ...) returns it, the higher levels are pyrDown of it, lfvio_gft_detect and
+ * lfvio_gft_response see it.  cfg == NULL: off, and lfvio_klt_track does what it does without this call.  Off after lfvio_create;
+ * survives lfvio_klt_reset.
+ * lfvio_clahe_apply: one image in, the equalized image out; lut (or NULL) receives [tiles_y][tiles_x][256] bytes.  Touches neither
+ * the resident image nor the setting of lfvio_clahe_set.
+ * LFVIO_ERR_ARG (every output, the resident image and the setting untouched): null ctx / pixels / out, null cfg in lfvio_clahe_apply,
+ * a field outside its range, a NaN clip_limit, width or height outside [16, 8192].  Both run on the feature stream like
+ * lfvio_klt_track: they do not wait for an optimization in flight. */
+#define LFVIO_CLAHE_MAX_TILES 16
+typedef struct {
+  double clip_limit;    /* 0 .. 1024; the reference: 3.0; 0: no clipping */
+  int tiles_x, tiles_y; /* 1 .. 16 each; the reference: 8, 8 */
+} LfvioClaheIn;
+int lfvio_clahe_set(lfvio_ctx *ctx, const LfvioClaheIn *cfg /* NULL: off */);
+int lfvio_clahe_apply(lfvio_ctx *ctx, const LfvioClaheIn *cfg, int width, int height, const unsigned char *pixels,
+                      unsigned char *out /* [height][width] */, unsigned char *lut /* [tiles_y][tiles_x][256], or NULL */);
 
 /* ---- landmark-sharded API (multi-GPU) ------------------------
  * Every rank passes the same window but linearizes only landmarks [lm_begin, lm_end) (caller order);

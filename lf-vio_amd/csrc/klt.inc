@@ -3,8 +3,9 @@
 // lfvio_hip.hip inside its extern "C" block.
 //
 // One call: validate and plan (klt_plan.h), pack [points | image] into the staging block of feat.inc, one copy up, the image into the
-// context's other pyramid buffer, k_klt_down per level, k_klt_track (grid N) from the resident pyramid into the new one, one copy
-// down of [next | status | iterations]; then the new pyramid is the resident one.  The pyramid buffers are the context's own: the
+// context's other pyramid buffer (a copy, or the three CLAHE launches of clahe.inc while lfvio_clahe_set is on), k_klt_down per level,
+// k_klt_track (grid N) from the resident pyramid into the new one, one copy down of [next | status | iterations]; then the new pyramid
+// is the resident one.  The pyramid buffers are the context's own: the
 // staging block is freed when it grows and overwritten by every feature call.
 
 // levels from + 1 .. to of the pyramid at `pyr` (offsets and sizes of `full`, which covers every level of this image size)
@@ -47,7 +48,11 @@ int lfvio_klt_track(lfvio_ctx *c, const LfvioKltIn *in, float *next_pts, unsigne
   std::memcpy(h + oI, in->image, nI);
   if (int rc = st.up(in_end)) return rc;
   unsigned char *fresh = k.d[nb];
-  HIPCHK(c, hipMemcpyAsync(fresh, d + oI, nI, hipMemcpyDeviceToDevice, st.fs));
+  if (c->clahe.on) {  // the equalized image is the image: k_clahe_map writes level 0 (clahe.inc)
+    if (int rc = clahe_run(c, st.fs, c->clahe.cfg, W, H, (const unsigned char *)(d + oI), fresh, nullptr)) return rc;
+  } else {
+    HIPCHK(c, hipMemcpyAsync(fresh, d + oI, nI, hipMemcpyDeviceToDevice, st.fs));
+  }
   if (int rc = klt_build(c, st.fs, fresh, full, 0, LU)) return rc;
   const bool same = k.valid && k.w == W && k.h == H;  // otherwise the new image is both images (:111-114)
   if (same && k.built < LU) {  // (an earlier call asked for fewer levels: a level is a function of the one below)

@@ -50,6 +50,7 @@ constexpr ncclDataType_t ncclDouble = 8;
 #include "kernels_sfmchain.h"
 #include "kernels_klt.h"
 #include "kernels_gft.h"
+#include "kernels_clahe.h"
 #include "window_pack.h"
 
 #define HIPCHK(ctx, call)                                                                      \
@@ -162,6 +163,14 @@ struct lfvio_ctx {
     char *work = nullptr;
     size_t work_cap = 0;
   } gft;
+  // lfvio_clahe_set / lfvio_clahe_apply (clahe.inc): the setting (off after lfvio_create; survives lfvio_klt_reset) and the
+  // [tiles][256] int table with the LUTs behind it, allocated at the first use; dirty: the table may hold counts
+  struct ClaheState {
+    bool on = false;
+    LfvioClaheIn cfg = {};
+    char *work = nullptr;
+    bool dirty = false;
+  } clahe;
   std::string err;
   int batch = 0;
   Layout L;
@@ -1502,6 +1511,7 @@ void lfvio_destroy(lfvio_ctx *c) {
     if (p) (void)hipFree(p);
   if (c->gft.mask) (void)hipFree(c->gft.mask);
   if (c->gft.work) (void)hipFree(c->gft.work);
+  if (c->clahe.work) (void)hipFree(c->clahe.work);
   if (c->h_stage) (void)hipHostFree(c->h_stage);
   if (c->h_down) (void)hipHostFree(c->h_down);
   if (c->d_asm) (void)hipFree(c->d_asm);
@@ -2063,6 +2073,8 @@ int lfvio_debug_query(lfvio_ctx *c, const char *key, double *out, int n) {
 #include "sfmba.inc"
 
 #include "sfmchain.inc"
+
+#include "clahe.inc"
 
 #include "klt.inc"
 

@@ -648,6 +648,14 @@ class GftOutC(C.Structure):
 
 GFT_MAX_CORNERS = 4096  # LFVIO_GFT_MAX_CORNERS
 
+
+class ClaheInC(C.Structure):
+    """LfvioClaheIn (include/lfvio.h)."""
+    _fields_ = [("clip_limit", C.c_double), ("tiles_x", C.c_int), ("tiles_y", C.c_int)]
+
+
+CLAHE_MAX_TILES = 16  # LFVIO_CLAHE_MAX_TILES
+
 RELPOSE_MIN_MATCHES = 20  # a pair runs when N > 20 (estimator.cpp:452)
 
 HIP_SYMBOLS = [
@@ -660,6 +668,7 @@ HIP_SYMBOLS = [
     "lfvio_shard_finish", "lfvio_shard_restart", "lfvio_shard_enqueue", "lfvio_shard_poll", "lfvio_triangulate", "lfvio_shift_depth", "lfvio_preintegrate",
     "lfvio_two_view", "lfvio_vi_align", "lfvio_pnp", "lfvio_sfm_ba", "lfvio_sfm_construct", "lfvio_relative_pose",
     "lfvio_klt_track", "lfvio_klt_reset", "lfvio_klt_level", "lfvio_gft_detect", "lfvio_gft_set_mask", "lfvio_gft_response",
+    "lfvio_clahe_set", "lfvio_clahe_apply",
     "lfvio_group_create", "lfvio_group_unique_id", "lfvio_group_create_rank", "lfvio_group_create_local", "lfvio_group_destroy",
     "lfvio_group_last_error", "lfvio_group_size", "lfvio_group_local", "lfvio_group_rank", "lfvio_group_ctx", "lfvio_group_backend",
     "lfvio_group_solve", "lfvio_group_upload", "lfvio_group_optimize", "lfvio_group_download", "lfvio_group_range",
@@ -742,6 +751,9 @@ def load_hip_library(path=None):
         lib.lfvio_gft_detect.argtypes = [C.c_void_p, C.POINTER(GftInC), C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(GftOutC)]
         lib.lfvio_gft_set_mask.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_ubyte)]
         lib.lfvio_gft_response.argtypes = [C.c_void_p, _dp]
+    if hasattr(lib, "lfvio_clahe_set"):
+        lib.lfvio_clahe_set.argtypes = [C.c_void_p, C.POINTER(ClaheInC)]
+        lib.lfvio_clahe_apply.argtypes = [C.c_void_p, C.POINTER(ClaheInC), C.c_int, C.c_int] + [C.POINTER(C.c_ubyte)] * 3
     lib.lfvio_shard_marg_linearize.argtypes = [C.c_void_p, C.c_int]
     lib.lfvio_shard_marg_finish.argtypes = [C.c_void_p, C.c_int, C.POINTER(Prior)]
     # multi-GPU groups (RCCL inside the library)

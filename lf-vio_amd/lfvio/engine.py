@@ -509,6 +509,38 @@ class Engine:
         self._check(self.lib.lfvio_gft_response(self.ctx, _p(out)), "lfvio_gft_response")
         return out
 
+    def clahe_set(self, clip_limit=3.0, tiles=(8, 8), check=True):
+        """lfvio_clahe_set: every later klt_track equalizes its image (CLAHE with `clip_limit` and tiles = (tiles_x, tiles_y)) before
+        the pyramid is built, so the resident image is the equalized one; clahe_set(None): off, the state of a fresh context.
+        Returns the error code."""
+        if clip_limit is None:
+            rc = self.lib.lfvio_clahe_set(self.ctx, None)
+        else:
+            rc = self.lib.lfvio_clahe_set(self.ctx, C.byref(abi.ClaheInC(clip_limit, tiles[0], tiles[1])))
+        if check:
+            self._check(rc, "lfvio_clahe_set")
+        return rc
+
+    def clahe_apply(self, img, clip_limit=3.0, tiles=(8, 8), want_lut=False, out=None, lut=None, size=None, check=True):
+        """lfvio_clahe_apply: `img` [height, width] uint8 equalized, as a new array; with want_lut (equalized, lut [tiles_y, tiles_x,
+        256] uint8).  Touches neither the resident image nor the setting of clahe_set.  out / lut: arrays to be written, size =
+        (width, height): the call's fields whatever the array says, img None: a null pointer (tests of what a refused call leaves
+        alone); check=False returns (error code, out, lut) instead."""
+        px = None if img is None else np.ascontiguousarray(img, dtype=np.uint8)
+        w, h = size if size is not None else (px.shape[1], px.shape[0])
+        up = C.POINTER(C.c_ubyte)
+        if out is None:
+            out = np.zeros((min(max(h, 1), 8192), min(max(w, 1), 8192)), dtype=np.uint8)
+        if lut is None and want_lut:
+            lut = np.zeros((min(max(tiles[1], 1), abi.CLAHE_MAX_TILES), min(max(tiles[0], 1), abi.CLAHE_MAX_TILES), 256), dtype=np.uint8)
+        cin = abi.ClaheInC(clip_limit, tiles[0], tiles[1])
+        rc = self.lib.lfvio_clahe_apply(self.ctx, C.byref(cin), w, h, None if px is None else px.ctypes.data_as(up), out.ctypes.data_as(up),
+                                        None if lut is None else lut.ctypes.data_as(up))
+        if not check:
+            return rc, out, lut
+        self._check(rc, "lfvio_clahe_apply")
+        return (out, lut) if want_lut else out
+
     def time_kernel(self, which, count, reps):
         ms = np.zeros(1)
         self._check(self.lib.lfvio_debug_time_kernel(self.ctx, which, count, reps, _p(ms)), "time_kernel")
