@@ -13,11 +13,7 @@ constexpr size_t CLAHE_LUT_BYTES = (size_t)LFVIO_CLAHE_MAX_TILES * LFVIO_CLAHE_M
 static int clahe_reserve(lfvio_ctx *c, hipStream_t fs) {
   lfvio_ctx::ClaheState &s = c->clahe;
   if (!s.work) {
-    if (hipMalloc((void **)&s.work, CLAHE_TABLE_BYTES + CLAHE_LUT_BYTES) != hipSuccess) {
-      s.work = nullptr;
-      c->err = "out of memory (CLAHE)";
-      return LFVIO_ERR_DEVICE;
-    }
+    if (!s.work.reserve(CLAHE_TABLE_BYTES + CLAHE_LUT_BYTES)) return out_of_memory(c, "out of memory (CLAHE)");
     s.dirty = true;
   }
   if (s.dirty) {  // fresh memory, or a call that failed between the histograms and the LUTs
@@ -33,8 +29,8 @@ static int clahe_run(lfvio_ctx *c, hipStream_t fs, const LfvioClaheIn &cfg, int 
   lfvio_ctx::ClaheState &s = c->clahe;
   const ClahePlan p = clahe_plan(W, H, cfg);
   const int tiles = cfg.tiles_x * cfg.tiles_y, bands = (p.th + CLAHE_BAND_ROWS - 1) / CLAHE_BAND_ROWS;
-  int *table = (int *)s.work;
-  if (!lut) lut = (unsigned char *)s.work + CLAHE_TABLE_BYTES;
+  int *table = (int *)s.work.get();
+  if (!lut) lut = (unsigned char *)s.work.get() + CLAHE_TABLE_BYTES;
   s.dirty = true;
   hipLaunchKernelGGL(k_clahe_hist, dim3(tiles, bands), dim3(CLAHE_THREADS), 0, fs, src, W, H, cfg.tiles_x, p.tw, p.th, table);
   HIPCHK(c, hipGetLastError());

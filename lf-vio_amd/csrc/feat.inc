@@ -6,16 +6,13 @@
 // pageable memory costs ~20 us each on this runtime: one packed pinned block instead of one copy per array.)
 
 static int feat_reserve(lfvio_ctx *c, size_t bytes) {
-  if (bytes <= c->feat_bytes) return LFVIO_OK;
-  if (c->d_feat) (void)hipFree(c->d_feat);
-  if (c->h_feat) (void)hipHostFree(c->h_feat);
-  c->d_feat = nullptr, c->h_feat = nullptr, c->feat_bytes = 0;
+  if (bytes <= c->h_feat.capacity()) return LFVIO_OK;  // (the two halves have one size, or are both empty)
+  (void)c->d_feat.reset(), (void)c->h_feat.reset();
   bytes = align_up(bytes + bytes / 4, 4096);
-  if (hipMalloc(&c->d_feat, bytes) != hipSuccess || hipHostMalloc((void **)&c->h_feat, bytes, hipHostMallocDefault) != hipSuccess) {
-    c->err = "out of memory (feature scratch)";
-    return LFVIO_ERR_DEVICE;
+  if (!c->d_feat.reserve(bytes) || !c->h_feat.reserve(bytes)) {
+    (void)c->d_feat.reset();
+    return out_of_memory(c, "out of memory (feature scratch)");
   }
-  c->feat_bytes = bytes;
   return LFVIO_OK;
 }
 

@@ -26,16 +26,7 @@ static GftWork gft_work(int W, int H) {
 }
 
 static int gft_reserve(lfvio_ctx *c, const GftWork &wk) {
-  lfvio_ctx::GftState &g = c->gft;
-  if (g.work_cap >= wk.bytes) return LFVIO_OK;
-  if (g.work) (void)hipFree(g.work);
-  g.work = nullptr, g.work_cap = 0;
-  if (hipMalloc((void **)&g.work, wk.bytes) != hipSuccess) {
-    c->err = "out of memory (corner detection)";
-    return LFVIO_ERR_DEVICE;
-  }
-  g.work_cap = wk.bytes;
-  return LFVIO_OK;
+  return c->gft.work.reserve(wk.bytes) ? LFVIO_OK : out_of_memory(c, "out of memory (corner detection)");
 }
 
 static int gft_launch_response(lfvio_ctx *c, hipStream_t fs, const GftWork &wk, const unsigned char *base, int r, int max_count) {
@@ -121,15 +112,11 @@ int lfvio_gft_set_mask(lfvio_ctx *c, int width, int height, const unsigned char 
   FeatStage st(c);
   const size_t oM = st.take(n);
   if (int rc = st.reserve()) return rc;
-  if (g.mask_cap < n) {
-    unsigned char *fresh = nullptr;
-    if (hipMalloc((void **)&fresh, n) != hipSuccess) {
-      c->err = "out of memory (base mask)";
-      return LFVIO_ERR_DEVICE;
-    }
+  if (g.mask.capacity() < n) {  // the new block first: a failure leaves the old mask, and mask_set, as they are
+    DevBuf<unsigned char> fresh;
+    if (!fresh.reserve(n)) return out_of_memory(c, "out of memory (base mask)");
     HIPCHK(c, hipStreamSynchronize(st.fs));
-    if (g.mask) (void)hipFree(g.mask);
-    g.mask = fresh, g.mask_cap = n, g.mask_set = false;
+    g.mask = std::move(fresh), g.mask_set = false;
   }
   std::memcpy(st.h + oM, pixels, n);
   if (int rc = st.up(st.end)) return rc;

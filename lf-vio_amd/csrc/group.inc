@@ -143,13 +143,12 @@ struct lfvio_group {
   bool uploaded = false, armed = false;
   int N = 0, M = 0, max_iter = 0;
   std::vector<int> cuts;
-  double *d_gather = nullptr;        // rank mode: inverse depths of all ranks, padded to equal counts (ncclAllGather)
-  size_t gather_cap = 0;
+  DevBuf<double> d_gather;           // rank mode: inverse depths of all ranks, padded to equal counts (ncclAllGather)
   int last_passes = 0, last_collectives = 0;
   bool force_collective = false;
   std::vector<char> failed;          // local contexts that failed in the running call: they enqueue nothing more, but every collective goes out
   int inject_ctx = -1, inject_pass = -1, inject_phase = -1;  // lfvio_debug_group_inject_failure (tests)
-  double *h_one = nullptr;           // pinned 1.0: what a failed rank writes into XS_ERR in front of every collective it still issues
+  PinBuf<double> h_one;              // pinned 1.0: what a failed rank writes into XS_ERR in front of every collective it still issues
   // independent windows split over the devices: slot s -> context s % L, local slot s / L
   int batch = 0;
 };
@@ -165,11 +164,13 @@ int group_fail(lfvio_group *g, int rc, const std::string &what) {
     ncclResult_t r_ = (call);                                                                       \
     if (r_ != ncclSuccess) return group_fail(g, LFVIO_ERR_DEVICE, std::string(#call) + ": " + rccl_api()->GetErrorString(r_)); \
   } while (0)
-#define GHIP(g, call)                                                                                \
+#define GHIP(g, call) GHIP_AS(g, call, #call)
+#define GHIP_AS(g, call, text)                                                                      \
   do {                                                                                              \
     hipError_t e_ = (call);                                                                         \
-    if (e_ != hipSuccess) return group_fail(g, LFVIO_ERR_DEVICE, std::string(#call) + ": " + hipGetErrorString(e_)); \
+    if (e_ != hipSuccess) return group_fail(g, LFVIO_ERR_DEVICE, std::string(text) + ": " + hipGetErrorString(e_)); \
   } while (0)
+#define GMEM(g, ok, text) GHIP_AS(g, (ok) ? hipSuccess : hipPeekAtLastError(), text)  // (as MEMCHK)
 #define GCTX(g, i, call)                                                                            \
   do {                                                                                              \
     int rc_ = (call);                                                                               \
@@ -191,7 +192,7 @@ int group_allreduce(lfvio_group *g, const XRanges &xr) {
       lfvio_ctx *c = g->ctx[i];
       GHIP(g, hipSetDevice(c->device));
       if (!g->h_one) {
-        GHIP(g, hipHostMalloc((void **)&g->h_one, sizeof(double), hipHostMallocDefault));
+        GMEM(g, g->h_one.reserve(sizeof(double)), "hipHostMalloc((void **)&g->h_one, sizeof(double), hipHostMallocDefault)");
         *g->h_one = 1.0;
       }
       GHIP(g, hipMemcpyAsync(c->d_base + c->L.xch + (size_t)(XOFF_C + XS_ERR) * 8, g->h_one, sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -332,13 +333,10 @@ void lfvio_group_destroy(lfvio_group *g) {
     }
   for (auto &e : g->ev)
     if (e) (void)hipEventDestroy(e);
-  if (g->d_gather) {
-    (void)hipSetDevice(g->ctx[0]->device);
-    (void)hipFree(g->d_gather);
-  }
-  if (g->h_one) (void)hipHostFree(g->h_one);
-  for (lfvio_ctx *c : g->ctx) lfvio_destroy(c);
-  delete g;
+  if (g->d_gather) (void)hipSetDevice(g->ctx[0]->device);
+  const std::vector<lfvio_ctx *> ctx = std::move(g->ctx);
+  delete g;  // its buffers, before the contexts
+  for (lfvio_ctx *c : ctx) lfvio_destroy(c);
 }
 
 const char *lfvio_group_last_error(const lfvio_group *g) { return g ? g->err.c_str() : "null group"; }
@@ -539,11 +537,9 @@ int lfvio_group_download(lfvio_group *g, LfvioSolution *sol, LfvioPrior *prior) 
     lfvio_ctx *c = g->ctx[0];
     GHIP(g, hipSetDevice(c->device));
     const size_t need = (size_t)pad * (g->world + 1) * sizeof(double);
-    if (need > g->gather_cap) {
-      if (g->d_gather) GHIP(g, hipFree(g->d_gather));
-      g->d_gather = nullptr, g->gather_cap = 0;
-      GHIP(g, hipMalloc((void **)&g->d_gather, need));
-      g->gather_cap = need;
+    if (need > g->d_gather.capacity()) {
+      GMEM(g, g->d_gather.reset(), "hipFree(g->d_gather)");
+      GMEM(g, g->d_gather.reserve(need), "hipMalloc((void **)&g->d_gather, need)");
     }
     double *send = g->d_gather, *recv = g->d_gather + pad;
     const int b = g->cuts[g->rank0], n = g->cuts[g->rank0 + 1] - b;

@@ -34,15 +34,7 @@ int lfvio_klt_track(lfvio_ctx *c, const LfvioKltIn *in, float *next_pts, unsigne
   const size_t oN = st.take((size_t)N * 8), oS = st.take((size_t)N), oT = st.take(nT);
   if (int rc = st.reserve()) return rc;
   const int nb = 1 - k.cur;  // (every earlier call on the feature stream has been waited for: nobody reads this buffer)
-  if (k.cap[nb] < full.bytes) {
-    if (k.d[nb]) (void)hipFree(k.d[nb]);
-    k.d[nb] = nullptr, k.cap[nb] = 0;
-    if (hipMalloc((void **)&k.d[nb], full.bytes) != hipSuccess) {
-      c->err = "out of memory (image pyramid)";
-      return LFVIO_ERR_DEVICE;
-    }
-    k.cap[nb] = full.bytes;
-  }
+  if (!k.d[nb].reserve(full.bytes)) return out_of_memory(c, "out of memory (image pyramid)");
   char *d = st.d, *h = st.h;
   if (N) std::memcpy(h + oP, in->prev_pts, (size_t)N * 8);
   std::memcpy(h + oI, in->image, nI);

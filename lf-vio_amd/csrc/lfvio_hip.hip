@@ -52,15 +52,19 @@ constexpr ncclDataType_t ncclDouble = 8;
 #include "kernels_gft.h"
 #include "kernels_clahe.h"
 #include "window_pack.h"
+#include "dev_mem.h"
 
-#define HIPCHK(ctx, call)                                                                      \
+#define HIPCHK(ctx, call) HIPCHK_AS(ctx, call, #call)
+#define HIPCHK_AS(ctx, call, text)                                                             \
   do {                                                                                         \
     hipError_t e_ = (call);                                                                    \
     if (e_ != hipSuccess) {                                                                    \
-      (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_);                          \
+      (ctx)->err = std::string(text) + ": " + hipGetErrorString(e_);                           \
       return LFVIO_ERR_DEVICE;                                                                 \
     }                                                                                          \
   } while (0)
+// a Buf's reserve() / reset() (dev_mem.h) under the text of the runtime call behind it, whose error is the runtime's last one
+#define MEMCHK(ctx, ok, text) HIPCHK_AS(ctx, (ok) ? hipSuccess : hipPeekAtLastError(), text)
 
 namespace {
 
@@ -140,44 +144,59 @@ struct GraphKey {
 
 }  // namespace
 
-struct lfvio_ctx {
+// The streams and events of a context, as its base: ~lfvio_ctx frees every buffer (the members) before this destroys a stream
+struct CtxQueues {
+  hipStream_t stream = nullptr, fstream = nullptr;
+  static constexpr int WORKERS = 2;  // two, so that the newest accepted state never waits for the round of an older one to notice it is stale
+  hipStream_t sstream[WORKERS] = {};
+  // the copies out of h_stage are awaited by the NEXT user of the staging block, not by the upload that enqueued them
+  hipEvent_t stage_event = nullptr;
+  static constexpr int FLAG_RING = 4;
+  hipEvent_t flag_event[FLAG_RING] = {};  // all four, or none (shard.inc)
+  ~CtxQueues() {
+    for (auto &e : flag_event)
+      if (e) (void)hipEventDestroy(e);
+    if (stage_event) (void)hipEventDestroy(stage_event);
+    if (fstream) (void)hipStreamDestroy(fstream);
+    for (auto &st : sstream)
+      if (st) (void)hipStreamDestroy(st);
+    if (stream) (void)hipStreamDestroy(stream);
+  }
+};
+
+// Every d_* (device) and h_* (pinned) block below is a Buf (dev_mem.h): owned here, grow-only, freed with the context.
+struct lfvio_ctx : CtxQueues {
   int device = 0;
-  hipStream_t stream = nullptr;
-  char *d_feat = nullptr;  // scratch of lfvio_triangulate / lfvio_shift_depth (grow-only)
-  size_t feat_bytes = 0;
-  char *h_feat = nullptr;  // pinned mirror of d_feat: the inputs of a feature step go up as ONE copy, its outputs come down as one
-  // lfvio_klt_track (klt.inc): two pyramid buffers of their own (grow-only); `cur` holds the resident image's levels 0 .. built
+  DevBuf<char> d_feat;  // scratch of lfvio_triangulate / lfvio_shift_depth
+  PinBuf<char> h_feat;  // pinned mirror of d_feat: the inputs of a feature step go up as ONE copy, its outputs come down as one
+  // lfvio_klt_track (klt.inc): two pyramid buffers of their own; `cur` holds the resident image's levels 0 .. built
   struct KltState {
-    unsigned char *d[2] = {nullptr, nullptr};
-    size_t cap[2] = {0, 0};
+    DevBuf<unsigned char> d[2];
     int cur = 0, w = 0, h = 0, built = 0;
     bool valid = false;
   } klt;
   // lfvio_gft_detect (gft.inc): the base mask (all 255 until lfvio_gft_set_mask; survives lfvio_klt_reset) and the work arrays of one
-  // image size (lambda, final mask, candidates, kept pixels, GftDev), both grow-only
+  // image size (lambda, final mask, candidates, kept pixels, GftDev)
   struct GftState {
-    unsigned char *mask = nullptr;
-    size_t mask_cap = 0;
+    DevBuf<unsigned char> mask;
     int mw = 0, mh = 0;
     bool mask_set = false;
-    char *work = nullptr;
-    size_t work_cap = 0;
+    DevBuf<char> work;
   } gft;
   // lfvio_clahe_set / lfvio_clahe_apply (clahe.inc): the setting (off after lfvio_create; survives lfvio_klt_reset) and the
   // [tiles][256] int table with the LUTs behind it, allocated at the first use; dirty: the table may hold counts
   struct ClaheState {
     bool on = false;
     LfvioClaheIn cfg = {};
-    char *work = nullptr;
+    DevBuf<char> work;
     bool dirty = false;
   } clahe;
   std::string err;
   int batch = 0;
   Layout L;
-  char *d_base = nullptr;
-  char *h_stage = nullptr;  // pinned, one slot's header + inputs
-  char *h_down = nullptr;   // pinned download buffer
-  size_t h_down_bytes = 0;
+  DevBuf<char> d_base;
+  PinBuf<char> h_stage;  // one slot's header + inputs
+  PinBuf<char> h_down;   // download buffer
   std::vector<SlotHostInfo> info;
   std::vector<int> perm_build;  // pack_window (window_pack.h) builds the next permutation here; commit_slot_info swaps it in
   // cached graph of the solve loop
@@ -193,38 +212,34 @@ struct lfvio_ctx {
   int predict_passes = 4;           // passes the first graph of the next call carries: the most any of the last four calls needed (predict()); tail[flag]: force-done + gated gauge fix + marginalization
   double pass_seconds = 2e-4;       // measured duration of one pass of a continuation chunk (sizes the first graph of a call with a wall-clock cap)
   GraphKey chunk_key;  // of chunk, tail, first and the workers' graphs
-  int *d_pending = nullptr;  // number of slots whose trust-region loop is not done
-  PendingBlock *h_pending = nullptr;
+  DevBuf<int> d_pending;  // number of slots whose trust-region loop is not done
+  PinBuf<PendingBlock> h_pending;
   // lfvio_batch_optimize_begin / _finish: the solution of slot 0 arrives in host memory the gated gauge fix writes directly
   // (Slot::mail, dev_types.h MAIL_*) while the marginalization of the same graph is still running.  What is in flight then, and what
   // every entry point has to wait for, is `call` (call_state.h: the state table; join_inflight: every entry point that touches the
   // slots or the stream starts with it).  The landmark-parallel steps either side of optimization()
   // (triangulate / shift_depth / preintegrate) have their own stream and scratch and do not wait for the tail.
   CallState call;
-  char *h_mail = nullptr, *d_mail = nullptr;
-  hipStream_t fstream = nullptr;
+  PinBuf<char, hipHostMallocMapped | hipHostMallocCoherent> h_mail;
+  char *d_mail = nullptr;  // h_mail in the device's address space
   // The marginalization run ahead of the loop's end (kernels_spec.h): a SHADOW slot behind the last one (contexts of one small
   // window), workers on a stream of their own (lowest priority: a third pool of hardware queues), one graph of SIDE_ROUNDS rounds
   // per marginalization flag and hand-over variant.  MAIL_TICKET: the ticket of the call in flight, echoed into MAIL_ECHO by the worker
   // that delivers its prior.
-  static constexpr int WORKERS = 2;  // two, so that the newest accepted state never waits for the round of an older one to notice it is stale
-  hipStream_t sstream[WORKERS] = {};
   bool shadow = false;          // the blob has batch + WORKERS slots, the last ones the shadows of slot 0
   bool marg_ahead = true;       // debug (lfvio_debug_configure): off = every call ends with the serial tail
   hipGraphExec_t side[WORKERS][2][2] = {};  // [worker][marg_flag][publish]
   long long stat_ahead_calls = 0, stat_ahead_hits = 0;  // calls with workers | priors a worker delivered
-  // the copies out of h_stage are awaited by the NEXT user of the staging block, not by the upload that enqueued them
-  hipEvent_t stage_event = nullptr;
-  bool stage_busy = false;
+  bool stage_busy = false;  // stage_event is recorded and not yet waited for
   double up_us[4] = {0, 0, 0, 0};  // last upload: host packing | collecting the chained prior | prior + copies enqueued | final synchronization (lfvio_debug_query "upload_times")
   // a prior collected on the caller's behalf because the slots had to be re-allocated while its call was in flight
   // (reserve, CallState::HELD): lfvio_batch_optimize_finish / lfvio_batch_upload_chained hand it over
   std::unique_ptr<LfvioPrior> held;
   int mail_seq = 0;             // sequence number of the last upload (Slot::mail_seq)
   std::unique_ptr<LfvioPrior> chain_struct;  // the structure-only prior of a device-chained upload
-  // lfvio_solve_relo (relo.inc): the route's device blob and pinned staging blob (grow-only), the loop's `done` word read per pass
-  char *d_relo = nullptr, *h_relo = nullptr;
-  size_t relo_dev_cap = 0, relo_stage_cap = 0;
+  // lfvio_solve_relo (relo.inc): the route's device blob and pinned staging blob, the loop's `done` word read per pass
+  DevBuf<char> d_relo;
+  PinBuf<char> h_relo;
   int relo_done_word = 0;
   bool relo_force = false;  // lfvio_debug_configure "relo_route": the relo route even without a match
   bool debug_break_chain = false;  // lfvio_debug_configure "break_next_chain": the next device-chained upload promises a prior of another size than the device will find
@@ -234,8 +249,8 @@ struct lfvio_ctx {
   int last_iters = 0;   // ... and, for one window, the iterations they covered: a window whose steps are mostly rejected gets more speculative candidates per pass
   bool fixed_spec = false;  // lfvio_debug_configure "spec_count": a fixed number of candidates (measurements)
   int spec_count = 3;   // candidates per pass of a speculating launch: radius, radius / 2, radius / 4 (, radius / 8)
-  int *d_lwt = nullptr;  // static table of k_linw's phase 3 (kernels_linw.h LWT_*)
-  int *d_asm = nullptr;  // static scatter table of k_solve_dense<true> (kernels_solve.h ASM_*)
+  DevBuf<int> d_lwt;  // static table of k_linw's phase 3 (kernels_linw.h LWT_*)
+  DevBuf<int> d_asm;  // static scatter table of k_solve_dense<true> (kernels_solve.h ASM_*)
   bool shard_group = false;  // the resident shard is driven by an lfvio_group (two collectives per pass: shard.inc phase 4)
   int shard_kmax0 = -1;  // lfvio_shard_begin: the longest track among the WHOLE window's frame-0 landmarks (0: none), for the marginalization's plan
   int lm_half = 1;       // windows of at most SPEC_MAX_LM landmarks: 8 lanes per track in k_lin's landmark role (lfvio_debug_configure "lm_half" 0: the 4-lane form)
@@ -249,14 +264,16 @@ struct lfvio_ctx {
   int shard_begin = 0, shard_end = 0, shard_state = 0;
   std::vector<int> sh_start, sh_off;
   // stream-ordered sharded driver: ring of pinned flag records, one per enqueued decision (shard.inc)
-  static constexpr int FLAG_RING = 4;
-  int *h_flags = nullptr;
-  hipEvent_t flag_event[FLAG_RING] = {};
+  PinBuf<int> h_flags;
   long long flag_head = 0, flag_tail = 0;
 };
 
 namespace {
 
+int out_of_memory(lfvio_ctx *c, const char *what) {  // a Buf that could not grow, under the text its call site has always reported
+  c->err = what;
+  return LFVIO_ERR_DEVICE;
+}
 // keep_side: the workers' graphs (kernels_spec.h) stay — they are captured for the slot's CAPACITY, not for the resident window's launch
 // dimensions, and a stream of windows changes those every few frames
 void destroy_graph(lfvio_ctx *c, bool keep_side = false) {
@@ -303,7 +320,7 @@ void record_call(lfvio_ctx *c, int passes, int iters, unsigned act) {
   c->last_passes = std::max(passes, 1), c->last_iters = iters;
   if (act & CallState::FEED_PREDICTION) predict(c);
 }
-volatile int *mail_word(lfvio_ctx *c, MailWord w) { return (volatile int *)c->h_mail + w; }
+volatile int *mail_word(lfvio_ctx *c, MailWord w) { return (volatile int *)c->h_mail.get() + w; }
 // The call whose loop has just ended on stream 0 left its prior to a worker on the second stream (TAIL_WORKER, kernels_spec.h): wait
 // for the worker's echo of the call's ticket — it follows the prior's arrival in slot 0 (and in the mailbox) behind a system-scope
 // fence.  Stream 0 is idle when this is called.
@@ -355,7 +372,7 @@ int join_inflight(lfvio_ctx *c, CallState::Overtake overtake = CallState::WAIT) 
 // (the flag is the sequence number of the resident window's upload: a window optimized behind the marginalization of the one
 // before must not take that one's late prior flag for its own)
 bool wait_early(lfvio_ctx *c) {
-  int *flag = (int *)c->h_mail + MAIL_STATE_FLAG;
+  int *flag = (int *)c->h_mail.get() + MAIL_STATE_FLAG;
   const int want = c->info[0].mail_seq;
   for (;;) {
     if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == want) return true;
@@ -376,21 +393,19 @@ int reserve(lfvio_ctx *c, int batch, int maxN, int maxM) {
   maxN = std::max(maxN, c->L.maxN);
   maxM = std::max(maxM, c->L.maxM);
   destroy_graph(c);
-  if (c->d_base) HIPCHK(c, hipFree(c->d_base));
-  if (c->h_stage) HIPCHK(c, hipHostFree(c->h_stage));
-  if (c->h_down) HIPCHK(c, hipHostFree(c->h_down));
-  c->d_base = nullptr, c->h_stage = nullptr, c->h_down = nullptr;
+  MEMCHK(c, c->d_base.reset(), "hipFree(c->d_base)");
+  MEMCHK(c, c->h_stage.reset(), "hipHostFree(c->h_stage)");
+  MEMCHK(c, c->h_down.reset(), "hipHostFree(c->h_down)");
   c->stage_busy = false;  // (hipFree above waited for the device)
   // grow with headroom so a slowly growing window does not re-allocate every frame
   Layout L = make_layout(maxN + maxN / 4 + 64, maxM + maxM / 4 + 256);
   // one small window: a shadow slot behind it for the marginalization run ahead (kernels_spec.h)
   c->shadow = batch == 1 && L.maxN <= SHADOW_MAX_LM && c->sstream[0] && c->sstream[lfvio_ctx::WORKERS - 1] && c->d_mail;
   const size_t slots = (size_t)batch + (c->shadow ? lfvio_ctx::WORKERS : 0);
-  HIPCHK(c, hipMalloc((void **)&c->d_base, L.total * slots));
+  MEMCHK(c, c->d_base.reserve(L.total * slots), "hipMalloc((void **)&c->d_base, L.total * slots)");
   HIPCHK(c, hipMemsetAsync(c->d_base, 0, L.total * slots, c->stream));
-  HIPCHK(c, hipHostMalloc((void **)&c->h_stage, L.linw_end, hipHostMallocDefault));
-  c->h_down_bytes = down_bytes(L.maxN);
-  HIPCHK(c, hipHostMalloc((void **)&c->h_down, c->h_down_bytes, hipHostMallocDefault));
+  MEMCHK(c, c->h_stage.reserve(L.linw_end), "hipHostMalloc((void **)&c->h_stage, L.linw_end, hipHostMallocDefault)");
+  MEMCHK(c, c->h_down.reserve(down_bytes(L.maxN)), "hipHostMalloc((void **)&c->h_down, c->h_down_bytes, hipHostMallocDefault)");
   c->L = L;
   c->batch = batch;
   c->info.assign(batch, SlotHostInfo());
@@ -985,7 +1000,7 @@ int enqueue_marg(lfvio_ctx *c, const CallPlan &p, MargKind kind);
 // then *early = the solution is in the mailbox while the rest of the graph is still running (wait_early)
 template <class F>
 int launch_watched(lfvio_ctx *c, hipGraphExec_t graph, bool watch, bool *early, F &&behind) {
-  if (watch) __atomic_store_n((int *)c->h_mail + MAIL_PRIOR_FLAG, 0, __ATOMIC_RELAXED), __atomic_store_n((int *)c->h_mail + MAIL_STATE_FLAG, 0, __ATOMIC_RELEASE);
+  if (watch) __atomic_store_n((int *)c->h_mail.get() + MAIL_PRIOR_FLAG, 0, __ATOMIC_RELAXED), __atomic_store_n((int *)c->h_mail.get() + MAIL_STATE_FLAG, 0, __ATOMIC_RELEASE);
   HIPCHK(c, hipGraphLaunch(graph, c->stream));
   if (int rc = behind()) return rc;
   *early = watch && wait_early(c);
@@ -1012,8 +1027,8 @@ int loop_graphs(lfvio_ctx *c, const Route &r, const CallPlan &p, int passes, Loo
   // evaluated (measured with a fixed count: 0.532 / 0.511 ms resident with 3 / 4, 0.950 / 0.963 ms on the stream).
   if (speculate && !c->fixed_spec) c->spec_count = (c->last_iters > 0 && c->last_iters >= 2 * c->last_passes) ? std::min(4, 1 + SPEC_EXTRA) : 3;
   if (!c->d_pending) {
-    HIPCHK(c, hipMalloc((void **)&c->d_pending, 256));
-    HIPCHK(c, hipHostMalloc((void **)&c->h_pending, 256, hipHostMallocDefault));
+    MEMCHK(c, c->d_pending.reserve(256), "hipMalloc((void **)&c->d_pending, 256)");
+    MEMCHK(c, c->h_pending.reserve(256), "hipHostMalloc((void **)&c->h_pending, 256, hipHostMallocDefault)");
   }
   const int offs = r.offs;
   const GraphKey key = graph_key(r, (int)speculate, 0, true);
@@ -1431,11 +1446,10 @@ lfvio_ctx *lfvio_create(int device) {
       if (least == greatest || hipStreamCreateWithPriority(&c->sstream[wk], hipStreamNonBlocking, least) != hipSuccess) c->sstream[wk] = nullptr;
   }
   // the mailbox: fine-grained host memory mapped into the device's address space.  Without it begin() simply waits for the end.
-  if (hipHostMalloc((void **)&c->h_mail, MAIL_BYTES, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess) {
+  if (c->h_mail.reserve(MAIL_BYTES)) {
     std::memset(c->h_mail, 0, MAIL_BYTES);
     if (hipHostGetDevicePointer((void **)&c->d_mail, c->h_mail, 0) != hipSuccess) c->d_mail = nullptr;
   } else {
-    c->h_mail = nullptr;
     (void)hipGetLastError();
   }
   // kernels that need more than the default 64 KiB of LDS
@@ -1468,7 +1482,7 @@ lfvio_ctx *lfvio_create(int device) {
       if (r == 72 || cc == 72) at |= LWT_TD;
       tab[e] = at;
     }
-    if (hipMalloc((void **)&c->d_lwt, sizeof(int) * tab.size()) != hipSuccess ||
+    if (!c->d_lwt.reserve(sizeof(int) * tab.size()) ||
         hipMemcpy(c->d_lwt, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice) != hipSuccess) {
       lfvio_destroy(c);
       return nullptr;
@@ -1488,7 +1502,7 @@ lfvio_ctx *lfvio_create(int device) {
       std::sort(ent.begin(), ent.end());
       for (size_t k = 0; k < ent.size(); k++) tab[ASM_VIS + par * ASM_IMU_HALF + k] = ent[k].second | (ent[k].first << 16);
     }
-    if (hipMalloc((void **)&c->d_asm, sizeof(int) * tab.size()) != hipSuccess ||
+    if (!c->d_asm.reserve(sizeof(int) * tab.size()) ||
         hipMemcpy(c->d_asm, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice) != hipSuccess) {
       lfvio_destroy(c);
       return nullptr;
@@ -1504,33 +1518,7 @@ void lfvio_destroy(lfvio_ctx *c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
   destroy_graph(c);
-  if (c->d_base) (void)hipFree(c->d_base);
-  if (c->d_feat) (void)hipFree(c->d_feat);
-  if (c->h_feat) (void)hipHostFree(c->h_feat);
-  for (auto &p : c->klt.d)
-    if (p) (void)hipFree(p);
-  if (c->gft.mask) (void)hipFree(c->gft.mask);
-  if (c->gft.work) (void)hipFree(c->gft.work);
-  if (c->clahe.work) (void)hipFree(c->clahe.work);
-  if (c->h_stage) (void)hipHostFree(c->h_stage);
-  if (c->h_down) (void)hipHostFree(c->h_down);
-  if (c->d_asm) (void)hipFree(c->d_asm);
-  if (c->d_relo) (void)hipFree(c->d_relo);
-  if (c->h_relo) (void)hipHostFree(c->h_relo);
-  if (c->d_lwt) (void)hipFree(c->d_lwt);
-  if (c->d_pending) (void)hipFree(c->d_pending);
-  if (c->h_pending) (void)hipHostFree(c->h_pending);
-  if (c->h_flags) {
-    (void)hipHostFree(c->h_flags);
-    for (auto &e : c->flag_event) (void)hipEventDestroy(e);
-  }
-  if (c->stage_event) (void)hipEventDestroy(c->stage_event);
-  if (c->h_mail) (void)hipHostFree(c->h_mail);
-  if (c->fstream) (void)hipStreamDestroy(c->fstream);
-  for (auto &st : c->sstream)
-    if (st) (void)hipStreamDestroy(st);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
-  delete c;
+  delete c;  // the buffers, then the events and streams (CtxQueues)
 }
 
 const char *lfvio_last_error(const lfvio_ctx *c) { return c ? c->err.c_str() : "null context"; }
@@ -1712,7 +1700,7 @@ int lfvio_batch_optimize_finish(lfvio_ctx *c, LfvioPrior *prior) {
   }
   if (c->call.early() && prior) {
     // the marginalization ends by pushing its prior into the mailbox (publish_prior): wait for that word, not for the stream
-    int *flag = (int *)c->h_mail + MAIL_PRIOR_FLAG;
+    int *flag = (int *)c->h_mail.get() + MAIL_PRIOR_FLAG;
     const int want = c->info[0].mail_seq;
     bool there = false;
     for (;;) {

@@ -67,16 +67,8 @@ ReloLayout relo_layout(int N, int M, int K, int R, int pn) {
 }
 
 int relo_grow(lfvio_ctx *c, size_t dev_bytes, size_t stage_bytes) {
-  if (dev_bytes > c->relo_dev_cap) {
-    if (c->d_relo) (void)hipFree(c->d_relo), c->d_relo = nullptr, c->relo_dev_cap = 0;
-    HIPCHK(c, hipMalloc((void **)&c->d_relo, dev_bytes));
-    c->relo_dev_cap = dev_bytes;
-  }
-  if (stage_bytes > c->relo_stage_cap) {
-    if (c->h_relo) (void)hipHostFree(c->h_relo), c->h_relo = nullptr, c->relo_stage_cap = 0;
-    HIPCHK(c, hipHostMalloc((void **)&c->h_relo, stage_bytes, hipHostMallocDefault));
-    c->relo_stage_cap = stage_bytes;
-  }
+  MEMCHK(c, c->d_relo.reserve(dev_bytes), "hipMalloc((void **)&c->d_relo, dev_bytes)");
+  MEMCHK(c, c->h_relo.reserve(stage_bytes), "hipHostMalloc((void **)&c->h_relo, stage_bytes, hipHostMallocDefault)");
   return LFVIO_OK;
 }
 

@@ -102,7 +102,7 @@ int lfvio_shard_decide(lfvio_ctx *c, int *state) {
   if (!c || !c->shard_active || !state) return LFVIO_ERR_ARG;
   hipLaunchKernelGGL(k_decide, dim3(1, 1), dim3(64), 0, c->stream, c->d_base, c->L.total);
   HIPCHK(c, hipGetLastError());
-  TRState *tr = (TRState *)c->h_down;
+  TRState *tr = (TRState *)c->h_down.get();
   HIPCHK(c, hipMemcpyAsync(tr, c->d_base + offsetof(Slot, tr), offsetof(TRState, it), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (tr->done) c->shard_state = 2;
@@ -170,9 +170,15 @@ int lfvio_shard_enqueue(lfvio_ctx *c, int phase) {
         c->err = "more than FLAG_RING decisions in flight: poll first";
         return LFVIO_ERR_ARG;
       }
-      if (!c->h_flags) {
-        HIPCHK(c, hipHostMalloc((void **)&c->h_flags, sizeof(int) * 16 * lfvio_ctx::FLAG_RING, hipHostMallocDefault));
-        for (auto &e : c->flag_event) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+      if (!c->h_flags) {  // the ring and its four events, or (a failure) neither
+        MEMCHK(c, c->h_flags.reserve(sizeof(int) * 16 * lfvio_ctx::FLAG_RING), "hipHostMalloc((void **)&c->h_flags, sizeof(int) * 16 * lfvio_ctx::FLAG_RING, hipHostMallocDefault)");
+        hipError_t made = hipSuccess;
+        for (auto &e : c->flag_event)
+          if (made == hipSuccess) made = hipEventCreateWithFlags(&e, hipEventDisableTiming);
+        for (auto &e : c->flag_event)
+          if (made != hipSuccess && e) (void)hipEventDestroy(e), e = nullptr;
+        if (made != hipSuccess) (void)c->h_flags.reset();
+        HIPCHK_AS(c, made, "hipEventCreateWithFlags(&e, hipEventDisableTiming)");
       }
       hipLaunchKernelGGL(k_decide, dim3(1, 1), dim3(64), 0, c->stream, c->d_base, st);
       const int slot = c->flag_head % lfvio_ctx::FLAG_RING;
