@@ -640,8 +640,9 @@ int lfvio_relative_pose(lfvio_ctx *ctx, const LfvioRelativePoseIn *in, unsigned 
 
 /* lfvio_klt_track: the optical flow of FeatureTracker::readImage — cv::calcOpticalFlowPyrLK(cur_img, forw_img, cur_pts, forw_pts,
  * status, err, cv::Size(41, 41), 3) at feature_tracker/src/feature_tracker.cpp:127 and the inBorder test of :6-12, :129-131.  The
- * goodFeaturesToTrack and setMask are lfvio_gft_detect below, the CLAHE of :101-107 is lfvio_clahe_set below them; the rest of
- * feature_tracker/ (rejectWithF, undistortedPoints) stays the caller's.
+ * goodFeaturesToTrack and setMask are lfvio_gft_detect below, the CLAHE of :101-107 is lfvio_clahe_set below them, rejectWithF and
+ * undistortedPoints are lfvio_track_reject / lfvio_track_undistort below those; what stays the caller's is the host class around
+ * these calls (the vectors, reduceVector, updateID) and the images in the trace format.
  * One call uploads `image`, builds its pyramid, tracks the N points from the pyramid of the PREVIOUS call's image (resident in the
  * context: cur_img = forw_img, :180) into the new one, and makes the new pyramid the resident one.  A context with no resident image —
  * after lfvio_create, after lfvio_klt_reset, or when width or height differ from the resident image's — treats `image` as both
@@ -767,6 +768,76 @@ typedef struct {
 int lfvio_clahe_set(lfvio_ctx *ctx, const LfvioClaheIn *cfg /* NULL: off */);
 int lfvio_clahe_apply(lfvio_ctx *ctx, const LfvioClaheIn *cfg, int width, int height, const unsigned char *pixels,
                       unsigned char *out /* [height][width] */, unsigned char *lut /* [tiles_y][tiles_x][256], or NULL */);
+
+/* lfvio_track_reject / lfvio_track_undistort / lfvio_track_reset: the two steps of FeatureTracker::readImage that need the camera —
+ * rejectWithF() (feature_tracker/src/feature_tracker.cpp:329-386, with myfindFundamentalMat :266-327) and undistortedPoints()
+ * (:441-504) — with OCAMCamera::liftProjective (camera_model/src/camera_models/ScaramuzzaCamera.cc:623-645) on the device.
+ *   the lift  of a pixel (px, py) (cv::Point2f), in double, every operation rounded on its own (nothing fused):
+ *             x = (double)px - cx, y = (double)py - cy; xa = inv_scale * (x - d * y), ya = inv_scale * (-e * x + c * y) with
+ *             inv_scale = 1.0 / (c - d * e), computed once on the host; phi = sqrt(xa * xa + ya * ya); z = 0, p = 1, for i = 0 .. 4:
+ *             z += p * poly[i], p *= phi; P = (xa, ya, -z) (the sign is the reference's, :644).
+ *   the norm  n = sqrt((P.x P.x + P.y P.y) + P.z P.z), left to right.  Eigen's own reduction may order the three terms differently
+ *             and differ in the last bit; the reference does not build without Eigen and OpenCV, so the two were never compared.
+ * tests/track_ref.py restates both calls in numpy and is the specification; the device gives its bits.
+ *
+ * lfvio_track_reject: the bearings are P / n, a true division per component, of cur_pts (corr1) and forw_pts (corr2).  Per sample
+ * set compute_E_21 and check_inliers; the first hypothesis with the largest score > 0 wins; the refit over the winner's inliers and
+ * check_inliers again; that mask is status[].  compute_E_21 (:186-217) and check_inliers (:218-264) are those of
+ * initial_ex_rotation.cpp: this is lfvio_two_view's arithmetic up to its mask, bit for bit on the same bearings and sample sets,
+ * without the decomposition and the triangulations.  The sample sets are an INPUT, as for lfvio_two_view.
+ *   out->status 0   a model was found; status[] is its mask, num_inliers its count, E the refit's.
+ *   out->status 1   no hypothesis scored > 0, or the winner has fewer than 8 inliers.  status[] is all 1 (nothing is rejected), E is
+ *                   untouched, best_sample and num_inliers are as lfvio_two_view reports them.  A stated deviation: the reference
+ *                   throws from vector::at there.
+ *   out->status 2   N < 8 (the test of :331 failing): no device work, status[] all 1, best_sample -1, num_inliers 0, best_score 0,
+ *                   E and the bearing outputs untouched.
+ * bearing_cur / bearing_forw (or NULL) receive the unit bearings where the device ran (status 0 and 1).
+ * LFVIO_ERR_ARG (every output untouched): null ctx / in / camera / status / out, cur_pts or forw_pts null with N > 0, a model other
+ * than LFVIO_CAM_OCAM, N outside [0, 4096]; with N >= 8: samples null, S outside [1, 1024], a sample index outside [0, N).
+ *
+ * lfvio_track_undistort: un_pts = ((float)(P.x / P.z), (float)(P.y / P.z)); un_pts_3d = (float)(P.k / n) per component.  The
+ * context keeps what prev_un_pts_map_3d is: the (id, un_pts_3d) pairs of the PREVIOUS call, with std::map::insert semantics — the
+ * first occurrence of an id wins; ids are taken AS PASSED, so a point that was -1 in that call is in the map under -1, even if the
+ * caller numbered it afterwards, and -1 is never looked up: a new corner has zero velocity on its second frame too (the
+ * reference's behaviour, restated, not repaired).  Velocity of point i: with ids[i] != -1 and the id found at index j of the
+ * previous call, (float)((double)(cur_3d[i].k - prev_3d[j].k) / dt), the subtraction in float (cv::Point3f members), dt = time -
+ * (the previous call's time) in double; otherwise 0.  All velocities are 0 when the map is empty: a first call, a call after
+ * lfvio_track_reset, a call after a call with N = 0.  dt == 0 and non-finite pixels keep IEEE semantics.  matched (or NULL)
+ * receives j, or -1.  After the call the map and the time are this call's.  A stated deviation: the reference forgets to clear
+ * pts_velocity_3d in the empty-map branch; here the output has exactly N entries.
+ * LFVIO_ERR_ARG (every output, the resident map and the time untouched): null ctx / in / camera, pts, ids, un_pts, un_pts_3d or
+ * velocity_3d null with N > 0, a model other than LFVIO_CAM_OCAM, N outside [0, 4096], a NaN time.
+ * All three run on the feature stream like lfvio_klt_track: they do not wait for an optimization in flight.  The two maps live in
+ * device memory of their own (2 x 64 KiB, allocated at the first use), not in the feature calls' staging block. */
+#define LFVIO_CAM_OCAM 0
+#define LFVIO_TRACK_MAX_POINTS 4096
+typedef struct {
+  int model;           /* LFVIO_CAM_OCAM; anything else: LFVIO_ERR_ARG */
+  double cx, cy;       /* center_x, center_y */
+  double c, d, e;      /* the affine part; inv_scale = 1.0 / (c - d * e) */
+  double poly[5];      /* SCARAMUZZA_POLY_SIZE */
+} LfvioCamera;
+typedef struct {
+  const LfvioCamera *camera;
+  int num_points;          /* N, 0 .. 4096 */
+  const float *cur_pts;    /* [N][2] cv::Point2f, after the flow's reduceVector */
+  const float *forw_pts;   /* [N][2] */
+  int num_samples;         /* S in [1, 1024]; the reference: 100 */
+  const int *samples;      /* [S][8] indices into the matches */
+} LfvioTrackRejectIn;
+typedef struct { int status, best_sample, num_inliers; double best_score, E[9]; } LfvioTrackRejectOut;
+int lfvio_track_reject(lfvio_ctx *ctx, const LfvioTrackRejectIn *in, unsigned char *status /* [N] */, LfvioTrackRejectOut *out,
+                       double *bearing_cur /* [N][3] or NULL */, double *bearing_forw /* [N][3] or NULL */);
+typedef struct {
+  const LfvioCamera *camera;
+  int num_points;      /* N, 0 .. 4096 */
+  const float *pts;    /* [N][2] cur_pts */
+  const int *ids;      /* [N], -1: not yet numbered */
+  double time;         /* cur_time */
+} LfvioTrackUndistortIn;
+int lfvio_track_undistort(lfvio_ctx *ctx, const LfvioTrackUndistortIn *in, float *un_pts /* [N][2] */, float *un_pts_3d /* [N][3] */,
+                          float *velocity_3d /* [N][3] */, int *matched /* [N]: index in the previous call, or -1; or NULL */);
+int lfvio_track_reset(lfvio_ctx *ctx);   /* forget the resident map and time */
 
 /* ---- landmark-sharded API (multi-GPU) ------------------------
  * Every rank passes the same window but linearizes only landmarks [lm_begin, lm_end) (caller order);

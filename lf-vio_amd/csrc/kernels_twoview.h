@@ -206,7 +206,9 @@ struct TvFit {
 // with 1 only f.best, f.n_in and f.best_score are.  UNIT: a match counts when both dot products DIVIDED BY THE NORMS of the
 // triangulated point are > 0 (recoverPose, solve_5pts.cpp:436-440: a non-finite point does not count) instead of the plain dot
 // products of testTriangulation (initial_ex_rotation.cpp:310-311).  Shared by k_tv_fit and k_rp_fit (kernels_relpose.h).
-template <bool UNIT>
+// MASK_ONLY: stop behind the returned mask (k_trk_fit, kernels_track.h: rejectWithF keeps nothing else); with 0 the mask, f.best,
+// f.n_in, f.best_score and f.E are written and nothing more.
+template <bool UNIT, bool MASK_ONLY = false>
 DEV int tv_fit_body(int N, int S, const double *bl, const double *br, const double *E_all, const float *score_all, double *A, unsigned char *mask,
                     TvFitLds &lds, TvFit &f) {
   constexpr int NT = TV_FIT_THREADS;
@@ -284,6 +286,7 @@ DEV int tv_fit_body(int N, int S, const double *bl, const double *br, const doub
   }
   n_in = block_sum<NT>(n_in, red, tid);
   f.n_in = (int)n_in;
+  if constexpr (MASK_ONLY) return 0;
   // decomposeE (:321-336) from the SVD the projection already holds: E = sigma_1 u_1 v_1^T + sigma_2 u_2 v_2^T.  u_3 and
   // v_3 are the cross products, so det U = det V = +1 and both candidates are proper rotations.
   d3 u1, u2, u3;

@@ -51,6 +51,7 @@ constexpr ncclDataType_t ncclDouble = 8;
 #include "kernels_klt.h"
 #include "kernels_gft.h"
 #include "kernels_clahe.h"
+#include "kernels_track.h"
 #include "window_pack.h"
 #include "dev_mem.h"
 
@@ -191,6 +192,13 @@ struct lfvio_ctx : CtxQueues {
     DevBuf<char> work;
     bool dirty = false;
   } clahe;
+  // lfvio_track_undistort (track.inc): the (id, un_pts_3d) pairs of the previous call — [4096 ints | 4096 x 3 floats] twice, allocated
+  // at the first use; `cur` holds the `count` resident pairs (0: the map is empty), `time` is that call's
+  struct TrackState {
+    DevBuf<char> map[2];
+    int cur = 0, count = 0;
+    double time = 0.0;
+  } track;
   std::string err;
   int batch = 0;
   Layout L;
@@ -2067,6 +2075,8 @@ int lfvio_debug_query(lfvio_ctx *c, const char *key, double *out, int n) {
 #include "klt.inc"
 
 #include "gft.inc"
+
+#include "track.inc"
 // ---- landmark-sharded API: declared in lfvio.h, implemented in shard.inc
 #include "shard.inc"
 // ---- multi-GPU groups (RCCL): declared in lfvio.h, implemented in group.inc

@@ -656,6 +656,38 @@ class ClaheInC(C.Structure):
 
 CLAHE_MAX_TILES = 16  # LFVIO_CLAHE_MAX_TILES
 
+
+class CameraC(C.Structure):
+    """LfvioCamera (include/lfvio.h)."""
+    _fields_ = [("model", C.c_int), ("cx", C.c_double), ("cy", C.c_double), ("c", C.c_double), ("d", C.c_double), ("e", C.c_double),
+                ("poly", C.c_double * 5)]
+
+
+class TrackRejectInC(C.Structure):
+    """LfvioTrackRejectIn (include/lfvio.h)."""
+    _fields_ = [
+        ("camera", C.POINTER(CameraC)),
+        ("num_points", C.c_int),
+        ("cur_pts", C.POINTER(C.c_float)),
+        ("forw_pts", C.POINTER(C.c_float)),
+        ("num_samples", C.c_int),
+        ("samples", C.POINTER(C.c_int)),
+    ]
+
+
+class TrackRejectOutC(C.Structure):
+    """LfvioTrackRejectOut (include/lfvio.h)."""
+    _fields_ = [("status", C.c_int), ("best_sample", C.c_int), ("num_inliers", C.c_int), ("best_score", C.c_double), ("E", C.c_double * 9)]
+
+
+class TrackUndistortInC(C.Structure):
+    """LfvioTrackUndistortIn (include/lfvio.h)."""
+    _fields_ = [("camera", C.POINTER(CameraC)), ("num_points", C.c_int), ("pts", C.POINTER(C.c_float)), ("ids", C.POINTER(C.c_int)),
+                ("time", C.c_double)]
+
+
+CAM_OCAM, TRACK_MAX_POINTS = 0, 4096  # LFVIO_CAM_OCAM, LFVIO_TRACK_MAX_POINTS
+
 RELPOSE_MIN_MATCHES = 20  # a pair runs when N > 20 (estimator.cpp:452)
 
 HIP_SYMBOLS = [
@@ -669,6 +701,7 @@ HIP_SYMBOLS = [
     "lfvio_two_view", "lfvio_vi_align", "lfvio_pnp", "lfvio_sfm_ba", "lfvio_sfm_construct", "lfvio_relative_pose",
     "lfvio_klt_track", "lfvio_klt_reset", "lfvio_klt_level", "lfvio_gft_detect", "lfvio_gft_set_mask", "lfvio_gft_response",
     "lfvio_clahe_set", "lfvio_clahe_apply",
+    "lfvio_track_reject", "lfvio_track_undistort", "lfvio_track_reset",
     "lfvio_group_create", "lfvio_group_unique_id", "lfvio_group_create_rank", "lfvio_group_create_local", "lfvio_group_destroy",
     "lfvio_group_last_error", "lfvio_group_size", "lfvio_group_local", "lfvio_group_rank", "lfvio_group_ctx", "lfvio_group_backend",
     "lfvio_group_solve", "lfvio_group_upload", "lfvio_group_optimize", "lfvio_group_download", "lfvio_group_range",
@@ -754,6 +787,10 @@ def load_hip_library(path=None):
     if hasattr(lib, "lfvio_clahe_set"):
         lib.lfvio_clahe_set.argtypes = [C.c_void_p, C.POINTER(ClaheInC)]
         lib.lfvio_clahe_apply.argtypes = [C.c_void_p, C.POINTER(ClaheInC), C.c_int, C.c_int] + [C.POINTER(C.c_ubyte)] * 3
+    if hasattr(lib, "lfvio_track_reject"):
+        lib.lfvio_track_reject.argtypes = [C.c_void_p, C.POINTER(TrackRejectInC), C.POINTER(C.c_ubyte), C.POINTER(TrackRejectOutC), _dp, _dp]
+        lib.lfvio_track_undistort.argtypes = [C.c_void_p, C.POINTER(TrackUndistortInC)] + [C.POINTER(C.c_float)] * 3 + [C.POINTER(C.c_int)]
+        lib.lfvio_track_reset.argtypes = [C.c_void_p]
     lib.lfvio_shard_marg_linearize.argtypes = [C.c_void_p, C.c_int]
     lib.lfvio_shard_marg_finish.argtypes = [C.c_void_p, C.c_int, C.POINTER(Prior)]
     # multi-GPU groups (RCCL inside the library)

@@ -541,6 +541,80 @@ class Engine:
         self._check(rc, "lfvio_clahe_apply")
         return (out, lut) if want_lut else out
 
+    @staticmethod
+    def camera(cam):
+        """A CameraC from a dict with cx, cy, c, d, e, poly [5] and, optionally, model (LFVIO_CAM_OCAM); None: a null pointer."""
+        if cam is None or isinstance(cam, abi.CameraC):
+            return cam
+        return abi.CameraC(int(cam.get("model", abi.CAM_OCAM)), cam["cx"], cam["cy"], cam["c"], cam["d"], cam["e"],
+                           (C.c_double * 5)(*[float(v) for v in cam["poly"]]))
+
+    def track_reject(self, cam, cur_pts, forw_pts, samples, want_bearings=False, status=None, out=None, bearings=None, num_points=None,
+                     num_samples=None, check=True):
+        """lfvio_track_reject: rejectWithF on the matches cur_pts -> forw_pts [N, 2] float32 of the camera `cam` (camera()) with the
+        sample sets [S, 8].  Returns the fields of LfvioTrackRejectOut as a dict plus mask (= status[], uint8 [N]), rc and, with
+        want_bearings, bearing_cur / bearing_forw [N, 3].  status / out / bearings = (cur, forw): buffers to be written, num_points /
+        num_samples: the struct's fields whatever the arrays say, cam / cur_pts / forw_pts / samples None: null pointers (tests of
+        what a refused call leaves alone); check=False returns the error code under `rc` instead of raising."""
+        fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int)
+        cur = None if cur_pts is None else np.ascontiguousarray(cur_pts, dtype=np.float32).reshape(-1, 2)
+        forw = None if forw_pts is None else np.ascontiguousarray(forw_pts, dtype=np.float32).reshape(-1, 2)
+        sm = None if samples is None else np.ascontiguousarray(samples, dtype=np.int32).reshape(-1, 8)
+        N = (0 if cur is None else len(cur)) if num_points is None else num_points
+        camc = self.camera(cam)
+        rin = abi.TrackRejectInC()
+        rin.camera = None if camc is None else C.pointer(camc)
+        rin.num_points, rin.num_samples = N, (0 if sm is None else len(sm)) if num_samples is None else num_samples
+        rin.cur_pts = None if cur is None else cur.ctypes.data_as(fp)
+        rin.forw_pts = None if forw is None else forw.ctypes.data_as(fp)
+        rin.samples = None if sm is None else sm.ctypes.data_as(ip)
+        cap = min(max(N, 1), abi.TRACK_MAX_POINTS)
+        stat = np.zeros(cap, dtype=np.uint8) if status is None else status
+        out = abi.TrackRejectOutC() if out is None else out
+        bc, bf = bearings if bearings is not None else ((np.zeros((cap, 3)), np.zeros((cap, 3))) if want_bearings else (None, None))
+        rc = self.lib.lfvio_track_reject(self.ctx, C.byref(rin), stat.ctypes.data_as(C.POINTER(C.c_ubyte)), C.byref(out),
+                                         None if bc is None else _p(bc), None if bf is None else _p(bf))
+        if check:
+            self._check(rc, "lfvio_track_reject")
+        n = min(max(N, 0), len(stat))
+        res = dict(status=int(out.status), best_sample=int(out.best_sample), num_inliers=int(out.num_inliers), best_score=float(out.best_score),
+                   E=np.array(out.E, dtype=np.float64), mask=stat[:n], rc=rc)
+        if bc is not None:
+            res.update(bearing_cur=bc[:n], bearing_forw=bf[:n])
+        return res
+
+    def track_undistort(self, cam, pts, ids, time, outs=None, num_points=None, want_matched=True, check=True):
+        """lfvio_track_undistort: undistortedPoints on cur_pts `pts` [N, 2] float32 with their ids [N] int32 (-1: not yet numbered) at
+        cur_time `time`, against the (id, un_pts_3d) pairs the previous call left in the context.  Returns a dict with un_pts [N, 2],
+        un_pts_3d [N, 3], velocity_3d [N, 3] (float32), matched [N] int32 (index in the previous call or -1; None without
+        want_matched) and rc.  outs = (un_pts, un_pts_3d, velocity_3d, matched): arrays to be written, num_points: the struct's
+        field whatever the arrays say, cam / pts / ids None: null pointers; check=False returns the error code under `rc`."""
+        fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int)
+        p = None if pts is None else np.ascontiguousarray(pts, dtype=np.float32).reshape(-1, 2)
+        idv = None if ids is None else np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        N = (0 if p is None else len(p)) if num_points is None else num_points
+        camc = self.camera(cam)
+        uin = abi.TrackUndistortInC()
+        uin.camera = None if camc is None else C.pointer(camc)
+        uin.num_points, uin.time = N, time
+        uin.pts = None if p is None else p.ctypes.data_as(fp)
+        uin.ids = None if idv is None else idv.ctypes.data_as(ip)
+        cap = min(max(N, 1), abi.TRACK_MAX_POINTS)
+        if outs is None:
+            outs = (np.zeros((cap, 2), np.float32), np.zeros((cap, 3), np.float32), np.zeros((cap, 3), np.float32),
+                    np.zeros(cap, np.int32) if want_matched else None)
+        un, un3, vel, mt = outs
+        rc = self.lib.lfvio_track_undistort(self.ctx, C.byref(uin), un.ctypes.data_as(fp), un3.ctypes.data_as(fp), vel.ctypes.data_as(fp),
+                                            None if mt is None else mt.ctypes.data_as(ip))
+        if check:
+            self._check(rc, "lfvio_track_undistort")
+        n = min(max(N, 0), len(un))
+        return dict(un_pts=un[:n], un_pts_3d=un3[:n], velocity_3d=vel[:n], matched=None if mt is None else mt[:n], rc=rc)
+
+    def track_reset(self):
+        """lfvio_track_reset: forget the resident (id, un_pts_3d) map and time; the next track_undistort gives zero velocities."""
+        self._check(self.lib.lfvio_track_reset(self.ctx), "lfvio_track_reset")
+
     def time_kernel(self, which, count, reps):
         ms = np.zeros(1)
         self._check(self.lib.lfvio_debug_time_kernel(self.ctx, which, count, reps, _p(ms)), "time_kernel")
