@@ -641,8 +641,9 @@ int lfvio_relative_pose(lfvio_ctx *ctx, const LfvioRelativePoseIn *in, unsigned 
 /* lfvio_klt_track: the optical flow of FeatureTracker::readImage — cv::calcOpticalFlowPyrLK(cur_img, forw_img, cur_pts, forw_pts,
  * status, err, cv::Size(41, 41), 3) at feature_tracker/src/feature_tracker.cpp:127 and the inBorder test of :6-12, :129-131.  The
  * goodFeaturesToTrack and setMask are lfvio_gft_detect below, the CLAHE of :101-107 is lfvio_clahe_set below them, rejectWithF and
- * undistortedPoints are lfvio_track_reject / lfvio_track_undistort below those; what stays the caller's is the host class around
- * these calls (the vectors, reduceVector, updateID) and the images in the trace format.
+ * undistortedPoints are lfvio_track_reject / lfvio_track_undistort below those, and lfvio_track_frame below them runs all
+ * of them, with reduceVector and updateID, on a track table resident in the context; what stays the caller's is a thin host class
+ * around that call and the images in the trace format.
  * One call uploads `image`, builds its pyramid, tracks the N points from the pyramid of the PREVIOUS call's image (resident in the
  * context: cur_img = forw_img, :180) into the new one, and makes the new pyramid the resident one.  A context with no resident image —
  * after lfvio_create, after lfvio_klt_reset, or when width or height differ from the resident image's — treats `image` as both
@@ -838,6 +839,73 @@ typedef struct {
 int lfvio_track_undistort(lfvio_ctx *ctx, const LfvioTrackUndistortIn *in, float *un_pts /* [N][2] */, float *un_pts_3d /* [N][3] */,
                           float *velocity_3d /* [N][3] */, int *matched /* [N]: index in the previous call, or -1; or NULL */);
 int lfvio_track_reset(lfvio_ctx *ctx);   /* forget the resident map and time */
+
+/* lfvio_track_frame / lfvio_track_frame_reset: one image through FeatureTracker::readImage (feature_tracker/src/feature_tracker.cpp:
+ * 95-184) and the node's updateID loop (feature_tracker_node.cpp:102-111) in ONE call: one copy up ([sample_words | image]), the
+ * stages below enqueued back to back, one copy down.  The track table (cur_pts, ids, track_cnt) is resident in the context, and so
+ * is n_id; the counts between the stages stay on the device.  The stages are those of the separate calls above, on the same
+ * kernels and the same resident state — the pyramid of lfvio_klt_track, the base mask of lfvio_gft_set_mask, the setting of
+ * lfvio_clahe_set, the (id, un_pts_3d) map and time of lfvio_track_undistort — and every one of these is left as the separate calls
+ * would have left it: a caller may mix the two routes (the table itself is only ever filled by this call).
+ *   1  the flow (lfvio_klt_track, the inBorder test included) from the resident table's points
+ *   2  cur, forw, ids and track_cnt keep the entries with status 1, in order (reduceVector); track_cnt += 1; n1 are left
+ *   3  publish != 0: the sample sets are drawn ON THE DEVICE, which alone knows n1, from the caller's words: for set s and k = 0 .. 7
+ *      r = sample_words[s][k] % (n1 - k); for every index c already chosen for this set, in ascending order, if (r >= c) r++;
+ *      samples[s][k] = r — eight distinct indices in [0, n1).  Then lfvio_track_reject on them (n1 < 8: nothing is drawn, status 2)
+ *      and reduceVector by its mask; n2 are left
+ *   4  publish != 0: lfvio_gft_detect; the table becomes [forw[kept] | corners], the corners with id -1 and count 1
+ *   5  lfvio_track_undistort on the table's points with the ids AS THEY ARE NOW, the -1 included (the quirk stated there is kept)
+ *   6  every id that is -1 takes the next n_id, in index order; num_new were numbered
+ * out: the scalars, `reject` and `detect` (all zero with publish == 0; reject.E is zero unless reject.status is 0), and the table
+ * with the outputs of step 5 in the caller's arrays of `capacity` entries, num_points written.  stages (or NULL), every pointer in it
+ * (or NULL) an array of `capacity` entries (samples: num_samples x 8): next_pts and status of the flow for the points the call began
+ * with, the sample sets as drawn (written where n1 >= 8), the rejection mask [num_tracked], kept [detect.num_kept] and corners
+ * [detect.num_corners][2].
+ * tests/track_frame_ref.py restates the mapping of step 3 and the frame; the device gives its bits.
+ * LFVIO_ERR_ARG (every output, the table, n_id, the resident image, the map and the time untouched): null ctx / in / out / image /
+ * camera / an array of out, null sample_words with publish != 0, a field outside the range that the separate call states for it, a
+ * model other than LFVIO_CAM_OCAM, num_samples outside [1, 1024], capacity < max(max_count, the table's count) or > 4096, a NaN
+ * time, with publish != 0 a base mask that is not the image's size.  A call that fails later changes nothing either: the table, like
+ * the pyramid and the map, is double-buffered and swapped when the call has succeeded.  Runs on the feature stream like
+ * lfvio_klt_track: it does not wait for an optimization in flight.
+ * lfvio_track_frame_reset: lfvio_klt_reset and lfvio_track_reset, the table empty and n_id = 0. */
+typedef struct {
+  int width, height;                /* as LfvioKltIn */
+  const unsigned char *image;
+  double time;                      /* cur_time; not NaN */
+  int publish;                      /* PUB_THIS_FRAME: 0 skips steps 3 and 4 */
+  const LfvioCamera *camera;
+  int win_size, max_level, max_iterations;   /* as LfvioKltIn */
+  double epsilon, min_eig_threshold;
+  int border;
+  int max_count;                    /* as LfvioGftIn */
+  double quality_level;
+  int min_distance, mask_radius;
+  int num_samples;                  /* S in [1, 1024]; the reference: 100 */
+  const unsigned int *sample_words; /* [S][8] uniform 32-bit words; may be NULL with publish == 0 */
+  int capacity;                     /* entries of each array of out and stages: max(max_count, the table's count) .. 4096 */
+} LfvioTrackFrameIn;
+typedef struct {
+  int num_points, num_new, levels_used, num_tracked /* n1 */, num_after_reject /* n2; = n1 with publish == 0 */;
+  LfvioTrackRejectOut reject;
+  LfvioGftOut detect;
+  float *pts;          /* [capacity][2] cur_pts after the call */
+  int *ids;            /* [capacity], numbered */
+  int *track_cnt;      /* [capacity] */
+  float *un_pts;       /* [capacity][2] */
+  float *un_pts_3d;    /* [capacity][3] */
+  float *velocity_3d;  /* [capacity][3] */
+} LfvioTrackFrameOut;
+typedef struct {
+  float *next_pts;        /* [capacity][2] */
+  unsigned char *status;  /* [capacity] */
+  int *samples;           /* [S][8] */
+  unsigned char *mask;    /* [capacity] */
+  int *kept;              /* [capacity] */
+  float *corners;         /* [capacity][2] */
+} LfvioTrackFrameStages;
+int lfvio_track_frame(lfvio_ctx *ctx, const LfvioTrackFrameIn *in, LfvioTrackFrameOut *out, const LfvioTrackFrameStages *stages /* or NULL */);
+int lfvio_track_frame_reset(lfvio_ctx *ctx);
 
 /* ---- landmark-sharded API (multi-GPU) ------------------------
  * Every rank passes the same window but linearizes only landmarks [lm_begin, lm_end) (caller order);

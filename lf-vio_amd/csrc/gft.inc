@@ -29,12 +29,38 @@ static int gft_reserve(lfvio_ctx *c, const GftWork &wk) {
   return c->gft.work.reserve(wk.bytes) ? LFVIO_OK : out_of_memory(c, "out of memory (corner detection)");
 }
 
-static int gft_launch_response(lfvio_ctx *c, hipStream_t fs, const GftWork &wk, const unsigned char *base, int r, int max_count) {
-  const lfvio_ctx::KltState &k = c->klt;
+// img: level 0 of a pyramid of W x H — the resident one, or the one lfvio_track_frame is about to make resident
+static int gft_launch_response(lfvio_ctx *c, hipStream_t fs, const GftWork &wk, const unsigned char *img, int W, int H, const unsigned char *base, int r,
+                               int max_count) {
   char *w = c->gft.work;
-  hipLaunchKernelGGL(k_gft_response, dim3((k.w + GFT_TX - 1) / GFT_TX, (k.h + GFT_TY - 1) / GFT_TY), dim3(GFT_THREADS), 0, fs,
-                     (const unsigned char *)k.d[k.cur], k.w, k.h, base, (const int *)(w + wk.kxy), r, max_count, (GftDev *)(w + wk.st),
-                     (double *)(w + wk.lam), (unsigned char *)(w + wk.mask));
+  hipLaunchKernelGGL(k_gft_response, dim3((W + GFT_TX - 1) / GFT_TX, (H + GFT_TY - 1) / GFT_TY), dim3(GFT_THREADS), 0, fs, img, W, H, base,
+                     (const int *)(w + wk.kxy), r, max_count, (GftDev *)(w + wk.st), (double *)(w + wk.lam), (unsigned char *)(w + wk.mask));
+  HIPCHK(c, hipGetLastError());
+  return LFVIO_OK;
+}
+
+// Everything behind k_gft_thin: the response, the candidates, the sort network and the greedy pick into corners / *out (device).
+static int gft_launch_detect(lfvio_ctx *c, hipStream_t fs, const GftWork &wk, const unsigned char *img, int W, int H, const unsigned char *base,
+                             const LfvioGftIn *in, float *corners, LfvioGftOut *out) {
+  char *w = c->gft.work;
+  const int MC = in->max_count;
+  GftDev *dev = (GftDev *)(w + wk.st);
+  unsigned long long *ck = (unsigned long long *)(w + wk.keys);
+  unsigned *ci = (unsigned *)(w + wk.idx);
+  if (int rc = gft_launch_response(c, fs, wk, img, W, H, base, in->mask_radius, MC)) return rc;
+  hipLaunchKernelGGL(k_gft_cand, dim3((W + GFT_THREADS - 1) / GFT_THREADS, (H + GFT_CAND_ROWS - 1) / GFT_CAND_ROWS), dim3(GFT_THREADS), 0, fs, (const double *)(w + wk.lam),
+                     (const unsigned char *)(w + wk.mask), W, H, in->quality_level, MC, dev, ck, ci);
+  HIPCHK(c, hipGetLastError());
+  // the network of the arrays' capacity: the candidate count stays on the device, a stage beyond it returns at once (gft_plan.h)
+  const unsigned chunks = (unsigned)std::min<size_t>(wk.capacity / GFT_CHUNK, GFT_SORT_GRID), halves = (unsigned)std::min<size_t>(wk.capacity / 2 / GFT_THREADS, GFT_SORT_GRID);
+  hipLaunchKernelGGL(k_gft_sort_local, dim3(chunks), dim3(GFT_SORT_THREADS), 0, fs, (const GftDev *)dev, ck, ci, 0u);
+  for (size_t kk = 2 * (size_t)GFT_CHUNK; kk <= wk.capacity; kk *= 2) {
+    for (size_t j = kk / 2; j >= (size_t)GFT_CHUNK; j /= 2)
+      hipLaunchKernelGGL(k_gft_sort_global, dim3(halves), dim3(GFT_THREADS), 0, fs, (const GftDev *)dev, ck, ci, (unsigned)kk, (unsigned)j);
+    hipLaunchKernelGGL(k_gft_sort_local, dim3(chunks), dim3(GFT_SORT_THREADS), 0, fs, (const GftDev *)dev, ck, ci, (unsigned)kk);
+  }
+  HIPCHK(c, hipGetLastError());
+  hipLaunchKernelGGL(k_gft_pick, dim3(1), dim3(GFT_THREADS), 0, fs, (const GftDev *)dev, (const unsigned *)ci, W, in->min_distance, MC, corners, out);
   HIPCHK(c, hipGetLastError());
   return LFVIO_OK;
 }
@@ -66,28 +92,10 @@ int lfvio_gft_detect(lfvio_ctx *c, const LfvioGftIn *in, int *kept, float *corne
     if (int rc = st.up(in_end)) return rc;
   }
   const unsigned char *base = g.mask_set ? g.mask : nullptr;
-  GftDev *dev = (GftDev *)(w + wk.st);
-  unsigned long long *ck = (unsigned long long *)(w + wk.keys);
-  unsigned *ci = (unsigned *)(w + wk.idx);
-  hipLaunchKernelGGL(k_gft_thin, dim3(1), dim3(GFT_THREADS), 0, st.fs, N, (const float *)(d + oP), (const int *)(d + oC), base, W, H, in->mask_radius, dev,
-                     (int *)(d + oK), (int *)(w + wk.kxy));
+  hipLaunchKernelGGL(k_gft_thin<int>, dim3(1), dim3(GFT_THREADS), 0, st.fs, N, (const float *)(d + oP), (const int *)(d + oC), base, W, H, in->mask_radius,
+                     (GftDev *)(w + wk.st), (int *)(d + oK), (int *)(w + wk.kxy));
   HIPCHK(c, hipGetLastError());
-  if (int rc = gft_launch_response(c, st.fs, wk, base, in->mask_radius, MC)) return rc;
-  hipLaunchKernelGGL(k_gft_cand, dim3((W + GFT_THREADS - 1) / GFT_THREADS, (H + GFT_CAND_ROWS - 1) / GFT_CAND_ROWS), dim3(GFT_THREADS), 0, st.fs, (const double *)(w + wk.lam),
-                     (const unsigned char *)(w + wk.mask), W, H, in->quality_level, MC, dev, ck, ci);
-  HIPCHK(c, hipGetLastError());
-  // the network of the arrays' capacity: the candidate count stays on the device, a stage beyond it returns at once (gft_plan.h)
-  const unsigned chunks = (unsigned)std::min<size_t>(wk.capacity / GFT_CHUNK, GFT_SORT_GRID), halves = (unsigned)std::min<size_t>(wk.capacity / 2 / GFT_THREADS, GFT_SORT_GRID);
-  hipLaunchKernelGGL(k_gft_sort_local, dim3(chunks), dim3(GFT_SORT_THREADS), 0, st.fs, (const GftDev *)dev, ck, ci, 0u);
-  for (size_t kk = 2 * (size_t)GFT_CHUNK; kk <= wk.capacity; kk *= 2) {
-    for (size_t j = kk / 2; j >= (size_t)GFT_CHUNK; j /= 2)
-      hipLaunchKernelGGL(k_gft_sort_global, dim3(halves), dim3(GFT_THREADS), 0, st.fs, (const GftDev *)dev, ck, ci, (unsigned)kk, (unsigned)j);
-    hipLaunchKernelGGL(k_gft_sort_local, dim3(chunks), dim3(GFT_SORT_THREADS), 0, st.fs, (const GftDev *)dev, ck, ci, (unsigned)kk);
-  }
-  HIPCHK(c, hipGetLastError());
-  hipLaunchKernelGGL(k_gft_pick, dim3(1), dim3(GFT_THREADS), 0, st.fs, (const GftDev *)dev, (const unsigned *)ci, W, in->min_distance, MC, (float *)(d + oX),
-                     (LfvioGftOut *)(d + oO));
-  HIPCHK(c, hipGetLastError());
+  if (int rc = gft_launch_detect(c, st.fs, wk, k.d[k.cur], W, H, base, in, (float *)(d + oX), (LfvioGftOut *)(d + oO))) return rc;
   if (int rc = st.down(oK, st.end)) return rc;
   LfvioGftOut o;
   std::memcpy(&o, h + oO, sizeof o);
@@ -136,7 +144,7 @@ int lfvio_gft_response(lfvio_ctx *c, double *response) {
   FeatStage st(c);
   if (int rc = gft_reserve(c, wk)) return rc;
   HIPCHK(c, hipMemsetAsync(c->gft.work + wk.st, 0, sizeof(GftDev), st.fs));  // no kept points
-  if (int rc = gft_launch_response(c, st.fs, wk, nullptr, 0, 1)) return rc;
+  if (int rc = gft_launch_response(c, st.fs, wk, c->klt.d[c->klt.cur], c->klt.w, c->klt.h, nullptr, 0, 1)) return rc;
   HIPCHK(c, hipMemcpyAsync(response, c->gft.work + wk.lam, (size_t)c->klt.w * c->klt.h * 8, hipMemcpyDeviceToHost, st.fs));
   HIPCHK(c, hipStreamSynchronize(st.fs));
   return LFVIO_OK;

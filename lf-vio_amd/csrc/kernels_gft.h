@@ -4,7 +4,8 @@
 // not depend on the order in which workgroups run.
 //
 //   k_gft_thin        : one workgroup.  Ranks the tracked points by (count descending, index ascending) by counting, then walks them
-//                       in that order (gft_greedy): kept indices, kept pixels, their number.  Resets the call's GftDev.
+//                       in that order (gft_greedy): kept indices, kept pixels, their number.  Resets the call's GftDev.  A template
+//                       over how the count arrives: an int (lfvio_gft_detect) or a pointer to it on the device (lfvio_track_frame).
 //   k_gft_response    : 32 x 8 tiles.  The image with a halo of 2 (reflect-101) in LDS, the three Sobel products with a halo of 1 —
 //                       a product outside the image is the product AT the reflected pixel, not the product of the reflected image's
 //                       gradients — their 3 x 3 sums, S, D, lambda as double.  The final mask per tile: the base-mask byte and the
@@ -73,11 +74,18 @@ DEV int gft_greedy(int n, int lim, int cap, XY xy, Emit emit, int *acc, int *bat
   return have;
 }
 
-__global__ __launch_bounds__(GFT_THREADS) void k_gft_thin(int N, const float *pts, const int *cnt, const unsigned char *base, int W, int H, int r,
+// a count as a kernel argument, or read from the device where the host knows only a bound of it (lfvio_track_frame)
+DEV int gft_count(int n) { return n; }
+DEV int gft_count(const int *n) { return *n; }
+
+// Count = int: lfvio_gft_detect's N.  Count = const int *: N from the device; N = 0 runs no loop below and writes num_kept = 0.
+template <class Count>
+__global__ __launch_bounds__(GFT_THREADS) void k_gft_thin(Count n_arg, const float *pts, const int *cnt, const unsigned char *base, int W, int H, int r,
                                                            GftDev *st, int *kept, int *kxy) {
   __shared__ int s_cnt[GFT_LIST];  // the counts, then the kept pixels
   __shared__ int s_xy[GFT_LIST], s_idx[GFT_LIST];  // pixel and index of the point of rank k
   __shared__ int s_batch[GFT_THREADS];
+  const int N = gft_count(n_arg);
   const int tid = threadIdx.x;
   for (int i = tid; i < N; i += GFT_THREADS) s_cnt[i] = cnt[i];
   __syncthreads();

@@ -14,6 +14,11 @@
 //                  result behind the loop, so nothing diverges.  At N <= 4096 this is cheaper than sorting.  The new (id, un_pts_3d)
 //                  pairs go to the OTHER resident map; the previous one is only read.
 //
+//   k_*_n        : the same bodies with N read from the device (and k_tv_hyp_n around tv_hyp_body) for lfvio_track_frame
+//                  (trackframe.inc), whose host knows only a bound of N and sizes the grid for it.  They take the cases the host
+//                  filters for the kernels above: N < 8 in the rejection (status 2, no sample index is read), N = 0 in
+//                  k_trk_undist_n (a workgroup without a point returns before any load).
+//
 // The lift is written operation by operation and the library is built with -ffp-contract=off: every product and sum is rounded on
 // its own, as the restatement's are.  The norm is sqrt((x x + y y) + z z), left to right as tv_residual forms its norms; Eigen's
 // own reduction may order the terms differently (the reference does not build here, so the two were never compared).
@@ -39,7 +44,7 @@ DEV d3 trk_lift(const TrackCam &cam, float px, float py) {
 
 DEV double trk_norm(d3 P) { return sqrt((P.x * P.x + P.y * P.y) + P.z * P.z); }
 
-__global__ __launch_bounds__(TRK_THREADS) void k_trk_lift(TrackCam cam, int N, const float *cur, const float *forw, double *bl, double *br) {
+DEV void trk_lift_body(const TrackCam &cam, int N, const float *cur, const float *forw, double *bl, double *br) {
   const int t = blockIdx.x * TRK_THREADS + threadIdx.x;
   if (t >= 2 * N) return;
   const bool second = t >= N;
@@ -50,11 +55,17 @@ __global__ __launch_bounds__(TRK_THREADS) void k_trk_lift(TrackCam cam, int N, c
   double *b = (second ? br : bl) + 3 * (size_t)i;
   b[0] = P.x / n, b[1] = P.y / n, b[2] = P.z / n;  // :343, :353
 }
+__global__ __launch_bounds__(TRK_THREADS) void k_trk_lift(TrackCam cam, int N, const float *cur, const float *forw, double *bl, double *br) {
+  trk_lift_body(cam, N, cur, forw, bl, br);
+}
+// N from the device (lfvio_track_frame): the grid is the host's bound of it
+__global__ __launch_bounds__(TRK_THREADS) void k_trk_lift_n(TrackCam cam, const int *N, const float *cur, const float *forw, double *bl, double *br) {
+  trk_lift_body(cam, *N, cur, forw, bl, br);
+}
 
 // One workgroup.  out is written on every path (E only with status 0); status[0 .. N) too.
-__global__ __launch_bounds__(TV_FIT_THREADS) void k_trk_fit(int N, int S, const double *bl, const double *br, const double *E_all,
-                                                            const float *score_all, double *A, unsigned char *status, LfvioTrackRejectOut *out) {
-  __shared__ TvFitLds lds;
+DEV void trk_fit_body(int N, int S, const double *bl, const double *br, const double *E_all, const float *score_all, double *A,
+                      unsigned char *status, LfvioTrackRejectOut *out, TvFitLds &lds) {
   TvFit f;
   const int st = tv_fit_body<false, true>(N, S, bl, br, E_all, score_all, A, status, lds, f);  // (the same in every thread)
   if (st != 0)
@@ -66,13 +77,37 @@ __global__ __launch_bounds__(TV_FIT_THREADS) void k_trk_fit(int N, int S, const 
     for (int j = 0; j < 9; j++) out->E[j] = f.E[j];
   }
 }
+__global__ __launch_bounds__(TV_FIT_THREADS) void k_trk_fit(int N, int S, const double *bl, const double *br, const double *E_all,
+                                                            const float *score_all, double *A, unsigned char *status, LfvioTrackRejectOut *out) {
+  __shared__ TvFitLds lds;
+  trk_fit_body(N, S, bl, br, E_all, score_all, A, status, out, lds);
+}
+// N from the device.  N < 8 is lfvio_track_reject's host branch (:331), which the host cannot take here: status 2, nothing rejected,
+// and no bearing, hypothesis or sample index is read (k_tv_hyp_n has not run).
+__global__ __launch_bounds__(TV_FIT_THREADS) void k_trk_fit_n(const int *Np, int S, const double *bl, const double *br, const double *E_all,
+                                                              const float *score_all, double *A, unsigned char *status, LfvioTrackRejectOut *out) {
+  __shared__ TvFitLds lds;
+  const int N = *Np;
+  if (N < TRACK_MIN_MATCHES) {
+    for (int i = threadIdx.x; i < N; i += TV_FIT_THREADS) status[i] = 1;
+    if (threadIdx.x == 0) out->status = 2, out->best_sample = -1, out->num_inliers = 0, out->best_score = 0.0;
+    return;
+  }
+  trk_fit_body(N, S, bl, br, E_all, score_all, A, status, out, lds);
+}
+// k_tv_hyp (kernels_twoview.h) with N from the device; N < 8: no sample set was drawn
+__global__ __launch_bounds__(TV_HYP_THREADS) void k_tv_hyp_n(const int *Np, const double *bl, const double *br, const int *samples, double *E_all,
+                                                             float *score_all) {
+  __shared__ double s2[TV_CHUNK], s1[TV_CHUNK];
+  const int N = *Np, k = blockIdx.x;
+  if (N < TRACK_MIN_MATCHES) return;
+  tv_hyp_body(N, bl, br, samples + 8 * (size_t)k, E_all + 9 * (size_t)k, score_all + k, s2, s1, threadIdx.x);
+}
 
 // grid ceil(N / 256).  prev_ids / prev_3d: the P pairs of the previous call (P = 0: the map is empty, every velocity is 0);
 // new_ids / new_3d: this call's, for the next one.
-__global__ __launch_bounds__(TRK_THREADS) void k_trk_undist(TrackCam cam, int N, const float *pts, const int *ids, double dt, int P,
-                                                            const int *prev_ids, const float *prev_3d, float *un, float *un3d, float *vel,
-                                                            int *matched, int *new_ids, float *new_3d) {
-  __shared__ int sid[LFVIO_TRACK_MAX_POINTS];
+DEV void trk_undist_body(const TrackCam &cam, int N, const float *pts, const int *ids, double dt, int P, const int *prev_ids,
+                         const float *prev_3d, float *un, float *un3d, float *vel, int *matched, int *new_ids, float *new_3d, int *sid) {
   const int tid = threadIdx.x, i = blockIdx.x * TRK_THREADS + tid;
   for (int j = tid; j < P; j += TRK_THREADS) sid[j] = prev_ids[j];
   __syncthreads();
@@ -100,4 +135,20 @@ __global__ __launch_bounds__(TRK_THREADS) void k_trk_undist(TrackCam cam, int N,
   matched[i] = found ? best : -1;
   new_ids[i] = id;
   new_3d[3 * (size_t)i] = bx, new_3d[3 * (size_t)i + 1] = by, new_3d[3 * (size_t)i + 2] = bz;
+}
+__global__ __launch_bounds__(TRK_THREADS) void k_trk_undist(TrackCam cam, int N, const float *pts, const int *ids, double dt, int P,
+                                                            const int *prev_ids, const float *prev_3d, float *un, float *un3d, float *vel,
+                                                            int *matched, int *new_ids, float *new_3d) {
+  __shared__ int sid[LFVIO_TRACK_MAX_POINTS];
+  trk_undist_body(cam, N, pts, ids, dt, P, prev_ids, prev_3d, un, un3d, vel, matched, new_ids, new_3d, sid);
+}
+// N from the device, the grid sized for the host's bound of it.  A workgroup with no point of its own returns before any load: with
+// N = 0 the clamp `ii = N - 1` of the body would read index -1.
+__global__ __launch_bounds__(TRK_THREADS) void k_trk_undist_n(TrackCam cam, const int *Np, const float *pts, const int *ids, double dt, int P,
+                                                              const int *prev_ids, const float *prev_3d, float *un, float *un3d, float *vel,
+                                                              int *matched, int *new_ids, float *new_3d) {
+  __shared__ int sid[LFVIO_TRACK_MAX_POINTS];
+  const int N = *Np;
+  if ((int)(blockIdx.x * TRK_THREADS) >= N) return;
+  trk_undist_body(cam, N, pts, ids, dt, P, prev_ids, prev_3d, un, un3d, vel, matched, new_ids, new_3d, sid);
 }

@@ -18,6 +18,40 @@ static int klt_build(lfvio_ctx *c, hipStream_t fs, unsigned char *pyr, const Klt
   return LFVIO_OK;
 }
 
+// The image at d_image (device, W x H) into the context's other pyramid buffer — a copy, or CLAHE while it is on — with the levels
+// 1 .. LU, and the levels of the resident pyramid that an earlier call did not build.  *prev: the pyramid to track from (the new one
+// when none of this size is resident, :111-114).  Returns the new pyramid, which the caller makes resident with klt_commit once the
+// call has succeeded.  (Every earlier call on the feature stream has been waited for: nobody reads the other buffer.)
+static int klt_pyramid(lfvio_ctx *c, hipStream_t fs, const unsigned char *d_image, int W, int H, const KltPlan &full, int LU,
+                       const unsigned char **prev, unsigned char **fresh_out) {
+  lfvio_ctx::KltState &k = c->klt;
+  unsigned char *fresh = k.d[1 - k.cur];
+  if (c->clahe.on) {  // the equalized image is the image: k_clahe_map writes level 0 (clahe.inc)
+    if (int rc = clahe_run(c, fs, c->clahe.cfg, W, H, d_image, fresh, nullptr)) return rc;
+  } else {
+    HIPCHK(c, hipMemcpyAsync(fresh, d_image, (size_t)W * H, hipMemcpyDeviceToDevice, fs));
+  }
+  if (int rc = klt_build(c, fs, fresh, full, 0, LU)) return rc;
+  const bool same = k.valid && k.w == W && k.h == H;  // otherwise the new image is both images (:111-114)
+  if (same && k.built < LU) {  // (an earlier call asked for fewer levels: a level is a function of the one below)
+    if (int rc = klt_build(c, fs, k.d[k.cur], full, k.built, LU)) return rc;
+    k.built = LU;
+  }
+  *prev = same ? (const unsigned char *)k.d[k.cur] : fresh, *fresh_out = fresh;
+  return LFVIO_OK;
+}
+static void klt_commit(lfvio_ctx *c, int W, int H, int LU) {
+  lfvio_ctx::KltState &k = c->klt;
+  k.cur = 1 - k.cur, k.w = W, k.h = H, k.built = LU, k.valid = true;
+}
+static KltArgs klt_args(const LfvioKltIn *in, const KltPlan &full, int LU) {
+  KltArgs a;
+  a.win = in->win_size, a.levels_used = LU, a.max_level = in->max_level, a.max_iter = in->max_iterations, a.border = in->border;
+  a.eps2 = in->epsilon * in->epsilon, a.min_eig = in->min_eig_threshold;
+  for (int l = 0; l < KLT_LEVELS; l++) a.w[l] = full.w[l], a.h[l] = full.h[l], a.off[l] = (long long)full.off[l];
+  return a;
+}
+
 int lfvio_klt_track(lfvio_ctx *c, const LfvioKltIn *in, float *next_pts, unsigned char *status, int *iterations, LfvioKltOut *out) {
   if (!c || !in || !next_pts || !status || !out) return LFVIO_ERR_ARG;
   if (const char *why = klt_check(in)) {
@@ -39,24 +73,11 @@ int lfvio_klt_track(lfvio_ctx *c, const LfvioKltIn *in, float *next_pts, unsigne
   if (N) std::memcpy(h + oP, in->prev_pts, (size_t)N * 8);
   std::memcpy(h + oI, in->image, nI);
   if (int rc = st.up(in_end)) return rc;
-  unsigned char *fresh = k.d[nb];
-  if (c->clahe.on) {  // the equalized image is the image: k_clahe_map writes level 0 (clahe.inc)
-    if (int rc = clahe_run(c, st.fs, c->clahe.cfg, W, H, (const unsigned char *)(d + oI), fresh, nullptr)) return rc;
-  } else {
-    HIPCHK(c, hipMemcpyAsync(fresh, d + oI, nI, hipMemcpyDeviceToDevice, st.fs));
-  }
-  if (int rc = klt_build(c, st.fs, fresh, full, 0, LU)) return rc;
-  const bool same = k.valid && k.w == W && k.h == H;  // otherwise the new image is both images (:111-114)
-  if (same && k.built < LU) {  // (an earlier call asked for fewer levels: a level is a function of the one below)
-    if (int rc = klt_build(c, st.fs, k.d[k.cur], full, k.built, LU)) return rc;
-    k.built = LU;
-  }
+  unsigned char *fresh;
+  const unsigned char *prev;
+  if (int rc = klt_pyramid(c, st.fs, (const unsigned char *)(d + oI), W, H, full, LU, &prev, &fresh)) return rc;
   if (N) {
-    KltArgs a;
-    a.win = in->win_size, a.levels_used = LU, a.max_level = ML, a.max_iter = in->max_iterations, a.border = in->border;
-    a.eps2 = in->epsilon * in->epsilon, a.min_eig = in->min_eig_threshold;
-    for (int l = 0; l < KLT_LEVELS; l++) a.w[l] = full.w[l], a.h[l] = full.h[l], a.off[l] = (long long)full.off[l];
-    hipLaunchKernelGGL(k_klt_track, dim3(N), dim3(KLT_THREADS), 0, st.fs, a, N, (const unsigned char *)(same ? k.d[k.cur] : fresh),
+    hipLaunchKernelGGL(k_klt_track, dim3(N), dim3(KLT_THREADS), 0, st.fs, klt_args(in, full, LU), N, prev,
                        (const unsigned char *)fresh, (const float *)(d + oP), (float *)(d + oN), (unsigned char *)(d + oS),
                        iterations ? (int *)(d + oT) : (int *)nullptr);
     HIPCHK(c, hipGetLastError());
@@ -72,7 +93,7 @@ int lfvio_klt_track(lfvio_ctx *c, const LfvioKltIn *in, float *next_pts, unsigne
     for (int i = 0; i < N; i++) tracked += status[i] != 0;
   }
   out->levels_used = LU, out->num_tracked = tracked;
-  k.cur = nb, k.w = W, k.h = H, k.built = LU, k.valid = true;
+  klt_commit(c, W, H, LU);
   return LFVIO_OK;
 }
 

@@ -52,6 +52,7 @@ constexpr ncclDataType_t ncclDouble = 8;
 #include "kernels_gft.h"
 #include "kernels_clahe.h"
 #include "kernels_track.h"
+#include "kernels_trackframe.h"
 #include "window_pack.h"
 #include "dev_mem.h"
 
@@ -199,6 +200,12 @@ struct lfvio_ctx : CtxQueues {
     int cur = 0, count = 0;
     double time = 0.0;
   } track;
+  // lfvio_track_frame (trackframe.inc): the track table — [4096 x 2 floats | 4096 ids | 4096 counts] twice, allocated at the first
+  // use; `cur` holds the `count` resident entries, n_id is the next id to hand out
+  struct TrackFrameState {
+    DevBuf<char> table[2];
+    int cur = 0, count = 0, n_id = 0;
+  } tframe;
   std::string err;
   int batch = 0;
   Layout L;
@@ -2077,6 +2084,8 @@ int lfvio_debug_query(lfvio_ctx *c, const char *key, double *out, int n) {
 #include "gft.inc"
 
 #include "track.inc"
+
+#include "trackframe.inc"
 // ---- landmark-sharded API: declared in lfvio.h, implemented in shard.inc
 #include "shard.inc"
 // ---- multi-GPU groups (RCCL): declared in lfvio.h, implemented in group.inc

@@ -1,0 +1,71 @@
+// trackframe_plan.h — the host side of lfvio_track_frame (include/lfvio.h) that needs no device: the argument check, which calls
+// the checks of the separate calls (klt_check, gft_check, track_common_check) on the fields the frame shares with them, and the
+// bounds the host knows for the counts that stay on the device.  Plain C++ (no HIP): trackframe.inc uses it,
+// tests/test_track_frame_ref.py compiles it alone with g++ and holds it to the checks of tests/track_frame_ref.py.
+#pragma once
+#include <algorithm>
+#include <cmath>
+
+#include "gft_plan.h"
+#include "track_plan.h"
+
+// the flow's and the detection's inputs as the separate calls take them, without points
+inline LfvioKltIn trackframe_klt(const LfvioTrackFrameIn *in) {
+  LfvioKltIn k = {};
+  k.width = in->width, k.height = in->height, k.image = in->image;
+  k.win_size = in->win_size, k.max_level = in->max_level, k.max_iterations = in->max_iterations;
+  k.epsilon = in->epsilon, k.min_eig_threshold = in->min_eig_threshold, k.border = in->border;
+  return k;
+}
+inline LfvioGftIn trackframe_gft(const LfvioTrackFrameIn *in) {
+  LfvioGftIn g = {};
+  g.max_count = in->max_count, g.quality_level = in->quality_level, g.min_distance = in->min_distance, g.mask_radius = in->mask_radius;
+  return g;
+}
+
+// nullptr, or what is wrong with the fields of *in beside a table of table_count entries (the pointers of out are the entry's to check)
+inline const char *trackframe_check(const LfvioTrackFrameIn *in, int table_count) {
+  const LfvioKltIn k = trackframe_klt(in);
+  if (const char *why = klt_check(&k)) return why;
+  const LfvioGftIn g = trackframe_gft(in);
+  if (const char *why = gft_check(&g)) return why;
+  if (const char *why = track_common_check(in->camera, 0)) return why;
+  if (in->num_samples < 1 || in->num_samples > TRACK_MAX_SAMPLES) return "lfvio_track_frame: num_samples outside [1, 1024]";
+  if (in->publish && !in->sample_words) return "lfvio_track_frame: null sample_words";
+  if (in->capacity < std::max(in->max_count, table_count) || in->capacity > LFVIO_TRACK_MAX_POINTS)
+    return "lfvio_track_frame: capacity below max(max_count, the table's count) or above 4096";
+  if (std::isnan(in->time)) return "lfvio_track_frame: time is NaN";
+  return nullptr;
+}
+
+// What the host knows of the counts: n1 and n2 are at most the table's count, the count after the call at most this.
+inline int trackframe_bound(int table_count, int max_count, bool publish) { return publish ? std::max(table_count, max_count) : table_count; }
+
+// Sample set from eight words over n >= 8 matches (include/lfvio.h, step 3): the k-th draw is the (words[k] % (n - k))-th of the
+// indices not yet chosen.  The same function on the device (kernels_trackframe.h) and on the host.
+#if defined(__HIPCC__)
+#define TF_HD __host__ __device__ inline
+#define TF_UNROLL _Pragma("unroll")
+#else
+#define TF_HD inline
+#define TF_UNROLL
+#endif
+// (Fixed trip counts and constant indices once unrolled: on the device `chosen` stays in registers.)
+TF_HD void trackframe_draw(const unsigned *words, int n, int *out) {
+  int chosen[8] = {};  // the first k entries: the indices drawn so far, ascending
+  TF_UNROLL
+  for (int k = 0; k < 8; k++) {
+    int r = (int)(words[k] % (unsigned)(n - k));
+    TF_UNROLL
+    for (int j = 0; j < 8; j++)
+      if (j < k && r >= chosen[j]) r++;  // (ascending: once r is below one of them it is below the rest)
+    out[k] = r;
+    chosen[k] = r;
+    TF_UNROLL
+    for (int j = 7; j > 0; j--)
+      if (j <= k && chosen[j - 1] > chosen[j]) {
+        const int t = chosen[j];
+        chosen[j] = chosen[j - 1], chosen[j - 1] = t;
+      }
+  }
+}

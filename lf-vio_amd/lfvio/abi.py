@@ -688,6 +688,62 @@ class TrackUndistortInC(C.Structure):
 
 CAM_OCAM, TRACK_MAX_POINTS = 0, 4096  # LFVIO_CAM_OCAM, LFVIO_TRACK_MAX_POINTS
 
+
+class TrackFrameInC(C.Structure):
+    """LfvioTrackFrameIn (include/lfvio.h)."""
+    _fields_ = [
+        ("width", C.c_int),
+        ("height", C.c_int),
+        ("image", C.POINTER(C.c_ubyte)),
+        ("time", C.c_double),
+        ("publish", C.c_int),
+        ("camera", C.POINTER(CameraC)),
+        ("win_size", C.c_int),
+        ("max_level", C.c_int),
+        ("max_iterations", C.c_int),
+        ("epsilon", C.c_double),
+        ("min_eig_threshold", C.c_double),
+        ("border", C.c_int),
+        ("max_count", C.c_int),
+        ("quality_level", C.c_double),
+        ("min_distance", C.c_int),
+        ("mask_radius", C.c_int),
+        ("num_samples", C.c_int),
+        ("sample_words", C.POINTER(C.c_uint)),
+        ("capacity", C.c_int),
+    ]
+
+
+class TrackFrameOutC(C.Structure):
+    """LfvioTrackFrameOut (include/lfvio.h)."""
+    _fields_ = [
+        ("num_points", C.c_int),
+        ("num_new", C.c_int),
+        ("levels_used", C.c_int),
+        ("num_tracked", C.c_int),
+        ("num_after_reject", C.c_int),
+        ("reject", TrackRejectOutC),
+        ("detect", GftOutC),
+        ("pts", C.POINTER(C.c_float)),
+        ("ids", C.POINTER(C.c_int)),
+        ("track_cnt", C.POINTER(C.c_int)),
+        ("un_pts", C.POINTER(C.c_float)),
+        ("un_pts_3d", C.POINTER(C.c_float)),
+        ("velocity_3d", C.POINTER(C.c_float)),
+    ]
+
+
+class TrackFrameStagesC(C.Structure):
+    """LfvioTrackFrameStages (include/lfvio.h)."""
+    _fields_ = [
+        ("next_pts", C.POINTER(C.c_float)),
+        ("status", C.POINTER(C.c_ubyte)),
+        ("samples", C.POINTER(C.c_int)),
+        ("mask", C.POINTER(C.c_ubyte)),
+        ("kept", C.POINTER(C.c_int)),
+        ("corners", C.POINTER(C.c_float)),
+    ]
+
 RELPOSE_MIN_MATCHES = 20  # a pair runs when N > 20 (estimator.cpp:452)
 
 HIP_SYMBOLS = [
@@ -701,7 +757,7 @@ HIP_SYMBOLS = [
     "lfvio_two_view", "lfvio_vi_align", "lfvio_pnp", "lfvio_sfm_ba", "lfvio_sfm_construct", "lfvio_relative_pose",
     "lfvio_klt_track", "lfvio_klt_reset", "lfvio_klt_level", "lfvio_gft_detect", "lfvio_gft_set_mask", "lfvio_gft_response",
     "lfvio_clahe_set", "lfvio_clahe_apply",
-    "lfvio_track_reject", "lfvio_track_undistort", "lfvio_track_reset",
+    "lfvio_track_reject", "lfvio_track_undistort", "lfvio_track_reset", "lfvio_track_frame", "lfvio_track_frame_reset",
     "lfvio_group_create", "lfvio_group_unique_id", "lfvio_group_create_rank", "lfvio_group_create_local", "lfvio_group_destroy",
     "lfvio_group_last_error", "lfvio_group_size", "lfvio_group_local", "lfvio_group_rank", "lfvio_group_ctx", "lfvio_group_backend",
     "lfvio_group_solve", "lfvio_group_upload", "lfvio_group_optimize", "lfvio_group_download", "lfvio_group_range",
@@ -791,6 +847,9 @@ def load_hip_library(path=None):
         lib.lfvio_track_reject.argtypes = [C.c_void_p, C.POINTER(TrackRejectInC), C.POINTER(C.c_ubyte), C.POINTER(TrackRejectOutC), _dp, _dp]
         lib.lfvio_track_undistort.argtypes = [C.c_void_p, C.POINTER(TrackUndistortInC)] + [C.POINTER(C.c_float)] * 3 + [C.POINTER(C.c_int)]
         lib.lfvio_track_reset.argtypes = [C.c_void_p]
+    if hasattr(lib, "lfvio_track_frame"):
+        lib.lfvio_track_frame.argtypes = [C.c_void_p, C.POINTER(TrackFrameInC), C.POINTER(TrackFrameOutC), C.POINTER(TrackFrameStagesC)]
+        lib.lfvio_track_frame_reset.argtypes = [C.c_void_p]
     lib.lfvio_shard_marg_linearize.argtypes = [C.c_void_p, C.c_int]
     lib.lfvio_shard_marg_finish.argtypes = [C.c_void_p, C.c_int, C.POINTER(Prior)]
     # multi-GPU groups (RCCL inside the library)

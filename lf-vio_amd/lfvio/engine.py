@@ -615,6 +615,81 @@ class Engine:
         """lfvio_track_reset: forget the resident (id, un_pts_3d) map and time; the next track_undistort gives zero velocities."""
         self._check(self.lib.lfvio_track_reset(self.ctx), "lfvio_track_reset")
 
+    TRACK_FRAME_DEFAULTS = dict(win_size=41, max_level=3, max_iterations=30, epsilon=0.01, min_eig_threshold=1e-4, border=1, max_count=150,
+                                quality_level=0.01, min_distance=30, mask_radius=30, num_samples=None, capacity=None, width=None, height=None)
+
+    def track_frame(self, img, time, cam, publish=True, words=None, stages=False, out=None, arrays=None, null=(), check=True, **params):
+        """lfvio_track_frame: `img` [height, width] uint8 at cur_time `time` through readImage on the context's resident track table,
+        camera `cam` (camera()), the sample sets drawn on the device from `words` [S, 8] uint32.  params: the fields of
+        LfvioTrackFrameIn (TRACK_FRAME_DEFAULTS; num_samples, capacity, width and height default to what the arrays say; capacity to
+        4096).  Returns a dict: pts, ids, track_cnt, un_pts, un_pts_3d, velocity_3d (num_points entries each), num_points, num_new,
+        levels_used, num_tracked, num_after_reject, reject and detect (dicts of LfvioTrackRejectOut / LfvioGftOut), rc and, with
+        stages, stages = dict(next, status, samples (None where none were drawn), mask, kept, corners).  out: a TrackFrameOutC to
+        be written; arrays: a dict of the six output arrays; null: names among the six whose pointer is passed as NULL; img / cam /
+        words None: null pointers (tests of what a refused call leaves alone); check=False returns the error code under `rc`."""
+        unknown = set(params) - set(self.TRACK_FRAME_DEFAULTS)
+        if unknown:
+            raise TypeError(f"track_frame: unknown parameters {sorted(unknown)}")
+        p = dict(self.TRACK_FRAME_DEFAULTS, **params)
+        fp, ip, up = C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_ubyte)
+        px = None if img is None else np.ascontiguousarray(img, dtype=np.uint8)
+        wd = None if words is None else np.ascontiguousarray(words, dtype=np.uint32).reshape(-1, 8)
+        camc = self.camera(cam)
+        fin = abi.TrackFrameInC()
+        fin.width = p["width"] if p["width"] is not None else (0 if px is None else px.shape[1])
+        fin.height = p["height"] if p["height"] is not None else (0 if px is None else px.shape[0])
+        fin.image = None if px is None else px.ctypes.data_as(up)
+        fin.time, fin.publish = time, int(publish)
+        fin.camera = None if camc is None else C.pointer(camc)
+        for key in ("win_size", "max_level", "max_iterations", "epsilon", "min_eig_threshold", "border", "max_count", "quality_level",
+                    "min_distance", "mask_radius"):
+            setattr(fin, key, p[key])
+        fin.num_samples = p["num_samples"] if p["num_samples"] is not None else (1 if wd is None else len(wd))
+        fin.sample_words = None if wd is None else wd.ctypes.data_as(C.POINTER(C.c_uint))
+        fin.capacity = abi.TRACK_MAX_POINTS if p["capacity"] is None else p["capacity"]
+        cap = abi.TRACK_MAX_POINTS
+        if arrays is None:
+            arrays = dict(pts=np.zeros((cap, 2), np.float32), ids=np.zeros(cap, np.int32), track_cnt=np.zeros(cap, np.int32),
+                          un_pts=np.zeros((cap, 2), np.float32), un_pts_3d=np.zeros((cap, 3), np.float32), velocity_3d=np.zeros((cap, 3), np.float32))
+        out = abi.TrackFrameOutC() if out is None else out
+        for key, a in arrays.items():
+            setattr(out, key, None if key in null else a.ctypes.data_as(ip if a.dtype == np.int32 else fp))
+        sg = None
+        if stages:
+            S = min(max(fin.num_samples, 1), 1024)
+            sg = dict(next=np.zeros((cap, 2), np.float32), status=np.zeros(cap, np.uint8), samples=np.zeros((S, 8), np.int32),
+                      mask=np.zeros(cap, np.uint8), kept=np.zeros(cap, np.int32), corners=np.zeros((cap, 2), np.float32))
+            sc = abi.TrackFrameStagesC(sg["next"].ctypes.data_as(fp), sg["status"].ctypes.data_as(up), sg["samples"].ctypes.data_as(ip),
+                                       sg["mask"].ctypes.data_as(up), sg["kept"].ctypes.data_as(ip), sg["corners"].ctypes.data_as(fp))
+        before = self.track_frame_count
+        rc = self.lib.lfvio_track_frame(self.ctx, C.byref(fin), C.byref(out), C.byref(sc) if stages else None)
+        if check:
+            self._check(rc, "lfvio_track_frame")
+        n = min(max(int(out.num_points), 0), cap) if rc == 0 else 0
+        res = {key: a[:n] for key, a in arrays.items()}
+        rj, dt = out.reject, out.detect
+        res.update(num_points=int(out.num_points), num_new=int(out.num_new), levels_used=int(out.levels_used), num_tracked=int(out.num_tracked),
+                   num_after_reject=int(out.num_after_reject), rc=rc,
+                   reject=dict(status=int(rj.status), best_sample=int(rj.best_sample), num_inliers=int(rj.num_inliers),
+                               best_score=float(rj.best_score), E=np.array(rj.E, dtype=np.float64)),
+                   detect=dict(num_kept=int(dt.num_kept), num_corners=int(dt.num_corners), num_candidates=int(dt.num_candidates),
+                               max_response=float(dt.max_response)))
+        if rc == 0:
+            self.track_frame_count = n
+            if stages:
+                n1 = int(out.num_tracked)
+                res["stages"] = dict(next=sg["next"][:before], status=sg["status"][:before],
+                                     samples=sg["samples"] if publish and n1 >= 8 else None, mask=sg["mask"][:n1] if publish else None,
+                                     kept=sg["kept"][:dt.num_kept] if publish else None, corners=sg["corners"][:dt.num_corners] if publish else None)
+        return res
+
+    def track_frame_reset(self):
+        """lfvio_track_frame_reset: klt_reset and track_reset, the track table empty and the next id 0."""
+        self._check(self.lib.lfvio_track_frame_reset(self.ctx), "lfvio_track_frame_reset")
+        self.track_frame_count = 0
+
+    track_frame_count = 0  # entries of the context's track table, as the last track_frame reported it
+
     def time_kernel(self, which, count, reps):
         ms = np.zeros(1)
         self._check(self.lib.lfvio_debug_time_kernel(self.ctx, which, count, reps, _p(ms)), "time_kernel")
