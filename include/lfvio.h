@@ -642,8 +642,9 @@ int lfvio_relative_pose(lfvio_ctx *ctx, const LfvioRelativePoseIn *in, unsigned 
  * status, err, cv::Size(41, 41), 3) at feature_tracker/src/feature_tracker.cpp:127 and the inBorder test of :6-12, :129-131.  The
  * goodFeaturesToTrack and setMask are lfvio_gft_detect below, the CLAHE of :101-107 is lfvio_clahe_set below them, rejectWithF and
  * undistortedPoints are lfvio_track_reject / lfvio_track_undistort below those, and lfvio_track_frame below them runs all
- * of them, with reduceVector and updateID, on a track table resident in the context; what stays the caller's is a thin host class
- * around that call and the images in the trace format.
+ * of them, with reduceVector and updateID, on a track table resident in the context, and lfvio_track_frame_message adds the node's
+ * feature message; what stays the caller's is the node's bookkeeping around that call — the first image dropped, the discontinuity
+ * restart, the FREQ gate, the skipped first publication: host/image_gate.h and host/feature_tracker.h, on images in the trace format.
  * One call uploads `image`, builds its pyramid, tracks the N points from the pyramid of the PREVIOUS call's image (resident in the
  * context: cur_img = forw_img, :180) into the new one, and makes the new pyramid the resident one.  A context with no resident image —
  * after lfvio_create, after lfvio_klt_reset, or when width or height differ from the resident image's — treats `image` as both
@@ -906,6 +907,22 @@ typedef struct {
 } LfvioTrackFrameStages;
 int lfvio_track_frame(lfvio_ctx *ctx, const LfvioTrackFrameIn *in, LfvioTrackFrameOut *out, const LfvioTrackFrameStages *stages /* or NULL */);
 int lfvio_track_frame_reset(lfvio_ctx *ctx);
+
+/* lfvio_track_frame_message: lfvio_track_frame — the same checks, stages and resident state afterwards, the same bits in out and
+ * stages — and, with in->publish != 0, the feature message the node builds behind readImage (feature_tracker_node.cpp:113-170), built
+ * on the device by one more kernel behind undistortedPoints and brought down in the same block: no second copy, no second wait.
+ * One row for every table entry i with track_cnt[i] > 1, in table order, the nine floats of a type-2 trace record (host/replay.h):
+ *   un_pts_3d[i].x, .y, .z | (float)(ids[i] * NUM_OF_CAM + 0), NUM_OF_CAM = 1, rounded to nearest even | pts[i].x, .y |
+ *   velocity_3d[i].x, .y, .z
+ * with the numbered ids of step 6.  rows has in->capacity rows.  publish == 0: nothing more is launched, num_rows = 0, rows untouched.
+ * Whether the message goes out (the FREQ gate, the skipped first publication) is the caller's: host/image_gate.h.
+ * LFVIO_ERR_ARG as lfvio_track_frame, and for a null msg or msg->rows; everything, msg included, untouched. */
+typedef struct {
+  int num_rows;
+  float *rows; /* [capacity][9] */
+} LfvioTrackMessage;
+int lfvio_track_frame_message(lfvio_ctx *ctx, const LfvioTrackFrameIn *in, LfvioTrackFrameOut *out, const LfvioTrackFrameStages *stages /* or NULL */,
+                              LfvioTrackMessage *msg);
 
 /* ---- landmark-sharded API (multi-GPU) ------------------------
  * Every rank passes the same window but linearizes only landmarks [lm_begin, lm_end) (caller order);

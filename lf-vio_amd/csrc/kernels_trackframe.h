@@ -15,6 +15,10 @@
 //                 without: (forw1, ids1, cnt1) as they are.  ids_raw keeps the -1 for k_trk_undist_n; in the table every -1 takes
 //                 n_id + (the number of -1 before it).  Written twice: into the context's other table buffer and into the block that
 //                 goes down to the host.  num_points, num_new.
+//   k_tf_message: lfvio_track_frame_message only, behind k_trk_undist_n.  Entries with track_cnt > 1 of the table that goes down and of
+//                 undistortedPoints' outputs -> the nine-float rows of the node's feature message (feature_tracker_node.cpp:113-170), in
+//                 table order; num_rows.  The ids are the numbered ones k_tf_finish wrote, not ids_raw.  Count and scan as the others;
+//                 the scan leaves every entry's row in LDS and the write goes over (row, column) with the whole workgroup.
 #pragma once
 #include "kernels_gft.h"
 #include "kernels_track.h"
@@ -136,4 +140,42 @@ __global__ __launch_bounds__(TF_THREADS) void k_tf_finish(int detect, TfTable sr
     }
   }
   if (tid == 0) dev->num_points = n, dev->num_new = num_new;
+}
+
+// rows: [cap][9] = un_pts_3d | (float)(id * NUM_OF_CAM + 0), NUM_OF_CAM = 1 | pts | velocity_3d; cap: the host's bound on num_points
+__global__ __launch_bounds__(TF_THREADS) void k_tf_message(const TfDev *dev, int cap, TfTable down, const float *un_pts_3d, const float *velocity_3d,
+                                                           int *num_rows, float *rows) {
+  __shared__ int s[2][TF_THREADS];
+  __shared__ int slot[LFVIO_TRACK_MAX_POINTS];  // the row of entry i, or -1
+  const int n = min(dev->num_points, cap), tid = threadIdx.x, first = tid * TF_PER, last = min(first + TF_PER, n);
+  int c[TF_PER];
+  int mine = 0;
+#pragma unroll
+  for (int e = 0; e < TF_PER; e++) {
+    c[e] = first + e < last ? down.cnt[first + e] : 0;
+    mine += c[e] > 1;
+  }
+  int total;
+  int at = tf_scan(mine, s, total);
+#pragma unroll
+  for (int e = 0; e < TF_PER; e++)
+    if (first + e < last) slot[first + e] = c[e] > 1 ? at++ : -1;
+  __syncthreads();
+  // the ordered write, an element a thread: the rows are short (150 entries in the node's configuration), sixteen of them one after
+  // the other in a thread would be sixteen round trips to memory
+  for (int k = tid; k < 9 * n; k += TF_THREADS) {
+    const int i = k / 9, col = k - 9 * i, o = slot[i];
+    if (o < 0) continue;
+    float v;
+    if (col < 3)
+      v = un_pts_3d[3 * i + col];
+    else if (col == 3)
+      v = (float)down.ids[i];  // (int -> float: nearest even)
+    else if (col < 6)
+      v = down.pts[2 * i + col - 4];
+    else
+      v = velocity_3d[3 * i + col - 6];
+    rows[9 * o + col] = v;
+  }
+  if (tid == 0) *num_rows = total;
 }

@@ -14,7 +14,9 @@ constexpr size_t TF_TABLE_BYTES = (size_t)LFVIO_TRACK_MAX_POINTS * 16;
 // [n][2] floats | n ids | n counts at p
 static TfTable tf_table(char *p, size_t n) { return TfTable{(float *)p, (int *)(p + n * 8), (int *)(p + n * 12)}; }
 
-int lfvio_track_frame(lfvio_ctx *c, const LfvioTrackFrameIn *in, LfvioTrackFrameOut *out, const LfvioTrackFrameStages *stages) {
+// lfvio_track_frame (msg null) and lfvio_track_frame_message: with a message and publish the rows are one more segment of the block
+// that comes down (trackframe_message_bytes), written by k_tf_message behind k_trk_undist_n.
+static int track_frame_run(lfvio_ctx *c, const LfvioTrackFrameIn *in, LfvioTrackFrameOut *out, const LfvioTrackFrameStages *stages, LfvioTrackMessage *msg) {
   if (!c || !in || !out) return LFVIO_ERR_ARG;
   lfvio_ctx::TrackFrameState &f = c->tframe;
   lfvio_ctx::TrackState &t = c->track;
@@ -45,7 +47,9 @@ int lfvio_track_frame(lfvio_ctx *c, const LfvioTrackFrameIn *in, LfvioTrackFrame
   const size_t oA = st.take(std::max<size_t>(N0, 9) * 72), oSc = st.take((size_t)S * 4), oE = st.take((size_t)S * 72);
   const size_t oRaw = st.take(B * 4), oMt = st.take(B * 4);
   // down: the counts and records, the table, the outputs of undistortedPoints; the stages behind them, for a caller who asks
-  const size_t oD = st.take(sizeof(TfDev)), oTab = st.take(B * 16), oU = st.take(B * 8), o3 = st.take(B * 12), oV = st.take(B * 12), main_end = st.end;
+  const size_t oD = st.take(sizeof(TfDev)), oTab = st.take(B * 16), oU = st.take(B * 8), o3 = st.take(B * 12), oV = st.take(B * 12);
+  const bool rows = msg && pub;
+  const size_t oMsg = rows ? st.take(trackframe_message_bytes(B)) : 0, main_end = st.end;
   const size_t oN = st.take(N0 * 8), oSt = st.take(N0), oSm = st.take((size_t)S * 32), oM = st.take(N0), oK = st.take(N0 * 4), oX = st.take((size_t)MC * 8);
   if (int rc = st.reserve()) return rc;
   if (pub)
@@ -112,11 +116,17 @@ int lfvio_track_frame(lfvio_ctx *c, const LfvioTrackFrameIn *in, LfvioTrackFrame
                        (float *)(d + oU), (float *)(d + o3), (float *)(d + oV), (int *)(d + oMt), (int *)nm, (float *)(nm + TRACK_MAP_IDS));
     HIPCHK(c, hipGetLastError());
   }
+  if (rows) {
+    hipLaunchKernelGGL(k_tf_message, dim3(1), dim3(TF_THREADS), 0, st.fs, (const TfDev *)dev, (int)B, down, (const float *)(d + o3), (const float *)(d + oV),
+                       (int *)(d + oMsg), (float *)(d + oMsg + TF_MSG_HEAD));
+    HIPCHK(c, hipGetLastError());
+  }
   if (int rc = st.down(oD, stages ? st.end : main_end)) return rc;
 
   const TfDev *o = (const TfDev *)(h + oD);
   const size_t n = (size_t)o->num_points, n1 = (size_t)o->n1;
-  if (o->num_points < 0 || n > B || o->n1 < 0 || n1 > N0 ||
+  const int num_rows = rows ? *(const int *)(h + oMsg) : 0;
+  if (o->num_points < 0 || n > B || o->n1 < 0 || n1 > N0 || num_rows < 0 || (size_t)num_rows > n ||
       (pub && (o->detect.num_kept < 0 || (size_t)o->detect.num_kept > N0 || o->detect.num_corners < 0 || o->detect.num_corners > MC))) {
     c->err = "lfvio_track_frame: a count from the device beyond its bound";
     return LFVIO_ERR_DEVICE;
@@ -138,6 +148,10 @@ int lfvio_track_frame(lfvio_ctx *c, const LfvioTrackFrameIn *in, LfvioTrackFrame
   std::memcpy(out->un_pts, h + oU, n * 8);
   std::memcpy(out->un_pts_3d, h + o3, n * 12);
   std::memcpy(out->velocity_3d, h + oV, n * 12);
+  if (msg) {
+    msg->num_rows = num_rows;
+    if (num_rows) std::memcpy(msg->rows, h + oMsg + TF_MSG_HEAD, (size_t)num_rows * 36);
+  }
   if (stages) {
     if (stages->next_pts) std::memcpy(stages->next_pts, h + oN, N0 * 8);
     if (stages->status) std::memcpy(stages->status, h + oSt, N0);
@@ -154,6 +168,19 @@ int lfvio_track_frame(lfvio_ctx *c, const LfvioTrackFrameIn *in, LfvioTrackFrame
   t.count = (int)n, t.time = in->time;
   f.cur = 1 - f.cur, f.count = (int)n, f.n_id += o->num_new;
   return LFVIO_OK;
+}
+
+int lfvio_track_frame(lfvio_ctx *c, const LfvioTrackFrameIn *in, LfvioTrackFrameOut *out, const LfvioTrackFrameStages *stages) {
+  return track_frame_run(c, in, out, stages, nullptr);
+}
+
+int lfvio_track_frame_message(lfvio_ctx *c, const LfvioTrackFrameIn *in, LfvioTrackFrameOut *out, const LfvioTrackFrameStages *stages, LfvioTrackMessage *msg) {
+  if (!c) return LFVIO_ERR_ARG;
+  if (const char *why = trackframe_message_check(msg)) {
+    c->err = why;
+    return LFVIO_ERR_ARG;
+  }
+  return track_frame_run(c, in, out, stages, msg);
 }
 
 int lfvio_track_frame_reset(lfvio_ctx *c) {

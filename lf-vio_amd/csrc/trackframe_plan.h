@@ -38,6 +38,15 @@ inline const char *trackframe_check(const LfvioTrackFrameIn *in, int table_count
   return nullptr;
 }
 
+// lfvio_track_frame_message's own: the message it fills.  (rows has in->capacity rows, and a message has at most as many as the table.)
+inline const char *trackframe_message_check(const LfvioTrackMessage *msg) {
+  if (!msg || !msg->rows) return "lfvio_track_frame_message: null msg or msg->rows";
+  return nullptr;
+}
+// bytes of the message's segment of the block that comes down: [num_rows | pad to 16 | bound x 9 floats]
+constexpr size_t TF_MSG_HEAD = 16;
+inline size_t trackframe_message_bytes(size_t bound) { return TF_MSG_HEAD + bound * 36; }
+
 // What the host knows of the counts: n1 and n2 are at most the table's count, the count after the call at most this.
 inline int trackframe_bound(int table_count, int max_count, bool publish) { return publish ? std::max(table_count, max_count) : table_count; }
 

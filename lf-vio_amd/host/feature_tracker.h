@@ -1,0 +1,64 @@
+// feature_tracker.h — the feature tracker node on the host: img_callback (feature_tracker/src/feature_tracker_node.cpp:28-178) around ONE
+// device call per image, lfvio_track_frame_message (include/lfvio.h), which runs readImage, updateID and the feature message on a
+// track table resident in the context.  What is left here is the node's bookkeeping (image_gate.h), the row repacking of an image
+// whose step is not its width, the base mask and CLAHE setting at the first use, and the generator of rejectWithF's sample sets.
+// Not compiled into the test suite's CPU build of the host sources (oracle/Makefile): only host/Makefile builds it.
+#pragma once
+#include <random>
+#include <string>
+#include <vector>
+
+#include "../../include/lfvio.h"
+#include "image_gate.h"
+#include "replay.h"
+
+namespace lfvio {
+
+struct TrackerConfig {
+  LfvioCamera camera = {};
+  int max_cnt = 150;   // MAX_CNT
+  int min_dist = 30;   // MIN_DIST: goodFeaturesToTrack's distance and the radius of setMask's discs
+  int freq = 10;       // FREQ
+  bool equalize = false;  // EQUALIZE: CLAHE (3.0, 8 x 8) before the pyramid
+  // the base mask (fisheye_mask): pixels of the image's size, or the annulus min_r^2 < (x - center_x)^2 + (y - center_y)^2 <= max_r^2
+  // rasterised at the first image (Euclidean discs, as lfvio.engine.annulus_mask), or neither: every pixel allowed
+  std::vector<unsigned char> mask;
+  int mask_width = 0, mask_height = 0;
+  bool annulus = false;
+  double center_x = 0, center_y = 0, max_r = 0, min_r = 0;
+  int num_samples = 100;     // rejectWithF's sample sets
+  unsigned ransac_seed = 0;  // 0: seeded from std::random_device, as Config::ransac_seed
+};
+
+class FeatureTracker {
+ public:
+  enum Result { DROPPED = 0, RESTART = 1, TRACKED_ONLY = 2, FIRST_PUBLICATION_SKIPPED = 3, PUBLISHED = 4 };
+  // ctx: the context to run on (the estimator's), or null for one of its own on `device`.  The track table, the pyramid and the map of
+  // the context are reset: a tracker starts empty.
+  explicit FeatureTracker(const TrackerConfig &config, lfvio_ctx *ctx = nullptr, int device = 0);
+  ~FeatureTracker();
+  FeatureTracker(const FeatureTracker &) = delete;
+  FeatureTracker &operator=(const FeatureTracker &) = delete;
+
+  // One sensor_msgs/Image (mono8, `step` bytes per row).  Returns a Result, or the negative status of the device call that failed
+  // (`status`, error()): no silent continuation.  PUBLISHED: *msg is the feature message, stamped `stamp`; otherwise msg is untouched.
+  int onImage(double stamp, int width, int height, int step, const unsigned char *pixels, TraceImage *msg);
+
+  const char *error() const;
+  int status = LFVIO_OK;
+  int last_points = 0;  // the table's count after the last image that reached the tracker
+  ImageGate gate;
+
+ private:
+  TrackerConfig cfg_;
+  lfvio_ctx *ctx_ = nullptr;
+  bool own_ = false, ready_ = false;
+  std::mt19937 rng_;
+  std::vector<unsigned char> packed_;
+  std::vector<unsigned> words_;
+  std::vector<float> pts_, un_pts_, un_pts_3d_, velocity_3d_, rows_;
+  std::vector<int> ids_, track_cnt_;
+  std::string error_;
+};
+
+}  // namespace lfvio

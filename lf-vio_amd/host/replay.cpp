@@ -15,21 +15,53 @@ bool Trace::load(const char *path) {
     error = std::string("cannot open ") + path;
     return false;
   }
+  const bool ok = read(f);
+  std::fclose(f);
+  return ok;
+}
+
+bool Trace::read(std::FILE *f) {
   char magic[4];
   uint32_t version = 0;
   if (std::fread(magic, 1, 4, f) != 4 || std::memcmp(magic, "LFVT", 4) != 0 || std::fread(&version, 4, 1, f) != 1 || version != 1) {
     error = "not an LFVT version 1 trace";
-    std::fclose(f);
     return false;
   }
   std::vector<char> buf;
   for (;;) {
     uint32_t head[2];
     if (std::fread(head, 4, 2, f) != 2) break;  // end of file
+    if (head[0] == 10) {  // a raw image: its header, and past its pixels
+      struct {
+        double t;
+        uint32_t width, height, step, encoding;
+      } ih;
+      static_assert(sizeof ih == 24, "packed");
+      if (head[1] < sizeof ih || std::fread(&ih, sizeof ih, 1, f) != 1) {
+        error = "image record shorter than its header";
+        return false;
+      }
+      if (ih.width < 16 || ih.width > 8192 || ih.height < 16 || ih.height > 8192 || ih.step < ih.width || ih.encoding != 0 ||
+          head[1] != sizeof ih + (uint64_t)ih.height * ih.step) {
+        error = "image record: a size outside [16, 8192], step < width, an unknown encoding or a wrong length";
+        return false;
+      }
+      if (!raw_images.empty() && (raw_images[0].width != ih.width || raw_images[0].height != ih.height)) {
+        error = "images of differing size";
+        return false;
+      }
+      const long at = std::ftell(f);
+      char last;  // (a seek past the end succeeds: read the last pixel instead)
+      if (at < 0 || std::fseek(f, at + (long)(head[1] - sizeof ih) - 1, SEEK_SET) != 0 || std::fread(&last, 1, 1, f) != 1) {
+        error = "truncated record";
+        return false;
+      }
+      raw_images.push_back({ih.t, ih.width, ih.height, ih.step, (uint64_t)at});
+      continue;
+    }
     buf.resize(head[1]);
     if (head[1] && std::fread(buf.data(), 1, head[1], f) != head[1]) {
       error = "truncated record";
-      std::fclose(f);
       return false;
     }
     const double *d = (const double *)buf.data();
@@ -40,7 +72,6 @@ bool Trace::load(const char *path) {
       std::memcpy(&n, buf.data() + 8, 4);
       if (head[1] != 12 + (size_t)n * 36) {
         error = "feature record with a wrong length";
-        std::fclose(f);
         return false;
       }
       TraceImage m;
@@ -82,7 +113,6 @@ bool Trace::load(const char *path) {
       const size_t K = (head[1] - 10 * sizeof(double)) / (3 * sizeof(double));
       if ((size_t)d[9] != K) {
         error = "relocalization record with a wrong length";
-        std::fclose(f);
         return false;
       }
       for (size_t k = 0; k < K; k++) r.points.push_back(Vector3d(d[10 + 3 * k], d[11 + 3 * k], d[12 + 3 * k]));
@@ -93,7 +123,6 @@ bool Trace::load(const char *path) {
       std::memcpy(&n, buf.data() + 8, 4);
       if (head[1] != 12 + (size_t)n * 13 * sizeof(double)) {
         error = "SfM record with a wrong length";
-        std::fclose(f);
         return false;
       }
       TraceSfm s;
@@ -112,7 +141,6 @@ bool Trace::load(const char *path) {
       std::memcpy(kp, buf.data() + 8, 8);
       if (head[1] != 16 + ((size_t)kp[0] * 8 + (size_t)kp[1] * 4) * sizeof(double)) {
         error = "SfM structure record with a wrong length";
-        std::fclose(f);
         return false;
       }
       TraceStructure s;
@@ -136,7 +164,6 @@ bool Trace::load(const char *path) {
     } else if (head[0] == 9) {
       if (head[1] != 8 + 4 + 12 * sizeof(double)) {
         error = "relative pose record with a wrong length";
-        std::fclose(f);
         return false;
       }
       TraceRelative r;
@@ -150,7 +177,10 @@ bool Trace::load(const char *path) {
       relatives.push_back(std::move(r));
     }
   }
-  std::fclose(f);
+  if (!raw_images.empty() && !images.empty()) {
+    error = "a recording holds raw images or feature messages, not both";
+    return false;
+  }
   return true;
 }
 

@@ -40,9 +40,18 @@
 //                                     (WindowEstimator::constructSfm), then the PnP loop and the same alignment.  A bootstrap
 //                                     record, an SfM result or an SfM structure for the same image wins.
 //
+//   type 10 = sensor_msgs/Image       f64 stamp, u32 width, u32 height, u32 step, u32 encoding (0: mono8 / 8UC1), then height x step bytes:
+//                                     a raw camera image, for the tracker of feature_tracker.h (image_replay.h runs it over a recording
+//                                     and replaces every image by what the node would have published for it).  The loader keeps the
+//                                     stamp, the sizes and the file offset of the pixels, not the pixels.  Refused: a record shorter
+//                                     or longer than its sizes say, step < width, a width or height outside [16, 8192], another
+//                                     encoding, images of differing size, a file that holds both type 2 and type 10.  replay()
+//                                     does not look at raw images.
+//
 // Unknown record types are skipped, so a recorder can add its own.
 #pragma once
 #include <cstdint>
+#include <cstdio>
 #include <string>
 #include <vector>
 
@@ -58,6 +67,11 @@ struct TraceImage {
   double t;
   std::vector<float> v;  // n x 9
   size_t size() const { return v.size() / 9; }
+};
+struct TraceRawImage {  // record type 10, without its pixels
+  double t;
+  uint32_t width, height, step;
+  uint64_t offset;  // of the first pixel, from the start of the file
 };
 struct TraceBoot {
   WindowEstimator::Bootstrap state;
@@ -94,6 +108,7 @@ struct Trace {
   std::vector<TraceRelo> relos;       // in file order
   std::vector<TraceImu> imu;
   std::vector<TraceImage> images;
+  std::vector<TraceRawImage> raw_images;  // in file order
   std::vector<TraceBoot> boots;       // in file order
   std::vector<size_t> restarts;       // restart messages: number of images recorded before each
   bool has_bootstrap = false;         // the first bootstrap record (what a recording without reboots has)
@@ -102,6 +117,7 @@ struct Trace {
   double td = 0;
   std::string error;
   bool load(const char *path);
+  bool read(std::FILE *f);  // the same from an open stream at its start (closed by the caller)
 };
 
 struct ReplayStats {

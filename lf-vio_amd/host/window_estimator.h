@@ -386,13 +386,13 @@ class WindowEstimator {
   int status = LFVIO_OK;
   lfvio_ctx *gpu = nullptr;      // the context (of the first device of the mask): triangulation, depth shifts, preintegration
   lfvio_group *group = nullptr;  // more than one device in Config::device_mask: the sharded optimization()
+  bool device();  // creates `gpu` (and `group`) at the first use; false, with `status` set, where there is no device
 
  private:
   LfvioPrior next_;  // the prior being downloaded (240 KB: a member, not a stack object; only header + n x n + n are copied)
   bool chain_upload_ = false;   // pack() on behalf of an optimization() whose upload collects the pending prior itself
   bool prior_pending_ = false;  // the marginalization of the last optimization() has not been collected yet (collectPrior)
   bool prior_on_device_ = false;  // the resident window took its prior over on the device (lfvio_batch_upload_chained_device): `prior` is stale
-  bool device();
   bool applyBootstrap();
   ImageFrame pending_;  // tmp_pre_integration: the samples since the last image
   void advanceWindow(double stamp);  // processImage() behind the keyframe test and the calibration (estimator.cpp:161-220)

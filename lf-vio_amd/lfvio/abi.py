@@ -744,6 +744,12 @@ class TrackFrameStagesC(C.Structure):
         ("corners", C.POINTER(C.c_float)),
     ]
 
+
+class TrackMessageC(C.Structure):
+    """LfvioTrackMessage (include/lfvio.h)."""
+    _fields_ = [("num_rows", C.c_int), ("rows", C.POINTER(C.c_float))]
+
+
 RELPOSE_MIN_MATCHES = 20  # a pair runs when N > 20 (estimator.cpp:452)
 
 HIP_SYMBOLS = [
@@ -758,6 +764,7 @@ HIP_SYMBOLS = [
     "lfvio_klt_track", "lfvio_klt_reset", "lfvio_klt_level", "lfvio_gft_detect", "lfvio_gft_set_mask", "lfvio_gft_response",
     "lfvio_clahe_set", "lfvio_clahe_apply",
     "lfvio_track_reject", "lfvio_track_undistort", "lfvio_track_reset", "lfvio_track_frame", "lfvio_track_frame_reset",
+    "lfvio_track_frame_message",
     "lfvio_group_create", "lfvio_group_unique_id", "lfvio_group_create_rank", "lfvio_group_create_local", "lfvio_group_destroy",
     "lfvio_group_last_error", "lfvio_group_size", "lfvio_group_local", "lfvio_group_rank", "lfvio_group_ctx", "lfvio_group_backend",
     "lfvio_group_solve", "lfvio_group_upload", "lfvio_group_optimize", "lfvio_group_download", "lfvio_group_range",
@@ -850,6 +857,9 @@ def load_hip_library(path=None):
     if hasattr(lib, "lfvio_track_frame"):
         lib.lfvio_track_frame.argtypes = [C.c_void_p, C.POINTER(TrackFrameInC), C.POINTER(TrackFrameOutC), C.POINTER(TrackFrameStagesC)]
         lib.lfvio_track_frame_reset.argtypes = [C.c_void_p]
+    if hasattr(lib, "lfvio_track_frame_message"):
+        lib.lfvio_track_frame_message.argtypes = [C.c_void_p, C.POINTER(TrackFrameInC), C.POINTER(TrackFrameOutC), C.POINTER(TrackFrameStagesC),
+                                                  C.POINTER(TrackMessageC)]
     lib.lfvio_shard_marg_linearize.argtypes = [C.c_void_p, C.c_int]
     lib.lfvio_shard_marg_finish.argtypes = [C.c_void_p, C.c_int, C.POINTER(Prior)]
     # multi-GPU groups (RCCL inside the library)

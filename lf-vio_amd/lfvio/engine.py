@@ -618,7 +618,8 @@ class Engine:
     TRACK_FRAME_DEFAULTS = dict(win_size=41, max_level=3, max_iterations=30, epsilon=0.01, min_eig_threshold=1e-4, border=1, max_count=150,
                                 quality_level=0.01, min_distance=30, mask_radius=30, num_samples=None, capacity=None, width=None, height=None)
 
-    def track_frame(self, img, time, cam, publish=True, words=None, stages=False, out=None, arrays=None, null=(), check=True, **params):
+    def track_frame(self, img, time, cam, publish=True, words=None, stages=False, out=None, arrays=None, null=(), check=True, _message=None,
+                    **params):
         """lfvio_track_frame: `img` [height, width] uint8 at cur_time `time` through readImage on the context's resident track table,
         camera `cam` (camera()), the sample sets drawn on the device from `words` [S, 8] uint32.  params: the fields of
         LfvioTrackFrameIn (TRACK_FRAME_DEFAULTS; num_samples, capacity, width and height default to what the arrays say; capacity to
@@ -626,7 +627,8 @@ class Engine:
         levels_used, num_tracked, num_after_reject, reject and detect (dicts of LfvioTrackRejectOut / LfvioGftOut), rc and, with
         stages, stages = dict(next, status, samples (None where none were drawn), mask, kept, corners).  out: a TrackFrameOutC to
         be written; arrays: a dict of the six output arrays; null: names among the six whose pointer is passed as NULL; img / cam /
-        words None: null pointers (tests of what a refused call leaves alone); check=False returns the error code under `rc`."""
+        words None: null pointers (tests of what a refused call leaves alone); check=False returns the error code under `rc`.
+        (_message: track_frame_message's, below.)"""
         unknown = set(params) - set(self.TRACK_FRAME_DEFAULTS)
         if unknown:
             raise TypeError(f"track_frame: unknown parameters {sorted(unknown)}")
@@ -662,9 +664,12 @@ class Engine:
             sc = abi.TrackFrameStagesC(sg["next"].ctypes.data_as(fp), sg["status"].ctypes.data_as(up), sg["samples"].ctypes.data_as(ip),
                                        sg["mask"].ctypes.data_as(up), sg["kept"].ctypes.data_as(ip), sg["corners"].ctypes.data_as(fp))
         before = self.track_frame_count
-        rc = self.lib.lfvio_track_frame(self.ctx, C.byref(fin), C.byref(out), C.byref(sc) if stages else None)
+        if _message is None:
+            rc = self.lib.lfvio_track_frame(self.ctx, C.byref(fin), C.byref(out), C.byref(sc) if stages else None)
+        else:
+            rc = self.lib.lfvio_track_frame_message(self.ctx, C.byref(fin), C.byref(out), C.byref(sc) if stages else None, _message["arg"])
         if check:
-            self._check(rc, "lfvio_track_frame")
+            self._check(rc, "lfvio_track_frame" if _message is None else "lfvio_track_frame_message")
         n = min(max(int(out.num_points), 0), cap) if rc == 0 else 0
         res = {key: a[:n] for key, a in arrays.items()}
         rj, dt = out.reject, out.detect
@@ -681,6 +686,21 @@ class Engine:
                 res["stages"] = dict(next=sg["next"][:before], status=sg["status"][:before],
                                      samples=sg["samples"] if publish and n1 >= 8 else None, mask=sg["mask"][:n1] if publish else None,
                                      kept=sg["kept"][:dt.num_kept] if publish else None, corners=sg["corners"][:dt.num_corners] if publish else None)
+        return res
+
+    def track_frame_message(self, img, time, cam, rows=None, msg="new", **kw):
+        """lfvio_track_frame_message: track_frame's arguments and its dict, plus rows [num_rows, 9] float32 (the node's feature message:
+        un_pts_3d, id, pts, velocity_3d of the entries with track_cnt > 1) and num_rows.  rows: the [capacity, 9] float32 array to be
+        written (default: a fresh one of 4096 rows); msg: a TrackMessageC to be written, or None for a null pointer; rows=False:
+        a null rows pointer (tests of what a refused call leaves alone)."""
+        fp = C.POINTER(C.c_float)
+        buf = np.zeros((abi.TRACK_MAX_POINTS, 9), np.float32) if rows is None else rows
+        m = abi.TrackMessageC() if isinstance(msg, str) else msg
+        if m is not None:
+            m.rows = None if buf is False else buf.ctypes.data_as(fp)
+        res = self.track_frame(img, time, cam, _message=dict(arg=None if m is None else C.byref(m)), **kw)
+        n = int(m.num_rows) if (m is not None and res["rc"] == 0) else 0
+        res.update(num_rows=n, rows=None if buf is False else buf[:n])
         return res
 
     def track_frame_reset(self):

@@ -77,6 +77,14 @@ class HostEstimator:
         L.lfvio_host_last_iterations.argtypes = [C.c_void_p]
         L.lfvio_host_last_cost.argtypes = [C.c_void_p]
         L.lfvio_host_last_cost.restype = C.c_double
+        # the image route (host/tracker_capi.cpp): the product build has it, the suite's CPU build of the estimator's sources does not
+        self.has_tracker = hasattr(L, "lfvio_host_track_trace")
+        if self.has_tracker:
+            L.lfvio_host_track_config.argtypes = [C.POINTER(abi.CameraC), ip, _dp, C.c_int, C.c_int, C.POINTER(C.c_ubyte)]
+            L.lfvio_host_track_config.restype = None
+            L.lfvio_host_track_trace.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, _dp]
+            L.lfvio_host_replay_images.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_int, ip, _dp]
+            L.lfvio_host_trace_raw_images.argtypes = [C.c_char_p, C.c_int, _dp, C.c_char_p, C.c_int]
         self.L = L
         self.h = L.lfvio_host_create()
 
@@ -203,6 +211,49 @@ class HostEstimator:
         rc = self.L.lfvio_host_replay_timed(self.h, str(trace_path).encode(), str(traj_path).encode(), int(max_images),
                                             o.ctypes.data_as(C.POINTER(C.c_int)), _p(ms), cap, C.byref(n))
         return rc, dict(zip(self.STATS, (int(x) for x in o))), ms[:n.value].copy()
+
+    TRACK_STATS = ("raw_images", "dropped", "restarts", "tracked_only", "published", "rows", "tracker_ms")
+
+    def _tracker(self):
+        if not self.has_tracker:
+            raise RuntimeError("this build of the host library has no image route (host/tracker_capi.cpp): use the product build")
+
+    def track_config(self, cam, max_cnt=150, min_dist=30, freq=10, equalize=False, num_samples=100, seed=0, annulus=None, mask=None):
+        """lfvio_host_track_config: the tracker of the next track_trace / replay_images.  cam: a dict as Engine.camera takes (or a
+        CameraC); annulus = (center_x, center_y, max_r, min_r) or mask [height, width] uint8: the base mask; seed 0: std::random_device."""
+        self._tracker()
+        camc = cam if isinstance(cam, abi.CameraC) else abi.CameraC(int(cam.get("model", abi.CAM_OCAM)), cam["cx"], cam["cy"], cam["c"], cam["d"],
+                                                                      cam["e"], (C.c_double * 5)(*[float(v) for v in cam["poly"]]))
+        iv = np.array([max_cnt, min_dist, freq, int(bool(equalize)), num_samples, seed], dtype=np.uint32).view(np.int32)
+        an = None if annulus is None else _f(annulus)
+        m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
+        self.L.lfvio_host_track_config(C.byref(camc), iv.ctypes.data_as(C.POINTER(C.c_int)), None if an is None else _p(an),
+                                       0 if m is None else m.shape[1], 0 if m is None else m.shape[0],
+                                       None if m is None else m.ctypes.data_as(C.POINTER(C.c_ubyte)))
+
+    def track_trace(self, in_path, out_path):
+        """lfvio_host_track_trace: the recording with its raw images (type 10) replaced by what the tracker published for them.
+        -> (rc, track stats dict); rc 0 ok, -1 cannot write, -2 a device call failed, -3 unreadable or refused trace."""
+        self._tracker()
+        ts = np.zeros(len(self.TRACK_STATS))
+        rc = self.L.lfvio_host_track_trace(self.h, str(in_path).encode(), str(out_path).encode(), _p(ts))
+        return rc, dict(zip(self.TRACK_STATS, (float(x) for x in ts)))
+
+    def replay_images(self, trace_path, traj_path="", max_images=0):
+        """lfvio_host_replay_images: pixels to poses -> (rc, stats dict as replay(), track stats dict)."""
+        self._tracker()
+        o, ts = np.zeros(len(self.STATS), dtype=np.int32), np.zeros(len(self.TRACK_STATS))
+        rc = self.L.lfvio_host_replay_images(self.h, str(trace_path).encode(), str(traj_path).encode(), int(max_images),
+                                             o.ctypes.data_as(C.POINTER(C.c_int)), _p(ts))
+        return rc, dict(zip(self.STATS, (int(x) for x in o))), dict(zip(self.TRACK_STATS, (float(x) for x in ts)))
+
+    def trace_raw_images(self, trace_path, cap=4096):
+        """The raw images of a trace file as the host loader keeps them -> (n or -3, array [n, 5] = stamp, width, height, step, offset
+        of the pixels in the file, the loader's message where it refused)."""
+        self._tracker()
+        o, err = np.zeros((cap, 5)), C.create_string_buffer(256)
+        n = self.L.lfvio_host_trace_raw_images(str(trace_path).encode(), cap, _p(o), err, 256)
+        return n, o[:max(min(n, cap), 0)].copy(), err.value.decode()
 
     def decode_features(self, trace_path, image_index, cap=4096):
         ids, pts, st = np.zeros(cap, dtype=np.int32), np.zeros((cap, 8)), np.zeros(1)

@@ -7,7 +7,9 @@ tools/bag_to_lfvt.py.  Message layouts are the published ROS 1 serialization of
                            linear_acceleration (3) + covariance (9)                (imu_callback, estimator_node.cpp:136-161)
   sensor_msgs/PointCloud   header, points[] (u32 n, n x 3 f32), channels[] (u32 m, each: string name, f32[] values)
                            (feature_tracker_node.cpp:113-178 -> estimator_node.cpp:292-312)
-  std_msgs/Bool            u8                                                        (restart_callback, :187-204)
+  sensor_msgs/Image        header, u32 height, u32 width, string encoding, u8 is_bigendian, u32 step, u8[] data — the camera topic
+                           img_callback takes (feature_tracker_node.cpp:28-78), for recordings with raw images (record type 10)
+  std_msgs/Bool            u8                                                       (restart_callback, :187-204)
   std_msgs/Float64MultiArray  layout (dim[], data_offset), f64[] data — the bootstrap record the dump hook of
                            INTEGRATION.md section 3 publishes (247 doubles + the stamp of Headers[WINDOW_SIZE])
 header = u32 seq, u32 stamp.sec, u32 stamp.nsec, string frame_id; string = u32 length + bytes; little-endian throughout.
@@ -119,6 +121,35 @@ def de_match_points(buf):
     return stamp, int(v[7]), v[0:3].copy(), np.array([v[4], v[5], v[6], v[3]]), pts
 
 
+def ser_image(seq, stamp, img, step=None, encoding=b"mono8", frame_id=b"camera"):
+    """sensor_msgs/Image: header, u32 height, u32 width, string encoding, u8 is_bigendian, u32 step, u8[] data.  img [height, width]
+    uint8; step: bytes per row (default width; larger: zero padding)."""
+    a = np.ascontiguousarray(img, dtype=np.uint8)
+    h, w = a.shape
+    step = w if step is None else int(step)
+    assert step >= w
+    if step != w:
+        a = np.concatenate([a, np.zeros((h, step - w), np.uint8)], axis=1)
+    return _header(seq, stamp, frame_id) + struct.pack("<II", h, w) + _string(encoding) + struct.pack("<BI", 0, step) + struct.pack("<I", h * step) + a.tobytes()
+
+
+def de_image(buf):
+    """-> (stamp, img [height, width] uint8, step, encoding) of a sensor_msgs/Image in one of the encodings img_callback takes as
+    they are, mono8 and 8UC1 (feature_tracker_node.cpp:64-78); anything else raises ValueError."""
+    stamp, o = _read_header(buf, 0)
+    h, w = struct.unpack_from("<II", buf, o)
+    (ln,) = struct.unpack_from("<I", buf, o + 8)
+    enc = bytes(buf[o + 12:o + 12 + ln])
+    o += 12 + ln
+    _, step = struct.unpack_from("<BI", buf, o)
+    (n,) = struct.unpack_from("<I", buf, o + 5)
+    if enc not in (b"mono8", b"8UC1"):
+        raise ValueError(f"sensor_msgs/Image encoding {enc!r}: only mono8 / 8UC1")
+    if step < w or n != h * step:
+        raise ValueError(f"sensor_msgs/Image: {n} bytes are not {h} rows of {step} (width {w})")
+    return stamp, np.frombuffer(buf, dtype=np.uint8, count=n, offset=o + 9).reshape(h, step)[:, :w].copy(), step, enc.decode()
+
+
 def ser_bool(v):
     return struct.pack("<B", 1 if v else 0)
 
@@ -148,6 +179,7 @@ TYPES = {
     "sensor_msgs/PointCloud": "d8e9c3f5afbdd8a130fd1d2763945fca",
     "std_msgs/Bool": "8b94c1b53db61fb6aed406028ad6332a",
     "std_msgs/Float64MultiArray": "4b7d974086d4060e7db4613a7e6c3ba4",
+    "sensor_msgs/Image": "060021388200f6f0f447d0fcd9c64743",
 }
 
 

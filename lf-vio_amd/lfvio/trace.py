@@ -11,6 +11,7 @@ from . import abi, synth
 
 MAGIC = b"LFVT"
 REC_IMU, REC_FEATURES, REC_BOOTSTRAP, REC_TRUTH, REC_RESTART, REC_RELO, REC_SFM, REC_STRUCTURE, REC_RELATIVE = 1, 2, 3, 4, 5, 6, 7, 8, 9
+REC_IMAGE = 10
 
 
 class TraceWriter:
@@ -84,13 +85,25 @@ class TraceWriter:
     def truth(self, t, p, q_xyzw):
         self._rec(REC_TRUTH, struct.pack("<8d", t, *p, *q_xyzw))
 
+    def image(self, t, img, step=None):
+        """One sensor_msgs/Image, mono8 (type 10): img [height, width] uint8; step: bytes per row in the record (default: width;
+        larger: rows padded with zeros, as a driver with aligned rows sends them)."""
+        a = np.ascontiguousarray(img, dtype=np.uint8)
+        h, w = a.shape
+        step = w if step is None else int(step)
+        assert step >= w
+        if step != w:
+            a = np.concatenate([a, np.zeros((h, step - w), np.uint8)], axis=1)
+        self._rec(REC_IMAGE, struct.pack("<dIIII", t, w, h, step, 0) + a.tobytes())
+
     def close(self):
         self.f.close()
 
 
 def read_trace(path):
-    """-> dict(imu [n,7], images [(t, array[n,9] float32)], bootstrap array or None, truth [n,8])"""
-    out = dict(imu=[], images=[], bootstrap=None, bootstraps=[], restarts=[], truth=[], relos=[], sfms=[], structures=[], relatives=[], order=[])
+    """-> dict(imu [n,7], images [(t, array[n,9] float32)], bootstrap array or None, truth [n,8], raw_images [(t, array[h,w] uint8)],
+    restart_stamps [stamp or None], order [record types])"""
+    out = dict(imu=[], images=[], raw_images=[], raw_steps=[], restart_stamps=[], bootstrap=None, bootstraps=[], restarts=[], truth=[], relos=[], sfms=[], structures=[], relatives=[], order=[])
     with open(path, "rb") as f:
         head = f.read(8)
         assert head[:4] == MAGIC and struct.unpack("<I", head[4:])[0] == 1
@@ -112,6 +125,7 @@ def read_trace(path):
                     out["bootstrap"] = out["bootstraps"][0]
             elif kind == REC_RESTART:
                 out["restarts"].append(len(out["images"]))
+                out["restart_stamps"].append(struct.unpack("<d", p)[0] if len(p) == 8 else None)
             elif kind == REC_RELO:
                 d = np.frombuffer(p, dtype="<f8")
                 out["relos"].append(dict(at_image=len(out["images"]), stamp=float(d[0]), index=int(d[1]), relo_t=d[2:5].copy(),
@@ -133,6 +147,11 @@ def read_trace(path):
                 out["relatives"].append(dict(at_image=len(out["images"]), stamp=stamp, l=l, R=d[:9].reshape(3, 3).copy(), T=d[9:12].copy()))
             elif kind == REC_TRUTH:
                 out["truth"].append(struct.unpack("<8d", p))
+            elif kind == REC_IMAGE:
+                t, w, h, step, enc = struct.unpack("<dIIII", p[:24])
+                assert enc == 0 and len(p) == 24 + h * step
+                out["raw_images"].append((t, np.frombuffer(p[24:], dtype=np.uint8).reshape(h, step)[:, :w].copy()))
+                out["raw_steps"].append(step)
     out["imu"] = np.array(out["imu"]).reshape(-1, 7)
     out["truth"] = np.array(out["truth"]).reshape(-1, 8)
     return out
@@ -269,6 +288,106 @@ def make_stream(path, seed=0, n_frames=40, n_points=600, max_cnt=150, cam_offset
             boot_record(boots_due[k], stamp=stamp)
     w.close()
     return dict(scene=scene, truth=truth, images=images, bootstrap=boot, n_ids=next_id, Xw=Xw, id_point=sp_pt[np.argsort(sp_id)])
+
+
+def image_camera(s):
+    """The PAL camera (synth.OCAM_*) for an image `s` times smaller, 1280 / s x 960 / s, as a dict for Engine.camera: the polynomial
+    in pixels of the small image, z' (phi') = z (s phi') / s, the centre divided by s.  -> (camera, width, height, annulus) with
+    annulus = (center_x, center_y, max_r, min_r): the pixel radii of 120 and 40 degrees from the axis, the window every recording
+    of this module looks through."""
+    s = float(s)
+    cam = dict(cx=synth.OCAM_CX / s, cy=synth.OCAM_CY / s, c=1.0, d=0.0, e=0.0, poly=tuple(c * s ** i / s for i, c in enumerate(synth.OCAM_POLY)))
+    rho = [sum(c * np.deg2rad(a - 90.0) ** i for i, c in enumerate(synth.OCAM_INV)) / s for a in (120.0, 40.0)]
+    # (three pixels inside the window's rims: a corner's response looks at its 3 x 3 neighbours' 3 x 3 gradients, and the rim is an edge)
+    return cam, int(round(synth.OCAM_W / s)), int(round(synth.OCAM_H / s)), (cam["cx"], cam["cy"], float(rho[0]) - 3.0, float(rho[1]) + 3.0)
+
+
+def make_image_stream(path, seed=0, n_frames=36, scale=4, cam_offset=0.0023, boot_noise=(0.02, 0.5), frame_dt=None, box=(2.5, 3.5, 2.0), waves=80,
+                      wavelength=(0.25, 2.5), contrast=40.0):
+    """make_stream's scene, trajectory, IMU, truth and clock convention with rendered IMAGES (record type 10) in place of the feature
+    messages: `n_frames` images of 1280 / scale x 960 / scale pixels through image_camera(scale).  Image k is exposed at
+    frame_dt k + cam_offset on the IMU clock and stamped that minus TD0.  Every pixel is lifted to its ray, rotated into the world
+    and intersected with the INSIDE of the box |x| <= box[0], |y| <= box[1], |z| <= box[2] (metres, around the trajectory, which stays
+    within 0.6 m of the origin): six walls at different distances, not one plane, on which the eight-point fit of rejectWithF would
+    be degenerate.  The texture is a seeded sum of `waves` sinusoids in SPACE (wavelengths uniform in `wavelength` metres, amplitude
+    proportional to the wavelength, standard deviation `contrast` grey levels around 127.5), evaluated where the ray hits the wall,
+    so it has no seams at the edges.  Pixels outside the 40-120 degree annulus are black; the matching base mask is the annulus of
+    image_camera.
+
+    The bootstrap record is the truth (+ boot_noise, as make_stream) of the window of the first eleven PUBLISHED messages, stamped
+    with the last of them.  At 10 Hz with FREQ = 10 the node drops image 0, publishes every later image and skips the first
+    publication (image 1): the window is images 2 .. 12, and the record stands in front of image 12.
+    -> dict(scene, truth [(stamp, P, R, V)], stamps, camera, annulus, width, height, bootstrap, first_window)."""
+    fdt = synth.KF_DT if frame_dt is None else float(frame_dt)
+    scene = synth.Scene(seed, n_total=n_frames + 2 if frame_dt is None else int(np.ceil(n_frames * fdt / synth.KF_DT)) + 3)
+    rng = np.random.default_rng([seed, 15485863])
+    traj = scene.traj
+    cam, W, H, annulus = image_camera(scale)
+    # the texture
+    lam = rng.uniform(wavelength[0], wavelength[1], waves)
+    kdir = rng.normal(size=(waves, 3))
+    kvec = kdir / np.linalg.norm(kdir, axis=1, keepdims=True) * (2 * np.pi / lam)[:, None]
+    ph = rng.uniform(0, 2 * np.pi, waves)
+    amp = lam * (contrast / np.sqrt(0.5 * (lam * lam).sum()))
+    # the rays of the pixels in the camera frame
+    u, v = np.meshgrid(np.arange(W, dtype=np.float64), np.arange(H, dtype=np.float64))
+    x, y = u - cam["cx"], v - cam["cy"]
+    phi = np.hypot(x, y)
+    z = sum(c * phi ** i for i, c in enumerate(cam["poly"]))
+    ray = np.stack([x, y, -z], axis=-1)
+    ray /= np.linalg.norm(ray, axis=-1, keepdims=True)
+    ang = np.degrees(np.arccos(np.clip(ray[..., 2], -1, 1)))
+    lit = (ang >= 40.0) & (ang <= 120.0)
+    rays = ray[lit]  # [n, 3]
+    half = np.asarray(box, np.float64)
+
+    def render(t):
+        P, R = traj.pos(t), traj.R_at(t)
+        o = P + R @ synth.TIC
+        d = rays @ (R @ synth.RIC).T
+        with np.errstate(divide="ignore"):
+            tt = np.where(d > 0, (half - o) / d, np.where(d < 0, (-half - o) / d, np.inf))
+        X = o + d * tt.min(axis=1)[:, None]
+        g = np.zeros(len(X))
+        for k in range(waves):
+            g += amp[k] * np.sin(X @ kvec[k] + ph[k])
+        img = np.zeros((H, W), np.uint8)
+        img[lit] = np.clip(np.rint(127.5 + g), 1, 255).astype(np.uint8)
+        return img
+
+    w = TraceWriter(path)
+    first_window = 2
+
+    def boot_record(first, stamp):
+        Ps, Rs, Vs = [], [], []
+        for j in range(first, first + abi.NUM_FRAMES):
+            tj = fdt * j + cam_offset
+            Ps.append(traj.pos(tj) + rng.normal(0, boot_noise[0], 3))
+            Rs.append(traj.R_at(tj) @ synth.exp_so3(rng.normal(0, np.deg2rad(boot_noise[1]), 3)))
+            Vs.append(traj.vel(tj) + rng.normal(0, 0.02, 3))
+        Bgs = np.tile(scene.bg + rng.normal(0, 0.0005, 3), (abi.NUM_FRAMES, 1))
+        b = dict(Ps=np.array(Ps), Rs=np.array(Rs), Vs=np.array(Vs), Bas=np.zeros((abi.NUM_FRAMES, 3)), Bgs=Bgs,
+                 g=np.array([0.0, 0.0, synth.G_NORM]), tic=synth.TIC, ric=synth.RIC, td=synth.TD0)
+        w.bootstrap(stamp=stamp, **b)
+        return b
+
+    t_imu, k_imu, truth, stamps, boot = traj.t, 0, [], [], None
+    for k in range(n_frames):
+        t_img = fdt * k + cam_offset
+        while k_imu < len(t_imu) and t_imu[k_imu] <= t_img + synth.IMU_DT:  # up to and including the first sample after the image
+            w.imu(t_imu[k_imu], scene.acc_m[k_imu], scene.gyr_m[k_imu])
+            k_imu += 1
+        stamp = t_img - synth.TD0
+        if k == first_window + abi.WINDOW_SIZE:
+            boot = boot_record(first_window, stamp)
+        w.image(stamp, render(t_img))
+        P, R = traj.pos(t_img), traj.R_at(t_img)
+        q = synth.R_to_q(R)  # [w x y z]
+        w.truth(stamp, P, [q[1], q[2], q[3], q[0]])
+        truth.append((stamp, P, R, traj.vel(t_img)))
+        stamps.append(stamp)
+    w.close()
+    return dict(scene=scene, truth=truth, stamps=stamps, camera=cam, annulus=annulus, width=W, height=H, bootstrap=boot, first_window=first_window)
 
 
 def sfm_from_truth(stamps, Ps, Rs, keyframe=0, scale=1.0, rot_noise_deg=0.0, pos_noise=0.0, seed=0, tic=None, ric=None):

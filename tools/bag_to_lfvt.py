@@ -11,7 +11,11 @@ INTEGRATION.md section 3 (one std_msgs/Float64MultiArray per successful initialS
 order the bag received them, contents unchanged (float32 bearings and channels stay float32).  --truth adds ground-truth
 records from a `stamp x y z qx qy qz qw` text file for tools/ate.py.  /pose_graph/match_points (a pose-graph node's loop
 closures, estimator_node.cpp:197-201) becomes record type 6; /vins_estimator/lfvt_sfm (the SfM hook of INTEGRATION.md section 3:
-all_image_frame's stamps, R, T just before visualInitialAlign()) becomes record type 7.  No ROS installation is needed."""
+all_image_frame's stamps, R, T just before visualInitialAlign()) becomes record type 7.  No ROS installation is needed.
+
+--image TOPIC: a bag of the CAMERA topic (sensor_msgs/Image, mono8 or 8UC1) and the IMU, recorded without the reference's tracker:
+every image becomes a raw-image record (type 10) and the feature and restart topics are left out — the tracker of this library
+publishes both when the recording is tracked (lfvio_host_track_trace / lfvio_host_replay_images)."""
 import argparse
 import os
 import sys
@@ -22,7 +26,7 @@ sys.path.insert(0, os.path.join(ROOT, "lf-vio_amd"))
 
 def convert(bag_path, out_path, imu_topic="/imu0", feature_topic="/feature_tracker/feature", restart_topic="/feature_tracker/restart",
             bootstrap_topic="/vins_estimator/lfvt_bootstrap", truth_path=None, relo_topic="/pose_graph/match_points",
-            sfm_topic="/vins_estimator/lfvt_sfm"):
+            sfm_topic="/vins_estimator/lfvt_sfm", image_topic=None):
     import numpy as np
     from lfvio import rosmsg, trace
 
@@ -33,6 +37,12 @@ def convert(bag_path, out_path, imu_topic="/imu0", feature_topic="/feature_track
             stamp, acc, gyr = rosmsg.de_imu(payload)
             w.imu(stamp, acc, gyr)
             n["imu"] += 1
+        elif image_topic and topic == image_topic:
+            stamp, img, step, _ = rosmsg.de_image(payload)
+            w.image(stamp, img, step=step)
+            n["raw_images"] = n.get("raw_images", 0) + 1
+        elif image_topic and topic in (feature_topic, restart_topic):  # somebody else's tracker: a recording holds one or the other
+            n["other"] += 1
         elif topic == feature_topic:
             stamp, rec = rosmsg.de_pointcloud(payload)
             w._rec(trace.REC_FEATURES, __import__("struct").pack("<dI", stamp, len(rec)) + rec.tobytes())
@@ -76,5 +86,6 @@ if __name__ == "__main__":
     ap.add_argument("--truth", default=None)
     ap.add_argument("--relo", default="/pose_graph/match_points")
     ap.add_argument("--sfm", default="/vins_estimator/lfvt_sfm")
+    ap.add_argument("--image", default=None, help="camera topic: write raw-image records (type 10) instead of the feature topic")
     a = ap.parse_args()
-    print(convert(a.bag, a.out, a.imu, a.features, a.restart, a.bootstrap, a.truth, a.relo, a.sfm))
+    print(convert(a.bag, a.out, a.imu, a.features, a.restart, a.bootstrap, a.truth, a.relo, a.sfm, a.image))
