@@ -643,7 +643,8 @@ int lfvio_relative_pose(lfvio_ctx *ctx, const LfvioRelativePoseIn *in, unsigned 
  * goodFeaturesToTrack and setMask are lfvio_gft_detect below, the CLAHE of :101-107 is lfvio_clahe_set below them, rejectWithF and
  * undistortedPoints are lfvio_track_reject / lfvio_track_undistort below those, and lfvio_track_frame below them runs all
  * of them, with reduceVector and updateID, on a track table resident in the context, and lfvio_track_frame_message adds the node's
- * feature message; what stays the caller's is the node's bookkeeping around that call — the first image dropped, the discontinuity
+ * feature message, and lfvio_track_batch_frame below that takes many independent image streams through it in one batched call; what
+ * stays the caller's is the node's bookkeeping around that call — the first image dropped, the discontinuity
  * restart, the FREQ gate, the skipped first publication: host/image_gate.h and host/feature_tracker.h, on images in the trace format.
  * One call uploads `image`, builds its pyramid, tracks the N points from the pyramid of the PREVIOUS call's image (resident in the
  * context: cur_img = forw_img, :180) into the new one, and makes the new pyramid the resident one.  A context with no resident image —
@@ -923,6 +924,44 @@ typedef struct {
 } LfvioTrackMessage;
 int lfvio_track_frame_message(lfvio_ctx *ctx, const LfvioTrackFrameIn *in, LfvioTrackFrameOut *out, const LfvioTrackFrameStages *stages /* or NULL */,
                               LfvioTrackMessage *msg);
+
+/* lfvio_track_batch_*: many image streams through lfvio_track_frame_message in ONE call.  A SLOT is one stream's resident tracker
+ * state — everything a context holds for the single route: the two pyramid buffers and the resident image's size, the base mask, the
+ * detector's arrays, the two track tables with n_id and the count, the two (id, un_pts_3d) maps and the time.  The slots are the
+ * batch's own: the calls above never touch a slot, and the calls below never touch the state of the calls above.  A batch call makes
+ * the launches of ONE frame, each with the slot as the third grid dimension, one copy up ([slot descriptors | sample_words of the
+ * publishing slots | images]) and one copy down, whatever the number of slots.
+ * THE CONTRACT: after any sequence of batch calls, slot i's outputs (LfvioTrackFrameOut with its arrays, and the message) and its
+ * resident state are, bit for bit, those of a fresh context given slot i's active frames, in order, through
+ * lfvio_track_frame_message with the same base mask and CLAHE setting.  The kernels run the single route's device functions.
+ * There are no `stages` here: lfvio_track_frame remains the route for looking inside a frame.
+ *   lfvio_track_batch_reserve   slots in [1, 64]; 0 frees the batch's memory.  Every slot is empty afterwards, as a fresh context is
+ *                               (no image, no mask, an empty table, n_id = 0); the CLAHE setting, which is the batch's, stays.  An
+ *                               allocation that fails is LFVIO_ERR_DEVICE and leaves the previous reservation usable.
+ *   lfvio_track_batch_set_mask  lfvio_gft_set_mask for one slot, or for every slot with slot = -1.  pixels NULL: all 255 again.
+ *   lfvio_track_batch_clahe     lfvio_clahe_set for the batch: one setting for every slot.  NULL: off.
+ *   lfvio_track_batch_frame     count must be the reserved slot count; entry i is slot i.  in[i].image == NULL: slot i is idle in
+ *                               this call — its state is untouched, out[i] is written with zero scalars (everything in front of the
+ *                               arrays) and nothing else, msg[i].num_rows = 0.  The active entries must agree on width, height,
+ *                               win_size, max_level, max_iterations, epsilon, min_eig_threshold, border, max_count, quality_level,
+ *                               min_distance, mask_radius, num_samples and capacity; they may differ in image, time, publish, camera
+ *                               and sample_words.  Every rule of lfvio_track_frame holds for every active entry, with that slot's
+ *                               table count and that slot's base mask.  A slot with no resident image, or one of another size,
+ *                               treats its image as both images.  msg: [count], every active entry's rows an array of capacity
+ *                               rows; or NULL for no messages.  All entries idle: accepted, nothing is launched.
+ *                               ATOMIC over the batch: a refused call (LFVIO_ERR_ARG), a call that fails later and a call that
+ *                               reads a count from the device beyond its bound leave every out, every msg and every slot untouched;
+ *                               the double buffers of all active slots are swapped only after the one download has been checked.
+ *   lfvio_track_batch_reset     lfvio_track_frame_reset for one slot, or for every slot with slot = -1 (the base masks stay).
+ * LFVIO_ERR_ARG besides: a slot index outside [-1, slots), any call but reserve with no slots reserved.  The calls run on the feature
+ * stream like lfvio_track_frame: they do not wait for an optimization in flight.   */
+#define LFVIO_TRACK_BATCH_MAX_SLOTS 64
+int lfvio_track_batch_reserve(lfvio_ctx *ctx, int slots);
+int lfvio_track_batch_set_mask(lfvio_ctx *ctx, int slot /* -1: every slot */, int width, int height, const unsigned char *pixels /* NULL: all 255 */);
+int lfvio_track_batch_clahe(lfvio_ctx *ctx, const LfvioClaheIn *cfg /* NULL: off */);
+int lfvio_track_batch_frame(lfvio_ctx *ctx, int count, const LfvioTrackFrameIn *in /* [count] */, LfvioTrackFrameOut *out /* [count] */,
+                            LfvioTrackMessage *msg /* [count], or NULL */);
+int lfvio_track_batch_reset(lfvio_ctx *ctx, int slot /* -1: every slot */);
 
 /* ---- landmark-sharded API (multi-GPU) ------------------------
  * Every rank passes the same window but linearizes only landmarks [lm_begin, lm_end) (caller order);

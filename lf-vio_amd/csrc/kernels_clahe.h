@@ -21,7 +21,7 @@
 constexpr int CLAHE_THREADS = 256;
 constexpr int CLAHE_MAP_COLS = 256;  // columns of one workgroup of k_clahe_map: 64 threads of 4 pixels, 4 rows at a time
 
-__global__ __launch_bounds__(CLAHE_THREADS) void k_clahe_hist(const unsigned char *src, int W, int H, int tiles_x, int tw, int th, int *table) {
+DEV void clahe_hist_body(const unsigned char *src, int W, int H, int tiles_x, int tw, int th, int *table) {
   __shared__ int bins[256];
   const int tid = threadIdx.x, tile = blockIdx.x;
   const int x0 = (tile % tiles_x) * tw, y0 = (tile / tiles_x) * th;
@@ -35,6 +35,9 @@ __global__ __launch_bounds__(CLAHE_THREADS) void k_clahe_hist(const unsigned cha
   __syncthreads();
   const int n = bins[tid];
   if (n) atomicAdd(&table[tile * 256 + tid], n);
+}
+__global__ __launch_bounds__(CLAHE_THREADS) void k_clahe_hist(const unsigned char *src, int W, int H, int tiles_x, int tw, int th, int *table) {
+  clahe_hist_body(src, W, H, tiles_x, tw, th, table);
 }
 
 // inclusive sums of v over the 256 threads, through s[256]; every thread may read s[255] (the total) until the next barrier
@@ -53,7 +56,7 @@ DEV int clahe_scan(int v, int *s, int tid) {
 
 DEV unsigned char clahe_u8(float v) { return (unsigned char)(int)fminf(fmaxf(rintf(v), 0.0f), 255.0f); }
 
-__global__ __launch_bounds__(CLAHE_THREADS) void k_clahe_lut(int *table, int clip, float lut_scale, unsigned char *lut) {
+DEV void clahe_lut_body(int *table, int clip, float lut_scale, unsigned char *lut) {
   __shared__ int s[256];
   const int tid = threadIdx.x, at = blockIdx.x * 256 + tid;
   int h = table[at];
@@ -73,6 +76,9 @@ __global__ __launch_bounds__(CLAHE_THREADS) void k_clahe_lut(int *table, int cli
   const int sum = clahe_scan(h, s, tid);
   lut[at] = clahe_u8(__fmul_rn((float)sum, lut_scale));
 }
+__global__ __launch_bounds__(CLAHE_THREADS) void k_clahe_lut(int *table, int clip, float lut_scale, unsigned char *lut) {
+  clahe_lut_body(table, clip, lut_scale, lut);
+}
 
 // floor(i * inv - 0.5): the (unclamped) first tile of pixel i of an axis
 DEV float clahe_tf(int i, float inv) { return __fsub_rn(__fmul_rn((float)i, inv), 0.5f); }
@@ -87,8 +93,8 @@ DEV int clahe_first_row(int t, int th, float inv_th, int H) {
 }
 
 template <bool VEC>
-__global__ __launch_bounds__(CLAHE_THREADS) void k_clahe_map(const unsigned char *src, unsigned char *dst, int W, int H, int tiles_x, int tiles_y, int th,
-                                                             int sub, float inv_tw, float inv_th, const unsigned char *lut) {
+DEV void clahe_map_body(const unsigned char *src, unsigned char *dst, int W, int H, int tiles_x, int tiles_y, int th, int sub, float inv_tw, float inv_th,
+                        const unsigned char *lut) {
   __shared__ __attribute__((aligned(16))) unsigned char L[2 * LFVIO_CLAHE_MAX_TILES * 256];
   const int tid = threadIdx.x;
   // segment s: the rows whose unclamped first tile row is s - 1; this workgroup's share of them
@@ -143,4 +149,9 @@ __global__ __launch_bounds__(CLAHE_THREADS) void k_clahe_map(const unsigned char
         if (x0 + j < W) dst[at + j] = o[j];
     }
   }
+}
+template <bool VEC>
+__global__ __launch_bounds__(CLAHE_THREADS) void k_clahe_map(const unsigned char *src, unsigned char *dst, int W, int H, int tiles_x, int tiles_y, int th,
+                                                             int sub, float inv_tw, float inv_th, const unsigned char *lut) {
+  clahe_map_body<VEC>(src, dst, W, H, tiles_x, tiles_y, th, sub, inv_tw, inv_th, lut);
 }

@@ -79,13 +79,11 @@ DEV int gft_count(int n) { return n; }
 DEV int gft_count(const int *n) { return *n; }
 
 // Count = int: lfvio_gft_detect's N.  Count = const int *: N from the device; N = 0 runs no loop below and writes num_kept = 0.
-template <class Count>
-__global__ __launch_bounds__(GFT_THREADS) void k_gft_thin(Count n_arg, const float *pts, const int *cnt, const unsigned char *base, int W, int H, int r,
-                                                           GftDev *st, int *kept, int *kxy) {
+// (the bodies are device functions: kernels_trackbatch.h runs the same code per slot)
+DEV void gft_thin_body(int N, const float *pts, const int *cnt, const unsigned char *base, int W, int H, int r, GftDev *st, int *kept, int *kxy) {
   __shared__ int s_cnt[GFT_LIST];  // the counts, then the kept pixels
   __shared__ int s_xy[GFT_LIST], s_idx[GFT_LIST];  // pixel and index of the point of rank k
   __shared__ int s_batch[GFT_THREADS];
-  const int N = gft_count(n_arg);
   const int tid = threadIdx.x;
   for (int i = tid; i < N; i += GFT_THREADS) s_cnt[i] = cnt[i];
   __syncthreads();
@@ -109,9 +107,14 @@ __global__ __launch_bounds__(GFT_THREADS) void k_gft_thin(Count n_arg, const flo
       N, r * r + 1, GFT_LIST, [&](int p) { return s_xy[p]; }, [&](int slot, int p, int v) { kept[slot] = s_idx[p], kxy[slot] = v; }, s_cnt, s_batch);
   if (tid == 0) st->max_bits = 0ull, st->num_kept = nk, st->num_cand = 0;
 }
+template <class Count>
+__global__ __launch_bounds__(GFT_THREADS) void k_gft_thin(Count n_arg, const float *pts, const int *cnt, const unsigned char *base, int W, int H, int r,
+                                                           GftDev *st, int *kept, int *kxy) {
+  gft_thin_body(gft_count(n_arg), pts, cnt, base, W, H, r, st, kept, kxy);
+}
 
-__global__ __launch_bounds__(GFT_THREADS) void k_gft_response(const unsigned char *img, int W, int H, const unsigned char *base, const int *kxy, int r,
-                                                               int max_count, GftDev *st, double *lam, unsigned char *mask) {
+DEV void gft_response_body(const unsigned char *img, int W, int H, const unsigned char *base, const int *kxy, int r, int max_count, GftDev *st,
+                           double *lam, unsigned char *mask) {
   __shared__ unsigned char raw[GFT_RAW_H][GFT_RAW_W];
   __shared__ int pxx[GFT_PRD_H][GFT_PRD_W], pxy[GFT_PRD_H][GFT_PRD_W], pyy[GFT_PRD_H][GFT_PRD_W];
   __shared__ int s_disc[GFT_LIST], s_nd;
@@ -167,9 +170,13 @@ __global__ __launch_bounds__(GFT_THREADS) void k_gft_response(const unsigned cha
   // (the value only grows: a workgroup that sees one at least as large already has nothing to add)
   if (tid == 0 && s_red[0] > *(volatile unsigned long long *)&st->max_bits) atomicMax(&st->max_bits, s_red[0]);
 }
+__global__ __launch_bounds__(GFT_THREADS) void k_gft_response(const unsigned char *img, int W, int H, const unsigned char *base, const int *kxy, int r,
+                                                               int max_count, GftDev *st, double *lam, unsigned char *mask) {
+  gft_response_body(img, W, H, base, kxy, r, max_count, st, lam, mask);
+}
 
-__global__ __launch_bounds__(GFT_THREADS) void k_gft_cand(const double *lam, const unsigned char *mask, int W, int H, double quality, int max_count, GftDev *st,
-                                                           unsigned long long *ck, unsigned *ci) {
+DEV void gft_cand_body(const double *lam, const unsigned char *mask, int W, int H, double quality, int max_count, GftDev *st, unsigned long long *ck,
+                       unsigned *ci) {
   __shared__ int s_count, s_first;
   if (max_count - st->num_kept <= 0 || st->max_bits == 0ull) return;
   const double thr = quality * __longlong_as_double((long long)st->max_bits);
@@ -200,6 +207,10 @@ __global__ __launch_bounds__(GFT_THREADS) void k_gft_cand(const double *lam, con
       ck[at] = (unsigned long long)__double_as_longlong(lam[p]), ci[at] = (unsigned)p, at++;
     }
 }
+__global__ __launch_bounds__(GFT_THREADS) void k_gft_cand(const double *lam, const unsigned char *mask, int W, int H, double quality, int max_count, GftDev *st,
+                                                           unsigned long long *ck, unsigned *ci) {
+  gft_cand_body(lam, mask, W, H, quality, max_count, st, ck, ci);
+}
 
 // the padded length of the network: a power of two, at least one chunk
 DEV unsigned gft_padded(int n) {
@@ -213,7 +224,7 @@ DEV unsigned gft_lower(unsigned t, unsigned j) { return ((t & ~(j - 1u)) << 1) |
 
 // stage = 0: loads a chunk (entries behind the candidates are (0, 0): behind every candidate, whose lambda is > 0), runs the stages
 // k = 2 .. GFT_CHUNK on it.  Otherwise: the steps j = GFT_CHUNK / 2 .. 1 of the stage k = stage.
-__global__ __launch_bounds__(GFT_SORT_THREADS) void k_gft_sort_local(const GftDev *st, unsigned long long *ck, unsigned *ci, unsigned stage) {
+DEV void gft_sort_local_body(const GftDev *st, unsigned long long *ck, unsigned *ci, unsigned stage) {
   __shared__ unsigned long long sk[GFT_CHUNK];
   __shared__ unsigned si[GFT_CHUNK];
   const unsigned n = (unsigned)st->num_cand, np = gft_padded((int)n), tid = threadIdx.x;
@@ -240,9 +251,12 @@ __global__ __launch_bounds__(GFT_SORT_THREADS) void k_gft_sort_local(const GftDe
     __syncthreads();
   }
 }
+__global__ __launch_bounds__(GFT_SORT_THREADS) void k_gft_sort_local(const GftDev *st, unsigned long long *ck, unsigned *ci, unsigned stage) {
+  gft_sort_local_body(st, ck, ci, stage);
+}
 
 // the step at distance j >= GFT_CHUNK of the stage k
-__global__ __launch_bounds__(GFT_THREADS) void k_gft_sort_global(const GftDev *st, unsigned long long *ck, unsigned *ci, unsigned k, unsigned j) {
+DEV void gft_sort_global_body(const GftDev *st, unsigned long long *ck, unsigned *ci, unsigned k, unsigned j) {
   const unsigned n = (unsigned)st->num_cand, np = gft_padded((int)n);
   if (n == 0 || k > np) return;
   for (unsigned t = blockIdx.x * GFT_THREADS + threadIdx.x; t < np / 2; t += gridDim.x * GFT_THREADS) {
@@ -253,8 +267,11 @@ __global__ __launch_bounds__(GFT_THREADS) void k_gft_sort_global(const GftDev *s
     if (desc ? gft_before(kb, ib, ka, ia) : gft_before(ka, ia, kb, ib)) ck[a] = kb, ck[b] = ka, ci[a] = ib, ci[b] = ia;
   }
 }
+__global__ __launch_bounds__(GFT_THREADS) void k_gft_sort_global(const GftDev *st, unsigned long long *ck, unsigned *ci, unsigned k, unsigned j) {
+  gft_sort_global_body(st, ck, ci, k, j);
+}
 
-__global__ __launch_bounds__(GFT_THREADS) void k_gft_pick(const GftDev *st, const unsigned *ci, int W, int d, int max_count, float *corners, LfvioGftOut *out) {
+DEV void gft_pick_body(const GftDev *st, const unsigned *ci, int W, int d, int max_count, float *corners, LfvioGftOut *out) {
   __shared__ int s_acc[GFT_LIST];
   __shared__ int s_batch[GFT_THREADS];
   const int nk = st->num_kept, budget = max_count - nk, n = budget > 0 ? st->num_cand : 0;
@@ -269,4 +286,7 @@ __global__ __launch_bounds__(GFT_THREADS) void k_gft_pick(const GftDev *st, cons
     out->num_kept = nk, out->num_corners = got, out->num_candidates = n;
     out->max_response = budget > 0 ? __longlong_as_double((long long)st->max_bits) : 0.0;
   }
+}
+__global__ __launch_bounds__(GFT_THREADS) void k_gft_pick(const GftDev *st, const unsigned *ci, int W, int d, int max_count, float *corners, LfvioGftOut *out) {
+  gft_pick_body(st, ci, W, d, max_count, corners, out);
 }

@@ -30,7 +30,8 @@ DEV int klt_reflect(int i, int n) {
   return i;
 }
 
-__global__ __launch_bounds__(256) void k_klt_down(const unsigned char *src, int sw, int sh, unsigned char *dst, int dw, int dh) {
+// (the bodies are device functions: kernels_trackbatch.h runs the same code per slot)
+DEV void klt_down_body(const unsigned char *src, int sw, int sh, unsigned char *dst, int dw, int dh) {
   const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (x >= dw || y >= dh) return;
   const int k[5] = {1, 4, 6, 4, 1};
@@ -48,13 +49,16 @@ __global__ __launch_bounds__(256) void k_klt_down(const unsigned char *src, int 
   }
   dst[(size_t)y * dw + x] = (unsigned char)((s + 128) >> 8);
 }
+__global__ __launch_bounds__(256) void k_klt_down(const unsigned char *src, int sw, int sh, unsigned char *dst, int dw, int dh) {
+  klt_down_body(src, sw, sh, dst, dw, dh);
+}
 
 // floor of a window's corner inside [-win, cols) x [-win, rows)?  (in doubles: a NaN or a huge coordinate is outside, and only an
 // inside one is converted to int)
 DEV bool klt_inside(double fx, double fy, int win, int cols, int rows) { return fx >= -win && fx < cols && fy >= -win && fy < rows; }
 
-__global__ __launch_bounds__(KLT_THREADS) void k_klt_track(KltArgs a, int N, const unsigned char *prev_pyr, const unsigned char *next_pyr,
-                                                           const float *pts, float *next, unsigned char *status, int *iters) {
+DEV void klt_track_body(const KltArgs &a, int N, const unsigned char *prev_pyr, const unsigned char *next_pyr, const float *pts, float *next,
+                        unsigned char *status, int *iters) {
   __shared__ unsigned char raw[KLT_RAW * KLT_RAW];
   __shared__ float pI[KLT_MAX_WIN * KLT_MAX_WIN], pX[KLT_MAX_WIN * KLT_MAX_WIN], pY[KLT_MAX_WIN * KLT_MAX_WIN];
   __shared__ double red[5 * KLT_THREADS / 64];
@@ -164,4 +168,8 @@ __global__ __launch_bounds__(KLT_THREADS) void k_klt_track(KltArgs a, int N, con
     if (iters)
       for (int L = a.levels_used + 1; L <= a.max_level; L++) iters[(size_t)pt * (a.max_level + 1) + L] = 0;
   }
+}
+__global__ __launch_bounds__(KLT_THREADS) void k_klt_track(KltArgs a, int N, const unsigned char *prev_pyr, const unsigned char *next_pyr,
+                                                           const float *pts, float *next, unsigned char *status, int *iters) {
+  klt_track_body(a, N, prev_pyr, next_pyr, pts, next, status, iters);
 }

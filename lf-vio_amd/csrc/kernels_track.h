@@ -84,16 +84,19 @@ __global__ __launch_bounds__(TV_FIT_THREADS) void k_trk_fit(int N, int S, const 
 }
 // N from the device.  N < 8 is lfvio_track_reject's host branch (:331), which the host cannot take here: status 2, nothing rejected,
 // and no bearing, hypothesis or sample index is read (k_tv_hyp_n has not run).
-__global__ __launch_bounds__(TV_FIT_THREADS) void k_trk_fit_n(const int *Np, int S, const double *bl, const double *br, const double *E_all,
-                                                              const float *score_all, double *A, unsigned char *status, LfvioTrackRejectOut *out) {
-  __shared__ TvFitLds lds;
-  const int N = *Np;
+DEV void trk_fit_n_body(int N, int S, const double *bl, const double *br, const double *E_all, const float *score_all, double *A,
+                        unsigned char *status, LfvioTrackRejectOut *out, TvFitLds &lds) {
   if (N < TRACK_MIN_MATCHES) {
     for (int i = threadIdx.x; i < N; i += TV_FIT_THREADS) status[i] = 1;
     if (threadIdx.x == 0) out->status = 2, out->best_sample = -1, out->num_inliers = 0, out->best_score = 0.0;
     return;
   }
   trk_fit_body(N, S, bl, br, E_all, score_all, A, status, out, lds);
+}
+__global__ __launch_bounds__(TV_FIT_THREADS) void k_trk_fit_n(const int *Np, int S, const double *bl, const double *br, const double *E_all,
+                                                              const float *score_all, double *A, unsigned char *status, LfvioTrackRejectOut *out) {
+  __shared__ TvFitLds lds;
+  trk_fit_n_body(*Np, S, bl, br, E_all, score_all, A, status, out, lds);
 }
 // k_tv_hyp (kernels_twoview.h) with N from the device; N < 8: no sample set was drawn
 __global__ __launch_bounds__(TV_HYP_THREADS) void k_tv_hyp_n(const int *Np, const double *bl, const double *br, const int *samples, double *E_all,

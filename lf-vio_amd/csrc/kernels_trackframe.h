@@ -56,9 +56,9 @@ DEV int tf_scan(int v, int (*s)[TF_THREADS], int &total) {
   return incl - v;
 }
 
-__global__ __launch_bounds__(TF_THREADS) void k_tf_flow(int n0, const unsigned char *status, const float *cur, const float *next, const int *ids,
-                                                        const int *cnt, float *cur1, TfTable t1, TfDev *dev, int S, const unsigned *words,
-                                                        int *samples) {
+// (the bodies are device functions: kernels_trackbatch.h runs the same code per slot)
+DEV void tf_flow_body(int n0, const unsigned char *status, const float *cur, const float *next, const int *ids, const int *cnt, float *cur1,
+                      const TfTable &t1, TfDev *dev, int S, const unsigned *words, int *samples) {
   __shared__ int s[2][TF_THREADS];
   const int tid = threadIdx.x, first = tid * TF_PER, last = min(first + TF_PER, n0);
   int mine = 0;
@@ -84,8 +84,13 @@ __global__ __launch_bounds__(TF_THREADS) void k_tf_flow(int n0, const unsigned c
       for (int j = 0; j < 8; j++) samples[8 * k + j] = out[j];
     }
 }
+__global__ __launch_bounds__(TF_THREADS) void k_tf_flow(int n0, const unsigned char *status, const float *cur, const float *next, const int *ids,
+                                                        const int *cnt, float *cur1, TfTable t1, TfDev *dev, int S, const unsigned *words,
+                                                        int *samples) {
+  tf_flow_body(n0, status, cur, next, ids, cnt, cur1, t1, dev, S, words, samples);
+}
 
-__global__ __launch_bounds__(TF_THREADS) void k_tf_reject(const unsigned char *mask, TfTable t1, TfTable t2, TfDev *dev) {
+DEV void tf_reject_body(const unsigned char *mask, const TfTable &t1, const TfTable &t2, TfDev *dev) {
   __shared__ int s[2][TF_THREADS];
   const int n1 = dev->n1, tid = threadIdx.x, first = tid * TF_PER, last = min(first + TF_PER, n1);
   int mine = 0;
@@ -100,10 +105,13 @@ __global__ __launch_bounds__(TF_THREADS) void k_tf_reject(const unsigned char *m
     }
   if (tid == 0) dev->n2 = n2;
 }
+__global__ __launch_bounds__(TF_THREADS) void k_tf_reject(const unsigned char *mask, TfTable t1, TfTable t2, TfDev *dev) {
+  tf_reject_body(mask, t1, t2, dev);
+}
 
 // src: (forw2, ids2, cnt2) with detect (kept, corners, dev->detect), otherwise (forw1, ids1, cnt1) and kept, corners unused
-__global__ __launch_bounds__(TF_THREADS) void k_tf_finish(int detect, TfTable src, const int *kept, const float *corners, int n_id, TfTable next,
-                                                          TfTable down, int *ids_raw, TfDev *dev) {
+DEV void tf_finish_body(int detect, const TfTable &src, const int *kept, const float *corners, int n_id, const TfTable &next, const TfTable &down,
+                        int *ids_raw, TfDev *dev) {
   __shared__ int s[2][TF_THREADS];
   const int nk = detect ? dev->detect.num_kept : dev->n1, n = nk + (detect ? dev->detect.num_corners : 0);
   const int tid = threadIdx.x, first = tid * TF_PER, last = min(first + TF_PER, n);
@@ -141,10 +149,13 @@ __global__ __launch_bounds__(TF_THREADS) void k_tf_finish(int detect, TfTable sr
   }
   if (tid == 0) dev->num_points = n, dev->num_new = num_new;
 }
+__global__ __launch_bounds__(TF_THREADS) void k_tf_finish(int detect, TfTable src, const int *kept, const float *corners, int n_id, TfTable next,
+                                                          TfTable down, int *ids_raw, TfDev *dev) {
+  tf_finish_body(detect, src, kept, corners, n_id, next, down, ids_raw, dev);
+}
 
 // rows: [cap][9] = un_pts_3d | (float)(id * NUM_OF_CAM + 0), NUM_OF_CAM = 1 | pts | velocity_3d; cap: the host's bound on num_points
-__global__ __launch_bounds__(TF_THREADS) void k_tf_message(const TfDev *dev, int cap, TfTable down, const float *un_pts_3d, const float *velocity_3d,
-                                                           int *num_rows, float *rows) {
+DEV void tf_message_body(const TfDev *dev, int cap, const TfTable &down, const float *un_pts_3d, const float *velocity_3d, int *num_rows, float *rows) {
   __shared__ int s[2][TF_THREADS];
   __shared__ int slot[LFVIO_TRACK_MAX_POINTS];  // the row of entry i, or -1
   const int n = min(dev->num_points, cap), tid = threadIdx.x, first = tid * TF_PER, last = min(first + TF_PER, n);
@@ -178,4 +189,8 @@ __global__ __launch_bounds__(TF_THREADS) void k_tf_message(const TfDev *dev, int
     rows[9 * o + col] = v;
   }
   if (tid == 0) *num_rows = total;
+}
+__global__ __launch_bounds__(TF_THREADS) void k_tf_message(const TfDev *dev, int cap, TfTable down, const float *un_pts_3d, const float *velocity_3d,
+                                                           int *num_rows, float *rows) {
+  tf_message_body(dev, cap, down, un_pts_3d, velocity_3d, num_rows, rows);
 }

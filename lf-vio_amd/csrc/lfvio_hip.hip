@@ -53,6 +53,7 @@ constexpr ncclDataType_t ncclDouble = 8;
 #include "kernels_clahe.h"
 #include "kernels_track.h"
 #include "kernels_trackframe.h"
+#include "kernels_trackbatch.h"
 #include "window_pack.h"
 #include "dev_mem.h"
 
@@ -206,6 +207,26 @@ struct lfvio_ctx : CtxQueues {
     DevBuf<char> table[2];
     int cur = 0, count = 0, n_id = 0;
   } tframe;
+  // lfvio_track_batch_* (trackbatch.inc): `slot.size()` independent streams, each with what the five states above hold for the single
+  // route.  fixed: per slot two track tables and two maps (TB_FIXED_BYTES); image: per slot [pyramid | pyramid | base mask | detector's
+  // arrays] with the capacities of `lay` (trackbatch_plan.h), allocated at the first frame or mask; clahe: per slot the int table and
+  // the LUTs, allocated at the first frame with the setting on.  None of it is the single route's, and the single route's is none of it.
+  struct TrackBatchState {
+    struct Slot {
+      int pcur = 0, w = 0, h = 0, built = 0;  // the pyramid buffers, as KltState
+      bool valid = false;
+      int mw = 0, mh = 0;                     // the base mask, as GftState
+      bool mask_set = false;
+      int tcur = 0, count = 0, n_id = 0;      // the track table, as TrackFrameState
+      int mcur = 0, mcount = 0;               // the (id, un_pts_3d) map, as TrackState
+      double time = 0.0;
+    };
+    std::vector<Slot> slot;
+    DevBuf<char> fixed, image, clahe;
+    TbImage lay = {0, 0, 0};
+    bool clahe_on = false, clahe_dirty = false;
+    LfvioClaheIn cfg = {};
+  } tbatch;
   std::string err;
   int batch = 0;
   Layout L;
@@ -2086,6 +2107,8 @@ int lfvio_debug_query(lfvio_ctx *c, const char *key, double *out, int n) {
 #include "track.inc"
 
 #include "trackframe.inc"
+
+#include "trackbatch.inc"
 // ---- landmark-sharded API: declared in lfvio.h, implemented in shard.inc
 #include "shard.inc"
 // ---- multi-GPU groups (RCCL): declared in lfvio.h, implemented in group.inc

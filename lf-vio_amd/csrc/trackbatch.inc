@@ -1,0 +1,349 @@
+// trackbatch.inc — host side of the lfvio_track_batch_* calls (include/lfvio.h): lfvio_track_frame_message for every slot of the
+// batch in the launches of ONE frame.  The kernels are those of kernels_trackbatch.h, the single route's device functions with the
+// slot in blockIdx.z; the checks, the bounds and every offset come from trackbatch_plan.h.  Included by lfvio_hip.hip inside its
+// extern "C" block, behind trackframe.inc.
+//
+// One call: check every entry, size grids and segments for the batch's bounds (n0_max, B_max), fill the descriptors, ONE copy up of
+// [descriptors | words | images], the launches of trackframe.inc once each with grid.z = slots, ONE copy down of every slot's down
+// segment.  Only then, with every count checked against its bound, are the outputs written and the double buffers of the active
+// slots swapped: a call that is refused or fails leaves every output and every slot as it was.
+
+static_assert(TB_TABLE_BYTES == TF_TABLE_BYTES && TB_MAP_BYTES == TRACK_MAP_BYTES && TB_MAP_IDS == TRACK_MAP_IDS, "a slot's tables and maps are the single route's");
+
+static int tb_copy(lfvio_ctx *c, hipStream_t fs, const char *src, size_t sstride, char *dst, size_t dstride, size_t bytes, int n) {
+  if (!bytes || n < 1) return LFVIO_OK;
+  hipLaunchKernelGGL(k_tb_copy, dim3((unsigned)((bytes + TB_COPY_BYTES - 1) / TB_COPY_BYTES), 1, n), dim3(TB_COPY_THREADS), 0, fs, (const unsigned char *)src,
+                     sstride, (unsigned char *)dst, dstride, bytes);
+  HIPCHK(c, hipGetLastError());
+  return LFVIO_OK;
+}
+
+// The slots' image blocks with at least the capacities of `need`.  A block that has to grow is allocated beside the old one, the
+// pyramids and the masks move over, then it replaces the old one: a failure leaves the batch as it was.
+static int tb_image_reserve(lfvio_ctx *c, hipStream_t fs, const TbImage &need) {
+  lfvio_ctx::TrackBatchState &b = c->tbatch;
+  if (b.image && trackbatch_image_covers(b.lay, need)) return LFVIO_OK;
+  const int n = (int)b.slot.size();
+  const TbImage lay = b.image ? trackbatch_image_grown(b.lay, need) : need;
+  DevBuf<char> fresh;
+  if (!fresh.reserve((size_t)n * lay.stride())) return out_of_memory(c, "out of memory (track batch images)");
+  if (b.image) {
+    for (int which = 0; which < 2; which++)
+      if (int rc = tb_copy(c, fs, b.image + b.lay.pyr_at(which), b.lay.stride(), fresh + lay.pyr_at(which), lay.stride(), b.lay.pyr, n)) return rc;
+    if (int rc = tb_copy(c, fs, b.image + b.lay.mask_at(), b.lay.stride(), fresh + lay.mask_at(), lay.stride(), b.lay.mask, n)) return rc;
+    HIPCHK(c, hipStreamSynchronize(fs));
+  }
+  b.image = std::move(fresh), b.lay = lay;
+  return LFVIO_OK;
+}
+
+int lfvio_track_batch_reserve(lfvio_ctx *c, int slots) {
+  if (!c) return LFVIO_ERR_ARG;
+  if (const char *why = trackbatch_reserve_check(slots)) {
+    c->err = why;
+    return LFVIO_ERR_ARG;
+  }
+  lfvio_ctx::TrackBatchState &b = c->tbatch;
+  FeatStage st(c);
+  DevBuf<char> fresh;
+  if (slots && !fresh.reserve((size_t)slots * TB_FIXED_BYTES)) return out_of_memory(c, "out of memory (track batch slots)");
+  HIPCHK(c, hipStreamSynchronize(st.fs));
+  b.fixed = std::move(fresh);
+  (void)b.image.reset(), (void)b.clahe.reset();
+  b.lay = TbImage{0, 0, 0}, b.clahe_dirty = false;
+  b.slot.assign((size_t)slots, lfvio_ctx::TrackBatchState::Slot());
+  return LFVIO_OK;
+}
+
+int lfvio_track_batch_reset(lfvio_ctx *c, int slot) {
+  if (!c) return LFVIO_ERR_ARG;
+  lfvio_ctx::TrackBatchState &b = c->tbatch;
+  if (const char *why = trackbatch_slot_check(slot, (int)b.slot.size())) {
+    c->err = why;
+    return LFVIO_ERR_ARG;
+  }
+  for (int i = 0; i < (int)b.slot.size(); i++) {
+    if (slot >= 0 && i != slot) continue;
+    lfvio_ctx::TrackBatchState::Slot &s = b.slot[i];
+    s.valid = false, s.mcount = 0, s.time = 0.0, s.count = 0, s.n_id = 0;  // (the base mask stays, as lfvio_track_frame_reset leaves it)
+  }
+  return LFVIO_OK;
+}
+
+int lfvio_track_batch_clahe(lfvio_ctx *c, const LfvioClaheIn *cfg) {
+  if (!c) return LFVIO_ERR_ARG;
+  if (!cfg) {
+    c->tbatch.clahe_on = false;
+    return LFVIO_OK;
+  }
+  if (const char *why = clahe_check(cfg)) {
+    c->err = why;
+    return LFVIO_ERR_ARG;
+  }
+  c->tbatch.cfg = *cfg, c->tbatch.clahe_on = true;
+  return LFVIO_OK;
+}
+
+int lfvio_track_batch_set_mask(lfvio_ctx *c, int slot, int width, int height, const unsigned char *pixels) {
+  if (!c) return LFVIO_ERR_ARG;
+  lfvio_ctx::TrackBatchState &b = c->tbatch;
+  const int n = (int)b.slot.size();
+  if (const char *why = trackbatch_slot_check(slot, n)) {
+    c->err = why;
+    return LFVIO_ERR_ARG;
+  }
+  const int first = slot < 0 ? 0 : slot, last = slot < 0 ? n : slot + 1;
+  if (!pixels) {
+    for (int i = first; i < last; i++) b.slot[i].mask_set = false;
+    return LFVIO_OK;
+  }
+  for (int i = first; i < last; i++)
+    if (const char *why = gft_mask_check(width, height, b.slot[i].valid ? b.slot[i].w : 0, b.slot[i].h)) {
+      c->err = why;
+      return LFVIO_ERR_ARG;
+    }
+  const size_t px = (size_t)width * height;
+  FeatStage st(c);
+  const size_t oM = st.take(px);
+  if (int rc = st.reserve()) return rc;
+  if (int rc = tb_image_reserve(c, st.fs, trackbatch_image(width, height, 0))) return rc;
+  std::memcpy(st.h + oM, pixels, px);
+  if (int rc = st.up(st.end)) return rc;
+  if (int rc = tb_copy(c, st.fs, st.d + oM, 0, b.image + (size_t)first * b.lay.stride() + b.lay.mask_at(), b.lay.stride(), px, last - first)) return rc;
+  HIPCHK(c, hipStreamSynchronize(st.fs));
+  for (int i = first; i < last; i++) b.slot[i].mw = width, b.slot[i].mh = height, b.slot[i].mask_set = true;
+  return LFVIO_OK;
+}
+
+// the scalars of an LfvioTrackFrameOut, everything in front of its arrays
+static void tb_zero_scalars(LfvioTrackFrameOut *o) {
+  o->num_points = o->num_new = o->levels_used = o->num_tracked = o->num_after_reject = 0;
+  std::memset(&o->reject, 0, sizeof o->reject);
+  std::memset(&o->detect, 0, sizeof o->detect);
+}
+
+int lfvio_track_batch_frame(lfvio_ctx *c, int count, const LfvioTrackFrameIn *in, LfvioTrackFrameOut *out, LfvioTrackMessage *msg) {
+  if (!c) return LFVIO_ERR_ARG;
+  if (!in || !out) {
+    c->err = "lfvio_track_batch_frame: null in or out";
+    return LFVIO_ERR_ARG;
+  }
+  lfvio_ctx::TrackBatchState &b = c->tbatch;
+  const int n = (int)b.slot.size();
+  int counts[LFVIO_TRACK_BATCH_MAX_SLOTS];
+  for (int i = 0; i < n; i++) counts[i] = b.slot[i].count;
+  if (const char *why = trackbatch_frame_check(n, count, in, counts)) {
+    c->err = why;
+    return LFVIO_ERR_ARG;
+  }
+  for (int i = 0; i < n; i++) {
+    if (!trackbatch_active(in[i])) continue;
+    const lfvio_ctx::TrackBatchState::Slot &s = b.slot[i];
+    const LfvioTrackFrameOut &o = out[i];
+    if (!o.pts || !o.ids || !o.track_cnt || !o.un_pts || !o.un_pts_3d || !o.velocity_3d ||
+        (in[i].publish && s.mask_set && (s.mw != in[i].width || s.mh != in[i].height)) || (msg && !msg[i].rows)) {
+      c->err = "lfvio_track_batch_frame: a null array in out or msg, or a base mask that is not the image's size";
+      return LFVIO_ERR_ARG;
+    }
+  }
+  const TbBounds bd = trackbatch_bounds(n, in, counts);
+  if (!bd.active) {  // nothing to do, and nothing on the device
+    for (int i = 0; i < n; i++) {
+      tb_zero_scalars(&out[i]);
+      if (msg) msg[i].num_rows = 0;
+    }
+    return LFVIO_OK;
+  }
+  const LfvioTrackFrameIn &f = in[bd.first];  // the shared fields
+  const int W = f.width, H = f.height, S = f.num_samples, MC = f.max_count;
+  const LfvioKltIn kin = trackframe_klt(&f);
+  const LfvioGftIn gin = trackframe_gft(&f);
+  const KltPlan full = klt_plan(W, H, 0, LFVIO_KLT_MAX_LEVEL);
+  const int LU = klt_plan(W, H, f.win_size, f.max_level).levels_used;
+  const GftWork gw = gft_work(W, H);
+  const TbWork wk = {gw.lam, gw.keys, gw.idx, gw.mask, gw.kxy, gw.st};
+  const size_t nI = (size_t)W * H;
+  const bool rows = msg != nullptr, any_pub = bd.publishing > 0;
+  TbShape shape = {};
+  shape.slots = n, shape.publishing = bd.publishing, shape.active = bd.active;
+  shape.n0_max = (size_t)bd.n0_max, shape.B_max = (size_t)bd.B_max, shape.S = (size_t)S, shape.max_count = (size_t)MC, shape.pixels = nI;
+  shape.dev_bytes = sizeof(TfDev), shape.rows = rows;
+  const TbStage o = trackbatch_stage(shape);
+  FeatStage st(c);
+  st.end = o.end;
+  if (int rc = st.reserve()) return rc;
+  if (int rc = tb_image_reserve(c, st.fs, trackbatch_image(W, H, gw.bytes))) return rc;
+  if (b.clahe_on) {
+    if (!b.clahe) {
+      if (!b.clahe.reserve((size_t)n * (CLAHE_TABLE_BYTES + CLAHE_LUT_BYTES))) return out_of_memory(c, "out of memory (CLAHE)");
+      b.clahe_dirty = true;
+    }
+    if (b.clahe_dirty) {  // fresh memory, or a call that failed between the histograms and the LUTs
+      HIPCHK(c, hipMemsetAsync(b.clahe, 0, (size_t)n * (CLAHE_TABLE_BYTES + CLAHE_LUT_BYTES), st.fs));
+      b.clahe_dirty = false;
+    }
+  }
+  char *d = st.d, *h = st.h;
+  const TbImage &lay = b.lay;
+  TbMem m = {};
+  m.stage = d, m.fixed = b.fixed, m.image = b.image, m.clahe = b.clahe_on ? b.clahe.get() : nullptr;
+  m.image_stride = lay.stride(), m.pyr = lay.pyr, m.mask_at = lay.mask_at(), m.work_at = lay.work_at(), m.clahe_stride = CLAHE_TABLE_BYTES + CLAHE_LUT_BYTES;
+  m.words_at = o.words, m.words_stride = trackbatch_words_at(o, shape, 1) - o.words, m.images_at = o.images, m.images_stride = trackbatch_image_at(o, shape, 1) - o.images;
+  TbSlot *desc = (TbSlot *)(h + o.desc);
+  std::memset(desc, 0, (size_t)n * sizeof(TbSlot));
+  bool build_resident = false;
+  for (int i = 0, ka = 0, kp = 0; i < n; i++) {
+    if (!trackbatch_active(in[i])) continue;
+    const lfvio_ctx::TrackBatchState::Slot &s = b.slot[i];
+    TbSlot &t = desc[i];
+    const bool same = s.valid && s.w == W && s.h == H;  // otherwise the new image is both images
+    t.active = 1, t.publish = in[i].publish != 0, t.n0 = s.count, t.n_id = s.n_id, t.prev_count = s.mcount;
+    t.prev_built = same ? s.built : LU, t.same = same;
+    t.pcur = s.pcur, t.tcur = s.tcur, t.mcur = s.mcur, t.masked = s.mask_set;
+    t.dt = in[i].time - s.time;
+    t.cam = track_cam(*in[i].camera);
+    t.image_k = ka++;
+    std::memcpy(h + trackbatch_image_at(o, shape, t.image_k), in[i].image, nI);
+    if (t.publish) {
+      t.words_k = kp++;
+      std::memcpy(h + trackbatch_words_at(o, shape, t.words_k), in[i].sample_words, (size_t)S * 32);
+    }
+    build_resident = build_resident || (same && s.built < LU);
+  }
+  if (int rc = st.up(o.in_end)) return rc;
+
+  const TbSlot *slots = (const TbSlot *)(d + o.desc);
+  const unsigned Z = (unsigned)n;
+  hipStream_t fs = st.fs;
+  // level 0 of every fresh pyramid: the image, or the equalized image
+  if (b.clahe_on) {
+    const ClahePlan p = clahe_plan(W, H, b.cfg);
+    const int tiles = b.cfg.tiles_x * b.cfg.tiles_y, bands = (p.th + CLAHE_BAND_ROWS - 1) / CLAHE_BAND_ROWS;
+    b.clahe_dirty = true;
+    hipLaunchKernelGGL(k_clahe_hist_b, dim3(tiles, bands, Z), dim3(CLAHE_THREADS), 0, fs, slots, m, o, W, H, b.cfg.tiles_x, p.tw, p.th);
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(k_clahe_lut_b, dim3(tiles, 1, Z), dim3(CLAHE_THREADS), 0, fs, slots, m, o, p.clip, p.lut_scale, CLAHE_TABLE_BYTES);
+    HIPCHK(c, hipGetLastError());
+    b.clahe_dirty = false;
+    const dim3 grid((W + CLAHE_MAP_COLS - 1) / CLAHE_MAP_COLS, (b.cfg.tiles_y + 1) * bands, Z);
+    if (W % 4 == 0)
+      hipLaunchKernelGGL(k_clahe_map_b<true>, grid, dim3(CLAHE_THREADS), 0, fs, slots, m, o, W, H, b.cfg.tiles_x, b.cfg.tiles_y, p.th, bands, p.inv_tw, p.inv_th,
+                         CLAHE_TABLE_BYTES);
+    else
+      hipLaunchKernelGGL(k_clahe_map_b<false>, grid, dim3(CLAHE_THREADS), 0, fs, slots, m, o, W, H, b.cfg.tiles_x, b.cfg.tiles_y, p.th, bands, p.inv_tw, p.inv_th,
+                         CLAHE_TABLE_BYTES);
+    HIPCHK(c, hipGetLastError());
+  } else {
+    hipLaunchKernelGGL(k_tb_image, dim3((unsigned)((nI + TB_COPY_BYTES - 1) / TB_COPY_BYTES), 1, Z), dim3(TB_COPY_THREADS), 0, fs, slots, m, o, nI);
+    HIPCHK(c, hipGetLastError());
+  }
+  // 1: the pyramids (the resident ones too, where an earlier call asked for fewer levels), the flow
+  for (int resident = 0; resident < (build_resident ? 2 : 1); resident++)
+    for (int k = 1; k <= LU; k++) {
+      hipLaunchKernelGGL(k_klt_down_b, dim3((full.w[k] + 63) / 64, (full.h[k] + 3) / 4, Z), dim3(256), 0, fs, slots, m, o, resident, k, full.off[k - 1], full.w[k - 1],
+                         full.h[k - 1], full.off[k], full.w[k], full.h[k]);
+      HIPCHK(c, hipGetLastError());
+    }
+  if (bd.n0_max) {
+    hipLaunchKernelGGL(k_klt_track_b, dim3(bd.n0_max, 1, Z), dim3(KLT_THREADS), 0, fs, slots, m, o, klt_args(&kin, full, LU));
+    HIPCHK(c, hipGetLastError());
+  }
+  // 2: reduceVector, track_cnt++, the sample sets
+  hipLaunchKernelGGL(k_tf_flow_b, dim3(1, 1, Z), dim3(TF_THREADS), 0, fs, slots, m, o, bd.n0_max, S);
+  HIPCHK(c, hipGetLastError());
+  if (any_pub) {
+    // 3: rejectWithF, reduceVector by its mask
+    if (bd.n0_max >= TRACK_MIN_MATCHES) {
+      hipLaunchKernelGGL(k_trk_lift_b, dim3((2 * bd.n0_max + TRK_THREADS - 1) / TRK_THREADS, 1, Z), dim3(TRK_THREADS), 0, fs, slots, m, o);
+      HIPCHK(c, hipGetLastError());
+      hipLaunchKernelGGL(k_tv_hyp_b, dim3(S, 1, Z), dim3(TV_HYP_THREADS), 0, fs, slots, m, o);
+      HIPCHK(c, hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_trk_fit_b, dim3(1, 1, Z), dim3(TV_FIT_THREADS), 0, fs, slots, m, o, S);
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(k_tf_reject_b, dim3(1, 1, Z), dim3(TF_THREADS), 0, fs, slots, m, o, bd.n0_max);
+    HIPCHK(c, hipGetLastError());
+    // 4: setMask and goodFeaturesToTrack on the new images; the sort network of the arrays' capacity, as gft_launch_detect
+    hipLaunchKernelGGL(k_gft_thin_b, dim3(1, 1, Z), dim3(GFT_THREADS), 0, fs, slots, m, o, wk, bd.n0_max, W, H, gin.mask_radius);
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(k_gft_response_b, dim3((W + GFT_TX - 1) / GFT_TX, (H + GFT_TY - 1) / GFT_TY, Z), dim3(GFT_THREADS), 0, fs, slots, m, o, wk, W, H, gin.mask_radius, MC);
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(k_gft_cand_b, dim3((W + GFT_THREADS - 1) / GFT_THREADS, (H + GFT_CAND_ROWS - 1) / GFT_CAND_ROWS, Z), dim3(GFT_THREADS), 0, fs, slots, m, o, wk, W, H,
+                       gin.quality_level, MC);
+    HIPCHK(c, hipGetLastError());
+    const unsigned chunks = (unsigned)std::min<size_t>(gw.capacity / GFT_CHUNK, GFT_SORT_GRID), halves = (unsigned)std::min<size_t>(gw.capacity / 2 / GFT_THREADS, GFT_SORT_GRID);
+    hipLaunchKernelGGL(k_gft_sort_local_b, dim3(chunks, 1, Z), dim3(GFT_SORT_THREADS), 0, fs, slots, m, o, wk, 0u);
+    for (size_t kk = 2 * (size_t)GFT_CHUNK; kk <= gw.capacity; kk *= 2) {
+      for (size_t j = kk / 2; j >= (size_t)GFT_CHUNK; j /= 2)
+        hipLaunchKernelGGL(k_gft_sort_global_b, dim3(halves, 1, Z), dim3(GFT_THREADS), 0, fs, slots, m, o, wk, (unsigned)kk, (unsigned)j);
+      hipLaunchKernelGGL(k_gft_sort_local_b, dim3(chunks, 1, Z), dim3(GFT_SORT_THREADS), 0, fs, slots, m, o, wk, (unsigned)kk);
+    }
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(k_gft_pick_b, dim3(1, 1, Z), dim3(GFT_THREADS), 0, fs, slots, m, o, wk, W, gin.min_distance, MC);
+    HIPCHK(c, hipGetLastError());
+  }
+  // 4 and 6: the next tables, numbered; 5: undistortedPoints; the messages
+  hipLaunchKernelGGL(k_tf_finish_b, dim3(1, 1, Z), dim3(TF_THREADS), 0, fs, slots, m, o, bd.n0_max, bd.B_max);
+  HIPCHK(c, hipGetLastError());
+  if (bd.B_max) {
+    hipLaunchKernelGGL(k_trk_undist_b, dim3((bd.B_max + TRK_THREADS - 1) / TRK_THREADS, 1, Z), dim3(TRK_THREADS), 0, fs, slots, m, o);
+    HIPCHK(c, hipGetLastError());
+  }
+  if (rows && any_pub) {
+    hipLaunchKernelGGL(k_tf_message_b, dim3(1, 1, Z), dim3(TF_THREADS), 0, fs, slots, m, o, bd.B_max);
+    HIPCHK(c, hipGetLastError());
+  }
+  if (int rc = st.down(o.down, o.end)) return rc;
+
+  // every count of every active slot against its own bound, before anything is written
+  for (int i = 0; i < n; i++) {
+    if (!trackbatch_active(in[i])) continue;
+    const char *dn = h + trackbatch_down_at(o, i);
+    const TfDev *v = (const TfDev *)(dn + o.dev);
+    const bool pub = in[i].publish != 0;
+    const size_t Bi = (size_t)trackframe_bound(counts[i], MC, pub), N0 = (size_t)counts[i];
+    const int num_rows = rows && pub ? *(const int *)(dn + o.msg) : 0;
+    if (v->num_points < 0 || (size_t)v->num_points > Bi || v->n1 < 0 || (size_t)v->n1 > N0 || num_rows < 0 || num_rows > v->num_points ||
+        (pub && (v->detect.num_kept < 0 || (size_t)v->detect.num_kept > N0 || v->detect.num_corners < 0 || v->detect.num_corners > MC))) {
+      c->err = "lfvio_track_batch_frame: a count from the device beyond its bound";
+      return LFVIO_ERR_DEVICE;
+    }
+  }
+  const size_t B = shape.B_max;
+  for (int i = 0; i < n; i++) {
+    LfvioTrackFrameOut *w = &out[i];
+    tb_zero_scalars(w);
+    if (msg) msg[i].num_rows = 0;
+    if (!trackbatch_active(in[i])) continue;
+    lfvio_ctx::TrackBatchState::Slot &s = b.slot[i];
+    const char *dn = h + trackbatch_down_at(o, i);
+    const TfDev *v = (const TfDev *)(dn + o.dev);
+    const bool pub = in[i].publish != 0;
+    const size_t np = (size_t)v->num_points;
+    w->num_points = v->num_points, w->num_new = v->num_new, w->levels_used = LU, w->num_tracked = v->n1, w->num_after_reject = v->n2;
+    if (pub) {
+      if (v->reject.status == 0)
+        w->reject = v->reject;
+      else  // no model: E is zero
+        w->reject.status = v->reject.status, w->reject.best_sample = v->reject.best_sample, w->reject.num_inliers = v->reject.num_inliers,
+        w->reject.best_score = v->reject.best_score;
+      w->detect = v->detect;
+    }
+    std::memcpy(w->pts, dn + o.table, np * 8);
+    std::memcpy(w->ids, dn + o.table + B * 8, np * 4);
+    std::memcpy(w->track_cnt, dn + o.table + B * 12, np * 4);
+    std::memcpy(w->un_pts, dn + o.un, np * 8);
+    std::memcpy(w->un_pts_3d, dn + o.un3d, np * 12);
+    std::memcpy(w->velocity_3d, dn + o.vel, np * 12);
+    if (rows && pub) {
+      msg[i].num_rows = *(const int *)(dn + o.msg);
+      if (msg[i].num_rows) std::memcpy(msg[i].rows, dn + o.msg + TF_MSG_HEAD, (size_t)msg[i].num_rows * 36);
+    }
+    // the slot's double buffers, as track_frame_run swaps the context's
+    s.pcur = 1 - s.pcur, s.w = W, s.h = H, s.built = LU, s.valid = true;
+    if (np) s.mcur = 1 - s.mcur;
+    s.mcount = (int)np, s.time = in[i].time;
+    s.tcur = 1 - s.tcur, s.count = (int)np, s.n_id += v->num_new;
+  }
+  return LFVIO_OK;
+}

@@ -765,6 +765,7 @@ HIP_SYMBOLS = [
     "lfvio_clahe_set", "lfvio_clahe_apply",
     "lfvio_track_reject", "lfvio_track_undistort", "lfvio_track_reset", "lfvio_track_frame", "lfvio_track_frame_reset",
     "lfvio_track_frame_message",
+    "lfvio_track_batch_reserve", "lfvio_track_batch_set_mask", "lfvio_track_batch_clahe", "lfvio_track_batch_frame", "lfvio_track_batch_reset",
     "lfvio_group_create", "lfvio_group_unique_id", "lfvio_group_create_rank", "lfvio_group_create_local", "lfvio_group_destroy",
     "lfvio_group_last_error", "lfvio_group_size", "lfvio_group_local", "lfvio_group_rank", "lfvio_group_ctx", "lfvio_group_backend",
     "lfvio_group_solve", "lfvio_group_upload", "lfvio_group_optimize", "lfvio_group_download", "lfvio_group_range",
@@ -860,6 +861,12 @@ def load_hip_library(path=None):
     if hasattr(lib, "lfvio_track_frame_message"):
         lib.lfvio_track_frame_message.argtypes = [C.c_void_p, C.POINTER(TrackFrameInC), C.POINTER(TrackFrameOutC), C.POINTER(TrackFrameStagesC),
                                                   C.POINTER(TrackMessageC)]
+    if hasattr(lib, "lfvio_track_batch_frame"):
+        lib.lfvio_track_batch_reserve.argtypes = [C.c_void_p, C.c_int]
+        lib.lfvio_track_batch_set_mask.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_ubyte)]
+        lib.lfvio_track_batch_clahe.argtypes = [C.c_void_p, C.POINTER(ClaheInC)]
+        lib.lfvio_track_batch_frame.argtypes = [C.c_void_p, C.c_int, C.POINTER(TrackFrameInC), C.POINTER(TrackFrameOutC), C.POINTER(TrackMessageC)]
+        lib.lfvio_track_batch_reset.argtypes = [C.c_void_p, C.c_int]
     lib.lfvio_shard_marg_linearize.argtypes = [C.c_void_p, C.c_int]
     lib.lfvio_shard_marg_finish.argtypes = [C.c_void_p, C.c_int, C.POINTER(Prior)]
     # multi-GPU groups (RCCL inside the library)

@@ -710,6 +710,119 @@ class Engine:
 
     track_frame_count = 0  # entries of the context's track table, as the last track_frame reported it
 
+    # ---- many streams in one call: the slots of lfvio_track_batch_* (none of them the single route's state)
+    def track_batch_reserve(self, slots, check=True):
+        """lfvio_track_batch_reserve: `slots` (1 .. 64) empty slots; 0 frees the batch.  Returns the error code."""
+        rc = self.lib.lfvio_track_batch_reserve(self.ctx, slots)
+        if check:
+            self._check(rc, "lfvio_track_batch_reserve")
+        if rc == 0:
+            self.track_batch_slots = slots
+        return rc
+
+    def track_batch_set_mask(self, slot, mask, size=None, check=True):
+        """lfvio_track_batch_set_mask: gft_set_mask for slot `slot` (-1: every slot).  Returns the error code."""
+        if mask is None:
+            rc = self.lib.lfvio_track_batch_set_mask(self.ctx, slot, 0, 0, None)
+        else:
+            m = np.ascontiguousarray(mask, dtype=np.uint8)
+            w, h = size if size is not None else (m.shape[1], m.shape[0])
+            rc = self.lib.lfvio_track_batch_set_mask(self.ctx, slot, w, h, m.ctypes.data_as(C.POINTER(C.c_ubyte)))
+        if check:
+            self._check(rc, "lfvio_track_batch_set_mask")
+        return rc
+
+    def track_batch_clahe(self, clip_limit=3.0, tiles=(8, 8), check=True):
+        """lfvio_track_batch_clahe: clahe_set for the batch; track_batch_clahe(None): off.  Returns the error code."""
+        if clip_limit is None:
+            rc = self.lib.lfvio_track_batch_clahe(self.ctx, None)
+        else:
+            rc = self.lib.lfvio_track_batch_clahe(self.ctx, C.byref(abi.ClaheInC(clip_limit, tiles[0], tiles[1])))
+        if check:
+            self._check(rc, "lfvio_track_batch_clahe")
+        return rc
+
+    def track_batch_reset(self, slot=-1, check=True):
+        """lfvio_track_batch_reset: track_frame_reset for slot `slot` (-1: every slot).  Returns the error code."""
+        rc = self.lib.lfvio_track_batch_reset(self.ctx, slot)
+        if check:
+            self._check(rc, "lfvio_track_batch_reset")
+        return rc
+
+    def track_batch_frame(self, frames, message=True, count=None, buffers=None, check=True, **params):
+        """lfvio_track_batch_frame: frames is a list with one entry per slot — None (the slot is idle in this call) or a dict with img,
+        time, cam and, optionally, publish (True), words [S, 8] uint32 and params (fields of LfvioTrackFrameIn for this entry alone).
+        **params: the fields every entry shares (Engine.TRACK_FRAME_DEFAULTS).  Returns one dict per slot, shaped like track_frame's
+        plus rows [num_rows, 9] and num_rows (None and 0 without `message`); rc is the call's.  count: the call's count whatever the
+        list says; buffers: a list of (arrays, TrackFrameOutC, rows) per slot to be written, an array None for a null pointer (tests of
+        what a refused call leaves alone); check=False returns the error code under `rc` instead of raising."""
+        unknown = set(params) - set(self.TRACK_FRAME_DEFAULTS)
+        if unknown:
+            raise TypeError(f"track_batch_frame: unknown parameters {sorted(unknown)}")
+        fp, ip, up = C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_ubyte)
+        n, cap = len(frames), abi.TRACK_MAX_POINTS
+        fin, out, msg = (abi.TrackFrameInC * max(n, 1))(), (abi.TrackFrameOutC * max(n, 1))(), (abi.TrackMessageC * max(n, 1))()
+        keep, arrays, rows = [], [], []
+        for i, f in enumerate(frames):
+            if buffers is not None:
+                a, o, r = buffers[i]
+                C.memmove(C.byref(out[i]), C.byref(o), C.sizeof(o))
+            else:
+                a = dict(pts=np.zeros((cap, 2), np.float32), ids=np.zeros(cap, np.int32), track_cnt=np.zeros(cap, np.int32),
+                         un_pts=np.zeros((cap, 2), np.float32), un_pts_3d=np.zeros((cap, 3), np.float32), velocity_3d=np.zeros((cap, 3), np.float32))
+                r = np.zeros((cap, 9), np.float32)
+            arrays.append(a), rows.append(r)
+            for key, v in a.items():  # (None: a null pointer)
+                setattr(out[i], key, None if v is None else v.ctypes.data_as(ip if v.dtype == np.int32 else fp))
+            msg[i].rows = r.ctypes.data_as(fp)
+            if buffers is not None:
+                msg[i].num_rows = -77
+            if f is None:
+                continue
+            p = dict(self.TRACK_FRAME_DEFAULTS, **params)
+            p.update(f.get("params", {}))
+            px = None if f.get("img") is None else np.ascontiguousarray(f["img"], dtype=np.uint8)
+            wd = None if f.get("words") is None else np.ascontiguousarray(f["words"], dtype=np.uint32).reshape(-1, 8)
+            camc = self.camera(f.get("cam"))
+            keep.append((px, wd, camc))
+            e = fin[i]
+            e.width = p["width"] if p["width"] is not None else (0 if px is None else px.shape[1])
+            e.height = p["height"] if p["height"] is not None else (0 if px is None else px.shape[0])
+            e.image = None if px is None else px.ctypes.data_as(up)
+            e.time, e.publish = f["time"], int(f.get("publish", True))
+            e.camera = None if camc is None else C.pointer(camc)
+            for key in ("win_size", "max_level", "max_iterations", "epsilon", "min_eig_threshold", "border", "max_count", "quality_level",
+                        "min_distance", "mask_radius"):
+                setattr(e, key, p[key])
+            e.num_samples = p["num_samples"] if p["num_samples"] is not None else (1 if wd is None else len(wd))
+            e.sample_words = None if wd is None else wd.ctypes.data_as(C.POINTER(C.c_uint))
+            e.capacity = cap if p["capacity"] is None else p["capacity"]
+        rc = self.lib.lfvio_track_batch_frame(self.ctx, n if count is None else count, fin, out, msg if message else None)
+        if check:
+            self._check(rc, "lfvio_track_batch_frame")
+        res = []
+        for i in range(n):
+            o = out[i]
+            if buffers is not None:
+                C.memmove(C.byref(buffers[i][1]), C.byref(o), C.sizeof(o))
+            k = min(max(int(o.num_points), 0), cap) if rc == 0 else 0
+            r = {key: None if v is None else v[:k] for key, v in arrays[i].items()}
+            rj, dt = o.reject, o.detect
+            r.update(num_points=int(o.num_points), num_new=int(o.num_new), levels_used=int(o.levels_used), num_tracked=int(o.num_tracked),
+                     num_after_reject=int(o.num_after_reject), rc=rc,
+                     reject=dict(status=int(rj.status), best_sample=int(rj.best_sample), num_inliers=int(rj.num_inliers),
+                                 best_score=float(rj.best_score), E=np.array(rj.E, dtype=np.float64)),
+                     detect=dict(num_kept=int(dt.num_kept), num_corners=int(dt.num_corners), num_candidates=int(dt.num_candidates),
+                                 max_response=float(dt.max_response)))
+            m = int(msg[i].num_rows) if (message and rc == 0) else 0
+            r.update(num_rows=m, rows=rows[i][:m] if message else None)
+            if buffers is not None:
+                r["msg_num_rows"] = int(msg[i].num_rows)
+            res.append(r)
+        return res
+
+    track_batch_slots = 0  # as the last track_batch_reserve left it
+
     def time_kernel(self, which, count, reps):
         ms = np.zeros(1)
         self._check(self.lib.lfvio_debug_time_kernel(self.ctx, which, count, reps, _p(ms)), "time_kernel")
