@@ -782,6 +782,25 @@ int lfvio_clahe_apply(lfvio_ctx *ctx, const LfvioClaheIn *cfg, int width, int he
  *   the norm  n = sqrt((P.x P.x + P.y P.y) + P.z P.z), left to right.  Eigen's own reduction may order the three terms differently
  *             and differ in the last bit; the reference does not build without Eigen and OpenCV, so the two were never compared.
  * tests/track_ref.py restates both calls in numpy and is the specification; the device gives its bits.
+ *   the lift of LFVIO_CAM_PINHOLE and LFVIO_CAM_MEI (PinholeCamera.cc:450-510, CataCamera.cc:556-626), in double,
+ *             every operation rounded on its own, grouped as written here:
+ *             host, once: inv11 = 1.0 / fx, inv13 = -cx / fx, inv22 = 1.0 / fy, inv23 = -cy / fy,
+ *                         no_distortion = (k1 == 0 && k2 == 0 && p1 == 0 && p2 == 0)
+ *             mx_d = inv11 * (double)px + inv13, my_d = inv22 * (double)py + inv23
+ *             dist(x, y): mx2 = x * x, my2 = y * y, mxy = x * y, rho2 = mx2 + my2, rad = k1 * rho2 + (k2 * rho2) * rho2,
+ *                         dx = (x * rad + (2.0 * p1) * mxy) + p2 * (rho2 + 2.0 * mx2),
+ *                         dy = (y * rad + (2.0 * p2) * mxy) + p1 * (rho2 + 2.0 * my2)
+ *             no_distortion: (mx_u, my_u) = (mx_d, my_d); otherwise eight evaluations of dist: (mx_u, my_u) = (mx_d, my_d) -
+ *             dist(mx_d, my_d), then seven times (mx_u, my_u) = (mx_d, my_d) - dist(mx_u, my_u).
+ *             PINHOLE: P = (mx_u, my_u, 1.0).  MEI: P = (mx_u, my_u, z) with, for xi == 1.0, z = ((1.0 - mx_u * mx_u) - my_u * my_u)
+ *             / 2.0, and otherwise rho2 = mx_u * mx_u + my_u * my_u, z = 1.0 - (xi * (rho2 + 1.0)) / (xi + sqrt(1.0 + (1.0 - xi * xi)
+ *             * rho2)).  Non-finite results keep IEEE semantics (the root's argument goes negative far outside the image for
+ *             xi > 1).  Everything behind the lift (the norm, P / n, un_pts, the casts, the map, the velocity) is the same for
+ *             all models.  tests/camera_ref.py restates these two lifts; they were never compared with the reference's Eigen build
+ *             either.  KANNALA_BRANDT (EquidistantCamera) is not served: its lift has no bitwise specification.
+ *   the camera LFVIO_ERR_ARG of every call that takes an LfvioCamera: model 1 and any model outside {0, 2, 3}; for PINHOLE and MEI a
+ *             non-finite value among cx, cy, fx, fy, k1, k2, p1, p2, fx == 0 or fy == 0, and for MEI a non-finite xi.  An OCam
+ *             camera's fx .. xi are not read, a PINHOLE or MEI camera's c, d, e, poly are not: they may be indeterminate.
  *
  * lfvio_track_reject: the bearings are P / n, a true division per component, of cur_pts (corr1) and forw_pts (corr2).  Per sample
  * set compute_E_21 and check_inliers; the first hypothesis with the largest score > 0 wins; the refit over the winner's inliers and
@@ -795,8 +814,8 @@ int lfvio_clahe_apply(lfvio_ctx *ctx, const LfvioClaheIn *cfg, int width, int he
  *   out->status 2   N < 8 (the test of :331 failing): no device work, status[] all 1, best_sample -1, num_inliers 0, best_score 0,
  *                   E and the bearing outputs untouched.
  * bearing_cur / bearing_forw (or NULL) receive the unit bearings where the device ran (status 0 and 1).
- * LFVIO_ERR_ARG (every output untouched): null ctx / in / camera / status / out, cur_pts or forw_pts null with N > 0, a model other
- * than LFVIO_CAM_OCAM, N outside [0, 4096]; with N >= 8: samples null, S outside [1, 1024], a sample index outside [0, N).
+ * LFVIO_ERR_ARG (every output untouched): null ctx / in / camera / status / out, cur_pts or forw_pts null with N > 0, a camera
+ * refused above, N outside [0, 4096]; with N >= 8: samples null, S outside [1, 1024], a sample index outside [0, N).
  *
  * lfvio_track_undistort: un_pts = ((float)(P.x / P.z), (float)(P.y / P.z)); un_pts_3d = (float)(P.k / n) per component.  The
  * context keeps what prev_un_pts_map_3d is: the (id, un_pts_3d) pairs of the PREVIOUS call, with std::map::insert semantics — the
@@ -809,16 +828,21 @@ int lfvio_clahe_apply(lfvio_ctx *ctx, const LfvioClaheIn *cfg, int width, int he
  * receives j, or -1.  After the call the map and the time are this call's.  A stated deviation: the reference forgets to clear
  * pts_velocity_3d in the empty-map branch; here the output has exactly N entries.
  * LFVIO_ERR_ARG (every output, the resident map and the time untouched): null ctx / in / camera, pts, ids, un_pts, un_pts_3d or
- * velocity_3d null with N > 0, a model other than LFVIO_CAM_OCAM, N outside [0, 4096], a NaN time.
+ * velocity_3d null with N > 0, a camera refused above (lfvio_track_reject), N outside [0, 4096], a NaN time.
  * All three run on the feature stream like lfvio_klt_track: they do not wait for an optimization in flight.  The two maps live in
  * device memory of their own (2 x 64 KiB, allocated at the first use), not in the feature calls' staging block. */
 #define LFVIO_CAM_OCAM 0
+#define LFVIO_CAM_PINHOLE 2
+#define LFVIO_CAM_MEI     3   /* 1 is refused, like every model outside {0, 2, 3} */
 #define LFVIO_TRACK_MAX_POINTS 4096
 typedef struct {
-  int model;           /* LFVIO_CAM_OCAM; anything else: LFVIO_ERR_ARG */
-  double cx, cy;       /* center_x, center_y */
-  double c, d, e;      /* the affine part; inv_scale = 1.0 / (c - d * e) */
-  double poly[5];      /* SCARAMUZZA_POLY_SIZE */
+  int model;             /* LFVIO_CAM_OCAM, LFVIO_CAM_PINHOLE or LFVIO_CAM_MEI; anything else: LFVIO_ERR_ARG */
+  double cx, cy;         /* OCam: center_x, center_y; PINHOLE: cx, cy; MEI: u0, v0 */
+  double c, d, e;        /* OCam only: the affine part; inv_scale = 1.0 / (c - d * e) */
+  double poly[5];        /* OCam only: SCARAMUZZA_POLY_SIZE */
+  double fx, fy;         /* PINHOLE: fx, fy; MEI: gamma1, gamma2.  Not read for OCam, like everything below */
+  double k1, k2, p1, p2; /* PINHOLE and MEI: distortion_parameters */
+  double xi;             /* MEI: mirror_parameters.xi */
 } LfvioCamera;
 typedef struct {
   const LfvioCamera *camera;
@@ -866,7 +890,7 @@ int lfvio_track_reset(lfvio_ctx *ctx);   /* forget the resident map and time */
  * tests/track_frame_ref.py restates the mapping of step 3 and the frame; the device gives its bits.
  * LFVIO_ERR_ARG (every output, the table, n_id, the resident image, the map and the time untouched): null ctx / in / out / image /
  * camera / an array of out, null sample_words with publish != 0, a field outside the range that the separate call states for it, a
- * model other than LFVIO_CAM_OCAM, num_samples outside [1, 1024], capacity < max(max_count, the table's count) or > 4096, a NaN
+ * camera that lfvio_track_reject refuses, num_samples outside [1, 1024], capacity < max(max_count, the table's count) or > 4096, a NaN
  * time, with publish != 0 a base mask that is not the image's size.  A call that fails later changes nothing either: the table, like
  * the pyramid and the map, is double-buffered and swapped when the call has succeeded.  Runs on the feature stream like
  * lfvio_klt_track: it does not wait for an optimization in flight.

@@ -1,7 +1,8 @@
 // kernels_track.h — the two steps of FeatureTracker::readImage that need the camera (feature_tracker/src/feature_tracker.cpp):
 // rejectWithF (:329-386) behind lfvio_track_reject and undistortedPoints (:441-504) behind lfvio_track_undistort, with
-// OCAMCamera::liftProjective (ScaramuzzaCamera.cc:623-645) as a device function.  The specification is in include/lfvio.h and, as
-// numpy, in tests/track_ref.py.
+// the lift of three camera models as device functions: OCAMCamera::liftProjective (ScaramuzzaCamera.cc:623-645),
+// PinholeCamera::liftProjective (PinholeCamera.cc:450-510) and CataCamera::liftProjective (CataCamera.cc:556-626).  The specification
+// is in include/lfvio.h and, as numpy, in tests/track_ref.py (OCam) and tests/camera_ref.py (PINHOLE, MEI).
 //
 //   k_trk_lift   : a thread per point of BOTH sets (2 N threads): the unit bearing of cur_pts[i] / forw_pts[i] in double, into the
 //                  staging block where k_tv_hyp (kernels_twoview.h, reused as it is) and k_trk_fit read them.
@@ -28,8 +29,48 @@
 
 constexpr int TRK_THREADS = 256;
 
-// OCAMCamera::liftProjective of the pixel (px, py)
+// PinholeCamera::distortion (PinholeCamera.cc:646-662; CataCamera's is the same text): grouped as include/lfvio.h states it
+DEV void trk_distortion(const TrackCam &cam, double x, double y, double &dx, double &dy) {
+  const double mx2 = x * x, my2 = y * y, mxy = x * y, rho2 = mx2 + my2;
+  const double rad = cam.k1 * rho2 + (cam.k2 * rho2) * rho2;
+  dx = (x * rad + (2.0 * cam.p1) * mxy) + cam.p2 * (rho2 + 2.0 * mx2);
+  dy = (y * rad + (2.0 * cam.p2) * mxy) + cam.p1 * (rho2 + 2.0 * my2);
+}
+
+// The part both liftProjective share (PinholeCamera.cc:456-506, CataCamera.cc:562-612): the normalised plane and the recursive
+// distortion model, n = 8 evaluations.  The trip count is fixed, so nothing diverges within a wave.
+DEV void trk_undistorted_plane(const TrackCam &cam, float px, float py, double &mx_u, double &my_u) {
+  const double mx_d = cam.inv11 * (double)px + cam.inv13, my_d = cam.inv22 * (double)py + cam.inv23;
+  mx_u = mx_d, my_u = my_d;
+  if (cam.no_distortion) return;
+  for (int i = 0; i < 8; i++) {
+    double dx, dy;
+    trk_distortion(cam, mx_u, my_u, dx, dy);
+    mx_u = mx_d - dx, my_u = my_d - dy;
+  }
+}
+
+// PinholeCamera::liftProjective (:450-510)
+DEV d3 trk_lift_pinhole(const TrackCam &cam, float px, float py) {
+  double mx_u, my_u;
+  trk_undistorted_plane(cam, px, py, mx_u, my_u);
+  return mk3(mx_u, my_u, 1.0);
+}
+
+// CataCamera::liftProjective (:556-626)
+DEV d3 trk_lift_mei(const TrackCam &cam, float px, float py) {
+  double mx_u, my_u;
+  trk_undistorted_plane(cam, px, py, mx_u, my_u);
+  if (cam.xi == 1.0) return mk3(mx_u, my_u, ((1.0 - mx_u * mx_u) - my_u * my_u) / 2.0);  // :618
+  const double rho2 = mx_u * mx_u + my_u * my_u;
+  return mk3(mx_u, my_u, 1.0 - (cam.xi * (rho2 + 1.0)) / (cam.xi + sqrt(1.0 + (1.0 - cam.xi * cam.xi) * rho2)));  // :624
+}
+
+// liftProjective of the pixel (px, py).  The model is the same in every thread of a workgroup (a kernel argument, or the slot's
+// camera in the batched route), so the branches below are uniform.  OCAMCamera::liftProjective:
 DEV d3 trk_lift(const TrackCam &cam, float px, float py) {
+  if (cam.model == LFVIO_CAM_PINHOLE) return trk_lift_pinhole(cam, px, py);
+  if (cam.model == LFVIO_CAM_MEI) return trk_lift_mei(cam, px, py);
   const double x = (double)px - cam.cx, y = (double)py - cam.cy;  // :627
   const double xa = cam.inv_scale * (x - cam.d * y), ya = cam.inv_scale * (-cam.e * x + cam.c * y);  // :631-632
   const double phi = sqrt(xa * xa + ya * ya);

@@ -1,6 +1,7 @@
 // track_plan.h — the host side of lfvio_track_reject / lfvio_track_undistort (include/lfvio.h) that needs no device: the argument
 // checks of both calls, and the camera as the kernels take it (TrackCam: LfvioCamera's numbers with inv_scale = 1.0 / (c - d * e),
-// divided once, on the host, in double — ScaramuzzaCamera.cc:197).  Plain C++ (no HIP): track.inc uses it, tests/test_track_ref.py
+// divided once, on the host, in double — ScaramuzzaCamera.cc:197; for PINHOLE and MEI the inverse projection matrix's four entries
+// and the no-distortion flag, PinholeCamera.cc:281-289).  Plain C++ (no HIP): track.inc uses it, tests/test_track_ref.py
 // compiles it alone with g++ and holds it to the checks of tests/track_ref.py.
 #pragma once
 #include <cmath>
@@ -9,22 +10,41 @@
 
 constexpr int TRACK_MAX_SAMPLES = 1024, TRACK_MIN_MATCHES = 8;  // forw_pts.size() >= 8 (feature_tracker.cpp:331)
 
-struct TrackCam {  // a kernel argument, by value
-  double cx, cy, c, d, e, inv_scale, poly[5];
+struct TrackCam {  // a kernel argument, by value; the members a model does not use are zero
+  double cx, cy, c, d, e, inv_scale, poly[5];          // OCam
+  double inv11, inv13, inv22, inv23, k1, k2, p1, p2, xi;  // PINHOLE and MEI (xi: MEI), PinholeCamera.cc:281-289
+  int model, no_distortion;
 };
 
+// LfvioCamera's fx .. xi are read only for PINHOLE and MEI, its c, d, e, poly only for OCam: callers may leave the others indeterminate
 inline TrackCam track_cam(const LfvioCamera &k) {
-  TrackCam t;
-  t.cx = k.cx, t.cy = k.cy, t.c = k.c, t.d = k.d, t.e = k.e;
-  t.inv_scale = 1.0 / (k.c - k.d * k.e);
-  for (int i = 0; i < 5; i++) t.poly[i] = k.poly[i];
+  TrackCam t = {};
+  t.model = k.model, t.cx = k.cx, t.cy = k.cy;
+  if (k.model == LFVIO_CAM_OCAM) {
+    t.c = k.c, t.d = k.d, t.e = k.e;
+    t.inv_scale = 1.0 / (k.c - k.d * k.e);
+    for (int i = 0; i < 5; i++) t.poly[i] = k.poly[i];
+    return t;
+  }
+  t.inv11 = 1.0 / k.fx, t.inv13 = -k.cx / k.fx, t.inv22 = 1.0 / k.fy, t.inv23 = -k.cy / k.fy;
+  t.k1 = k.k1, t.k2 = k.k2, t.p1 = k.p1, t.p2 = k.p2;
+  t.no_distortion = k.k1 == 0.0 && k.k2 == 0.0 && k.p1 == 0.0 && k.p2 == 0.0;
+  if (k.model == LFVIO_CAM_MEI) t.xi = k.xi;
   return t;
 }
 
 // nullptr, or what is wrong with the camera or the point count
 inline const char *track_common_check(const LfvioCamera *cam, int N) {
   if (!cam) return "lfvio_track: null camera";
-  if (cam->model != LFVIO_CAM_OCAM) return "lfvio_track: a camera model other than LFVIO_CAM_OCAM";
+  if (cam->model != LFVIO_CAM_OCAM && cam->model != LFVIO_CAM_PINHOLE && cam->model != LFVIO_CAM_MEI)
+    return "lfvio_track: a camera model other than LFVIO_CAM_OCAM, LFVIO_CAM_PINHOLE and LFVIO_CAM_MEI";
+  if (cam->model != LFVIO_CAM_OCAM) {
+    const double v[8] = {cam->cx, cam->cy, cam->fx, cam->fy, cam->k1, cam->k2, cam->p1, cam->p2};
+    for (double x : v)
+      if (!std::isfinite(x)) return "lfvio_track: a non-finite camera parameter";
+    if (cam->fx == 0.0 || cam->fy == 0.0) return "lfvio_track: fx or fy is zero";
+    if (cam->model == LFVIO_CAM_MEI && !std::isfinite(cam->xi)) return "lfvio_track: a non-finite xi";
+  }
   if (N < 0 || N > LFVIO_TRACK_MAX_POINTS) return "lfvio_track: num_points outside [0, 4096]";
   return nullptr;
 }

@@ -658,9 +658,11 @@ CLAHE_MAX_TILES = 16  # LFVIO_CLAHE_MAX_TILES
 
 
 class CameraC(C.Structure):
-    """LfvioCamera (include/lfvio.h)."""
+    """LfvioCamera (include/lfvio.h).  The fields behind poly are PINHOLE's and MEI's; positional construction with the eleven
+    values of an OCam camera leaves them zero."""
     _fields_ = [("model", C.c_int), ("cx", C.c_double), ("cy", C.c_double), ("c", C.c_double), ("d", C.c_double), ("e", C.c_double),
-                ("poly", C.c_double * 5)]
+                ("poly", C.c_double * 5), ("fx", C.c_double), ("fy", C.c_double), ("k1", C.c_double), ("k2", C.c_double),
+                ("p1", C.c_double), ("p2", C.c_double), ("xi", C.c_double)]
 
 
 class TrackRejectInC(C.Structure):
@@ -687,6 +689,7 @@ class TrackUndistortInC(C.Structure):
 
 
 CAM_OCAM, TRACK_MAX_POINTS = 0, 4096  # LFVIO_CAM_OCAM, LFVIO_TRACK_MAX_POINTS
+CAM_PINHOLE, CAM_MEI = 2, 3  # LFVIO_CAM_PINHOLE, LFVIO_CAM_MEI
 
 
 class TrackFrameInC(C.Structure):

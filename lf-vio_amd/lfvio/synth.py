@@ -316,6 +316,61 @@ def ocam_lift_projective(p):
     return np.stack([x, y, -z], axis=-1)
 
 
+# The reference's two other camera models that have a lift in + - * / and sqrt alone: PINHOLE (PinholeCamera.cc) and MEI
+# (CataCamera.cc).  A camera is a dict: model (CAM_PINHOLE / CAM_MEI), cx, cy, fx, fy (MEI: u0, v0, gamma1, gamma2), k1, k2, p1, p2 and,
+# for MEI, xi.  These two make INPUTS (pixels of rays, rays of pixels); the specification of the device's lift is tests/camera_ref.py.
+CAM_PINHOLE, CAM_MEI = 2, 3
+
+
+def _camera_distortion(cam, x, y):
+    """PinholeCamera::distortion (PinholeCamera.cc:646-662; CataCamera's is the same)."""
+    k1, k2, p1, p2 = (float(cam.get(k, 0.0)) for k in ("k1", "k2", "p1", "p2"))
+    mx2, my2, mxy = x * x, y * y, x * y
+    rho2 = mx2 + my2
+    rad = k1 * rho2 + k2 * rho2 * rho2
+    return x * rad + 2.0 * p1 * mxy + p2 * (rho2 + 2.0 * mx2), y * rad + 2.0 * p2 * mxy + p1 * (rho2 + 2.0 * my2)
+
+
+def _camera_no_distortion(cam):
+    return all(float(cam.get(k, 0.0)) == 0.0 for k in ("k1", "k2", "p1", "p2"))
+
+
+def camera_lift(cam, px):
+    """liftProjective of pixels px [..., 2] -> rays [..., 3], not normalised (PinholeCamera.cc:450-510, CataCamera.cc:556-626)."""
+    px = np.asarray(px, np.float64)
+    if cam["model"] not in (CAM_PINHOLE, CAM_MEI):
+        raise ValueError("camera_lift: a PINHOLE or MEI camera")
+    with np.errstate(all="ignore"):
+        xd, yd = (px[..., 0] - cam["cx"]) / cam["fx"], (px[..., 1] - cam["cy"]) / cam["fy"]
+        xu, yu = xd, yd
+        if not _camera_no_distortion(cam):
+            for _ in range(8):
+                dx, dy = _camera_distortion(cam, xu, yu)
+                xu, yu = xd - dx, yd - dy
+        if cam["model"] == CAM_PINHOLE:
+            z = np.ones_like(xu)
+        elif cam["xi"] == 1.0:
+            z = (1.0 - xu * xu - yu * yu) / 2.0
+        else:
+            xi, rho2 = float(cam["xi"]), xu * xu + yu * yu
+            z = 1.0 - xi * (rho2 + 1.0) / (xi + np.sqrt(1.0 + (1.0 - xi * xi) * rho2))
+    return np.stack([xu, yu, z], axis=-1)
+
+
+def camera_space_to_plane(cam, P):
+    """spaceToPlane of rays P [..., 3] -> pixels [..., 2] (PinholeCamera.cc:520-550, CataCamera.cc:636-659)."""
+    P = np.asarray(P, np.float64)
+    if cam["model"] not in (CAM_PINHOLE, CAM_MEI):
+        raise ValueError("camera_space_to_plane: a PINHOLE or MEI camera")
+    with np.errstate(all="ignore"):
+        z = P[..., 2] if cam["model"] == CAM_PINHOLE else P[..., 2] + float(cam["xi"]) * np.linalg.norm(P, axis=-1)
+        x, y = P[..., 0] / z, P[..., 1] / z
+        if not _camera_no_distortion(cam):
+            dx, dy = _camera_distortion(cam, x, y)
+            x, y = x + dx, y + dy
+        return np.stack([cam["fx"] * x + cam["cx"], cam["fy"] * y + cam["cy"]], axis=-1)
+
+
 def _landmarks(rng, scene, kf0, n_landmarks, td_frames, min_track=2, camera="sphere"):
     """CSR landmark/observation arrays for the window kf0..kf0+10 (vectorised).
 

@@ -303,7 +303,7 @@ def image_camera(s):
 
 
 def make_image_stream(path, seed=0, n_frames=36, scale=4, cam_offset=0.0023, boot_noise=(0.02, 0.5), frame_dt=None, box=(2.5, 3.5, 2.0), waves=80,
-                      wavelength=(0.25, 2.5), contrast=40.0):
+                      wavelength=(0.25, 2.5), contrast=40.0, camera=None):
     """make_stream's scene, trajectory, IMU, truth and clock convention with rendered IMAGES (record type 10) in place of the feature
     messages: `n_frames` images of 1280 / scale x 960 / scale pixels through image_camera(scale).  Image k is exposed at
     frame_dt k + cam_offset on the IMU clock and stamped that minus TD0.  Every pixel is lifted to its ray, rotated into the world
@@ -313,6 +313,9 @@ def make_image_stream(path, seed=0, n_frames=36, scale=4, cam_offset=0.0023, boo
     proportional to the wavelength, standard deviation `contrast` grey levels around 127.5), evaluated where the ray hits the wall,
     so it has no seams at the edges.  Pixels outside the 40-120 degree annulus are black; the matching base mask is the annulus of
     image_camera.
+    camera = (camera dict, width, height): a PINHOLE or MEI camera (Engine.camera) in place of image_camera(scale), which `scale`
+    then does not touch.  The pixels' rays are synth.camera_lift's, every pixel with a finite ray is lit, and the base mask is all
+    255: the returned annulus is None and `mask` [height, width] is that mask.
 
     The bootstrap record is the truth (+ boot_noise, as make_stream) of the window of the first eleven PUBLISHED messages, stamped
     with the last of them.  At 10 Hz with FREQ = 10 the node drops image 0, publishes every later image and skips the first
@@ -322,7 +325,10 @@ def make_image_stream(path, seed=0, n_frames=36, scale=4, cam_offset=0.0023, boo
     scene = synth.Scene(seed, n_total=n_frames + 2 if frame_dt is None else int(np.ceil(n_frames * fdt / synth.KF_DT)) + 3)
     rng = np.random.default_rng([seed, 15485863])
     traj = scene.traj
-    cam, W, H, annulus = image_camera(scale)
+    if camera is None:
+        cam, W, H, annulus = image_camera(scale)
+    else:
+        (cam, W, H), annulus = camera, None
     # the texture
     lam = rng.uniform(wavelength[0], wavelength[1], waves)
     kdir = rng.normal(size=(waves, 3))
@@ -331,13 +337,19 @@ def make_image_stream(path, seed=0, n_frames=36, scale=4, cam_offset=0.0023, boo
     amp = lam * (contrast / np.sqrt(0.5 * (lam * lam).sum()))
     # the rays of the pixels in the camera frame
     u, v = np.meshgrid(np.arange(W, dtype=np.float64), np.arange(H, dtype=np.float64))
-    x, y = u - cam["cx"], v - cam["cy"]
-    phi = np.hypot(x, y)
-    z = sum(c * phi ** i for i, c in enumerate(cam["poly"]))
-    ray = np.stack([x, y, -z], axis=-1)
-    ray /= np.linalg.norm(ray, axis=-1, keepdims=True)
-    ang = np.degrees(np.arccos(np.clip(ray[..., 2], -1, 1)))
-    lit = (ang >= 40.0) & (ang <= 120.0)
+    if camera is None:
+        x, y = u - cam["cx"], v - cam["cy"]
+        phi = np.hypot(x, y)
+        z = sum(c * phi ** i for i, c in enumerate(cam["poly"]))
+        ray = np.stack([x, y, -z], axis=-1)
+        ray /= np.linalg.norm(ray, axis=-1, keepdims=True)
+        ang = np.degrees(np.arccos(np.clip(ray[..., 2], -1, 1)))
+        lit = (ang >= 40.0) & (ang <= 120.0)
+    else:
+        with np.errstate(all="ignore"):
+            ray = synth.camera_lift(cam, np.stack([u, v], axis=-1))
+            ray /= np.linalg.norm(ray, axis=-1, keepdims=True)
+        lit = np.isfinite(ray).all(axis=-1)
     rays = ray[lit]  # [n, 3]
     half = np.asarray(box, np.float64)
 
@@ -387,7 +399,10 @@ def make_image_stream(path, seed=0, n_frames=36, scale=4, cam_offset=0.0023, boo
         truth.append((stamp, P, R, traj.vel(t_img)))
         stamps.append(stamp)
     w.close()
-    return dict(scene=scene, truth=truth, stamps=stamps, camera=cam, annulus=annulus, width=W, height=H, bootstrap=boot, first_window=first_window)
+    out = dict(scene=scene, truth=truth, stamps=stamps, camera=cam, annulus=annulus, width=W, height=H, bootstrap=boot, first_window=first_window)
+    if camera is not None:
+        out["mask"] = np.full((H, W), 255, np.uint8)
+    return out
 
 
 def sfm_from_truth(stamps, Ps, Rs, keyframe=0, scale=1.0, rot_noise_deg=0.0, pos_noise=0.0, seed=0, tic=None, ric=None):
