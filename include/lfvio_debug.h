@@ -1,6 +1,6 @@
 /*
  * lfvio_debug.h — parity / inspection hooks of liblfvio_hip.so used by tests/, tools/ and bench.py only.
- * Not part of the drop-in boundary (include/lfvio.h).  Nine entry points: two that take a key, seven that look inside.
+ * Not part of the drop-in boundary (include/lfvio.h).  Ten entry points: two that take a key, eight that look inside.
  */
 #ifndef LFVIO_DEBUG_H
 #define LFVIO_DEBUG_H
@@ -64,6 +64,31 @@ int lfvio_debug_time_kernel(lfvio_ctx *ctx, int which, int count, int reps, doub
  * < 0 on error. */
 int lfvio_debug_resident_pass(lfvio_ctx *ctx, int count, int slot, double *gp, double *schur, double *lm_sum, double *a, double *b, double *gn_p, double *q,
                               double *x_cost);
+/* What the dense solve (k_solve_dense, csrc/kernels_solve.h) read and what it wrote, for tests/test_solve_hp.py.  Launches exactly what
+ * lfvio_debug_resident_pass launches on the resident slots [0, count) — k_setup, the sweep and the solve of the launch's own route; with
+ * mu > 0, tr.mu of every slot's header is set to it between k_setup and the sweep (mu <= 0: the 1e-8 k_setup leaves) — adds no kernel and
+ * no kernel argument, and copies down memory the pass leaves in slot `slot`.  Every pointer of `io` may be NULL.  Returns the sweep
+ * kernel as lfvio_debug_resident_pass does, < 0 on error.
+ *   read by the solve    H        the H region of the exchange buffer, 14 878 packed doubles (lower triangle, entry (i, j <= i) at
+ *                                 i (i + 1) / 2 + j): complete H_pp behind k_sum / k_sumb; behind k_linw only the visual terms of the camera
+ *                                 rows (i < 73), the rest of it is whatever an earlier pass left
+ *                        gp[172], schur[15 x 256] (tile layout), lm_sum[16], imu_out[10 x 932] (per factor: its 30 x 30 block over
+ *                        [pose_f | sb_f | pose_f+1 | sb_f+1] row-major — behind k_linw only the entries whose tangent row is not above
+ *                        their tangent column, the ones the solve takes — 30 gradient entries, the cost), prior_A[prior_n x prior_n] (room
+ *                        for 172 x 172), prior_cmap[172] (prior column -> tangent column)
+ *   read by the sweep's Schur phase   a[N], b[N], W[N x 73]: device landmark order, W unpacked from the rows the route leaves
+ *                        (the compact rows behind k_lin, the transposed ones behind k_linw / k_linb) over each landmark's span
+ *   written by the solve scale_p, diag_p, grad_p, gn_p [172 each], uc_grad, uc_gn [80 each: 73 entries and the zero padding], q[16]
+ *   scalars, always filled in: the trust-region header after the pass and the sizes the arrays above go with */
+typedef struct LfvioPassIO {
+  double *H, *gp, *schur, *lm_sum, *imu_out, *prior_A;
+  int *prior_cmap;
+  double *a, *b, *W;
+  double *scale_p, *diag_p, *grad_p, *gn_p, *uc_grad, *uc_gn, *q;
+  double alpha, grad_sq_total, x_cost, mu, prior_cost; /* tr.alpha, tr.grad_sq_total, tr.x_cost, tr.mu; prior_g[172], the prior's cost */
+  int chol_fail, prior_n, est_ex, est_td, num_landmarks;
+} LfvioPassIO;
+int lfvio_debug_pass_io(lfvio_ctx *ctx, int count, int slot, double mu, LfvioPassIO *io);
 /* tests: the local context `local_ctx` of the group reports a failure when it enqueues phase `phase` (0 the sweep, 4 solve ..
  * candidate cost, 3 bookkeeping) of pass `pass` of the next lfvio_group_optimize(); local_ctx < 0 clears it.
  * The call must still issue every collective of its sequence (the peers of a real group are waiting in them), end the loops of all

@@ -2011,6 +2011,86 @@ int lfvio_debug_resident_pass(lfvio_ctx *c, int count, int slot, double *gp, dou
   return r.sweep;
 }
 
+// The same pass as lfvio_debug_resident_pass — at the caller's mu where it gives one — and everything k_solve_dense read and wrote in slot
+// `slot` (include/lfvio_debug.h): plain copies of what the pass leaves.  tests/test_solve_hp.py holds the solve to a 50-digit reference
+// formed from these very inputs.
+int lfvio_debug_pass_io(lfvio_ctx *c, int count, int slot, double mu, LfvioPassIO *io) {
+  if (!c || !c->d_base || !io || count <= 0 || count > c->batch || slot < 0 || slot >= count) return LFVIO_ERR_ARG;
+  (void)hipSetDevice(c->device);
+  if (int rc = join_inflight(c)) return rc;
+  for (int s = 0; s < count; s++)
+    if (!c->info[s].resident) return LFVIO_ERR_ARG;
+  const size_t st = c->L.total;
+  const Layout &L = c->L;
+  const Route r = route_for(c, count, MODE_SOLVE);
+  launch_setup(c, r, MODE_SOLVE);
+  if (mu > 0.0) {  // (k_setup arms the header with Ceres' initial mu: the caller's replaces it before the sweep weighs the landmarks with it)
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int s = 0; s < count; s++)
+      HIPCHK(c, hipMemcpy(c->d_base + (size_t)s * st + offsetof(Slot, tr) + offsetof(TRState, mu), &mu, sizeof mu, hipMemcpyHostToDevice));
+  }
+  launch_sweep(c, r, MODE_SOLVE, true);
+  launch_solve(c, count, r.sweep == Route::LINW);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const char *d = c->d_base + (size_t)slot * st;
+  const int N = c->info[slot].N;
+  auto get = [&](void *dst, size_t off, size_t bytes) { return !dst || !bytes ? hipSuccess : hipMemcpy(dst, d + off, bytes, hipMemcpyDeviceToHost); };
+  int hdr[2] = {0, 0}, prior[2] = {0, 0};  // est_ex, est_td | prior_valid, prior_n
+  HIPCHK(c, get(hdr, offsetof(Slot, est_ex), sizeof hdr));
+  HIPCHK(c, get(prior, offsetof(Slot, prior_valid), sizeof prior));
+  static_assert(offsetof(Slot, est_td) == offsetof(Slot, est_ex) + sizeof(int) && offsetof(Slot, prior_n) == offsetof(Slot, prior_valid) + sizeof(int), "read in pairs");
+  io->est_ex = hdr[0], io->est_td = hdr[1], io->prior_n = prior[0] ? prior[1] : 0, io->num_landmarks = N;
+  if (io->prior_n < 0 || io->prior_n > KP) return LFVIO_ERR_ARG;
+  HIPCHK(c, get(io->H, L.xch + (size_t)XOFF_H * 8, (size_t)PACKED * 8));
+  HIPCHK(c, get(io->gp, L.xch + (size_t)XOFF_G * 8, KP * 8));
+  HIPCHK(c, get(io->schur, L.xch + (size_t)XOFF_S * 8, SCHUR_LEN * 8));
+  HIPCHK(c, get(io->lm_sum, offsetof(Slot, lm_sum), LMS * 8));
+  HIPCHK(c, get(io->imu_out, L.imu_out, (size_t)LFVIO_WINDOW_SIZE * IMU_OUT * 8));
+  HIPCHK(c, get(io->prior_A, L.prior_A, (size_t)io->prior_n * io->prior_n * 8));
+  HIPCHK(c, get(io->prior_cmap, offsetof(Slot, prior_cmap), KP * sizeof(int)));
+  HIPCHK(c, get(&io->prior_cost, offsetof(Slot, prior_g) + (size_t)KP * 8, 8));
+  HIPCHK(c, get(io->a, L.a, (size_t)N * 8));
+  HIPCHK(c, get(io->b, L.b, (size_t)N * 8));
+  if (io->W && N) {
+    std::vector<int> woff(N + 1), lst(N), lcn(N);
+    HIPCHK(c, get(woff.data(), L.lm_woff, sizeof(int) * (N + 1)));
+    HIPCHK(c, get(lst.data(), L.lm_start, sizeof(int) * N));
+    HIPCHK(c, get(lcn.data(), L.lm_cnt, sizeof(int) * N));
+    std::fill(io->W, io->W + (size_t)N * KC, 0.0);
+    // a landmark's span: its track's frames, then ex (6) and td
+    auto col_of = [&](int dl, int ci) { return ci < 6 * lcn[dl] ? 6 * lst[dl] + ci : 66 + (ci - 6 * lcn[dl]); };
+    if (r.sweep == Route::ROLES) {
+      if (woff[N] < 0 || (size_t)woff[N] > (size_t)N * (KC + 2)) return LFVIO_ERR_ARG;
+      std::vector<double> Wv((size_t)woff[N] + 1);
+      HIPCHK(c, get(Wv.data(), L.W, sizeof(double) * woff[N]));
+      for (int dl = 0; dl < N; dl++)
+        for (int ci = 0; ci < 6 * lcn[dl] + 7; ci++) io->W[(size_t)dl * KC + col_of(dl, ci)] = Wv[(size_t)woff[dl] + ci];
+    } else {  // the transposed rows: column pair p of landmark l at [p][l], the pairs wld landmarks apart
+      const size_t wld = r.sweep == Route::LINB ? (size_t)L.capLmBlocks * LM_BLOCK : (size_t)SPEC_MAX_LM;
+      if ((size_t)N > wld) return LFVIO_ERR_ARG;
+      std::vector<double> Wt((size_t)WT_PAIRS * wld * 2);
+      HIPCHK(c, get(Wt.data(), L.Wt, Wt.size() * 8));
+      for (int dl = 0; dl < N; dl++)
+        for (int ci = 0; ci < 6 * lcn[dl] + 7; ci++) {
+          const int col = col_of(dl, ci);
+          io->W[(size_t)dl * KC + col] = Wt[((size_t)(col >> 1) * wld + dl) * 2 + (col & 1)];
+        }
+    }
+  }
+  HIPCHK(c, get(io->scale_p, offsetof(Slot, scale_p), KP * 8));
+  HIPCHK(c, get(io->diag_p, offsetof(Slot, diag_p), KP * 8));
+  HIPCHK(c, get(io->grad_p, offsetof(Slot, grad_p), KP * 8));
+  HIPCHK(c, get(io->gn_p, offsetof(Slot, gn_p), KP * 8));
+  HIPCHK(c, get(io->uc_grad, offsetof(Slot, uc_grad), WLD * 8));
+  HIPCHK(c, get(io->uc_gn, offsetof(Slot, uc_gn), WLD * 8));
+  TRHead th;
+  HIPCHK(c, get(&th, offsetof(Slot, tr), sizeof th));
+  if (io->q) std::copy(th.q, th.q + Q_COUNT, io->q);
+  io->alpha = th.alpha, io->grad_sq_total = th.grad_sq_total, io->x_cost = th.x_cost, io->mu = th.mu, io->chol_fail = th.chol_fail;
+  return r.sweep;
+}
+
 // Every switch of the debug interface in one call (include/lfvio_debug.h).  The product entry points read no environment: a tool
 // that wants LFVIO_DEBUG="key=value,key=value" honoured asks for it with the key "env".
 int lfvio_debug_configure(lfvio_ctx *c, const char *key, double value) {

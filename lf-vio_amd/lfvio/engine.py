@@ -93,6 +93,36 @@ class Engine:
         out["a"], out["b"], out["linw"] = out["a"][:n_landmarks], out["b"][:n_landmarks], rc
         return out
 
+    class _PassIO(C.Structure):  # LfvioPassIO of include/lfvio_debug.h
+        _ARRAYS = ("H", "gp", "schur", "lm_sum", "imu_out", "prior_A", "prior_cmap", "a", "b", "W",
+                   "scale_p", "diag_p", "grad_p", "gn_p", "uc_grad", "uc_gn", "q")
+        _fields_ = ([(k, C.POINTER(C.c_int) if k == "prior_cmap" else _dp) for k in _ARRAYS]
+                    + [(k, C.c_double) for k in ("alpha", "grad_sq_total", "x_cost", "mu", "prior_cost")]
+                    + [(k, C.c_int) for k in ("chol_fail", "prior_n", "est_ex", "est_td", "num_landmarks")])
+
+    def pass_io(self, count, slot, n_landmarks, mu=0.0):
+        """One linearization + dense solve of the resident slots [0, count) at `mu` (0: the 1e-8 the setup leaves): everything the
+        solve of `slot` read and wrote, as a dict (lfvio_debug_pass_io).  W is [N, 73] in device landmark order, prior_A [n, n]."""
+        N, KP = n_landmarks, abi.KP
+        out = dict(H=np.zeros(KP * (KP + 1) // 2), gp=np.zeros(KP), schur=np.zeros(15 * 256), lm_sum=np.zeros(16), imu_out=np.zeros((10, 932)),
+                   prior_A=np.zeros(KP * KP), prior_cmap=np.zeros(KP, np.int32), a=np.zeros(max(N, 1)), b=np.zeros(max(N, 1)),
+                   W=np.zeros((max(N, 1), abi.KC)), scale_p=np.zeros(KP), diag_p=np.zeros(KP), grad_p=np.zeros(KP), gn_p=np.zeros(KP),
+                   uc_grad=np.zeros(80), uc_gn=np.zeros(80), q=np.zeros(16))
+        io = Engine._PassIO()
+        for k in Engine._PassIO._ARRAYS:
+            setattr(io, k, out[k].ctypes.data_as(C.POINTER(C.c_int) if k == "prior_cmap" else _dp))
+        self.lib.lfvio_debug_pass_io.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.POINTER(Engine._PassIO)]
+        rc = self.lib.lfvio_debug_pass_io(self.ctx, count, slot, float(mu), C.byref(io))
+        if rc < 0:
+            self._check(rc, "pass_io")
+        assert io.num_landmarks == N, (io.num_landmarks, N)
+        n = io.prior_n
+        out.update(a=out["a"][:N], b=out["b"][:N], W=out["W"][:N], prior_A=out["prior_A"][:n * n].reshape(n, n).copy(),
+                   prior_cmap=out["prior_cmap"][:n].copy(), linw=rc)
+        for k in ("alpha", "grad_sq_total", "x_cost", "mu", "prior_cost", "chol_fail", "prior_n", "est_ex", "est_td"):
+            out[k] = getattr(io, k)
+        return out
+
     def set_function_tolerance(self, tol):
         """Solver::Options::function_tolerance of the windows uploaded from now on (Ceres' default 1e-6)."""
         self.configure("function_tolerance", float(tol))

@@ -48,6 +48,7 @@ def lib():
         L.oracle_gauge_fix.argtypes = [C.POINTER(abi.WindowC), C.POINTER(abi.SolutionC)]
         L.oracle_linearize.argtypes = [C.POINTER(abi.WindowC), _dp, _dp, _dp, _dp, _dp, _dp]
         L.oracle_cost.argtypes = [C.POINTER(abi.WindowC), _dp]
+        L.oracle_schur_step.argtypes = [C.POINTER(abi.WindowC), C.c_double, _dp]
         L.oracle_prior_evaluate.argtypes = [C.POINTER(abi.WindowC), _dp, _dp]
         L.oracle_preintegrate.argtypes = [_dp, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, C.POINTER(abi.Preintegration)]
         L.oracle_imu_evaluate.argtypes = [C.POINTER(abi.Preintegration)] + [_dp] * 11
@@ -120,6 +121,15 @@ def linearize(win):
     rc = lib().oracle_linearize(C.byref(win.c()), _p(H), _p(g), _p(a), _p(b), _p(W), _p(cost))
     assert rc == 0
     return dict(H=H, g=g, a=a[:N], b=b[:N], W=W[:N], cost=float(cost[0]))
+
+
+def schur_step(win, mu):
+    """y[172 + N] of the oracle's own schur_solve at the window's state and `mu` (scaling and diagonal_ of iteration 0)."""
+    y = np.zeros(abi.KP + win.N)
+    rc = lib().oracle_schur_step(C.byref(win.c()), float(mu), _p(y))
+    if rc:
+        raise np.linalg.LinAlgError("oracle schur_solve: the factorization failed")
+    return y
 
 
 def cost(win):

@@ -85,6 +85,9 @@ int oracle_linearize(const LfvioWindow *w, double *Hpp, double *gp, double *a, d
 
 int oracle_solve(const LfvioWindow *w, LfvioSolution *out) { return solve(*w, out); }
 
+// y[172 + N] of the first Gauss-Newton solve at `mu` (schur_solve on the oracle's own linearization); 1: the factorization failed
+int oracle_schur_step(const LfvioWindow *w, double mu, double *y) { return schur_step(*w, mu, y); }
+
 static void state_from_solution(const LfvioSolution *s, int N, State *x) {
   std::memcpy(x->pose, s->para_pose, sizeof x->pose);
   std::memcpy(x->sb, s->para_speed_bias, sizeof x->sb);

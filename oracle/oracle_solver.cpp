@@ -353,6 +353,22 @@ static bool schur_solve(const Problem &pb, const Linearization &lin, const std::
   return finite_all(*y);
 }
 
+int schur_step(const LfvioWindow &w, double mu, double *y_out) {
+  Problem pb(w);
+  const int N = pb.N, n = kP + N;
+  Linearization lin;
+  pb.evaluate(pb.initial_state(), &lin);
+  std::vector<double> scale(n), diagonal(n), y;
+  for (int i = 0; i < n; i++) {  // as solve() forms them at iteration 0
+    const double h = i < kP ? lin.Hpp[(size_t)i * kP + i] : lin.a[i - kP];
+    scale[i] = 1.0 / (1.0 + std::sqrt(h));
+    diagonal[i] = std::sqrt(std::min(std::max(scale[i] * scale[i] * h, 1e-6), 1e32));
+  }
+  if (!schur_solve(pb, lin, scale, diagonal, mu, &y)) return 1;
+  std::copy(y.begin(), y.end(), y_out);
+  return 0;
+}
+
 // x^T Hs x  with Hs = S H S the scaled Gauss-Newton Hessian (== ||J_s x||^2)
 static double quad_form(const Problem &pb, const Linearization &lin, const std::vector<double> &scale,
                         const std::vector<double> &x) {

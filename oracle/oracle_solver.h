@@ -58,6 +58,9 @@ struct Problem {
 };
 
 int solve(const LfvioWindow &w, LfvioSolution *out);
+// The first ComputeGaussNewtonStep of solve() at a given mu: y[kP + N] of (Hs + mu D^2) y = gs at the window's state, with the
+// Jacobi scaling and diagonal_ of iteration 0.  Returns 0, or 1 if the Cholesky factorization failed.
+int schur_step(const LfvioWindow &w, double mu, double *y);
 
 // double2vector() gauge fix followed by vector2double() (estimator.cpp:532-600, 488-530)
 // pre: state before the solve; post (in/out): solved state -> re-anchored state.
