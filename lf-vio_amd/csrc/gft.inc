@@ -7,24 +7,6 @@
 // pyramid of klt.inc and is only read.  The base mask and the work arrays (lambda, final mask, candidates) are device memory of the
 // context's own, grow-only: no allocation once they have reached the image's size.
 
-struct GftWork {  // offsets in lfvio_ctx::GftState::work for one image size
-  size_t lam, keys, idx, mask, kxy, st, bytes, capacity;
-};
-static GftWork gft_work(int W, int H) {
-  GftWork o;
-  const size_t px = (size_t)W * H;
-  o.capacity = gft_capacity(W, H);
-  size_t end = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = end;
-    end = align_up(end + bytes, 256);
-    return at;
-  };
-  o.lam = take(px * 8), o.keys = take(o.capacity * 8), o.idx = take(o.capacity * 4), o.mask = take(px), o.kxy = take((size_t)GFT_LIST * 4);
-  o.st = take(sizeof(GftDev)), o.bytes = end;
-  return o;
-}
-
 static int gft_reserve(lfvio_ctx *c, const GftWork &wk) {
   return c->gft.work.reserve(wk.bytes) ? LFVIO_OK : out_of_memory(c, "out of memory (corner detection)");
 }
@@ -52,13 +34,10 @@ static int gft_launch_detect(lfvio_ctx *c, hipStream_t fs, const GftWork &wk, co
                      (const unsigned char *)(w + wk.mask), W, H, in->quality_level, MC, dev, ck, ci);
   HIPCHK(c, hipGetLastError());
   // the network of the arrays' capacity: the candidate count stays on the device, a stage beyond it returns at once (gft_plan.h)
-  const unsigned chunks = (unsigned)std::min<size_t>(wk.capacity / GFT_CHUNK, GFT_SORT_GRID), halves = (unsigned)std::min<size_t>(wk.capacity / 2 / GFT_THREADS, GFT_SORT_GRID);
-  hipLaunchKernelGGL(k_gft_sort_local, dim3(chunks), dim3(GFT_SORT_THREADS), 0, fs, (const GftDev *)dev, ck, ci, 0u);
-  for (size_t kk = 2 * (size_t)GFT_CHUNK; kk <= wk.capacity; kk *= 2) {
-    for (size_t j = kk / 2; j >= (size_t)GFT_CHUNK; j /= 2)
-      hipLaunchKernelGGL(k_gft_sort_global, dim3(halves), dim3(GFT_THREADS), 0, fs, (const GftDev *)dev, ck, ci, (unsigned)kk, (unsigned)j);
-    hipLaunchKernelGGL(k_gft_sort_local, dim3(chunks), dim3(GFT_SORT_THREADS), 0, fs, (const GftDev *)dev, ck, ci, (unsigned)kk);
-  }
+  const GftSortGrid sg = gft_sort_grid(wk.capacity);
+  gft_sort_stages(
+      wk.capacity, [&](unsigned kk) { hipLaunchKernelGGL(k_gft_sort_local, dim3(sg.chunks), dim3(GFT_SORT_THREADS), 0, fs, (const GftDev *)dev, ck, ci, kk); },
+      [&](unsigned kk, unsigned j) { hipLaunchKernelGGL(k_gft_sort_global, dim3(sg.halves), dim3(GFT_THREADS), 0, fs, (const GftDev *)dev, ck, ci, kk, j); });
   HIPCHK(c, hipGetLastError());
   hipLaunchKernelGGL(k_gft_pick, dim3(1), dim3(GFT_THREADS), 0, fs, (const GftDev *)dev, (const unsigned *)ci, W, in->min_distance, MC, corners, out);
   HIPCHK(c, hipGetLastError());
@@ -71,10 +50,10 @@ int lfvio_gft_detect(lfvio_ctx *c, const LfvioGftIn *in, int *kept, float *corne
     c->err = why;
     return LFVIO_ERR_ARG;
   }
-  const lfvio_ctx::KltState &k = c->klt;
+  const TrackStream &k = c->tstream;
   lfvio_ctx::GftState &g = c->gft;
   const int N = in->num_points, MC = in->max_count;
-  if ((N > 0 && !kept) || !k.valid || (g.mask_set && (g.mw != k.w || g.mh != k.h))) {
+  if ((N > 0 && !kept) || !k.valid || !k.mask_fits(k.w, k.h)) {
     c->err = "lfvio_gft_detect: null kept, no resident image, or a base mask that is not the resident image's size";
     return LFVIO_ERR_ARG;
   }
@@ -91,11 +70,11 @@ int lfvio_gft_detect(lfvio_ctx *c, const LfvioGftIn *in, int *kept, float *corne
     std::memcpy(h + oC, in->track_cnt, (size_t)N * 4);
     if (int rc = st.up(in_end)) return rc;
   }
-  const unsigned char *base = g.mask_set ? g.mask : nullptr;
+  const unsigned char *base = k.mask_set ? g.mask : nullptr;
   hipLaunchKernelGGL(k_gft_thin<int>, dim3(1), dim3(GFT_THREADS), 0, st.fs, N, (const float *)(d + oP), (const int *)(d + oC), base, W, H, in->mask_radius,
                      (GftDev *)(w + wk.st), (int *)(d + oK), (int *)(w + wk.kxy));
   HIPCHK(c, hipGetLastError());
-  if (int rc = gft_launch_detect(c, st.fs, wk, k.d[k.cur], W, H, base, in, (float *)(d + oX), (LfvioGftOut *)(d + oO))) return rc;
+  if (int rc = gft_launch_detect(c, st.fs, wk, c->klt.d[k.pcur], W, H, base, in, (float *)(d + oX), (LfvioGftOut *)(d + oO))) return rc;
   if (int rc = st.down(oK, st.end)) return rc;
   LfvioGftOut o;
   std::memcpy(&o, h + oO, sizeof o);
@@ -109,10 +88,10 @@ int lfvio_gft_set_mask(lfvio_ctx *c, int width, int height, const unsigned char 
   if (!c) return LFVIO_ERR_ARG;
   lfvio_ctx::GftState &g = c->gft;
   if (!pixels) {
-    g.mask_set = false;
+    c->tstream.mask_cleared();
     return LFVIO_OK;
   }
-  if (const char *why = gft_mask_check(width, height, c->klt.valid ? c->klt.w : 0, c->klt.h)) {
+  if (const char *why = gft_mask_check(width, height, c->tstream.resident_w(), c->tstream.h)) {
     c->err = why;
     return LFVIO_ERR_ARG;
   }
@@ -124,28 +103,29 @@ int lfvio_gft_set_mask(lfvio_ctx *c, int width, int height, const unsigned char 
     DevBuf<unsigned char> fresh;
     if (!fresh.reserve(n)) return out_of_memory(c, "out of memory (base mask)");
     HIPCHK(c, hipStreamSynchronize(st.fs));
-    g.mask = std::move(fresh), g.mask_set = false;
+    g.mask = std::move(fresh), c->tstream.mask_cleared();
   }
   std::memcpy(st.h + oM, pixels, n);
   if (int rc = st.up(st.end)) return rc;
   HIPCHK(c, hipMemcpyAsync(g.mask, st.d + oM, n, hipMemcpyDeviceToDevice, st.fs));
   HIPCHK(c, hipStreamSynchronize(st.fs));
-  g.mw = width, g.mh = height, g.mask_set = true;
+  c->tstream.mask_is(width, height);
   return LFVIO_OK;
 }
 
 int lfvio_gft_response(lfvio_ctx *c, double *response) {
   if (!c || !response) return LFVIO_ERR_ARG;
-  if (!c->klt.valid) {
+  const TrackStream &k = c->tstream;
+  if (!k.valid) {
     c->err = "lfvio_gft_response: no resident image";
     return LFVIO_ERR_ARG;
   }
-  const GftWork wk = gft_work(c->klt.w, c->klt.h);
+  const GftWork wk = gft_work(k.w, k.h);
   FeatStage st(c);
   if (int rc = gft_reserve(c, wk)) return rc;
   HIPCHK(c, hipMemsetAsync(c->gft.work + wk.st, 0, sizeof(GftDev), st.fs));  // no kept points
-  if (int rc = gft_launch_response(c, st.fs, wk, c->klt.d[c->klt.cur], c->klt.w, c->klt.h, nullptr, 0, 1)) return rc;
-  HIPCHK(c, hipMemcpyAsync(response, c->gft.work + wk.lam, (size_t)c->klt.w * c->klt.h * 8, hipMemcpyDeviceToHost, st.fs));
+  if (int rc = gft_launch_response(c, st.fs, wk, c->klt.d[k.pcur], k.w, k.h, nullptr, 0, 1)) return rc;
+  HIPCHK(c, hipMemcpyAsync(response, c->gft.work + wk.lam, (size_t)k.w * k.h * 8, hipMemcpyDeviceToHost, st.fs));
   HIPCHK(c, hipStreamSynchronize(st.fs));
   return LFVIO_OK;
 }

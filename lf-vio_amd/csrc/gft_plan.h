@@ -1,5 +1,6 @@
 // gft_plan.h — the host-side plan of lfvio_gft_detect / lfvio_gft_set_mask (include/lfvio.h): the argument checks and the sizes of
-// the candidate sort.  Plain C++ (no HIP): gft.inc uses it, tests/test_gft_ref.py compiles it alone with g++.
+// the candidate sort, its launches and the work arrays.  Plain C++ (no HIP): gft.inc, trackframe.inc and trackbatch.inc use it,
+// tests/test_gft_ref.py compiles it alone with g++.
 #pragma once
 #include <cstddef>
 
@@ -7,6 +8,9 @@
 
 constexpr int GFT_MAX_DIST = 1024;   // of min_distance and mask_radius
 constexpr int GFT_CHUNK = 4096;      // candidates one workgroup orders in LDS (k_gft_sort_local)
+constexpr int GFT_THREADS = 256;     // a workgroup of every kernel but k_gft_sort_local
+constexpr int GFT_SORT_GRID = 512;   // workgroups of a launch of the sort network, at most
+constexpr int GFT_LIST = LFVIO_GFT_MAX_CORNERS;  // of the kept points and of the accepted corners (= LFVIO_KLT_MAX_POINTS)
 
 // nullptr, or what is wrong with the fields of *in (the pointers for the outputs are the entry's to check)
 inline const char *gft_check(const LfvioGftIn *in) {
@@ -35,13 +39,55 @@ inline size_t gft_capacity(int width, int height) {
   return p;
 }
 
-// launches of the bitonic network over `capacity` entries: one k_gft_sort_local for the stages inside a chunk, then per stage
-// k = 2 GFT_CHUNK .. capacity one k_gft_sort_global per distance j = k / 2 .. GFT_CHUNK and one k_gft_sort_local for the rest
-inline int gft_sort_launches(size_t capacity) {
-  int n = 1;
+// The bitonic network over `capacity` entries, launch by launch: local(0) for the stages inside a chunk, then per stage
+// k = 2 GFT_CHUNK .. capacity one global(k, j) per distance j = k / 2 .. GFT_CHUNK and one local(k) for the rest.  The single route
+// launches k_gft_sort_local / _global from it, the batched route their _b variants.
+template <class Local, class Global>
+inline void gft_sort_stages(size_t capacity, Local local, Global global) {
+  local(0u);
   for (size_t k = 2 * (size_t)GFT_CHUNK; k <= capacity; k *= 2) {
-    for (size_t j = k / 2; j >= (size_t)GFT_CHUNK; j /= 2) n++;
-    n++;
+    for (size_t j = k / 2; j >= (size_t)GFT_CHUNK; j /= 2) global((unsigned)k, (unsigned)j);
+    local((unsigned)k);
   }
+}
+inline int gft_sort_launches(size_t capacity) {
+  int n = 0;
+  gft_sort_stages(capacity, [&](unsigned) { n++; }, [&](unsigned, unsigned) { n++; });
   return n;
+}
+// ... and the grids of the two kernels: at most GFT_SORT_GRID workgroups each, which stride over the padded candidate count
+struct GftSortGrid {
+  unsigned chunks, halves;  // of k_gft_sort_local (a chunk per workgroup) and k_gft_sort_global (a pair per thread)
+};
+inline GftSortGrid gft_sort_grid(size_t capacity) {
+  const size_t chunks = capacity / GFT_CHUNK, halves = capacity / 2 / GFT_THREADS;
+  return GftSortGrid{(unsigned)(chunks < (size_t)GFT_SORT_GRID ? chunks : (size_t)GFT_SORT_GRID), (unsigned)(halves < (size_t)GFT_SORT_GRID ? halves : (size_t)GFT_SORT_GRID)};
+}
+
+// The detector's work arrays of one image size, one block: lambda, the candidates' keys and indices, the final mask, the kept
+// pixels, GftDev.  GftOffsets is what a kernel of the batched route takes by value, beside the block's base.
+struct GftDev {  // one call's state on the device
+  unsigned long long max_bits;  // of the largest lambda under the final mask; 0: none
+  int num_kept, num_cand;
+};
+struct GftOffsets {
+  size_t lam, keys, idx, mask, kxy, st;
+};
+static_assert(sizeof(GftOffsets) == 48, "a kernel argument: six offsets");
+struct GftWork : GftOffsets {
+  size_t bytes, capacity;
+};
+inline GftWork gft_work(int W, int H) {
+  GftWork o;
+  const size_t px = (size_t)W * H;
+  o.capacity = gft_capacity(W, H);
+  size_t end = 0;
+  auto take = [&](size_t bytes) {
+    const size_t at = end;
+    end = (end + bytes + 255) / 256 * 256;
+    return at;
+  };
+  o.lam = take(px * 8), o.keys = take(o.capacity * 8), o.idx = take(o.capacity * 4), o.mask = take(px), o.kxy = take((size_t)GFT_LIST * 4);
+  o.st = take(sizeof(GftDev)), o.bytes = end;
+  return o;
 }

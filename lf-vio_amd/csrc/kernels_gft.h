@@ -24,18 +24,12 @@
 #include "gft_plan.h"
 #include "kernels_klt.h"
 
-constexpr int GFT_THREADS = 256, GFT_TX = 32, GFT_TY = 8;
+constexpr int GFT_TX = 32, GFT_TY = 8;  // (GFT_THREADS, GFT_SORT_GRID, GFT_LIST and GftDev: gft_plan.h)
 constexpr int GFT_RAW_W = GFT_TX + 4, GFT_RAW_H = GFT_TY + 4, GFT_PRD_W = GFT_TX + 2, GFT_PRD_H = GFT_TY + 2;
-constexpr int GFT_SORT_THREADS = 512, GFT_SORT_GRID = 512;
+constexpr int GFT_SORT_THREADS = 512;
 constexpr int GFT_CAND_ROWS = 8;  // rows of 256 pixels per workgroup of k_gft_cand
-constexpr int GFT_LIST = LFVIO_GFT_MAX_CORNERS;  // of the kept points and of the accepted corners (= LFVIO_KLT_MAX_POINTS)
 static_assert(LFVIO_GFT_MAX_CORNERS == LFVIO_KLT_MAX_POINTS, "one list length for both greedy passes");
 static_assert(GFT_TX * GFT_TY == GFT_THREADS, "a pixel per thread");
-
-struct GftDev {  // one call's state on the device
-  unsigned long long max_bits;  // of the largest lambda under the final mask; 0: none
-  int num_kept, num_cand;
-};
 
 // a pixel as one int: y << 16 | x (both < 8192); negative: no pixel
 DEV int gft_pack(int x, int y) { return y << 16 | x; }

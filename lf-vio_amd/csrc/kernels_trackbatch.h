@@ -17,15 +17,7 @@
 #include "kernels_trackframe.h"
 #include "trackbatch_plan.h"
 
-constexpr size_t TB_MAP_IDS = (size_t)LFVIO_TRACK_MAX_POINTS * 4;  // the ids of a map, the un_pts_3d behind them
 constexpr int TB_COPY_THREADS = 256, TB_COPY_BYTES = TB_COPY_THREADS * 16;
-
-struct TbWork {  // offsets of the detector's arrays in TbSlot::work (GftWork of gft.inc)
-  size_t lam, keys, idx, mask, kxy, st;
-};
-
-// [n][2] floats | n ids | n counts at p
-__host__ __device__ inline TfTable tb_table(char *p, size_t n) { return TfTable{(float *)p, (int *)(p + n * 8), (int *)(p + n * 12)}; }
 
 // This workgroup's slot: the descriptor's numbers (scalar loads: the index is uniform) and the slot's pointers, every one formed
 // from a pointer ARGUMENT of the kernel — the compiler knows them to be global memory, as it knows the single kernels' arguments,
@@ -115,9 +107,9 @@ __global__ __launch_bounds__(KLT_THREADS) void k_klt_track_b(const TbSlot *slots
 __global__ __launch_bounds__(TF_THREADS) void k_tf_flow_b(const TbSlot *slots, TbMem m, TbStage o, int n0_max, int S) {
   const TbView s = tb_view(slots, m, o);
   if (!s.active) return;
-  const TfTable have = tb_table(s.have, LFVIO_TRACK_MAX_POINTS);
+  const TfTable have = tf_table(s.have, LFVIO_TRACK_MAX_POINTS);
   tf_flow_body(s.n0, (const unsigned char *)(s.mid + o.status), have.pts, (const float *)(s.mid + o.next), have.ids, have.cnt, (float *)(s.mid + o.c1),
-               tb_table(s.mid + o.t1, n0_max), (TfDev *)(s.down + o.dev), S, s.publish ? s.words : nullptr, (int *)(s.mid + o.samples));
+               tf_table(s.mid + o.t1, n0_max), (TfDev *)(s.down + o.dev), S, s.publish ? s.words : nullptr, (int *)(s.mid + o.samples));
 }
 __global__ __launch_bounds__(TRK_THREADS) void k_trk_lift_b(const TbSlot *slots, TbMem m, TbStage o) {
   const TbView s = tb_view(slots, m, o);
@@ -145,40 +137,40 @@ __global__ __launch_bounds__(TV_FIT_THREADS) void k_trk_fit_b(const TbSlot *slot
 __global__ __launch_bounds__(TF_THREADS) void k_tf_reject_b(const TbSlot *slots, TbMem m, TbStage o, int n0_max) {
   const TbView s = tb_view(slots, m, o);
   if (!s.active || !s.publish) return;
-  tf_reject_body((const unsigned char *)(s.mid + o.mask), tb_table(s.mid + o.t1, n0_max), tb_table(s.mid + o.t2, n0_max), (TfDev *)(s.down + o.dev));
+  tf_reject_body((const unsigned char *)(s.mid + o.mask), tf_table(s.mid + o.t1, n0_max), tf_table(s.mid + o.t2, n0_max), (TfDev *)(s.down + o.dev));
 }
 
 // ---- setMask and goodFeaturesToTrack on level 0 of the fresh pyramid
-__global__ __launch_bounds__(GFT_THREADS) void k_gft_thin_b(const TbSlot *slots, TbMem m, TbStage o, TbWork wk, int n0_max, int W, int H, int r) {
+__global__ __launch_bounds__(GFT_THREADS) void k_gft_thin_b(const TbSlot *slots, TbMem m, TbStage o, GftOffsets wk, int n0_max, int W, int H, int r) {
   const TbView s = tb_view(slots, m, o);
   if (!s.active || !s.publish) return;
-  const TfTable t2 = tb_table(s.mid + o.t2, n0_max);
+  const TfTable t2 = tf_table(s.mid + o.t2, n0_max);
   gft_thin_body(((const TfDev *)(s.down + o.dev))->n2, t2.pts, t2.cnt, s.base, W, H, r, (GftDev *)(s.work + wk.st), (int *)(s.mid + o.kept),
                 (int *)(s.work + wk.kxy));
 }
-__global__ __launch_bounds__(GFT_THREADS) void k_gft_response_b(const TbSlot *slots, TbMem m, TbStage o, TbWork wk, int W, int H, int r, int max_count) {
+__global__ __launch_bounds__(GFT_THREADS) void k_gft_response_b(const TbSlot *slots, TbMem m, TbStage o, GftOffsets wk, int W, int H, int r, int max_count) {
   const TbView s = tb_view(slots, m, o);
   if (!s.active || !s.publish) return;
   gft_response_body(s.fresh, W, H, s.base, (const int *)(s.work + wk.kxy), r, max_count, (GftDev *)(s.work + wk.st), (double *)(s.work + wk.lam),
                     (unsigned char *)(s.work + wk.mask));
 }
-__global__ __launch_bounds__(GFT_THREADS) void k_gft_cand_b(const TbSlot *slots, TbMem m, TbStage o, TbWork wk, int W, int H, double quality, int max_count) {
+__global__ __launch_bounds__(GFT_THREADS) void k_gft_cand_b(const TbSlot *slots, TbMem m, TbStage o, GftOffsets wk, int W, int H, double quality, int max_count) {
   const TbView s = tb_view(slots, m, o);
   if (!s.active || !s.publish) return;
   gft_cand_body((const double *)(s.work + wk.lam), (const unsigned char *)(s.work + wk.mask), W, H, quality, max_count, (GftDev *)(s.work + wk.st),
                 (unsigned long long *)(s.work + wk.keys), (unsigned *)(s.work + wk.idx));
 }
-__global__ __launch_bounds__(GFT_SORT_THREADS) void k_gft_sort_local_b(const TbSlot *slots, TbMem m, TbStage o, TbWork wk, unsigned stage) {
+__global__ __launch_bounds__(GFT_SORT_THREADS) void k_gft_sort_local_b(const TbSlot *slots, TbMem m, TbStage o, GftOffsets wk, unsigned stage) {
   const TbView s = tb_view(slots, m, o);
   if (!s.active || !s.publish) return;
   gft_sort_local_body((const GftDev *)(s.work + wk.st), (unsigned long long *)(s.work + wk.keys), (unsigned *)(s.work + wk.idx), stage);
 }
-__global__ __launch_bounds__(GFT_THREADS) void k_gft_sort_global_b(const TbSlot *slots, TbMem m, TbStage o, TbWork wk, unsigned k, unsigned j) {
+__global__ __launch_bounds__(GFT_THREADS) void k_gft_sort_global_b(const TbSlot *slots, TbMem m, TbStage o, GftOffsets wk, unsigned k, unsigned j) {
   const TbView s = tb_view(slots, m, o);
   if (!s.active || !s.publish) return;
   gft_sort_global_body((const GftDev *)(s.work + wk.st), (unsigned long long *)(s.work + wk.keys), (unsigned *)(s.work + wk.idx), k, j);
 }
-__global__ __launch_bounds__(GFT_THREADS) void k_gft_pick_b(const TbSlot *slots, TbMem m, TbStage o, TbWork wk, int W, int d, int max_count) {
+__global__ __launch_bounds__(GFT_THREADS) void k_gft_pick_b(const TbSlot *slots, TbMem m, TbStage o, GftOffsets wk, int W, int d, int max_count) {
   const TbView s = tb_view(slots, m, o);
   if (!s.active || !s.publish) return;
   gft_pick_body((const GftDev *)(s.work + wk.st), (const unsigned *)(s.work + wk.idx), W, d, max_count, (float *)(s.mid + o.corners),
@@ -189,8 +181,8 @@ __global__ __launch_bounds__(GFT_THREADS) void k_gft_pick_b(const TbSlot *slots,
 __global__ __launch_bounds__(TF_THREADS) void k_tf_finish_b(const TbSlot *slots, TbMem m, TbStage o, int n0_max, int B_max) {
   const TbView s = tb_view(slots, m, o);
   if (!s.active) return;
-  tf_finish_body(s.publish, tb_table(s.mid + (s.publish ? o.t2 : o.t1), n0_max), (const int *)(s.mid + o.kept), (const float *)(s.mid + o.corners), s.n_id,
-                 tb_table(s.next, LFVIO_TRACK_MAX_POINTS), tb_table(s.down + o.table, B_max), (int *)(s.mid + o.raw), (TfDev *)(s.down + o.dev));
+  tf_finish_body(s.publish, tf_table(s.mid + (s.publish ? o.t2 : o.t1), n0_max), (const int *)(s.mid + o.kept), (const float *)(s.mid + o.corners), s.n_id,
+                 tf_table(s.next, LFVIO_TRACK_MAX_POINTS), tf_table(s.down + o.table, B_max), (int *)(s.mid + o.raw), (TfDev *)(s.down + o.dev));
 }
 __global__ __launch_bounds__(TRK_THREADS) void k_trk_undist_b(const TbSlot *slots, TbMem m, TbStage o) {
   __shared__ int sid[LFVIO_TRACK_MAX_POINTS];
@@ -199,12 +191,12 @@ __global__ __launch_bounds__(TRK_THREADS) void k_trk_undist_b(const TbSlot *slot
   const int N = ((const TfDev *)(s.down + o.dev))->num_points;
   if ((int)(blockIdx.x * TRK_THREADS) >= N) return;
   trk_undist_body(*s.cam, N, (const float *)(s.down + o.table), (const int *)(s.mid + o.raw), s.dt, s.prev_count, (const int *)s.prev_map,
-                  (const float *)(s.prev_map + TB_MAP_IDS), (float *)(s.down + o.un), (float *)(s.down + o.un3d), (float *)(s.down + o.vel),
-                  (int *)(s.mid + o.matched), (int *)s.next_map, (float *)(s.next_map + TB_MAP_IDS), sid);
+                  (const float *)(s.prev_map + TRACK_MAP_IDS), (float *)(s.down + o.un), (float *)(s.down + o.un3d), (float *)(s.down + o.vel),
+                  (int *)(s.mid + o.matched), (int *)s.next_map, (float *)(s.next_map + TRACK_MAP_IDS), sid);
 }
 __global__ __launch_bounds__(TF_THREADS) void k_tf_message_b(const TbSlot *slots, TbMem m, TbStage o, int B_max) {
   const TbView s = tb_view(slots, m, o);
   if (!s.active || !s.publish) return;
-  tf_message_body((const TfDev *)(s.down + o.dev), B_max, tb_table(s.down + o.table, B_max), (const float *)(s.down + o.un3d), (const float *)(s.down + o.vel),
+  tf_message_body((const TfDev *)(s.down + o.dev), B_max, tf_table(s.down + o.table, B_max), (const float *)(s.down + o.un3d), (const float *)(s.down + o.vel),
                   (int *)(s.down + o.msg), (float *)(s.down + o.msg + TF_MSG_HEAD));
 }

@@ -27,17 +27,13 @@
 constexpr int TF_THREADS = 256, TF_PER = LFVIO_TRACK_MAX_POINTS / TF_THREADS;
 static_assert(TF_PER * TF_THREADS == LFVIO_TRACK_MAX_POINTS && LFVIO_TRACK_MAX_POINTS == LFVIO_KLT_MAX_POINTS, "one thread, TF_PER entries");
 
-struct TfDev {  // one call's counts and records on the device; the head of the block that goes down
-  int n1, n2, num_points, num_new;
-  LfvioTrackRejectOut reject;  // k_trk_fit_n
-  LfvioGftOut detect;          // k_gft_pick
-};
-
-// a table as three arrays: [n][2] floats, ids, counts
+// a table as three arrays: [n][2] floats, ids, counts.  (TfDev, the counts every kernel here reads and writes: trackframe_plan.h)
 struct TfTable {
   float *pts;
   int *ids, *cnt;
 };
+// [n][2] floats | n ids | n counts at p
+__host__ __device__ inline TfTable tf_table(char *p, size_t n) { return TfTable{(float *)p, (int *)(p + n * 8), (int *)(p + n * 12)}; }
 
 // Exclusive scan of v over the workgroup (Hillis-Steele on two rows of LDS); total: the sum, in every thread.
 DEV int tf_scan(int v, int (*s)[TF_THREADS], int &total) {

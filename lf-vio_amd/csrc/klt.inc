@@ -20,29 +20,24 @@ static int klt_build(lfvio_ctx *c, hipStream_t fs, unsigned char *pyr, const Klt
 
 // The image at d_image (device, W x H) into the context's other pyramid buffer — a copy, or CLAHE while it is on — with the levels
 // 1 .. LU, and the levels of the resident pyramid that an earlier call did not build.  *prev: the pyramid to track from (the new one
-// when none of this size is resident, :111-114).  Returns the new pyramid, which the caller makes resident with klt_commit once the
+// when none of this size is resident, :111-114).  Returns the new pyramid, which the caller makes resident with a commit of the stream once the
 // call has succeeded.  (Every earlier call on the feature stream has been waited for: nobody reads the other buffer.)
 static int klt_pyramid(lfvio_ctx *c, hipStream_t fs, const unsigned char *d_image, int W, int H, const KltPlan &full, int LU,
                        const unsigned char **prev, unsigned char **fresh_out) {
-  lfvio_ctx::KltState &k = c->klt;
-  unsigned char *fresh = k.d[1 - k.cur];
+  TrackStream &s = c->tstream;
+  unsigned char *fresh = c->klt.d[1 - s.pcur], *resident = c->klt.d[s.pcur];
   if (c->clahe.on) {  // the equalized image is the image: k_clahe_map writes level 0 (clahe.inc)
     if (int rc = clahe_run(c, fs, c->clahe.cfg, W, H, d_image, fresh, nullptr)) return rc;
   } else {
     HIPCHK(c, hipMemcpyAsync(fresh, d_image, (size_t)W * H, hipMemcpyDeviceToDevice, fs));
   }
   if (int rc = klt_build(c, fs, fresh, full, 0, LU)) return rc;
-  const bool same = k.valid && k.w == W && k.h == H;  // otherwise the new image is both images (:111-114)
-  if (same && k.built < LU) {  // (an earlier call asked for fewer levels: a level is a function of the one below)
-    if (int rc = klt_build(c, fs, k.d[k.cur], full, k.built, LU)) return rc;
-    k.built = LU;
+  if (s.levels_missing(W, H, LU)) {  // (an earlier call asked for fewer levels)
+    if (int rc = klt_build(c, fs, resident, full, s.built, LU)) return rc;
+    s.resident_built(LU);
   }
-  *prev = same ? (const unsigned char *)k.d[k.cur] : fresh, *fresh_out = fresh;
+  *prev = s.resident(W, H) ? (const unsigned char *)resident : fresh, *fresh_out = fresh;  // otherwise the new image is both images (:111-114)
   return LFVIO_OK;
-}
-static void klt_commit(lfvio_ctx *c, int W, int H, int LU) {
-  lfvio_ctx::KltState &k = c->klt;
-  k.cur = 1 - k.cur, k.w = W, k.h = H, k.built = LU, k.valid = true;
 }
 static KltArgs klt_args(const LfvioKltIn *in, const KltPlan &full, int LU) {
   KltArgs a;
@@ -61,14 +56,13 @@ int lfvio_klt_track(lfvio_ctx *c, const LfvioKltIn *in, float *next_pts, unsigne
   const int N = in->num_points, W = in->width, H = in->height, ML = in->max_level;
   const KltPlan p = klt_plan(W, H, in->win_size, ML), full = klt_plan(W, H, 0, LFVIO_KLT_MAX_LEVEL);
   const int LU = p.levels_used;
-  lfvio_ctx::KltState &k = c->klt;
   FeatStage st(c);
   const size_t nI = (size_t)W * H, nT = (size_t)N * (ML + 1) * 4;
   const size_t oP = st.take((size_t)N * 8), oI = st.take(nI), in_end = st.end;
   const size_t oN = st.take((size_t)N * 8), oS = st.take((size_t)N), oT = st.take(nT);
   if (int rc = st.reserve()) return rc;
-  const int nb = 1 - k.cur;  // (every earlier call on the feature stream has been waited for: nobody reads this buffer)
-  if (!k.d[nb].reserve(full.bytes)) return out_of_memory(c, "out of memory (image pyramid)");
+  // (every earlier call on the feature stream has been waited for: nobody reads the other buffer)
+  if (!c->klt.d[1 - c->tstream.pcur].reserve(full.bytes)) return out_of_memory(c, "out of memory (image pyramid)");
   char *d = st.d, *h = st.h;
   if (N) std::memcpy(h + oP, in->prev_pts, (size_t)N * 8);
   std::memcpy(h + oI, in->image, nI);
@@ -93,19 +87,19 @@ int lfvio_klt_track(lfvio_ctx *c, const LfvioKltIn *in, float *next_pts, unsigne
     for (int i = 0; i < N; i++) tracked += status[i] != 0;
   }
   out->levels_used = LU, out->num_tracked = tracked;
-  klt_commit(c, W, H, LU);
+  c->tstream.commit_flow(W, H, LU);
   return LFVIO_OK;
 }
 
 int lfvio_klt_reset(lfvio_ctx *c) {
   if (!c) return LFVIO_ERR_ARG;
-  c->klt.valid = false;
+  c->tstream.reset_flow();
   return LFVIO_OK;
 }
 
 int lfvio_klt_level(lfvio_ctx *c, int level, int *width, int *height, unsigned char *pixels) {
   if (!c || !width || !height) return LFVIO_ERR_ARG;
-  const lfvio_ctx::KltState &k = c->klt;
+  const TrackStream &k = c->tstream;
   if (!k.valid || level < 0 || level > k.built) {
     c->err = "lfvio_klt_level: no resident image, or a level that is not built";
     return LFVIO_ERR_ARG;
@@ -113,7 +107,7 @@ int lfvio_klt_level(lfvio_ctx *c, int level, int *width, int *height, unsigned c
   const KltPlan full = klt_plan(k.w, k.h, 0, LFVIO_KLT_MAX_LEVEL);
   if (pixels) {
     FeatStage st(c);
-    HIPCHK(c, hipMemcpyAsync(pixels, k.d[k.cur] + full.off[level], (size_t)full.w[level] * full.h[level], hipMemcpyDeviceToHost, st.fs));
+    HIPCHK(c, hipMemcpyAsync(pixels, c->klt.d[k.pcur] + full.off[level], (size_t)full.w[level] * full.h[level], hipMemcpyDeviceToHost, st.fs));
     HIPCHK(c, hipStreamSynchronize(st.fs));
   }
   *width = full.w[level], *height = full.h[level];

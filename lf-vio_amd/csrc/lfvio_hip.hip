@@ -172,18 +172,17 @@ struct lfvio_ctx : CtxQueues {
   int device = 0;
   DevBuf<char> d_feat;  // scratch of lfvio_triangulate / lfvio_shift_depth
   PinBuf<char> h_feat;  // pinned mirror of d_feat: the inputs of a feature step go up as ONE copy, its outputs come down as one
-  // lfvio_klt_track (klt.inc): two pyramid buffers of their own; `cur` holds the resident image's levels 0 .. built
+  // The single route's image stream (track_stream.h): which of each pair of buffers below is the resident one and what it holds.
+  // Every separate tracker call and lfvio_track_frame move it; the buffers stay with the call that introduced them.
+  TrackStream tstream;
+  // lfvio_klt_track (klt.inc): two pyramid buffers of their own; tstream.pcur holds the resident image's levels 0 .. tstream.built
   struct KltState {
     DevBuf<unsigned char> d[2];
-    int cur = 0, w = 0, h = 0, built = 0;
-    bool valid = false;
   } klt;
   // lfvio_gft_detect (gft.inc): the base mask (all 255 until lfvio_gft_set_mask; survives lfvio_klt_reset) and the work arrays of one
   // image size (lambda, final mask, candidates, kept pixels, GftDev)
   struct GftState {
     DevBuf<unsigned char> mask;
-    int mw = 0, mh = 0;
-    bool mask_set = false;
     DevBuf<char> work;
   } gft;
   // lfvio_clahe_set / lfvio_clahe_apply (clahe.inc): the setting (off after lfvio_create; survives lfvio_klt_reset) and the
@@ -195,33 +194,21 @@ struct lfvio_ctx : CtxQueues {
     bool dirty = false;
   } clahe;
   // lfvio_track_undistort (track.inc): the (id, un_pts_3d) pairs of the previous call — [4096 ints | 4096 x 3 floats] twice, allocated
-  // at the first use; `cur` holds the `count` resident pairs (0: the map is empty), `time` is that call's
+  // at the first use; tstream.mcur holds the tstream.mcount resident pairs (0: the map is empty), tstream.time is that call's
   struct TrackState {
     DevBuf<char> map[2];
-    int cur = 0, count = 0;
-    double time = 0.0;
   } track;
   // lfvio_track_frame (trackframe.inc): the track table — [4096 x 2 floats | 4096 ids | 4096 counts] twice, allocated at the first
-  // use; `cur` holds the `count` resident entries, n_id is the next id to hand out
+  // use; tstream.tcur holds the tstream.count resident entries, tstream.n_id is the next id to hand out
   struct TrackFrameState {
     DevBuf<char> table[2];
-    int cur = 0, count = 0, n_id = 0;
   } tframe;
-  // lfvio_track_batch_* (trackbatch.inc): `slot.size()` independent streams, each with what the five states above hold for the single
-  // route.  fixed: per slot two track tables and two maps (TB_FIXED_BYTES); image: per slot [pyramid | pyramid | base mask | detector's
+  // lfvio_track_batch_* (trackbatch.inc): `slot.size()` independent streams, each a TrackStream as the single route's.  fixed: per slot
+  // two track tables and two maps (TB_FIXED_BYTES); image: per slot [pyramid | pyramid | base mask | detector's
   // arrays] with the capacities of `lay` (trackbatch_plan.h), allocated at the first frame or mask; clahe: per slot the int table and
   // the LUTs, allocated at the first frame with the setting on.  None of it is the single route's, and the single route's is none of it.
   struct TrackBatchState {
-    struct Slot {
-      int pcur = 0, w = 0, h = 0, built = 0;  // the pyramid buffers, as KltState
-      bool valid = false;
-      int mw = 0, mh = 0;                     // the base mask, as GftState
-      bool mask_set = false;
-      int tcur = 0, count = 0, n_id = 0;      // the track table, as TrackFrameState
-      int mcur = 0, mcount = 0;               // the (id, un_pts_3d) map, as TrackState
-      double time = 0.0;
-    };
-    std::vector<Slot> slot;
+    std::vector<TrackStream> slot;
     DevBuf<char> fixed, image, clahe;
     TbImage lay = {0, 0, 0};
     bool clahe_on = false, clahe_dirty = false;

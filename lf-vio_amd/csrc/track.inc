@@ -6,10 +6,8 @@
 // match, where lfvio_two_view takes 48), one copy up, k_trk_lift, k_tv_hyp (grid S), k_trk_fit (one workgroup), one copy down of
 // [LfvioTrackRejectOut | status | bearings] as far as the caller asked.
 // lfvio_track_undistort: [pts | ids] up, k_trk_undist, [un_pts | un_pts_3d | velocity_3d | matched] down.  The (id, un_pts_3d) pairs
-// live in two buffers of the context's own; the kernel reads `cur` and writes the other, and the host swaps them when the call has
+// live in two buffers of the context's own; the kernel reads the stream's `mcur` and writes the other, and the host swaps them when the call has
 // succeeded: a refused or failed call leaves the resident map and time as they were.
-
-constexpr size_t TRACK_MAP_IDS = (size_t)LFVIO_TRACK_MAX_POINTS * 4, TRACK_MAP_BYTES = TRACK_MAP_IDS + (size_t)LFVIO_TRACK_MAX_POINTS * 12;
 
 int lfvio_track_reject(lfvio_ctx *c, const LfvioTrackRejectIn *in, unsigned char *status, LfvioTrackRejectOut *out, double *bearing_cur,
                        double *bearing_forw) {
@@ -47,11 +45,7 @@ int lfvio_track_reject(lfvio_ctx *c, const LfvioTrackRejectIn *in, unsigned char
                      (LfvioTrackRejectOut *)(d + oO));
   HIPCHK(c, hipGetLastError());
   if (int rc = st.down(oO, bearing_cur || bearing_forw ? st.end : oM + (size_t)N)) return rc;
-  const LfvioTrackRejectOut *o = (const LfvioTrackRejectOut *)(h + oO);
-  if (o->status == 0)
-    *out = *o;
-  else  // no model: E stays as the caller had it
-    out->status = o->status, out->best_sample = o->best_sample, out->num_inliers = o->num_inliers, out->best_score = o->best_score;
+  track_reject_copy(out, *(const LfvioTrackRejectOut *)(h + oO));  // no model: E stays as the caller had it
   std::memcpy(status, h + oM, (size_t)N);
   if (bearing_cur) std::memcpy(bearing_cur, h + oL, (size_t)N * 24);
   if (bearing_forw) std::memcpy(bearing_forw, h + oR, (size_t)N * 24);
@@ -69,9 +63,9 @@ int lfvio_track_undistort(lfvio_ctx *c, const LfvioTrackUndistortIn *in, float *
     c->err = "lfvio_track_undistort: null outputs";
     return LFVIO_ERR_ARG;
   }
-  lfvio_ctx::TrackState &t = c->track;
+  TrackStream &t = c->tstream;
   if (N == 0) {  // an empty map (:462): the next call's velocities are all 0
-    t.count = 0, t.time = in->time;
+    t.commit_undistort(0, in->time);
     return LFVIO_OK;
   }
   const TrackCam cam = track_cam(*in->camera);
@@ -79,16 +73,16 @@ int lfvio_track_undistort(lfvio_ctx *c, const LfvioTrackUndistortIn *in, float *
   const size_t oP = st.take((size_t)N * 8), oI = st.take((size_t)N * 4), in_end = st.end;
   const size_t oU = st.take((size_t)N * 8), o3 = st.take((size_t)N * 12), oV = st.take((size_t)N * 12), oM = st.take((size_t)N * 4);
   if (int rc = st.reserve()) return rc;
-  for (auto &m : t.map)
+  for (auto &m : c->track.map)
     if (!m.reserve(TRACK_MAP_BYTES)) return out_of_memory(c, "out of memory (track map)");
   char *d = st.d, *h = st.h;
   std::memcpy(h + oP, in->pts, (size_t)N * 8);
   std::memcpy(h + oI, in->ids, (size_t)N * 4);
   if (int rc = st.up(in_end)) return rc;
-  const char *prev = t.map[t.cur];
-  char *next = t.map[1 - t.cur];
+  const char *prev = c->track.map[t.mcur];
+  char *next = c->track.map[1 - t.mcur];
   hipLaunchKernelGGL(k_trk_undist, dim3((N + TRK_THREADS - 1) / TRK_THREADS), dim3(TRK_THREADS), 0, st.fs, cam, N, (const float *)(d + oP),
-                     (const int *)(d + oI), in->time - t.time, t.count, (const int *)prev, (const float *)(prev + TRACK_MAP_IDS), (float *)(d + oU),
+                     (const int *)(d + oI), in->time - t.time, t.mcount, (const int *)prev, (const float *)(prev + TRACK_MAP_IDS), (float *)(d + oU),
                      (float *)(d + o3), (float *)(d + oV), (int *)(d + oM), (int *)next, (float *)(next + TRACK_MAP_IDS));
   HIPCHK(c, hipGetLastError());
   if (int rc = st.down(oU, st.end)) return rc;
@@ -96,12 +90,12 @@ int lfvio_track_undistort(lfvio_ctx *c, const LfvioTrackUndistortIn *in, float *
   std::memcpy(un_pts_3d, h + o3, (size_t)N * 12);
   std::memcpy(velocity_3d, h + oV, (size_t)N * 12);
   if (matched) std::memcpy(matched, h + oM, (size_t)N * 4);
-  t.cur = 1 - t.cur, t.count = N, t.time = in->time;
+  t.commit_undistort(N, in->time);
   return LFVIO_OK;
 }
 
 int lfvio_track_reset(lfvio_ctx *c) {
   if (!c) return LFVIO_ERR_ARG;
-  c->track.count = 0, c->track.time = 0.0;
+  c->tstream.reset_map();
   return LFVIO_OK;
 }

@@ -5,10 +5,25 @@
 // compiles it alone with g++ and holds it to the checks of tests/track_ref.py.
 #pragma once
 #include <cmath>
+#include <cstddef>
 
 #include "../../include/lfvio.h"
 
 constexpr int TRACK_MAX_SAMPLES = 1024, TRACK_MIN_MATCHES = 8;  // forw_pts.size() >= 8 (feature_tracker.cpp:331)
+
+// A stream's buffers, of either route.  The (id, un_pts_3d) map: [4096 ids | 4096 x 3 floats], the un_pts_3d at TRACK_MAP_IDS.  The
+// track table: [4096 x 2 floats | 4096 ids | 4096 counts].
+constexpr size_t TRACK_MAP_IDS = (size_t)LFVIO_TRACK_MAX_POINTS * 4, TRACK_MAP_BYTES = TRACK_MAP_IDS + (size_t)LFVIO_TRACK_MAX_POINTS * 12;
+constexpr size_t TRACK_TABLE_BYTES = (size_t)LFVIO_TRACK_MAX_POINTS * 16;
+
+// rejectWithF's record from the device's copy.  status != 0 is "no model": E is left as dst had it (the caller's own in
+// lfvio_track_reject, zeros in the frame routes, which clear dst first).
+inline void track_reject_copy(LfvioTrackRejectOut *dst, const LfvioTrackRejectOut &src) {
+  if (src.status == 0)
+    *dst = src;
+  else
+    dst->status = src.status, dst->best_sample = src.best_sample, dst->num_inliers = src.num_inliers, dst->best_score = src.best_score;
+}
 
 struct TrackCam {  // a kernel argument, by value; the members a model does not use are zero
   double cx, cy, c, d, e, inv_scale, poly[5];          // OCam

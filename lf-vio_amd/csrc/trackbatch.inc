@@ -8,8 +8,6 @@
 // segment.  Only then, with every count checked against its bound, are the outputs written and the double buffers of the active
 // slots swapped: a call that is refused or fails leaves every output and every slot as it was.
 
-static_assert(TB_TABLE_BYTES == TF_TABLE_BYTES && TB_MAP_BYTES == TRACK_MAP_BYTES && TB_MAP_IDS == TRACK_MAP_IDS, "a slot's tables and maps are the single route's");
-
 static int tb_copy(lfvio_ctx *c, hipStream_t fs, const char *src, size_t sstride, char *dst, size_t dstride, size_t bytes, int n) {
   if (!bytes || n < 1) return LFVIO_OK;
   hipLaunchKernelGGL(k_tb_copy, dim3((unsigned)((bytes + TB_COPY_BYTES - 1) / TB_COPY_BYTES), 1, n), dim3(TB_COPY_THREADS), 0, fs, (const unsigned char *)src,
@@ -51,7 +49,7 @@ int lfvio_track_batch_reserve(lfvio_ctx *c, int slots) {
   b.fixed = std::move(fresh);
   (void)b.image.reset(), (void)b.clahe.reset();
   b.lay = TbImage{0, 0, 0}, b.clahe_dirty = false;
-  b.slot.assign((size_t)slots, lfvio_ctx::TrackBatchState::Slot());
+  b.slot.assign((size_t)slots, TrackStream());
   return LFVIO_OK;
 }
 
@@ -62,11 +60,8 @@ int lfvio_track_batch_reset(lfvio_ctx *c, int slot) {
     c->err = why;
     return LFVIO_ERR_ARG;
   }
-  for (int i = 0; i < (int)b.slot.size(); i++) {
-    if (slot >= 0 && i != slot) continue;
-    lfvio_ctx::TrackBatchState::Slot &s = b.slot[i];
-    s.valid = false, s.mcount = 0, s.time = 0.0, s.count = 0, s.n_id = 0;  // (the base mask stays, as lfvio_track_frame_reset leaves it)
-  }
+  for (int i = 0; i < (int)b.slot.size(); i++)
+    if (slot < 0 || i == slot) b.slot[i].reset_frame();
   return LFVIO_OK;
 }
 
@@ -94,11 +89,11 @@ int lfvio_track_batch_set_mask(lfvio_ctx *c, int slot, int width, int height, co
   }
   const int first = slot < 0 ? 0 : slot, last = slot < 0 ? n : slot + 1;
   if (!pixels) {
-    for (int i = first; i < last; i++) b.slot[i].mask_set = false;
+    for (int i = first; i < last; i++) b.slot[i].mask_cleared();
     return LFVIO_OK;
   }
   for (int i = first; i < last; i++)
-    if (const char *why = gft_mask_check(width, height, b.slot[i].valid ? b.slot[i].w : 0, b.slot[i].h)) {
+    if (const char *why = gft_mask_check(width, height, b.slot[i].resident_w(), b.slot[i].h)) {
       c->err = why;
       return LFVIO_ERR_ARG;
     }
@@ -111,15 +106,8 @@ int lfvio_track_batch_set_mask(lfvio_ctx *c, int slot, int width, int height, co
   if (int rc = st.up(st.end)) return rc;
   if (int rc = tb_copy(c, st.fs, st.d + oM, 0, b.image + (size_t)first * b.lay.stride() + b.lay.mask_at(), b.lay.stride(), px, last - first)) return rc;
   HIPCHK(c, hipStreamSynchronize(st.fs));
-  for (int i = first; i < last; i++) b.slot[i].mw = width, b.slot[i].mh = height, b.slot[i].mask_set = true;
+  for (int i = first; i < last; i++) b.slot[i].mask_is(width, height);
   return LFVIO_OK;
-}
-
-// the scalars of an LfvioTrackFrameOut, everything in front of its arrays
-static void tb_zero_scalars(LfvioTrackFrameOut *o) {
-  o->num_points = o->num_new = o->levels_used = o->num_tracked = o->num_after_reject = 0;
-  std::memset(&o->reject, 0, sizeof o->reject);
-  std::memset(&o->detect, 0, sizeof o->detect);
 }
 
 int lfvio_track_batch_frame(lfvio_ctx *c, int count, const LfvioTrackFrameIn *in, LfvioTrackFrameOut *out, LfvioTrackMessage *msg) {
@@ -138,10 +126,7 @@ int lfvio_track_batch_frame(lfvio_ctx *c, int count, const LfvioTrackFrameIn *in
   }
   for (int i = 0; i < n; i++) {
     if (!trackbatch_active(in[i])) continue;
-    const lfvio_ctx::TrackBatchState::Slot &s = b.slot[i];
-    const LfvioTrackFrameOut &o = out[i];
-    if (!o.pts || !o.ids || !o.track_cnt || !o.un_pts || !o.un_pts_3d || !o.velocity_3d ||
-        (in[i].publish && s.mask_set && (s.mw != in[i].width || s.mh != in[i].height)) || (msg && !msg[i].rows)) {
+    if (!trackframe_out_check(&out[i], msg ? &msg[i] : nullptr) || (in[i].publish && !b.slot[i].mask_fits(in[i].width, in[i].height))) {
       c->err = "lfvio_track_batch_frame: a null array in out or msg, or a base mask that is not the image's size";
       return LFVIO_ERR_ARG;
     }
@@ -149,7 +134,7 @@ int lfvio_track_batch_frame(lfvio_ctx *c, int count, const LfvioTrackFrameIn *in
   const TbBounds bd = trackbatch_bounds(n, in, counts);
   if (!bd.active) {  // nothing to do, and nothing on the device
     for (int i = 0; i < n; i++) {
-      tb_zero_scalars(&out[i]);
+      trackframe_zero(&out[i]);
       if (msg) msg[i].num_rows = 0;
     }
     return LFVIO_OK;
@@ -161,7 +146,7 @@ int lfvio_track_batch_frame(lfvio_ctx *c, int count, const LfvioTrackFrameIn *in
   const KltPlan full = klt_plan(W, H, 0, LFVIO_KLT_MAX_LEVEL);
   const int LU = klt_plan(W, H, f.win_size, f.max_level).levels_used;
   const GftWork gw = gft_work(W, H);
-  const TbWork wk = {gw.lam, gw.keys, gw.idx, gw.mask, gw.kxy, gw.st};
+  const GftOffsets &wk = gw;  // what the kernels take
   const size_t nI = (size_t)W * H;
   const bool rows = msg != nullptr, any_pub = bd.publishing > 0;
   TbShape shape = {};
@@ -194,13 +179,9 @@ int lfvio_track_batch_frame(lfvio_ctx *c, int count, const LfvioTrackFrameIn *in
   bool build_resident = false;
   for (int i = 0, ka = 0, kp = 0; i < n; i++) {
     if (!trackbatch_active(in[i])) continue;
-    const lfvio_ctx::TrackBatchState::Slot &s = b.slot[i];
     TbSlot &t = desc[i];
-    const bool same = s.valid && s.w == W && s.h == H;  // otherwise the new image is both images
-    t.active = 1, t.publish = in[i].publish != 0, t.n0 = s.count, t.n_id = s.n_id, t.prev_count = s.mcount;
-    t.prev_built = same ? s.built : LU, t.same = same;
-    t.pcur = s.pcur, t.tcur = s.tcur, t.mcur = s.mcur, t.masked = s.mask_set;
-    t.dt = in[i].time - s.time;
+    t.active = 1, t.publish = in[i].publish != 0;
+    trackbatch_describe(t, b.slot[i], W, H, LU, in[i].time);
     t.cam = track_cam(*in[i].camera);
     t.image_k = ka++;
     std::memcpy(h + trackbatch_image_at(o, shape, t.image_k), in[i].image, nI);
@@ -208,7 +189,7 @@ int lfvio_track_batch_frame(lfvio_ctx *c, int count, const LfvioTrackFrameIn *in
       t.words_k = kp++;
       std::memcpy(h + trackbatch_words_at(o, shape, t.words_k), in[i].sample_words, (size_t)S * 32);
     }
-    build_resident = build_resident || (same && s.built < LU);
+    build_resident = build_resident || b.slot[i].levels_missing(W, H, LU) > 0;
   }
   if (int rc = st.up(o.in_end)) return rc;
 
@@ -263,7 +244,7 @@ int lfvio_track_batch_frame(lfvio_ctx *c, int count, const LfvioTrackFrameIn *in
     HIPCHK(c, hipGetLastError());
     hipLaunchKernelGGL(k_tf_reject_b, dim3(1, 1, Z), dim3(TF_THREADS), 0, fs, slots, m, o, bd.n0_max);
     HIPCHK(c, hipGetLastError());
-    // 4: setMask and goodFeaturesToTrack on the new images; the sort network of the arrays' capacity, as gft_launch_detect
+    // 4: setMask and goodFeaturesToTrack on the new images; the sort network of the arrays' capacity (gft_plan.h)
     hipLaunchKernelGGL(k_gft_thin_b, dim3(1, 1, Z), dim3(GFT_THREADS), 0, fs, slots, m, o, wk, bd.n0_max, W, H, gin.mask_radius);
     HIPCHK(c, hipGetLastError());
     hipLaunchKernelGGL(k_gft_response_b, dim3((W + GFT_TX - 1) / GFT_TX, (H + GFT_TY - 1) / GFT_TY, Z), dim3(GFT_THREADS), 0, fs, slots, m, o, wk, W, H, gin.mask_radius, MC);
@@ -271,13 +252,10 @@ int lfvio_track_batch_frame(lfvio_ctx *c, int count, const LfvioTrackFrameIn *in
     hipLaunchKernelGGL(k_gft_cand_b, dim3((W + GFT_THREADS - 1) / GFT_THREADS, (H + GFT_CAND_ROWS - 1) / GFT_CAND_ROWS, Z), dim3(GFT_THREADS), 0, fs, slots, m, o, wk, W, H,
                        gin.quality_level, MC);
     HIPCHK(c, hipGetLastError());
-    const unsigned chunks = (unsigned)std::min<size_t>(gw.capacity / GFT_CHUNK, GFT_SORT_GRID), halves = (unsigned)std::min<size_t>(gw.capacity / 2 / GFT_THREADS, GFT_SORT_GRID);
-    hipLaunchKernelGGL(k_gft_sort_local_b, dim3(chunks, 1, Z), dim3(GFT_SORT_THREADS), 0, fs, slots, m, o, wk, 0u);
-    for (size_t kk = 2 * (size_t)GFT_CHUNK; kk <= gw.capacity; kk *= 2) {
-      for (size_t j = kk / 2; j >= (size_t)GFT_CHUNK; j /= 2)
-        hipLaunchKernelGGL(k_gft_sort_global_b, dim3(halves, 1, Z), dim3(GFT_THREADS), 0, fs, slots, m, o, wk, (unsigned)kk, (unsigned)j);
-      hipLaunchKernelGGL(k_gft_sort_local_b, dim3(chunks, 1, Z), dim3(GFT_SORT_THREADS), 0, fs, slots, m, o, wk, (unsigned)kk);
-    }
+    const GftSortGrid sg = gft_sort_grid(gw.capacity);
+    gft_sort_stages(
+        gw.capacity, [&](unsigned kk) { hipLaunchKernelGGL(k_gft_sort_local_b, dim3(sg.chunks, 1, Z), dim3(GFT_SORT_THREADS), 0, fs, slots, m, o, wk, kk); },
+        [&](unsigned kk, unsigned j) { hipLaunchKernelGGL(k_gft_sort_global_b, dim3(sg.halves, 1, Z), dim3(GFT_THREADS), 0, fs, slots, m, o, wk, kk, j); });
     HIPCHK(c, hipGetLastError());
     hipLaunchKernelGGL(k_gft_pick_b, dim3(1, 1, Z), dim3(GFT_THREADS), 0, fs, slots, m, o, wk, W, gin.min_distance, MC);
     HIPCHK(c, hipGetLastError());
@@ -296,54 +274,25 @@ int lfvio_track_batch_frame(lfvio_ctx *c, int count, const LfvioTrackFrameIn *in
   if (int rc = st.down(o.down, o.end)) return rc;
 
   // every count of every active slot against its own bound, before anything is written
+  auto rows_at = [&](int i) { return rows && in[i].publish ? h + trackbatch_down_at(o, i) + o.msg : (const char *)nullptr; };
   for (int i = 0; i < n; i++) {
     if (!trackbatch_active(in[i])) continue;
-    const char *dn = h + trackbatch_down_at(o, i);
-    const TfDev *v = (const TfDev *)(dn + o.dev);
-    const bool pub = in[i].publish != 0;
-    const size_t Bi = (size_t)trackframe_bound(counts[i], MC, pub), N0 = (size_t)counts[i];
-    const int num_rows = rows && pub ? *(const int *)(dn + o.msg) : 0;
-    if (v->num_points < 0 || (size_t)v->num_points > Bi || v->n1 < 0 || (size_t)v->n1 > N0 || num_rows < 0 || num_rows > v->num_points ||
-        (pub && (v->detect.num_kept < 0 || (size_t)v->detect.num_kept > N0 || v->detect.num_corners < 0 || v->detect.num_corners > MC))) {
+    const char *r = rows_at(i);
+    if (!trackframe_counts_check(*(const TfDev *)(h + trackbatch_down_at(o, i) + o.dev), counts[i], MC, in[i].publish != 0, r ? *(const int *)r : 0)) {
       c->err = "lfvio_track_batch_frame: a count from the device beyond its bound";
       return LFVIO_ERR_DEVICE;
     }
   }
-  const size_t B = shape.B_max;
   for (int i = 0; i < n; i++) {
-    LfvioTrackFrameOut *w = &out[i];
-    tb_zero_scalars(w);
-    if (msg) msg[i].num_rows = 0;
-    if (!trackbatch_active(in[i])) continue;
-    lfvio_ctx::TrackBatchState::Slot &s = b.slot[i];
+    if (!trackbatch_active(in[i])) {
+      trackframe_zero(&out[i]);
+      if (msg) msg[i].num_rows = 0;
+      continue;
+    }
     const char *dn = h + trackbatch_down_at(o, i);
     const TfDev *v = (const TfDev *)(dn + o.dev);
-    const bool pub = in[i].publish != 0;
-    const size_t np = (size_t)v->num_points;
-    w->num_points = v->num_points, w->num_new = v->num_new, w->levels_used = LU, w->num_tracked = v->n1, w->num_after_reject = v->n2;
-    if (pub) {
-      if (v->reject.status == 0)
-        w->reject = v->reject;
-      else  // no model: E is zero
-        w->reject.status = v->reject.status, w->reject.best_sample = v->reject.best_sample, w->reject.num_inliers = v->reject.num_inliers,
-        w->reject.best_score = v->reject.best_score;
-      w->detect = v->detect;
-    }
-    std::memcpy(w->pts, dn + o.table, np * 8);
-    std::memcpy(w->ids, dn + o.table + B * 8, np * 4);
-    std::memcpy(w->track_cnt, dn + o.table + B * 12, np * 4);
-    std::memcpy(w->un_pts, dn + o.un, np * 8);
-    std::memcpy(w->un_pts_3d, dn + o.un3d, np * 12);
-    std::memcpy(w->velocity_3d, dn + o.vel, np * 12);
-    if (rows && pub) {
-      msg[i].num_rows = *(const int *)(dn + o.msg);
-      if (msg[i].num_rows) std::memcpy(msg[i].rows, dn + o.msg + TF_MSG_HEAD, (size_t)msg[i].num_rows * 36);
-    }
-    // the slot's double buffers, as track_frame_run swaps the context's
-    s.pcur = 1 - s.pcur, s.w = W, s.h = H, s.built = LU, s.valid = true;
-    if (np) s.mcur = 1 - s.mcur;
-    s.mcount = (int)np, s.time = in[i].time;
-    s.tcur = 1 - s.tcur, s.count = (int)np, s.n_id += v->num_new;
+    trackframe_emit(TfDown{v, dn + o.table, shape.B_max, dn + o.un, dn + o.un3d, dn + o.vel, rows_at(i)}, LU, in[i].publish != 0, &out[i], msg ? &msg[i] : nullptr);
+    b.slot[i].commit_frame(W, H, LU, v->num_points, v->num_new, in[i].time);
   }
   return LFVIO_OK;
 }

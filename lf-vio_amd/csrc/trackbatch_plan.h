@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <cstddef>
 
+#include "track_stream.h"
 #include "trackframe_plan.h"
 
 constexpr size_t TB_ALIGN = 256;
@@ -87,6 +88,13 @@ struct TbSlot {
   double dt;       // time - the previous call's
   TrackCam cam;
 };
+// what a slot's stream (track_stream.h) says to a call on a W x H image that uses LU levels, at time `time`
+inline void trackbatch_describe(TbSlot &t, const TrackStream &s, int W, int H, int LU, double time) {
+  t.n0 = s.count, t.n_id = s.n_id, t.prev_count = s.mcount;
+  t.prev_built = s.prev_built(W, H, LU), t.same = s.resident(W, H);
+  t.pcur = s.pcur, t.tcur = s.tcur, t.mcur = s.mcur, t.masked = s.mask_set;
+  t.dt = time - s.time;
+}
 struct TbMem {  // the bases and strides of the slots' memory
   char *stage, *fixed, *image, *clahe;  // the staging block; per slot: tables and maps | [pyramid | pyramid | mask | work] | CLAHE table and LUTs
   size_t image_stride, pyr, mask_at, work_at, clahe_stride;
@@ -145,10 +153,9 @@ inline size_t trackbatch_down_at(const TbStage &o, int slot) { return o.down + (
 // ---- the slot's memory.  Whatever the image size: two track tables and two (id, un_pts_3d) maps.  At an image size: two pyramid
 // buffers, the base mask and the detector's arrays, [pyramid | pyramid | mask | work] — the segments keep their capacity when a
 // smaller image follows, and grow to the largest seen.
-constexpr size_t TB_TABLE_BYTES = (size_t)LFVIO_TRACK_MAX_POINTS * 16, TB_MAP_BYTES = (size_t)LFVIO_TRACK_MAX_POINTS * 16;
-constexpr size_t TB_FIXED_BYTES = 2 * TB_TABLE_BYTES + 2 * TB_MAP_BYTES;
-constexpr size_t trackbatch_table_at(int which) { return (size_t)which * TB_TABLE_BYTES; }
-constexpr size_t trackbatch_map_at(int which) { return 2 * TB_TABLE_BYTES + (size_t)which * TB_MAP_BYTES; }
+constexpr size_t TB_FIXED_BYTES = 2 * TRACK_TABLE_BYTES + 2 * TRACK_MAP_BYTES;
+constexpr size_t trackbatch_table_at(int which) { return (size_t)which * TRACK_TABLE_BYTES; }
+constexpr size_t trackbatch_map_at(int which) { return 2 * TRACK_TABLE_BYTES + (size_t)which * TRACK_MAP_BYTES; }
 
 struct TbImage {
   size_t pyr, mask, work;  // capacities, aligned

@@ -6,29 +6,24 @@
 // The host knows only bounds: n0, the table's count, for n1 and n2, and B = max(n0, max_count) for the count after the call (n0
 // without publish).  Every grid and every segment of the staging block is sized for its bound; the kernels read the true count from
 // the TfDev at the head of the block that comes down, and the host reads it there afterwards.  The table, the pyramid and the
-// (id, un_pts_3d) map are each written into the context's OTHER buffer and swapped at the end: a call that is refused or fails
-// leaves all three, n_id and the time as they were.
-
-constexpr size_t TF_TABLE_BYTES = (size_t)LFVIO_TRACK_MAX_POINTS * 16;
-
-// [n][2] floats | n ids | n counts at p
-static TfTable tf_table(char *p, size_t n) { return TfTable{(float *)p, (int *)(p + n * 8), (int *)(p + n * 12)}; }
+// (id, un_pts_3d) map are each written into the context's OTHER buffer and swapped at the end (TrackStream::commit_frame): a call that
+// is refused or fails leaves all three, n_id and the time as they were.
 
 // lfvio_track_frame (msg null) and lfvio_track_frame_message: with a message and publish the rows are one more segment of the block
 // that comes down (trackframe_message_bytes), written by k_tf_message behind k_trk_undist_n.
 static int track_frame_run(lfvio_ctx *c, const LfvioTrackFrameIn *in, LfvioTrackFrameOut *out, const LfvioTrackFrameStages *stages, LfvioTrackMessage *msg) {
   if (!c || !in || !out) return LFVIO_ERR_ARG;
+  TrackStream &s = c->tstream;
   lfvio_ctx::TrackFrameState &f = c->tframe;
   lfvio_ctx::TrackState &t = c->track;
   lfvio_ctx::GftState &g = c->gft;
-  if (const char *why = trackframe_check(in, f.count)) {
+  if (const char *why = trackframe_check(in, s.count)) {
     c->err = why;
     return LFVIO_ERR_ARG;
   }
-  const int W = in->width, H = in->height, S = in->num_samples, MC = in->max_count, n0 = f.count;
+  const int W = in->width, H = in->height, S = in->num_samples, MC = in->max_count, n0 = s.count;
   const bool pub = in->publish != 0;
-  if (!out->pts || !out->ids || !out->track_cnt || !out->un_pts || !out->un_pts_3d || !out->velocity_3d ||
-      (pub && g.mask_set && (g.mw != W || g.mh != H))) {
+  if (!trackframe_out_check(out, nullptr) || (pub && !s.mask_fits(W, H))) {  // (a message's rows: lfvio_track_frame_message's check)
     c->err = "lfvio_track_frame: a null array in out, or a base mask that is not the image's size";
     return LFVIO_ERR_ARG;
   }
@@ -54,9 +49,9 @@ static int track_frame_run(lfvio_ctx *c, const LfvioTrackFrameIn *in, LfvioTrack
   if (int rc = st.reserve()) return rc;
   if (pub)
     if (int rc = gft_reserve(c, wk)) return rc;
-  if (!c->klt.d[1 - c->klt.cur].reserve(full.bytes)) return out_of_memory(c, "out of memory (image pyramid)");
+  if (!c->klt.d[1 - s.pcur].reserve(full.bytes)) return out_of_memory(c, "out of memory (image pyramid)");
   for (auto &b : f.table)
-    if (!b.reserve(TF_TABLE_BYTES)) return out_of_memory(c, "out of memory (track table)");
+    if (!b.reserve(TRACK_TABLE_BYTES)) return out_of_memory(c, "out of memory (track table)");
   for (auto &m : t.map)
     if (!m.reserve(TRACK_MAP_BYTES)) return out_of_memory(c, "out of memory (track map)");
   char *d = st.d, *h = st.h;
@@ -65,7 +60,7 @@ static int track_frame_run(lfvio_ctx *c, const LfvioTrackFrameIn *in, LfvioTrack
   if (int rc = st.up(in_end)) return rc;
 
   TfDev *dev = (TfDev *)(d + oD);
-  const TfTable have = tf_table(f.table[f.cur], LFVIO_TRACK_MAX_POINTS), next = tf_table(f.table[1 - f.cur], LFVIO_TRACK_MAX_POINTS);
+  const TfTable have = tf_table(f.table[s.tcur], LFVIO_TRACK_MAX_POINTS), next = tf_table(f.table[1 - s.tcur], LFVIO_TRACK_MAX_POINTS);
   const TfTable t1 = tf_table(d + oT1, N0), t2 = tf_table(d + oT2, N0), down = tf_table(d + oTab, B);
   // 1: the flow
   unsigned char *fresh;
@@ -97,22 +92,22 @@ static int track_frame_run(lfvio_ctx *c, const LfvioTrackFrameIn *in, LfvioTrack
     hipLaunchKernelGGL(k_tf_reject, dim3(1), dim3(TF_THREADS), 0, st.fs, (const unsigned char *)(d + oM), t1, t2, dev);
     HIPCHK(c, hipGetLastError());
     // 4: setMask and goodFeaturesToTrack on the new image
-    const unsigned char *base = g.mask_set ? (const unsigned char *)g.mask : nullptr;
+    const unsigned char *base = s.mask_set ? (const unsigned char *)g.mask : nullptr;
     hipLaunchKernelGGL(k_gft_thin<const int *>, dim3(1), dim3(GFT_THREADS), 0, st.fs, (const int *)&dev->n2, (const float *)t2.pts, (const int *)t2.cnt, base, W, H,
                        gin.mask_radius, (GftDev *)(g.work + wk.st), (int *)(d + oK), (int *)(g.work + wk.kxy));
     HIPCHK(c, hipGetLastError());
     if (int rc = gft_launch_detect(c, st.fs, wk, fresh, W, H, base, &gin, (float *)(d + oX), &dev->detect)) return rc;
   }
   // 4 and 6: the next table, numbered; ids_raw keeps the -1 for step 5
-  hipLaunchKernelGGL(k_tf_finish, dim3(1), dim3(TF_THREADS), 0, st.fs, pub ? 1 : 0, pub ? t2 : t1, (const int *)(d + oK), (const float *)(d + oX), f.n_id, next,
+  hipLaunchKernelGGL(k_tf_finish, dim3(1), dim3(TF_THREADS), 0, st.fs, pub ? 1 : 0, pub ? t2 : t1, (const int *)(d + oK), (const float *)(d + oX), s.n_id, next,
                      down, (int *)(d + oRaw), dev);
   HIPCHK(c, hipGetLastError());
   // 5: undistortedPoints
   if (B) {
-    const char *pm = t.map[t.cur];
-    char *nm = t.map[1 - t.cur];
+    const char *pm = t.map[s.mcur];
+    char *nm = t.map[1 - s.mcur];
     hipLaunchKernelGGL(k_trk_undist_n, dim3((unsigned)((B + TRK_THREADS - 1) / TRK_THREADS)), dim3(TRK_THREADS), 0, st.fs, cam, (const int *)&dev->num_points,
-                       (const float *)down.pts, (const int *)(d + oRaw), in->time - t.time, t.count, (const int *)pm, (const float *)(pm + TRACK_MAP_IDS),
+                       (const float *)down.pts, (const int *)(d + oRaw), in->time - s.time, s.mcount, (const int *)pm, (const float *)(pm + TRACK_MAP_IDS),
                        (float *)(d + oU), (float *)(d + o3), (float *)(d + oV), (int *)(d + oMt), (int *)nm, (float *)(nm + TRACK_MAP_IDS));
     HIPCHK(c, hipGetLastError());
   }
@@ -124,49 +119,22 @@ static int track_frame_run(lfvio_ctx *c, const LfvioTrackFrameIn *in, LfvioTrack
   if (int rc = st.down(oD, stages ? st.end : main_end)) return rc;
 
   const TfDev *o = (const TfDev *)(h + oD);
-  const size_t n = (size_t)o->num_points, n1 = (size_t)o->n1;
-  const int num_rows = rows ? *(const int *)(h + oMsg) : 0;
-  if (o->num_points < 0 || n > B || o->n1 < 0 || n1 > N0 || num_rows < 0 || (size_t)num_rows > n ||
-      (pub && (o->detect.num_kept < 0 || (size_t)o->detect.num_kept > N0 || o->detect.num_corners < 0 || o->detect.num_corners > MC))) {
+  if (!trackframe_counts_check(*o, n0, MC, pub, rows ? *(const int *)(h + oMsg) : 0)) {
     c->err = "lfvio_track_frame: a count from the device beyond its bound";
     return LFVIO_ERR_DEVICE;
   }
-  out->num_points = o->num_points, out->num_new = o->num_new, out->levels_used = LU, out->num_tracked = o->n1, out->num_after_reject = o->n2;
-  std::memset(&out->reject, 0, sizeof out->reject);
-  std::memset(&out->detect, 0, sizeof out->detect);
-  if (pub) {
-    if (o->reject.status == 0)
-      out->reject = o->reject;
-    else  // no model: E is zero
-      out->reject.status = o->reject.status, out->reject.best_sample = o->reject.best_sample, out->reject.num_inliers = o->reject.num_inliers,
-      out->reject.best_score = o->reject.best_score;
-    out->detect = o->detect;
-  }
-  std::memcpy(out->pts, h + oTab, n * 8);
-  std::memcpy(out->ids, h + oTab + B * 8, n * 4);
-  std::memcpy(out->track_cnt, h + oTab + B * 12, n * 4);
-  std::memcpy(out->un_pts, h + oU, n * 8);
-  std::memcpy(out->un_pts_3d, h + o3, n * 12);
-  std::memcpy(out->velocity_3d, h + oV, n * 12);
-  if (msg) {
-    msg->num_rows = num_rows;
-    if (num_rows) std::memcpy(msg->rows, h + oMsg + TF_MSG_HEAD, (size_t)num_rows * 36);
-  }
+  trackframe_emit(TfDown{o, h + oTab, B, h + oU, h + o3, h + oV, rows ? h + oMsg : nullptr}, LU, pub, out, msg);
   if (stages) {
     if (stages->next_pts) std::memcpy(stages->next_pts, h + oN, N0 * 8);
     if (stages->status) std::memcpy(stages->status, h + oSt, N0);
     if (pub) {
-      if (stages->samples && n1 >= (size_t)TRACK_MIN_MATCHES) std::memcpy(stages->samples, h + oSm, (size_t)S * 32);
-      if (stages->mask) std::memcpy(stages->mask, h + oM, n1);
+      if (stages->samples && o->n1 >= TRACK_MIN_MATCHES) std::memcpy(stages->samples, h + oSm, (size_t)S * 32);
+      if (stages->mask) std::memcpy(stages->mask, h + oM, (size_t)o->n1);
       if (stages->kept) std::memcpy(stages->kept, h + oK, (size_t)o->detect.num_kept * 4);
       if (stages->corners) std::memcpy(stages->corners, h + oX, (size_t)o->detect.num_corners * 8);
     }
   }
-  klt_commit(c, W, H, LU);
-  if (n)
-    t.cur = 1 - t.cur;  // (n = 0: the N = 0 branch of lfvio_track_undistort — an empty map, the next call's velocities are all 0)
-  t.count = (int)n, t.time = in->time;
-  f.cur = 1 - f.cur, f.count = (int)n, f.n_id += o->num_new;
+  s.commit_frame(W, H, LU, o->num_points, o->num_new, in->time);
   return LFVIO_OK;
 }
 
@@ -185,8 +153,6 @@ int lfvio_track_frame_message(lfvio_ctx *c, const LfvioTrackFrameIn *in, LfvioTr
 
 int lfvio_track_frame_reset(lfvio_ctx *c) {
   if (!c) return LFVIO_ERR_ARG;
-  c->klt.valid = false;
-  c->track.count = 0, c->track.time = 0.0;
-  c->tframe.count = 0, c->tframe.n_id = 0;
+  c->tstream.reset_frame();
   return LFVIO_OK;
 }

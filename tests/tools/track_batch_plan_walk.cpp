@@ -1,7 +1,9 @@
 // track_batch_plan_walk.cpp — a stand-alone walk over lf-vio_amd/csrc/trackbatch_plan.h for a CPU sanitizer build of the host side
 // of lfvio_track_batch_*: it does on the host's memory what trackbatch.inc does with the plan — checks the entries, takes the
 // bounds, lays the staging block out, then fills and reads EVERY byte of every segment of a block of exactly `end` bytes, so that an
-// offset or a size that is wrong lands outside the allocation, where AddressSanitizer sees it.
+// offset or a size that is wrong lands outside the allocation, where AddressSanitizer sees it.  Then the download of
+// trackframe_plan.h, as both routes run it behind the copy down: per active slot a down segment of exactly `down_stride` bytes with
+// every count at its bound, outputs of exactly `capacity` entries, trackframe_counts_check and trackframe_emit.
 //
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -I lf-vio_amd/csrc tests/tools/track_batch_plan_walk.cpp -o walk && ./walk
 //
@@ -20,12 +22,12 @@ static int fail(const char *what) {
 
 int main() {
   const int W = 161, H = 123, S = 100, MC = 40;
-  const size_t dev_bytes = 136;
+  const size_t dev_bytes = sizeof(TfDev);
   std::vector<unsigned char> image((size_t)W * H, 117);
   std::vector<unsigned> words((size_t)S * 8, 0x9e3779b9u);
   LfvioCamera cam = {};
   cam.model = LFVIO_CAM_OCAM, cam.c = 1.0;
-  long walked = 0;
+  long walked = 0, emitted = 0;
   unsigned seed = 12345;
   auto next = [&]() { return seed = seed * 1664525u + 1013904223u; };
   for (int slots = 1; slots <= LFVIO_TRACK_BATCH_MAX_SLOTS; slots += (slots < 8 ? 1 : 7)) {
@@ -45,6 +47,9 @@ int main() {
       }
       if (round == 23)
         for (auto &e : in) e.image = nullptr;  // all idle
+      int capacity = MC;  // the smallest the check accepts: the largest bound of the call is all of the caller's arrays
+      for (int n0 : counts) capacity = std::max(capacity, n0);
+      for (auto &e : in) e.capacity = capacity;
       if (const char *why = trackbatch_frame_check(slots, slots, in.data(), counts.data())) return fail(why);
       if (!trackbatch_frame_check(slots, slots + 1, in.data(), counts.data())) return fail("count != slots accepted");
       const TbBounds bd = trackbatch_bounds(slots, in.data(), counts.data());
@@ -97,6 +102,35 @@ int main() {
           if (d < o.down || d + o.down_stride > o.end) return fail("a down segment outside the range that comes down");
         }
         if (!sum) return fail("nothing walked");
+        for (int i = 0; i < slots; i++) {
+          const LfvioTrackFrameIn &e = in[(size_t)i];
+          if (!trackbatch_active(e)) continue;
+          const bool pub = e.publish != 0, msg_down = rows && pub;
+          const int n0 = counts[(size_t)i], np = trackframe_bound(n0, MC, pub);
+          char *seg = (char *)std::malloc(o.down_stride);  // exactly one slot's segment
+          if (!seg) return fail("malloc");
+          std::memset(seg, 0x5a, o.down_stride);
+          TfDev v = {};
+          v.n1 = v.n2 = n0, v.num_points = np, v.num_new = np, v.reject.status = i % 2, v.detect.num_kept = n0, v.detect.num_corners = MC;
+          std::memcpy(seg + o.dev, &v, sizeof v);
+          if (rows) std::memcpy(seg + o.msg, &np, sizeof np);
+          if (!trackframe_counts_check(v, n0, MC, pub, msg_down ? np : 0)) return fail("counts at their bounds refused");
+          TfDev w = v;
+          w.num_points = np + 1;
+          if (trackframe_counts_check(w, n0, MC, pub, 0)) return fail("num_points beyond its bound accepted");
+          const size_t cap = (size_t)capacity;
+          std::vector<float> pts(cap * 2), un(cap * 2), un3d(cap * 3), vel(cap * 3), mrows(cap * 9);
+          std::vector<int> ids(cap), cnt(cap);
+          LfvioTrackFrameOut out = {};
+          out.pts = pts.data(), out.ids = ids.data(), out.track_cnt = cnt.data(), out.un_pts = un.data(), out.un_pts_3d = un3d.data(), out.velocity_3d = vel.data();
+          LfvioTrackMessage msg = {0, mrows.data()};
+          if (!trackframe_out_check(&out, rows ? &msg : nullptr)) return fail("out check");
+          trackframe_emit(TfDown{(const TfDev *)(seg + o.dev), seg + o.table, B, seg + o.un, seg + o.un3d, seg + o.vel, msg_down ? seg + o.msg : nullptr}, 3, pub, &out,
+                          rows ? &msg : nullptr);
+          if (out.num_points != np || msg.num_rows != (msg_down ? np : 0)) return fail("emit's counts");
+          std::free(seg);
+          emitted++;
+        }
         std::free(block);
         walked++;
       }
@@ -116,6 +150,6 @@ int main() {
   if (trackbatch_reserve_check(65) == nullptr || trackbatch_reserve_check(0) != nullptr || trackbatch_slot_check(3, 3) == nullptr ||
       trackbatch_slot_check(-1, 3) != nullptr)
     return fail("a reserve or slot check");
-  std::printf("track_batch_plan_walk: %ld layouts walked\n", walked);
+  std::printf("track_batch_plan_walk: %ld layouts walked, %ld down segments emitted\n", walked, emitted);
   return 0;
 }
