@@ -674,7 +674,7 @@ int lfvio_relative_pose(lfvio_ctx *ctx, const LfvioRelativePoseIn *in, unsigned 
 #define LFVIO_KLT_MAX_POINTS 4096
 #define LFVIO_KLT_MAX_LEVEL 5
 typedef struct {
-  int width, height;           /* 8-bit grey image, rows contiguous; 16 <= width, height <= 8192 */
+  int width, height;           /* 8-bit grey image, rows contiguous (or as lfvio_image_format_set says); 16 <= width, height <= 8192 */
   const unsigned char *image;  /* forw_img */
   int num_points;              /* N, 0 <= N <= 4096: cur_pts */
   const float *prev_pts;       /* [N][2] x, y in the image of the PREVIOUS call (cv::Point2f) */
@@ -771,6 +771,48 @@ typedef struct {
 int lfvio_clahe_set(lfvio_ctx *ctx, const LfvioClaheIn *cfg /* NULL: off */);
 int lfvio_clahe_apply(lfvio_ctx *ctx, const LfvioClaheIn *cfg, int width, int height, const unsigned char *pixels,
                       unsigned char *out /* [height][width] */, unsigned char *lut /* [tiles_y][tiles_x][256], or NULL */);
+
+/* lfvio_image_format_set / lfvio_image_gray: colour and 16-bit camera images — what cv_bridge::toCvCopy(img_msg, MONO8) does in
+ * front of FeatureTracker::readImage (feature_tracker/src/feature_tracker_node.cpp:64-78) — converted on the device, in the write of
+ * level 0 of the fresh pyramid.  One code space, the ABI's and the type-10 record's (host/replay.h):
+ *
+ *   code  name                              bytes / pixel  grey value
+ *   0     LFVIO_IMG_MONO8 (also 8UC1)       1              v
+ *   2     LFVIO_IMG_BGR8                    3              (1868 B + 9617 G + 4899 R + 8192) >> 14
+ *   3     LFVIO_IMG_RGB8                    3              the same on R, G, B in their places
+ *   4     LFVIO_IMG_BGRA8                   4              the same; the fourth byte is never read into the value
+ *   5     LFVIO_IMG_RGBA8                   4              the same
+ *   6     LFVIO_IMG_MONO16 (little endian)  2              (v + 128) / 257, integer division
+ *   7     LFVIO_IMG_MONO16_BE               2              the same after the byte swap
+ *
+ * Code 1 and every code above 7 are refused everywhere.  The colour line is OpenCV 3.3's 8-bit RGB2Gray (14-bit coefficients, the
+ * rounding constant folded into its table); the 16-bit line is cv_bridge's convertTo(..., CV_8U, 255. / 65535.), whose rounded float
+ * product equals the integer form for all 65 536 values.  Both are written down from memory of those libraries and have not been
+ * compared with them; tests/image_ref.py restates them in numpy and is the specification, csrc/image_format.h is the
+ * same text for the host and the device.  Bayer patterns, 8UC3, 16UC1 and float images have no specification here.
+ * lfvio_image_format_set: fmt != NULL: `image` of every later lfvio_klt_track, lfvio_track_frame and lfvio_track_frame_message points
+ * to height * step bytes in that encoding (step 0: width * bytes per pixel), and everything the call does and leaves resident is, bit
+ * for bit, what it does without a format on the converted image: lfvio_klt_level(ctx, 0, ...) returns the grey image, or the equalized
+ * grey image.  fmt == NULL: off.  A mono8 format with step 0 or step == width is the same as none.  Off after lfvio_create; survives
+ * lfvio_klt_reset and lfvio_track_frame_reset.  lfvio_clahe_apply, lfvio_gft_set_mask and lfvio_track_batch_set_mask keep taking
+ * 8-bit grey.  One copy goes up as without a format, of height * step bytes; nothing more comes down.
+ * lfvio_image_gray: one image in, width * height grey bytes out; fmt NULL: mono8, rows contiguous.  Touches neither the resident
+ * image nor the setting.
+ * lfvio_track_batch_format (with the batch calls below): the setting of the batch, one for every slot.
+ * LFVIO_ERR_ARG (everything untouched): a code outside the table, step negative or above 65536; at the call that takes an image,
+ * 0 < step < width * bytes per pixel; for lfvio_image_gray null ctx / pixels / out or a width or height outside [16, 8192]. */
+#define LFVIO_IMG_MONO8 0
+#define LFVIO_IMG_BGR8 2
+#define LFVIO_IMG_RGB8 3
+#define LFVIO_IMG_BGRA8 4
+#define LFVIO_IMG_RGBA8 5
+#define LFVIO_IMG_MONO16 6
+#define LFVIO_IMG_MONO16_BE 7
+#define LFVIO_IMG_MAX_STEP 65536
+typedef struct { int encoding; int step; /* bytes per row; 0: width * bytes per pixel */ } LfvioImageFormat;
+int lfvio_image_format_set(lfvio_ctx *ctx, const LfvioImageFormat *fmt /* NULL: mono8, rows contiguous */);
+int lfvio_image_gray(lfvio_ctx *ctx, const LfvioImageFormat *fmt, int width, int height, const unsigned char *pixels,
+                     unsigned char *out /* [height][width] */);
 
 /* lfvio_track_reject / lfvio_track_undistort / lfvio_track_reset: the two steps of FeatureTracker::readImage that need the camera —
  * rejectWithF() (feature_tracker/src/feature_tracker.cpp:329-386, with myfindFundamentalMat :266-327) and undistortedPoints()
@@ -964,6 +1006,8 @@ int lfvio_track_frame_message(lfvio_ctx *ctx, const LfvioTrackFrameIn *in, Lfvio
  *                               allocation that fails is LFVIO_ERR_DEVICE and leaves the previous reservation usable.
  *   lfvio_track_batch_set_mask  lfvio_gft_set_mask for one slot, or for every slot with slot = -1.  pixels NULL: all 255 again.
  *   lfvio_track_batch_clahe     lfvio_clahe_set for the batch: one setting for every slot.  NULL: off.
+ *   lfvio_track_batch_format    lfvio_image_format_set for the batch: one setting for every slot, and the contract above holds with
+ *                               the converted images.  NULL: off.  A step below width * bytes per pixel refuses the frame call.
  *   lfvio_track_batch_frame     count must be the reserved slot count; entry i is slot i.  in[i].image == NULL: slot i is idle in
  *                               this call — its state is untouched, out[i] is written with zero scalars (everything in front of the
  *                               arrays) and nothing else, msg[i].num_rows = 0.  The active entries must agree on width, height,
@@ -983,6 +1027,7 @@ int lfvio_track_frame_message(lfvio_ctx *ctx, const LfvioTrackFrameIn *in, Lfvio
 int lfvio_track_batch_reserve(lfvio_ctx *ctx, int slots);
 int lfvio_track_batch_set_mask(lfvio_ctx *ctx, int slot /* -1: every slot */, int width, int height, const unsigned char *pixels /* NULL: all 255 */);
 int lfvio_track_batch_clahe(lfvio_ctx *ctx, const LfvioClaheIn *cfg /* NULL: off */);
+int lfvio_track_batch_format(lfvio_ctx *ctx, const LfvioImageFormat *fmt /* NULL: mono8, rows contiguous */);
 int lfvio_track_batch_frame(lfvio_ctx *ctx, int count, const LfvioTrackFrameIn *in /* [count] */, LfvioTrackFrameOut *out /* [count] */,
                             LfvioTrackMessage *msg /* [count], or NULL */);
 int lfvio_track_batch_reset(lfvio_ctx *ctx, int slot /* -1: every slot */);

@@ -11,9 +11,12 @@
 //
 //   k_tb_copy  : bytes from src + z * sstride to dst + z * dstride (the base mask into one slot or into all of them, the slots'
 //                images into a larger block); k_tb_image: a slot's staged image into level 0 of its fresh pyramid.  Where the single
-//                route asks the runtime for a device-to-device copy.
+//                route asks the runtime for a device-to-device copy.  k_img_gray_b: the same place under lfvio_track_batch_format — the
+//                staged image in its encoding into grey at level 0 (img_gray_body, kernels_imgfmt.h); the CLAHE kernels then read
+//                level 0 (from_fresh) and the map equalizes it in place.
 #pragma once
 #include "kernels_clahe.h"
+#include "kernels_imgfmt.h"
 #include "kernels_trackframe.h"
 #include "trackbatch_plan.h"
 
@@ -70,11 +73,17 @@ __global__ __launch_bounds__(TB_COPY_THREADS) void k_tb_image(const TbSlot *slot
   tb_copy_body(s.image, s.fresh, bytes);
 }
 
-// ---- CLAHE: the staged image into level 0 of the fresh pyramid
-__global__ __launch_bounds__(CLAHE_THREADS) void k_clahe_hist_b(const TbSlot *slots, TbMem m, TbStage o, int W, int H, int tiles_x, int tw, int th) {
+__global__ __launch_bounds__(IMG_THREADS) void k_img_gray_b(const TbSlot *slots, TbMem m, TbStage o, int code, size_t step, int W, int H) {
   const TbView s = tb_view(slots, m, o);
   if (!s.active) return;
-  clahe_hist_body(s.image, W, H, tiles_x, tw, th, (int *)s.clahe);
+  img_gray_body(code, s.image, step, s.fresh, W, H);
+}
+
+// ---- CLAHE: the staged image (from_fresh: the grey image k_img_gray_b left at level 0) into level 0 of the fresh pyramid
+__global__ __launch_bounds__(CLAHE_THREADS) void k_clahe_hist_b(const TbSlot *slots, TbMem m, TbStage o, int from_fresh, int W, int H, int tiles_x, int tw, int th) {
+  const TbView s = tb_view(slots, m, o);
+  if (!s.active) return;
+  clahe_hist_body(from_fresh ? (const unsigned char *)s.fresh : s.image, W, H, tiles_x, tw, th, (int *)s.clahe);
 }
 __global__ __launch_bounds__(CLAHE_THREADS) void k_clahe_lut_b(const TbSlot *slots, TbMem m, TbStage o, int clip, float lut_scale, size_t lut_at) {
   const TbView s = tb_view(slots, m, o);
@@ -82,11 +91,11 @@ __global__ __launch_bounds__(CLAHE_THREADS) void k_clahe_lut_b(const TbSlot *slo
   clahe_lut_body((int *)s.clahe, clip, lut_scale, (unsigned char *)s.clahe + lut_at);
 }
 template <bool VEC>
-__global__ __launch_bounds__(CLAHE_THREADS) void k_clahe_map_b(const TbSlot *slots, TbMem m, TbStage o, int W, int H, int tiles_x, int tiles_y, int th, int sub, float inv_tw,
-                                                               float inv_th, size_t lut_at) {
+__global__ __launch_bounds__(CLAHE_THREADS) void k_clahe_map_b(const TbSlot *slots, TbMem m, TbStage o, int from_fresh, int W, int H, int tiles_x, int tiles_y, int th, int sub,
+                                                               float inv_tw, float inv_th, size_t lut_at) {
   const TbView s = tb_view(slots, m, o);
   if (!s.active) return;
-  clahe_map_body<VEC>(s.image, s.fresh, W, H, tiles_x, tiles_y, th, sub, inv_tw, inv_th, (const unsigned char *)s.clahe + lut_at);
+  clahe_map_body<VEC>(from_fresh ? (const unsigned char *)s.fresh : s.image, s.fresh, W, H, tiles_x, tiles_y, th, sub, inv_tw, inv_th, (const unsigned char *)s.clahe + lut_at);
 }
 
 // ---- the flow.  resident == 0: level k of the fresh pyramid; 1: of the resident one, where an earlier call built fewer levels

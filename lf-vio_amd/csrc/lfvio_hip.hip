@@ -51,6 +51,7 @@ constexpr ncclDataType_t ncclDouble = 8;
 #include "kernels_klt.h"
 #include "kernels_gft.h"
 #include "kernels_clahe.h"
+#include "kernels_imgfmt.h"
 #include "kernels_track.h"
 #include "kernels_trackframe.h"
 #include "kernels_trackbatch.h"
@@ -193,6 +194,13 @@ struct lfvio_ctx : CtxQueues {
     DevBuf<char> work;
     bool dirty = false;
   } clahe;
+  // lfvio_image_format_set (imgfmt.inc): the encoding of the images the single route's calls take (off after lfvio_create; survives
+  // lfvio_klt_reset and lfvio_track_frame_reset).  get(): what imgfmt_plan (image_format.h) takes
+  struct ImageFormatState {
+    bool on = false;
+    LfvioImageFormat f = {};
+    const LfvioImageFormat *get() const { return on ? &f : nullptr; }
+  } imgfmt;
   // lfvio_track_undistort (track.inc): the (id, un_pts_3d) pairs of the previous call — [4096 ints | 4096 x 3 floats] twice, allocated
   // at the first use; tstream.mcur holds the tstream.mcount resident pairs (0: the map is empty), tstream.time is that call's
   struct TrackState {
@@ -213,6 +221,7 @@ struct lfvio_ctx : CtxQueues {
     TbImage lay = {0, 0, 0};
     bool clahe_on = false, clahe_dirty = false;
     LfvioClaheIn cfg = {};
+    ImageFormatState imgfmt;  // lfvio_track_batch_format: the batch's, one for every slot
   } tbatch;
   std::string err;
   int batch = 0;
@@ -2166,6 +2175,8 @@ int lfvio_debug_query(lfvio_ctx *c, const char *key, double *out, int n) {
 #include "sfmchain.inc"
 
 #include "clahe.inc"
+
+#include "imgfmt.inc"
 
 #include "klt.inc"
 

@@ -79,6 +79,11 @@ int lfvio_track_batch_clahe(lfvio_ctx *c, const LfvioClaheIn *cfg) {
   return LFVIO_OK;
 }
 
+int lfvio_track_batch_format(lfvio_ctx *c, const LfvioImageFormat *fmt) {
+  if (!c) return LFVIO_ERR_ARG;
+  return imgfmt_set(c, c->tbatch.imgfmt, fmt);
+}
+
 int lfvio_track_batch_set_mask(lfvio_ctx *c, int slot, int width, int height, const unsigned char *pixels) {
   if (!c) return LFVIO_ERR_ARG;
   lfvio_ctx::TrackBatchState &b = c->tbatch;
@@ -141,13 +146,18 @@ int lfvio_track_batch_frame(lfvio_ctx *c, int count, const LfvioTrackFrameIn *in
   }
   const LfvioTrackFrameIn &f = in[bd.first];  // the shared fields
   const int W = f.width, H = f.height, S = f.num_samples, MC = f.max_count;
+  if (const char *why = imgfmt_call_check(b.imgfmt, W, H)) {
+    c->err = why;
+    return LFVIO_ERR_ARG;
+  }
+  const ImgfmtPlan im = imgfmt_plan(b.imgfmt.get(), W, H);
   const LfvioKltIn kin = trackframe_klt(&f);
   const LfvioGftIn gin = trackframe_gft(&f);
   const KltPlan full = klt_plan(W, H, 0, LFVIO_KLT_MAX_LEVEL);
   const int LU = klt_plan(W, H, f.win_size, f.max_level).levels_used;
   const GftWork gw = gft_work(W, H);
   const GftOffsets &wk = gw;  // what the kernels take
-  const size_t nI = (size_t)W * H;
+  const size_t nI = im.bytes;  // of one staged image; level 0 has W * H
   const bool rows = msg != nullptr, any_pub = bd.publishing > 0;
   TbShape shape = {};
   shape.slots = n, shape.publishing = bd.publishing, shape.active = bd.active;
@@ -196,25 +206,30 @@ int lfvio_track_batch_frame(lfvio_ctx *c, int count, const LfvioTrackFrameIn *in
   const TbSlot *slots = (const TbSlot *)(d + o.desc);
   const unsigned Z = (unsigned)n;
   hipStream_t fs = st.fs;
-  // level 0 of every fresh pyramid: the image, or the equalized image
+  // level 0 of every fresh pyramid: the image (converted to grey under a format), or the equalized image
+  const int conv = im.convert ? 1 : 0;
+  if (conv) {
+    hipLaunchKernelGGL(k_img_gray_b, dim3((W + IMG_COLS - 1) / IMG_COLS, (H + IMG_ROWS - 1) / IMG_ROWS, Z), dim3(IMG_THREADS), 0, fs, slots, m, o, im.code, im.step, W, H);
+    HIPCHK(c, hipGetLastError());
+  }
   if (b.clahe_on) {
     const ClahePlan p = clahe_plan(W, H, b.cfg);
     const int tiles = b.cfg.tiles_x * b.cfg.tiles_y, bands = (p.th + CLAHE_BAND_ROWS - 1) / CLAHE_BAND_ROWS;
     b.clahe_dirty = true;
-    hipLaunchKernelGGL(k_clahe_hist_b, dim3(tiles, bands, Z), dim3(CLAHE_THREADS), 0, fs, slots, m, o, W, H, b.cfg.tiles_x, p.tw, p.th);
+    hipLaunchKernelGGL(k_clahe_hist_b, dim3(tiles, bands, Z), dim3(CLAHE_THREADS), 0, fs, slots, m, o, conv, W, H, b.cfg.tiles_x, p.tw, p.th);
     HIPCHK(c, hipGetLastError());
     hipLaunchKernelGGL(k_clahe_lut_b, dim3(tiles, 1, Z), dim3(CLAHE_THREADS), 0, fs, slots, m, o, p.clip, p.lut_scale, CLAHE_TABLE_BYTES);
     HIPCHK(c, hipGetLastError());
     b.clahe_dirty = false;
     const dim3 grid((W + CLAHE_MAP_COLS - 1) / CLAHE_MAP_COLS, (b.cfg.tiles_y + 1) * bands, Z);
     if (W % 4 == 0)
-      hipLaunchKernelGGL(k_clahe_map_b<true>, grid, dim3(CLAHE_THREADS), 0, fs, slots, m, o, W, H, b.cfg.tiles_x, b.cfg.tiles_y, p.th, bands, p.inv_tw, p.inv_th,
+      hipLaunchKernelGGL(k_clahe_map_b<true>, grid, dim3(CLAHE_THREADS), 0, fs, slots, m, o, conv, W, H, b.cfg.tiles_x, b.cfg.tiles_y, p.th, bands, p.inv_tw, p.inv_th,
                          CLAHE_TABLE_BYTES);
     else
-      hipLaunchKernelGGL(k_clahe_map_b<false>, grid, dim3(CLAHE_THREADS), 0, fs, slots, m, o, W, H, b.cfg.tiles_x, b.cfg.tiles_y, p.th, bands, p.inv_tw, p.inv_th,
+      hipLaunchKernelGGL(k_clahe_map_b<false>, grid, dim3(CLAHE_THREADS), 0, fs, slots, m, o, conv, W, H, b.cfg.tiles_x, b.cfg.tiles_y, p.th, bands, p.inv_tw, p.inv_th,
                          CLAHE_TABLE_BYTES);
     HIPCHK(c, hipGetLastError());
-  } else {
+  } else if (!conv) {
     hipLaunchKernelGGL(k_tb_image, dim3((unsigned)((nI + TB_COPY_BYTES - 1) / TB_COPY_BYTES), 1, Z), dim3(TB_COPY_THREADS), 0, fs, slots, m, o, nI);
     HIPCHK(c, hipGetLastError());
   }

@@ -22,6 +22,11 @@ static int track_frame_run(lfvio_ctx *c, const LfvioTrackFrameIn *in, LfvioTrack
     return LFVIO_ERR_ARG;
   }
   const int W = in->width, H = in->height, S = in->num_samples, MC = in->max_count, n0 = s.count;
+  if (const char *why = imgfmt_call_check(c->imgfmt, W, H)) {
+    c->err = why;
+    return LFVIO_ERR_ARG;
+  }
+  const ImgfmtPlan im = imgfmt_plan(c->imgfmt.get(), W, H);
   const bool pub = in->publish != 0;
   if (!trackframe_out_check(out, nullptr) || (pub && !s.mask_fits(W, H))) {  // (a message's rows: lfvio_track_frame_message's check)
     c->err = "lfvio_track_frame: a null array in out, or a base mask that is not the image's size";
@@ -33,7 +38,7 @@ static int track_frame_run(lfvio_ctx *c, const LfvioTrackFrameIn *in, LfvioTrack
   const int LU = klt_plan(W, H, in->win_size, in->max_level).levels_used;
   const TrackCam cam = track_cam(*in->camera);
   const GftWork wk = gft_work(W, H);
-  const size_t B = (size_t)trackframe_bound(n0, MC, pub), N0 = (size_t)n0, nI = (size_t)W * H;
+  const size_t B = (size_t)trackframe_bound(n0, MC, pub), N0 = (size_t)n0, nI = im.bytes;
   FeatStage st(c);
   // up
   const size_t oW = st.take(pub ? (size_t)S * 32 : 0), oI = st.take(nI), in_end = st.end;
@@ -65,7 +70,7 @@ static int track_frame_run(lfvio_ctx *c, const LfvioTrackFrameIn *in, LfvioTrack
   // 1: the flow
   unsigned char *fresh;
   const unsigned char *prev;
-  if (int rc = klt_pyramid(c, st.fs, (const unsigned char *)(d + oI), W, H, full, LU, &prev, &fresh)) return rc;
+  if (int rc = klt_pyramid(c, st.fs, (const unsigned char *)(d + oI), im, W, H, full, LU, &prev, &fresh)) return rc;
   if (n0) {
     hipLaunchKernelGGL(k_klt_track, dim3(n0), dim3(KLT_THREADS), 0, st.fs, klt_args(&kin, full, LU), n0, prev, (const unsigned char *)fresh,
                        (const float *)have.pts, (float *)(d + oN), (unsigned char *)(d + oSt), (int *)nullptr);

@@ -1,6 +1,8 @@
 // feature_tracker.cpp — see feature_tracker.h.  Reference lines are relative to the reference's feature_tracker/src.
 #include "feature_tracker.h"
 
+#include "../csrc/image_format.h"
+
 #include <algorithm>
 #include <cstring>
 #include <functional>
@@ -40,9 +42,14 @@ FeatureTracker::~FeatureTracker() {
 const char *FeatureTracker::error() const { return ctx_ && error_.empty() ? lfvio_last_error(ctx_) : error_.c_str(); }
 
 int FeatureTracker::onImage(double stamp, int width, int height, int step, const unsigned char *pixels, TraceImage *msg) {
+  return onImage(stamp, width, height, step, LFVIO_IMG_MONO8, pixels, msg);
+}
+
+int FeatureTracker::onImage(double stamp, int width, int height, int step, int encoding, const unsigned char *pixels, TraceImage *msg) {
   if (!ctx_) return status;
-  if (!pixels || !msg || width < 1 || height < 1 || step < width) {
-    error_ = "FeatureTracker::onImage: null pixels or msg, or step < width";
+  const LfvioImageFormat format = {encoding, step};
+  if (!pixels || !msg || width < 1 || height < 1 || step < 1 || imgfmt_check(format, width, height)) {
+    error_ = "FeatureTracker::onImage: null pixels or msg, an unknown encoding, or step < width * bytes per pixel";
     return status = LFVIO_ERR_ARG;
   }
   const ImageGate::Stamp what = gate.onStamp(stamp);  // feature_tracker_node.cpp:30-62
@@ -68,15 +75,15 @@ int FeatureTracker::onImage(double stamp, int width, int height, int step, const
       const LfvioClaheIn clahe = {3.0, 8, 8};
       rc = lfvio_clahe_set(ctx_, cfg_.equalize ? &clahe : nullptr);
     }
+    if (rc == LFVIO_OK) rc = lfvio_image_format_set(ctx_, &format);  // (mono8 with step == width: the same as none)
     if (rc != LFVIO_OK) return status = rc;
-    ready_ = true;
+    format_ = format, ready_ = true;
   }
-  const unsigned char *image = pixels;
-  if (step != width) {  // the device takes rows of `width` bytes
-    packed_.resize((size_t)width * height);
-    for (int y = 0; y < height; y++) std::memcpy(packed_.data() + (size_t)y * width, pixels + (size_t)y * step, (size_t)width);
-    image = packed_.data();
+  if (format.encoding != format_.encoding || format.step != format_.step) {  // a driver that changes its rows
+    if (int rc = lfvio_image_format_set(ctx_, &format)) return status = rc;
+    format_ = format;
   }
+  const unsigned char *image = pixels;  // height rows of step bytes: no repacking on the host
   const bool pub = gate.publish;
   const int S = cfg_.num_samples;
   if (pub) {  // num_samples x 8 raw outputs of the generator, row-major; nothing is drawn for a frame that is only tracked

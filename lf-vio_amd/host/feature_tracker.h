@@ -1,7 +1,8 @@
 // feature_tracker.h — the feature tracker node on the host: img_callback (feature_tracker/src/feature_tracker_node.cpp:28-178) around ONE
 // device call per image, lfvio_track_frame_message (include/lfvio.h), which runs readImage, updateID and the feature message on a
-// track table resident in the context.  What is left here is the node's bookkeeping (image_gate.h), the row repacking of an image
-// whose step is not its width, the base mask and CLAHE setting at the first use, and the generator of rejectWithF's sample sets.
+// track table resident in the context.  What is left here is the node's bookkeeping (image_gate.h), the base mask, the CLAHE setting and
+// the image format (lfvio_image_format_set: the record's rows go up as they are, padded, colour or 16-bit, and the device makes grey
+// of them) at the first use, and the generator of rejectWithF's sample sets.
 // Not compiled into the test suite's CPU build of the host sources (oracle/Makefile): only host/Makefile builds it.
 #pragma once
 #include <random>
@@ -43,6 +44,8 @@ class FeatureTracker {
   // One sensor_msgs/Image (mono8, `step` bytes per row).  Returns a Result, or the negative status of the device call that failed
   // (`status`, error()): no silent continuation.  PUBLISHED: *msg is the feature message, stamped `stamp`; otherwise msg is untouched.
   int onImage(double stamp, int width, int height, int step, const unsigned char *pixels, TraceImage *msg);
+  // ... in the encoding `encoding` (LFVIO_IMG_*, the type-10 record's code): height rows of `step` bytes, handed over as they are
+  int onImage(double stamp, int width, int height, int step, int encoding, const unsigned char *pixels, TraceImage *msg);
 
   const char *error() const;
   int status = LFVIO_OK;
@@ -54,7 +57,7 @@ class FeatureTracker {
   lfvio_ctx *ctx_ = nullptr;
   bool own_ = false, ready_ = false;
   std::mt19937 rng_;
-  std::vector<unsigned char> packed_;
+  LfvioImageFormat format_ = {LFVIO_IMG_MONO8, 0};  // what the context's format was last set to (ready_)
   std::vector<unsigned> words_;
   std::vector<float> pts_, un_pts_, un_pts_3d_, velocity_3d_, rows_;
   std::vector<int> ids_, track_cnt_;

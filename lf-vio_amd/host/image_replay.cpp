@@ -60,7 +60,7 @@ int trackRecording(FeatureTracker &tracker, const char *in_path, std::vector<cha
     std::memcpy(&stamp, buf.data(), 8), std::memcpy(dims, buf.data() + 8, 16);
     st.raw_images++;
     const auto t0 = std::chrono::steady_clock::now();
-    const int what = tracker.onImage(stamp, (int)dims[0], (int)dims[1], (int)dims[2], (const unsigned char *)buf.data() + 24, &msg);
+    const int what = tracker.onImage(stamp, (int)dims[0], (int)dims[1], (int)dims[2], (int)dims[3], (const unsigned char *)buf.data() + 24, &msg);
     st.tracker_ms += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e3;
     if (what < 0) {  // a device call failed: no silent continuation
       rc = -2;

@@ -2,6 +2,8 @@
 #include "replay.h"
 #include <chrono>
 
+#include "../csrc/image_format.h"
+
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
@@ -41,13 +43,19 @@ bool Trace::read(std::FILE *f) {
         error = "image record shorter than its header";
         return false;
       }
-      if (ih.width < 16 || ih.width > 8192 || ih.height < 16 || ih.height > 8192 || ih.step < ih.width || ih.encoding != 0 ||
+      // (step 0 is the ABI's "rows contiguous", not a record's: a record states its step)
+      const bool sized = ih.width <= 8192 && ih.height <= 8192 && ih.step >= 1 && ih.step <= LFVIO_IMG_MAX_STEP && ih.encoding <= LFVIO_IMG_MONO16_BE;
+      if (!sized || imgfmt_check(LfvioImageFormat{(int)ih.encoding, (int)ih.step}, (int)ih.width, (int)ih.height) ||
           head[1] != sizeof ih + (uint64_t)ih.height * ih.step) {
-        error = "image record: a size outside [16, 8192], step < width, an unknown encoding or a wrong length";
+        error = "image record: a size outside [16, 8192], step < width * bytes per pixel, an unknown encoding or a wrong length";
         return false;
       }
       if (!raw_images.empty() && (raw_images[0].width != ih.width || raw_images[0].height != ih.height)) {
         error = "images of differing size";
+        return false;
+      }
+      if (!raw_images.empty() && raw_images[0].encoding != ih.encoding) {
+        error = "images of differing encoding";
         return false;
       }
       const long at = std::ftell(f);
@@ -56,7 +64,7 @@ bool Trace::read(std::FILE *f) {
         error = "truncated record";
         return false;
       }
-      raw_images.push_back({ih.t, ih.width, ih.height, ih.step, (uint64_t)at});
+      raw_images.push_back({ih.t, ih.width, ih.height, ih.step, (uint64_t)at, ih.encoding});
       continue;
     }
     buf.resize(head[1]);

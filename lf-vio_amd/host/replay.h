@@ -40,12 +40,15 @@
 //                                     (WindowEstimator::constructSfm), then the PnP loop and the same alignment.  A bootstrap
 //                                     record, an SfM result or an SfM structure for the same image wins.
 //
-//   type 10 = sensor_msgs/Image       f64 stamp, u32 width, u32 height, u32 step, u32 encoding (0: mono8 / 8UC1), then height x step bytes:
-//                                     a raw camera image, for the tracker of feature_tracker.h (image_replay.h runs it over a recording
-//                                     and replaces every image by what the node would have published for it).  The loader keeps the
-//                                     stamp, the sizes and the file offset of the pixels, not the pixels.  Refused: a record shorter
-//                                     or longer than its sizes say, step < width, a width or height outside [16, 8192], another
-//                                     encoding, images of differing size, a file that holds both type 2 and type 10.  replay()
+//   type 10 = sensor_msgs/Image       f64 stamp, u32 width, u32 height, u32 step, u32 encoding, then height x step bytes: a raw camera
+//                                     image, for the tracker of feature_tracker.h (image_replay.h runs it over a recording and
+//                                     replaces every image by what the node would have published for it).  encoding: the codes of
+//                                     include/lfvio.h and csrc/image_format.h — 0 mono8 / 8UC1, 2 bgr8, 3 rgb8, 4 bgra8, 5 rgba8,
+//                                     6 mono16 (little endian), 7 mono16 (big endian); the device makes grey of them.  The loader
+//                                     keeps the stamp, the sizes, the code and the file offset of the pixels, not the pixels.
+//                                     Refused: a record shorter or longer than its sizes say, step < width * bytes per pixel or
+//                                     above 65536, a width or height outside [16, 8192], a code outside the table (1, or above 7),
+//                                     images of differing size or encoding, a file that holds both type 2 and type 10.  replay()
 //                                     does not look at raw images.
 //
 // Unknown record types are skipped, so a recorder can add its own.
@@ -72,6 +75,7 @@ struct TraceRawImage {  // record type 10, without its pixels
   double t;
   uint32_t width, height, step;
   uint64_t offset;  // of the first pixel, from the start of the file
+  uint32_t encoding;  // LFVIO_IMG_*
 };
 struct TraceBoot {
   WindowEstimator::Bootstrap state;

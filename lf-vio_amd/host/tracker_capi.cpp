@@ -67,7 +67,8 @@ int lfvio_host_replay_images(void *h, const char *path, const char *traj_path, i
 }
 
 // the raw images of a trace file as the loader sees them: out[cap][5] = {stamp, width, height, step, offset of the pixels}; returns
-// their number, -3: unreadable or refused (the loader's message in err[err_cap], if given)
+// their number, -3: unreadable or refused (the loader's message in err[err_cap], if given).  lfvio_host_trace_raw_encoding: the
+// code they share (a file of differing codes is refused), -1 without raw images, -3 as above.
 int lfvio_host_trace_raw_images(const char *path, int cap, double *out, char *err, int err_cap) {
   Trace trace;
   if (!trace.load(path)) {
@@ -79,6 +80,11 @@ int lfvio_host_trace_raw_images(const char *path, int cap, double *out, char *er
     out[5 * k] = r.t, out[5 * k + 1] = r.width, out[5 * k + 2] = r.height, out[5 * k + 3] = r.step, out[5 * k + 4] = (double)r.offset;
   }
   return (int)trace.raw_images.size();
+}
+int lfvio_host_trace_raw_encoding(const char *path) {
+  Trace trace;
+  if (!trace.load(path)) return -3;
+  return trace.raw_images.empty() ? -1 : (int)trace.raw_images[0].encoding;
 }
 
 }  // extern "C"

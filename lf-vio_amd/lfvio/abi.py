@@ -657,6 +657,17 @@ class ClaheInC(C.Structure):
 CLAHE_MAX_TILES = 16  # LFVIO_CLAHE_MAX_TILES
 
 
+class ImageFormatC(C.Structure):
+    """LfvioImageFormat (include/lfvio.h)."""
+    _fields_ = [("encoding", C.c_int), ("step", C.c_int)]
+
+
+# LFVIO_IMG_*: the encodings of lfvio_image_format_set and of the type-10 record
+IMG_MONO8, IMG_BGR8, IMG_RGB8, IMG_BGRA8, IMG_RGBA8, IMG_MONO16, IMG_MONO16_BE = 0, 2, 3, 4, 5, 6, 7
+IMG_BPP = {IMG_MONO8: 1, IMG_BGR8: 3, IMG_RGB8: 3, IMG_BGRA8: 4, IMG_RGBA8: 4, IMG_MONO16: 2, IMG_MONO16_BE: 2}
+IMG_MAX_STEP = 65536  # LFVIO_IMG_MAX_STEP
+
+
 class CameraC(C.Structure):
     """LfvioCamera (include/lfvio.h).  The fields behind poly are PINHOLE's and MEI's; positional construction with the eleven
     values of an OCam camera leaves them zero."""
@@ -765,7 +776,7 @@ HIP_SYMBOLS = [
     "lfvio_shard_finish", "lfvio_shard_restart", "lfvio_shard_enqueue", "lfvio_shard_poll", "lfvio_triangulate", "lfvio_shift_depth", "lfvio_preintegrate",
     "lfvio_two_view", "lfvio_vi_align", "lfvio_pnp", "lfvio_sfm_ba", "lfvio_sfm_construct", "lfvio_relative_pose",
     "lfvio_klt_track", "lfvio_klt_reset", "lfvio_klt_level", "lfvio_gft_detect", "lfvio_gft_set_mask", "lfvio_gft_response",
-    "lfvio_clahe_set", "lfvio_clahe_apply",
+    "lfvio_clahe_set", "lfvio_clahe_apply", "lfvio_image_format_set", "lfvio_image_gray", "lfvio_track_batch_format",
     "lfvio_track_reject", "lfvio_track_undistort", "lfvio_track_reset", "lfvio_track_frame", "lfvio_track_frame_reset",
     "lfvio_track_frame_message",
     "lfvio_track_batch_reserve", "lfvio_track_batch_set_mask", "lfvio_track_batch_clahe", "lfvio_track_batch_frame", "lfvio_track_batch_reset",
@@ -854,6 +865,10 @@ def load_hip_library(path=None):
     if hasattr(lib, "lfvio_clahe_set"):
         lib.lfvio_clahe_set.argtypes = [C.c_void_p, C.POINTER(ClaheInC)]
         lib.lfvio_clahe_apply.argtypes = [C.c_void_p, C.POINTER(ClaheInC), C.c_int, C.c_int] + [C.POINTER(C.c_ubyte)] * 3
+    if hasattr(lib, "lfvio_image_format_set"):
+        lib.lfvio_image_format_set.argtypes = [C.c_void_p, C.POINTER(ImageFormatC)]
+        lib.lfvio_image_gray.argtypes = [C.c_void_p, C.POINTER(ImageFormatC), C.c_int, C.c_int] + [C.POINTER(C.c_ubyte)] * 2
+        lib.lfvio_track_batch_format.argtypes = [C.c_void_p, C.POINTER(ImageFormatC)]
     if hasattr(lib, "lfvio_track_reject"):
         lib.lfvio_track_reject.argtypes = [C.c_void_p, C.POINTER(TrackRejectInC), C.POINTER(C.c_ubyte), C.POINTER(TrackRejectOutC), _dp, _dp]
         lib.lfvio_track_undistort.argtypes = [C.c_void_p, C.POINTER(TrackUndistortInC)] + [C.POINTER(C.c_float)] * 3 + [C.POINTER(C.c_int)]

@@ -571,6 +571,29 @@ class Engine:
         self._check(rc, "lfvio_clahe_apply")
         return (out, lut) if want_lut else out
 
+    def image_format(self, encoding=None, step=0, check=True):
+        """lfvio_image_format_set: the images of every later klt_track / track_frame / track_frame_message are `height` rows of `step`
+        bytes (0: width * bytes per pixel) in `encoding` (abi.IMG_*), passed as a uint8 array [height, step] with size / width and
+        height naming the image's own; image_format(None): off, the state of a fresh context.  Returns the error code."""
+        rc = self.lib.lfvio_image_format_set(self.ctx, None if encoding is None else C.byref(abi.ImageFormatC(encoding, step)))
+        if check:
+            self._check(rc, "lfvio_image_format_set")
+        return rc
+
+    def image_gray(self, rows, width, height, encoding=None, step=0, out=None, check=True):
+        """lfvio_image_gray: `rows` (uint8, height * step bytes in `encoding`; None: a null pointer) as the grey image [height, width]
+        uint8, a new array or `out`.  encoding None: a null format (mono8, rows contiguous).  check=False returns (error code, out)."""
+        up = C.POINTER(C.c_ubyte)
+        px = None if rows is None else np.ascontiguousarray(rows, dtype=np.uint8)
+        if out is None:
+            out = np.zeros((min(max(height, 1), 8192), min(max(width, 1), 8192)), dtype=np.uint8)
+        rc = self.lib.lfvio_image_gray(self.ctx, None if encoding is None else C.byref(abi.ImageFormatC(encoding, step)), width, height,
+                                       None if px is None else px.ctypes.data_as(up), out.ctypes.data_as(up))
+        if not check:
+            return rc, out
+        self._check(rc, "lfvio_image_gray")
+        return out
+
     @staticmethod
     def camera(cam):
         """A CameraC from a dict; None: a null pointer.  model (optional) LFVIO_CAM_OCAM: cx, cy, c, d, e, poly [5];
@@ -774,6 +797,13 @@ class Engine:
             rc = self.lib.lfvio_track_batch_clahe(self.ctx, C.byref(abi.ClaheInC(clip_limit, tiles[0], tiles[1])))
         if check:
             self._check(rc, "lfvio_track_batch_clahe")
+        return rc
+
+    def track_batch_format(self, encoding=None, step=0, check=True):
+        """lfvio_track_batch_format: image_format for the batch; track_batch_format(None): off.  Returns the error code."""
+        rc = self.lib.lfvio_track_batch_format(self.ctx, None if encoding is None else C.byref(abi.ImageFormatC(encoding, step)))
+        if check:
+            self._check(rc, "lfvio_track_batch_format")
         return rc
 
     def track_batch_reset(self, slot=-1, check=True):

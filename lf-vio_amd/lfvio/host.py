@@ -85,6 +85,8 @@ class HostEstimator:
             L.lfvio_host_track_trace.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, _dp]
             L.lfvio_host_replay_images.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_int, ip, _dp]
             L.lfvio_host_trace_raw_images.argtypes = [C.c_char_p, C.c_int, _dp, C.c_char_p, C.c_int]
+            if hasattr(L, "lfvio_host_trace_raw_encoding"):
+                L.lfvio_host_trace_raw_encoding.argtypes = [C.c_char_p]
         self.L = L
         self.h = L.lfvio_host_create()
 
@@ -256,6 +258,11 @@ class HostEstimator:
         o, err = np.zeros((cap, 5)), C.create_string_buffer(256)
         n = self.L.lfvio_host_trace_raw_images(str(trace_path).encode(), cap, _p(o), err, 256)
         return n, o[:max(min(n, cap), 0)].copy(), err.value.decode()
+
+    def trace_raw_encoding(self, trace_path):
+        """The encoding (abi.IMG_*) the raw images of a trace file share, as the host loader keeps it; -1: no raw images, -3: refused."""
+        self._tracker()
+        return self.L.lfvio_host_trace_raw_encoding(str(trace_path).encode())
 
     def decode_features(self, trace_path, image_index, cap=4096):
         ids, pts, st = np.zeros(cap, dtype=np.int32), np.zeros((cap, 8)), np.zeros(1)

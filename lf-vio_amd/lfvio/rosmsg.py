@@ -150,6 +150,41 @@ def de_image(buf):
     return stamp, np.frombuffer(buf, dtype=np.uint8, count=n, offset=o + 9).reshape(h, step)[:, :w].copy(), step, enc.decode()
 
 
+# the encodings cv_bridge::toCvCopy(img_msg, MONO8) makes grey of, as the codes of include/lfvio.h (LFVIO_IMG_*); mono16 becomes 7
+# where the message says is_bigendian
+IMAGE_CODES = {b"mono8": 0, b"8UC1": 0, b"bgr8": 2, b"rgb8": 3, b"bgra8": 4, b"rgba8": 5, b"mono16": 6}
+IMAGE_BPP = {0: 1, 2: 3, 3: 3, 4: 4, 5: 4, 6: 2, 7: 2}
+
+
+def ser_image_raw(seq, stamp, rows, width, encoding, is_bigendian=0, frame_id=b"camera"):
+    """sensor_msgs/Image from its rows as they are: rows [height, step] uint8 (padding included), `width` pixels per row, `encoding`
+    the message's string (bytes).  Nothing is checked: the tests write refused messages with it too."""
+    a = np.ascontiguousarray(rows, dtype=np.uint8)
+    h, step = a.shape
+    return _header(seq, stamp, frame_id) + struct.pack("<II", h, width) + _string(encoding) + struct.pack("<BI", is_bigendian, step) + struct.pack("<I", h * step) + a.tobytes()
+
+
+def de_image_any(buf):
+    """-> (stamp, rows [height, step] uint8, width, step, code) of a sensor_msgs/Image in one of the encodings the node's cv_bridge call
+    takes (feature_tracker_node.cpp:64-78): mono8, 8UC1, bgr8, rgb8, bgra8, rgba8, mono16 (IMAGE_CODES; big-endian mono16: code 7).
+    The rows are the message's, padding included.  Anything else, or a step below width * bytes per pixel, raises ValueError."""
+    stamp, o = _read_header(buf, 0)
+    h, w = struct.unpack_from("<II", buf, o)
+    (ln,) = struct.unpack_from("<I", buf, o + 8)
+    enc = bytes(buf[o + 12:o + 12 + ln])
+    o += 12 + ln
+    big, step = struct.unpack_from("<BI", buf, o)
+    (n,) = struct.unpack_from("<I", buf, o + 5)
+    if enc not in IMAGE_CODES:
+        raise ValueError(f"sensor_msgs/Image encoding {enc!r}: not one of {sorted(k.decode() for k in IMAGE_CODES)}")
+    code = IMAGE_CODES[enc]
+    if code == 6 and big:
+        code = 7
+    if step < w * IMAGE_BPP[code] or n != h * step:
+        raise ValueError(f"sensor_msgs/Image: {n} bytes are not {h} rows of {step} (width {w}, {IMAGE_BPP[code]} bytes per pixel)")
+    return stamp, np.frombuffer(buf, dtype=np.uint8, count=n, offset=o + 9).reshape(h, step).copy(), w, step, code
+
+
 def ser_bool(v):
     return struct.pack("<B", 1 if v else 0)
 

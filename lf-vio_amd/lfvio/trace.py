@@ -85,9 +85,16 @@ class TraceWriter:
     def truth(self, t, p, q_xyzw):
         self._rec(REC_TRUTH, struct.pack("<8d", t, *p, *q_xyzw))
 
-    def image(self, t, img, step=None):
-        """One sensor_msgs/Image, mono8 (type 10): img [height, width] uint8; step: bytes per row in the record (default: width;
-        larger: rows padded with zeros, as a driver with aligned rows sends them)."""
+    def image(self, t, img, step=None, encoding=0, width=None):
+        """One sensor_msgs/Image (type 10).  encoding 0 (mono8): img [height, width] uint8; step: bytes per row in the record (default:
+        width; larger: rows padded with zeros, as a driver with aligned rows sends them).  Another encoding (abi.IMG_*): img is the
+        message's rows as they are, [height, step] uint8 with `width` pixels in each (padding included; step is the array's)."""
+        if encoding != 0:
+            a = np.ascontiguousarray(img, dtype=np.uint8)
+            h, step = a.shape
+            assert width is not None and step >= width * abi.IMG_BPP[encoding]
+            self._rec(REC_IMAGE, struct.pack("<dIIII", t, width, h, step, encoding) + a.tobytes())
+            return
         a = np.ascontiguousarray(img, dtype=np.uint8)
         h, w = a.shape
         step = w if step is None else int(step)
@@ -101,9 +108,10 @@ class TraceWriter:
 
 
 def read_trace(path):
-    """-> dict(imu [n,7], images [(t, array[n,9] float32)], bootstrap array or None, truth [n,8], raw_images [(t, array[h,w] uint8)],
-    restart_stamps [stamp or None], order [record types])"""
-    out = dict(imu=[], images=[], raw_images=[], raw_steps=[], restart_stamps=[], bootstrap=None, bootstraps=[], restarts=[], truth=[], relos=[], sfms=[], structures=[], relatives=[], order=[])
+    """-> dict(imu [n,7], images [(t, array[n,9] float32)], bootstrap array or None, truth [n,8], raw_images [(t, array)],
+    raw_steps, raw_encodings, restart_stamps [stamp or None], order [record types]).  A raw image is [h, w] uint8 (mono8), [h, w, C]
+    uint8 in the record's channel order (the colour encodings) or [h, w] uint16 (mono16, either byte order, as values)."""
+    out = dict(imu=[], images=[], raw_images=[], raw_steps=[], raw_encodings=[], restart_stamps=[], bootstrap=None, bootstraps=[], restarts=[], truth=[], relos=[], sfms=[], structures=[], relatives=[], order=[])
     with open(path, "rb") as f:
         head = f.read(8)
         assert head[:4] == MAGIC and struct.unpack("<I", head[4:])[0] == 1
@@ -149,9 +157,17 @@ def read_trace(path):
                 out["truth"].append(struct.unpack("<8d", p))
             elif kind == REC_IMAGE:
                 t, w, h, step, enc = struct.unpack("<dIIII", p[:24])
-                assert enc == 0 and len(p) == 24 + h * step
-                out["raw_images"].append((t, np.frombuffer(p[24:], dtype=np.uint8).reshape(h, step)[:, :w].copy()))
+                assert enc in abi.IMG_BPP and len(p) == 24 + h * step
+                bpp = abi.IMG_BPP[enc]
+                px = np.frombuffer(p[24:], dtype=np.uint8).reshape(h, step)[:, :w * bpp].reshape(h, w, bpp)
+                if enc in (abi.IMG_MONO16, abi.IMG_MONO16_BE):
+                    lo, hi = (0, 1) if enc == abi.IMG_MONO16 else (1, 0)
+                    img = px[:, :, lo].astype(np.uint16) | (px[:, :, hi].astype(np.uint16) << 8)
+                else:
+                    img = px[:, :, 0].copy() if bpp == 1 else px.copy()
+                out["raw_images"].append((t, img))
                 out["raw_steps"].append(step)
+                out["raw_encodings"].append(enc)
     out["imu"] = np.array(out["imu"]).reshape(-1, 7)
     out["truth"] = np.array(out["truth"]).reshape(-1, 8)
     return out

@@ -13,8 +13,9 @@ records from a `stamp x y z qx qy qz qw` text file for tools/ate.py.  /pose_grap
 closures, estimator_node.cpp:197-201) becomes record type 6; /vins_estimator/lfvt_sfm (the SfM hook of INTEGRATION.md section 3:
 all_image_frame's stamps, R, T just before visualInitialAlign()) becomes record type 7.  No ROS installation is needed.
 
---image TOPIC: a bag of the CAMERA topic (sensor_msgs/Image, mono8 or 8UC1) and the IMU, recorded without the reference's tracker:
-every image becomes a raw-image record (type 10) and the feature and restart topics are left out — the tracker of this library
+--image TOPIC: a bag of the CAMERA topic (sensor_msgs/Image: mono8, 8UC1, bgr8, rgb8, bgra8, rgba8 or mono16 of either byte order —
+what the node's cv_bridge call takes) and the IMU, recorded without the reference's tracker: every image becomes a raw-image record
+(type 10), its rows written through unchanged in their encoding, and the feature and restart topics are left out — the tracker of this library
 publishes both when the recording is tracked (lfvio_host_track_trace / lfvio_host_replay_images)."""
 import argparse
 import os
@@ -38,8 +39,11 @@ def convert(bag_path, out_path, imu_topic="/imu0", feature_topic="/feature_track
             w.imu(stamp, acc, gyr)
             n["imu"] += 1
         elif image_topic and topic == image_topic:
-            stamp, img, step, _ = rosmsg.de_image(payload)
-            w.image(stamp, img, step=step)
+            stamp, rows, width, step, code = rosmsg.de_image_any(payload)
+            if code == 0:
+                w.image(stamp, rows[:, :width], step=step)
+            else:
+                w.image(stamp, rows, encoding=code, width=width)
             n["raw_images"] = n.get("raw_images", 0) + 1
         elif image_topic and topic in (feature_topic, restart_topic):  # somebody else's tracker: a recording holds one or the other
             n["other"] += 1
