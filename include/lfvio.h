@@ -839,10 +839,37 @@ int lfvio_image_gray(lfvio_ctx *ctx, const LfvioImageFormat *fmt, int width, int
  *             * rho2)).  Non-finite results keep IEEE semantics (the root's argument goes negative far outside the image for
  *             xi > 1).  Everything behind the lift (the norm, P / n, un_pts, the casts, the map, the velocity) is the same for
  *             all models.  tests/camera_ref.py restates these two lifts; they were never compared with the reference's Eigen build
- *             either.  KANNALA_BRANDT (EquidistantCamera) is not served: its lift has no bitwise specification.
- *   the camera LFVIO_ERR_ARG of every call that takes an LfvioCamera: model 1 and any model outside {0, 2, 3}; for PINHOLE and MEI a
- *             non-finite value among cx, cy, fx, fy, k1, k2, p1, p2, fx == 0 or fy == 0, and for MEI a non-finite xi.  An OCam
- *             camera's fx .. xi are not read, a PINHOLE or MEI camera's c, d, e, poly are not: they may be indeterminate.
+ *             either.
+ *   the lift of LFVIO_CAM_KANNALA_BRANDT (EquidistantCamera.cc:428-442 over backprojectSymmetric :716-818): the
+ *             reference's MATHEMATICS — theta is the smallest non-negative real root of f(theta) = theta + k2 theta^3 + k3 theta^5 +
+ *             k4 theta^7 + k5 theta^9 = r, P = (sin theta cos phi, sin theta sin phi, cos theta) — in a text of this library's own,
+ *             made of + - * / sqrt floor and comparisons alone, in double, every operation rounded on its own, grouped as written:
+ *             the fields: cx, cy = u0, v0; fx, fy = mu, mv; poly[0 .. 3] = k2, k3, k4, k5; nothing else is read.
+ *             F(th):  t = th * th, th * (1.0 + t * (k2 + t * (k3 + t * (k4 + t * k5))))
+ *             F'(th): t = th * th, 1.0 + t * (3.0 * k2 + t * (5.0 * k3 + t * (7.0 * k4 + t * (9.0 * k5))))
+ *             host, once per camera: inv11 .. inv23 as for PINHOLE; theta_lim = the last point of the grid j * (pi / 4096), j = 0 ..
+ *                         4096, up to which F' > 0 held at every grid point (pi if at all of them), r_lim = F(theta_lim): on
+ *                         [0, theta_lim] the polynomial increases from 0, so for r <= r_lim its root there is the smallest one.
+ *             x = inv11 * (double)px + inv13, y = inv22 * (double)py + inv23, r = sqrt(x * x + y * y)
+ *             th = r < theta_lim ? r : theta_lim; 13 times: th = th - (F(th) - r) / F'(th), th = th < 0.0 ? 0.0 : th,
+ *                         th = th > theta_lim ? theta_lim : th; theta = r <= r_lim ? th : r (beyond the monotone range and for a NaN
+ *                         theta = r: the reference's own fallback when it finds no admissible root, :809-812)
+ *             sin, cos:   n = floor(theta * invpio2 + 0.5), y = ((theta - n * pio2_1) - n * pio2_2) - n * pio2_2t, q = n - 4.0 *
+ *                         floor(n / 4.0), all in double; z = y * y, s = y + (z * y) * (S1 + z * (S2 + .. z * S6)), c = 1.0 - (0.5 * z
+ *                         - z * (z * (C1 + z * (C2 + .. z * C6)))) with fdlibm's constants (camera_kb.h); q = 1 and 3 swap s and c,
+ *                         the sine is negated for q = 2 and 3, the cosine for q = 1 and 2.  Nothing is converted to an integer.
+ *             r < 1e-10: cphi = 1.0, sphi = 0.0 (:722-725); otherwise cphi = x / r, sphi = y / r.  P = (s * cphi, s * sphi, c).
+ *             Stated deviations: x / r, y / r in place of cos(atan2(y, x)), sin(atan2(y, x)); Newton's method in place of the
+ *             companion matrix's eigenvalues; a calibration whose polynomial turns down and comes up again inside [0, pi] would
+ *             give the reference a root beyond theta_lim that this lift does not look for (none of the reference's three has one),
+ *             and the grid can miss a dip of F' narrower than a step.  tests/kb_ref.py restates this lift and holds it to a
+ *             50-digit evaluation of the reference's definition (tests/test_kb_ref.py: the root to 3.6 eps where F' >= 0.1, sin and
+ *             cos to 5.4 ulp, the bearing to 25.6 eps where F' >= 0.1); the device gives the restatement's bits.
+ *   the camera LFVIO_ERR_ARG of every call that takes an LfvioCamera: models 1 and 4 and any model outside {0, 2, 3, 5}; for PINHOLE
+ *             and MEI a non-finite value among cx, cy, fx, fy, k1, k2, p1, p2, fx == 0 or fy == 0, and for MEI a non-finite xi; for
+ *             KANNALA_BRANDT a non-finite value among cx, cy, fx, fy, poly[0 .. 3], fx == 0 or fy == 0.  An OCam camera's fx .. xi are
+ *             not read, a PINHOLE or MEI camera's c, d, e, poly are not, a KANNALA_BRANDT camera's c, d, e, poly[4], k1 .. xi are
+ *             not: they may be indeterminate.
  *
  * lfvio_track_reject: the bearings are P / n, a true division per component, of cur_pts (corr1) and forw_pts (corr2).  Per sample
  * set compute_E_21 and check_inliers; the first hypothesis with the largest score > 0 wins; the refit over the winner's inliers and
@@ -875,14 +902,15 @@ int lfvio_image_gray(lfvio_ctx *ctx, const LfvioImageFormat *fmt, int width, int
  * device memory of their own (2 x 64 KiB, allocated at the first use), not in the feature calls' staging block. */
 #define LFVIO_CAM_OCAM 0
 #define LFVIO_CAM_PINHOLE 2
-#define LFVIO_CAM_MEI     3   /* 1 is refused, like every model outside {0, 2, 3} */
+#define LFVIO_CAM_MEI     3   /* 1 and 4 are refused, like every model outside {0, 2, 3, 5} */
+#define LFVIO_CAM_KANNALA_BRANDT 5
 #define LFVIO_TRACK_MAX_POINTS 4096
 typedef struct {
-  int model;             /* LFVIO_CAM_OCAM, LFVIO_CAM_PINHOLE or LFVIO_CAM_MEI; anything else: LFVIO_ERR_ARG */
-  double cx, cy;         /* OCam: center_x, center_y; PINHOLE: cx, cy; MEI: u0, v0 */
+  int model;             /* LFVIO_CAM_OCAM, _PINHOLE, _MEI or _KANNALA_BRANDT; anything else: LFVIO_ERR_ARG */
+  double cx, cy;         /* OCam: center_x, center_y; PINHOLE: cx, cy; MEI and KANNALA_BRANDT: u0, v0 */
   double c, d, e;        /* OCam only: the affine part; inv_scale = 1.0 / (c - d * e) */
-  double poly[5];        /* OCam only: SCARAMUZZA_POLY_SIZE */
-  double fx, fy;         /* PINHOLE: fx, fy; MEI: gamma1, gamma2.  Not read for OCam, like everything below */
+  double poly[5];        /* OCam: SCARAMUZZA_POLY_SIZE; KANNALA_BRANDT: poly[0 .. 3] = k2, k3, k4, k5 (NOT the k1, k2 below) */
+  double fx, fy;         /* PINHOLE: fx, fy; MEI: gamma1, gamma2; KANNALA_BRANDT: mu, mv.  Not read for OCam, like everything below */
   double k1, k2, p1, p2; /* PINHOLE and MEI: distortion_parameters */
   double xi;             /* MEI: mirror_parameters.xi */
 } LfvioCamera;

@@ -1,8 +1,9 @@
 // kernels_track.h — the two steps of FeatureTracker::readImage that need the camera (feature_tracker/src/feature_tracker.cpp):
 // rejectWithF (:329-386) behind lfvio_track_reject and undistortedPoints (:441-504) behind lfvio_track_undistort, with
-// the lift of three camera models as device functions: OCAMCamera::liftProjective (ScaramuzzaCamera.cc:623-645),
-// PinholeCamera::liftProjective (PinholeCamera.cc:450-510) and CataCamera::liftProjective (CataCamera.cc:556-626).  The specification
-// is in include/lfvio.h and, as numpy, in tests/track_ref.py (OCam) and tests/camera_ref.py (PINHOLE, MEI).
+// the lift of four camera models as device functions: OCAMCamera::liftProjective (ScaramuzzaCamera.cc:623-645),
+// PinholeCamera::liftProjective (PinholeCamera.cc:450-510), CataCamera::liftProjective (CataCamera.cc:556-626) and
+// EquidistantCamera::liftProjective (EquidistantCamera.cc:428-442, restated in camera_kb.h).  The specification is in include/lfvio.h
+// and, as numpy, in tests/track_ref.py (OCam), tests/camera_ref.py (PINHOLE, MEI) and tests/kb_ref.py (KANNALA_BRANDT).
 //
 //   k_trk_lift   : a thread per point of BOTH sets (2 N threads): the unit bearing of cur_pts[i] / forw_pts[i] in double, into the
 //                  staging block where k_tv_hyp (kernels_twoview.h, reused as it is) and k_trk_fit read them.
@@ -66,11 +67,20 @@ DEV d3 trk_lift_mei(const TrackCam &cam, float px, float py) {
   return mk3(mx_u, my_u, 1.0 - (cam.xi * (rho2 + 1.0)) / (cam.xi + sqrt(1.0 + (1.0 - cam.xi * cam.xi) * rho2)));  // :624
 }
 
+// EquidistantCamera::liftProjective as camera_kb.h restates it: the normalised plane, the root by a fixed count of Newton steps, sin
+// and cos by the header's own routine, the bearing.  No trip count depends on the data.
+DEV d3 trk_lift_kb(const TrackCam &cam, float px, float py) {
+  d3 P;
+  kb_lift_pixel(cam.inv11, cam.inv13, cam.inv22, cam.inv23, cam.poly, cam.theta_lim, cam.r_lim, px, py, P.x, P.y, P.z);
+  return P;
+}
+
 // liftProjective of the pixel (px, py).  The model is the same in every thread of a workgroup (a kernel argument, or the slot's
 // camera in the batched route), so the branches below are uniform.  OCAMCamera::liftProjective:
 DEV d3 trk_lift(const TrackCam &cam, float px, float py) {
   if (cam.model == LFVIO_CAM_PINHOLE) return trk_lift_pinhole(cam, px, py);
   if (cam.model == LFVIO_CAM_MEI) return trk_lift_mei(cam, px, py);
+  if (cam.model == LFVIO_CAM_KANNALA_BRANDT) return trk_lift_kb(cam, px, py);
   const double x = (double)px - cam.cx, y = (double)py - cam.cy;  // :627
   const double xa = cam.inv_scale * (x - cam.d * y), ya = cam.inv_scale * (-cam.e * x + cam.c * y);  // :631-632
   const double phi = sqrt(xa * xa + ya * ya);

@@ -176,6 +176,7 @@ struct lfvio_ctx : CtxQueues {
   // The single route's image stream (track_stream.h): which of each pair of buffers below is the resident one and what it holds.
   // Every separate tracker call and lfvio_track_frame move it; the buffers stay with the call that introduced them.
   TrackStream tstream;
+  KbCache track_kb;  // the last KANNALA_BRANDT camera's monotone range (camera_kb.h), for every single-route call that takes a camera
   // lfvio_klt_track (klt.inc): two pyramid buffers of their own; tstream.pcur holds the resident image's levels 0 .. tstream.built
   struct KltState {
     DevBuf<unsigned char> d[2];
@@ -217,6 +218,7 @@ struct lfvio_ctx : CtxQueues {
   // the LUTs, allocated at the first frame with the setting on.  None of it is the single route's, and the single route's is none of it.
   struct TrackBatchState {
     std::vector<TrackStream> slot;
+    std::vector<KbCache> kb;  // per slot: the slot's last KANNALA_BRANDT camera's monotone range (camera_kb.h)
     DevBuf<char> fixed, image, clahe;
     TbImage lay = {0, 0, 0};
     bool clahe_on = false, clahe_dirty = false;

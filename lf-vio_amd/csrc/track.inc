@@ -22,7 +22,7 @@ int lfvio_track_reject(lfvio_ctx *c, const LfvioTrackRejectIn *in, unsigned char
     out->status = 2, out->best_sample = -1, out->num_inliers = 0, out->best_score = 0.0;
     return LFVIO_OK;
   }
-  const TrackCam cam = track_cam(*in->camera);
+  const TrackCam cam = track_cam(*in->camera, &c->track_kb);
   FeatStage st(c);
   const size_t NR = (size_t)std::max(N, 9);
   const size_t oP = st.take((size_t)N * 8), oQ = st.take((size_t)N * 8), oS = st.take((size_t)S * 32), in_end = st.end;
@@ -68,7 +68,7 @@ int lfvio_track_undistort(lfvio_ctx *c, const LfvioTrackUndistortIn *in, float *
     t.commit_undistort(0, in->time);
     return LFVIO_OK;
   }
-  const TrackCam cam = track_cam(*in->camera);
+  const TrackCam cam = track_cam(*in->camera, &c->track_kb);
   FeatStage st(c);
   const size_t oP = st.take((size_t)N * 8), oI = st.take((size_t)N * 4), in_end = st.end;
   const size_t oU = st.take((size_t)N * 8), o3 = st.take((size_t)N * 12), oV = st.take((size_t)N * 12), oM = st.take((size_t)N * 4);

@@ -1,13 +1,15 @@
 // track_plan.h — the host side of lfvio_track_reject / lfvio_track_undistort (include/lfvio.h) that needs no device: the argument
 // checks of both calls, and the camera as the kernels take it (TrackCam: LfvioCamera's numbers with inv_scale = 1.0 / (c - d * e),
 // divided once, on the host, in double — ScaramuzzaCamera.cc:197; for PINHOLE and MEI the inverse projection matrix's four entries
-// and the no-distortion flag, PinholeCamera.cc:281-289).  Plain C++ (no HIP): track.inc uses it, tests/test_track_ref.py
+// and the no-distortion flag, PinholeCamera.cc:281-289; for KANNALA_BRANDT the same four entries and the monotone range of camera_kb.h,
+// kept in a KbCache while the camera's numbers stay the same).  Plain C++ (no HIP): track.inc uses it, tests/test_track_ref.py
 // compiles it alone with g++ and holds it to the checks of tests/track_ref.py.
 #pragma once
 #include <cmath>
 #include <cstddef>
 
 #include "../../include/lfvio.h"
+#include "camera_kb.h"
 
 constexpr int TRACK_MAX_SAMPLES = 1024, TRACK_MIN_MATCHES = 8;  // forw_pts.size() >= 8 (feature_tracker.cpp:331)
 
@@ -29,12 +31,24 @@ struct TrackCam {  // a kernel argument, by value; the members a model does not 
   double cx, cy, c, d, e, inv_scale, poly[5];          // OCam
   double inv11, inv13, inv22, inv23, k1, k2, p1, p2, xi;  // PINHOLE and MEI (xi: MEI), PinholeCamera.cc:281-289
   int model, no_distortion;
+  double theta_lim, r_lim;  // KANNALA_BRANDT (camera_kb.h), with inv11 .. inv23 and k2 .. k5 in poly[0 .. 3]
 };
 
-// LfvioCamera's fx .. xi are read only for PINHOLE and MEI, its c, d, e, poly only for OCam: callers may leave the others indeterminate
-inline TrackCam track_cam(const LfvioCamera &k) {
+// LfvioCamera's fx .. xi are read only for PINHOLE and MEI, its c, d, e, poly only for OCam; KANNALA_BRANDT reads cx, cy, fx, fy and
+// poly[0 .. 3]: callers may leave the others indeterminate.  kb: where a KANNALA_BRANDT camera's constants are kept from one call to
+// the next (nullptr: formed anew); no other model looks at it.
+inline TrackCam track_cam(const LfvioCamera &k, KbCache *kb = nullptr) {
   TrackCam t = {};
   t.model = k.model, t.cx = k.cx, t.cy = k.cy;
+  if (k.model == LFVIO_CAM_KANNALA_BRANDT) {
+    const double key[8] = {k.cx, k.cy, k.fx, k.fy, k.poly[0], k.poly[1], k.poly[2], k.poly[3]};
+    KbCache once;
+    const KbConstants &c = (kb ? *kb : once).get(key);
+    t.inv11 = 1.0 / k.fx, t.inv13 = -k.cx / k.fx, t.inv22 = 1.0 / k.fy, t.inv23 = -k.cy / k.fy;
+    for (int i = 0; i < 4; i++) t.poly[i] = k.poly[i];
+    t.theta_lim = c.theta_lim, t.r_lim = c.r_lim;
+    return t;
+  }
   if (k.model == LFVIO_CAM_OCAM) {
     t.c = k.c, t.d = k.d, t.e = k.e;
     t.inv_scale = 1.0 / (k.c - k.d * k.e);
@@ -51,9 +65,14 @@ inline TrackCam track_cam(const LfvioCamera &k) {
 // nullptr, or what is wrong with the camera or the point count
 inline const char *track_common_check(const LfvioCamera *cam, int N) {
   if (!cam) return "lfvio_track: null camera";
-  if (cam->model != LFVIO_CAM_OCAM && cam->model != LFVIO_CAM_PINHOLE && cam->model != LFVIO_CAM_MEI)
-    return "lfvio_track: a camera model other than LFVIO_CAM_OCAM, LFVIO_CAM_PINHOLE and LFVIO_CAM_MEI";
-  if (cam->model != LFVIO_CAM_OCAM) {
+  if (cam->model != LFVIO_CAM_OCAM && cam->model != LFVIO_CAM_PINHOLE && cam->model != LFVIO_CAM_MEI && cam->model != LFVIO_CAM_KANNALA_BRANDT)
+    return "lfvio_track: a camera model other than LFVIO_CAM_OCAM, LFVIO_CAM_PINHOLE, LFVIO_CAM_MEI and LFVIO_CAM_KANNALA_BRANDT";
+  if (cam->model == LFVIO_CAM_KANNALA_BRANDT) {
+    const double v[8] = {cam->cx, cam->cy, cam->fx, cam->fy, cam->poly[0], cam->poly[1], cam->poly[2], cam->poly[3]};
+    for (double x : v)
+      if (!std::isfinite(x)) return "lfvio_track: a non-finite camera parameter";
+    if (cam->fx == 0.0 || cam->fy == 0.0) return "lfvio_track: fx or fy is zero";
+  } else if (cam->model != LFVIO_CAM_OCAM) {
     const double v[8] = {cam->cx, cam->cy, cam->fx, cam->fy, cam->k1, cam->k2, cam->p1, cam->p2};
     for (double x : v)
       if (!std::isfinite(x)) return "lfvio_track: a non-finite camera parameter";

@@ -50,6 +50,7 @@ int lfvio_track_batch_reserve(lfvio_ctx *c, int slots) {
   (void)b.image.reset(), (void)b.clahe.reset();
   b.lay = TbImage{0, 0, 0}, b.clahe_dirty = false;
   b.slot.assign((size_t)slots, TrackStream());
+  b.kb.assign((size_t)slots, KbCache());
   return LFVIO_OK;
 }
 
@@ -192,7 +193,7 @@ int lfvio_track_batch_frame(lfvio_ctx *c, int count, const LfvioTrackFrameIn *in
     TbSlot &t = desc[i];
     t.active = 1, t.publish = in[i].publish != 0;
     trackbatch_describe(t, b.slot[i], W, H, LU, in[i].time);
-    t.cam = track_cam(*in[i].camera);
+    t.cam = track_cam(*in[i].camera, &b.kb[i]);
     t.image_k = ka++;
     std::memcpy(h + trackbatch_image_at(o, shape, t.image_k), in[i].image, nI);
     if (t.publish) {

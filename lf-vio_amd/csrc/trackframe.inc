@@ -36,7 +36,7 @@ static int track_frame_run(lfvio_ctx *c, const LfvioTrackFrameIn *in, LfvioTrack
   const LfvioGftIn gin = trackframe_gft(in);
   const KltPlan full = klt_plan(W, H, 0, LFVIO_KLT_MAX_LEVEL);
   const int LU = klt_plan(W, H, in->win_size, in->max_level).levels_used;
-  const TrackCam cam = track_cam(*in->camera);
+  const TrackCam cam = track_cam(*in->camera, &c->track_kb);
   const GftWork wk = gft_work(W, H);
   const size_t B = (size_t)trackframe_bound(n0, MC, pub), N0 = (size_t)n0, nI = im.bytes;
   FeatStage st(c);

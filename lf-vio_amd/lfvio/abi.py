@@ -701,6 +701,20 @@ class TrackUndistortInC(C.Structure):
 
 CAM_OCAM, TRACK_MAX_POINTS = 0, 4096  # LFVIO_CAM_OCAM, LFVIO_TRACK_MAX_POINTS
 CAM_PINHOLE, CAM_MEI = 2, 3  # LFVIO_CAM_PINHOLE, LFVIO_CAM_MEI
+CAM_KANNALA_BRANDT = 5  # LFVIO_CAM_KANNALA_BRANDT
+
+
+def camera_c(cam):
+    """A CameraC from a camera dict.  model (optional) LFVIO_CAM_OCAM: cx, cy, c, d, e, poly [5]; LFVIO_CAM_PINHOLE: cx, cy, fx, fy,
+    k1, k2, p1, p2; LFVIO_CAM_MEI: those (u0, v0, gamma1, gamma2 under cx, cy, fx, fy) and xi; LFVIO_CAM_KANNALA_BRANDT: cx, cy, fx, fy
+    (u0, v0, mu, mv) and k2, k3, k4, k5, which go into poly[0 .. 3] and NOT into the struct's k1, k2.  The fields of the other
+    models may be left out (zero)."""
+    g = lambda k: float(cam.get(k, 0.0))
+    model = int(cam.get("model", CAM_OCAM))
+    if model == CAM_KANNALA_BRANDT:
+        return CameraC(model, cam["cx"], cam["cy"], 0.0, 0.0, 0.0, (C.c_double * 5)(g("k2"), g("k3"), g("k4"), g("k5"), 0.0), g("fx"), g("fy"))
+    return CameraC(model, cam["cx"], cam["cy"], g("c"), g("d"), g("e"), (C.c_double * 5)(*[float(v) for v in cam.get("poly", (0.0,) * 5)]),
+                   g("fx"), g("fy"), g("k1"), g("k2"), g("p1"), g("p2"), g("xi"))
 
 
 class TrackFrameInC(C.Structure):

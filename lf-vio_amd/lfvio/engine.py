@@ -597,14 +597,12 @@ class Engine:
     @staticmethod
     def camera(cam):
         """A CameraC from a dict; None: a null pointer.  model (optional) LFVIO_CAM_OCAM: cx, cy, c, d, e, poly [5];
-        LFVIO_CAM_PINHOLE: cx, cy, fx, fy, k1, k2, p1, p2; LFVIO_CAM_MEI: those (u0, v0, gamma1, gamma2 under cx, cy, fx, fy) and xi.
+        LFVIO_CAM_PINHOLE: cx, cy, fx, fy, k1, k2, p1, p2; LFVIO_CAM_MEI: those (u0, v0, gamma1, gamma2 under cx, cy, fx, fy) and xi;
+        LFVIO_CAM_KANNALA_BRANDT: cx, cy, fx, fy (u0, v0, mu, mv), k2, k3, k4, k5 (abi.camera_c).
         The fields of the other models may be left out (zero)."""
         if cam is None or isinstance(cam, abi.CameraC):
             return cam
-        g = lambda k: float(cam.get(k, 0.0))
-        return abi.CameraC(int(cam.get("model", abi.CAM_OCAM)), cam["cx"], cam["cy"], g("c"), g("d"), g("e"),
-                           (C.c_double * 5)(*[float(v) for v in cam.get("poly", (0.0,) * 5)]), g("fx"), g("fy"), g("k1"), g("k2"), g("p1"),
-                           g("p2"), g("xi"))
+        return abi.camera_c(cam)
 
     def track_reject(self, cam, cur_pts, forw_pts, samples, want_bearings=False, status=None, out=None, bearings=None, num_points=None,
                      num_samples=None, check=True):

@@ -224,10 +224,7 @@ class HostEstimator:
         """lfvio_host_track_config: the tracker of the next track_trace / replay_images.  cam: a dict as Engine.camera takes (or a
         CameraC); annulus = (center_x, center_y, max_r, min_r) or mask [height, width] uint8: the base mask; seed 0: std::random_device."""
         self._tracker()
-        g = lambda k: float(cam.get(k, 0.0))
-        camc = cam if isinstance(cam, abi.CameraC) else abi.CameraC(
-            int(cam.get("model", abi.CAM_OCAM)), cam["cx"], cam["cy"], g("c"), g("d"), g("e"), (C.c_double * 5)(*[float(v) for v in cam.get("poly", (0.0,) * 5)]),
-            g("fx"), g("fy"), g("k1"), g("k2"), g("p1"), g("p2"), g("xi"))
+        camc = cam if isinstance(cam, abi.CameraC) else abi.camera_c(cam)
         iv = np.array([max_cnt, min_dist, freq, int(bool(equalize)), num_samples, seed], dtype=np.uint32).view(np.int32)
         an = None if annulus is None else _f(annulus)
         m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)

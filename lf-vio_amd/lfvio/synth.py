@@ -320,6 +320,9 @@ def ocam_lift_projective(p):
 # (CataCamera.cc).  A camera is a dict: model (CAM_PINHOLE / CAM_MEI), cx, cy, fx, fy (MEI: u0, v0, gamma1, gamma2), k1, k2, p1, p2 and,
 # for MEI, xi.  These two make INPUTS (pixels of rays, rays of pixels); the specification of the device's lift is tests/camera_ref.py.
 CAM_PINHOLE, CAM_MEI = 2, 3
+# KANNALA_BRANDT (EquidistantCamera.cc): model, cx, cy, fx, fy (u0, v0, mu, mv) and k2, k3, k4, k5 of r(theta) = theta + k2 theta^3 +
+# k3 theta^5 + k4 theta^7 + k5 theta^9.  Inputs only, like the two above: the device's lift is specified in tests/kb_ref.py.
+CAM_KANNALA_BRANDT = 5
 
 
 def _camera_distortion(cam, x, y):
@@ -335,9 +338,53 @@ def _camera_no_distortion(cam):
     return all(float(cam.get(k, 0.0)) == 0.0 for k in ("k1", "k2", "p1", "p2"))
 
 
+def _kb_r(cam, th):
+    """EquidistantCamera::r and its derivative."""
+    k2, k3, k4, k5 = (float(cam.get(k, 0.0)) for k in ("k2", "k3", "k4", "k5"))
+    t = th * th
+    return th * (1.0 + t * (k2 + t * (k3 + t * (k4 + t * k5)))), 1.0 + t * (3.0 * k2 + t * (5.0 * k3 + t * (7.0 * k4 + t * 9.0 * k5)))
+
+
+def kb_monotone_limit(cam):
+    """(theta_lim, r_lim): the last point of the grid j pi / 4096 up to which r'(theta) > 0, pi at the most, and r there."""
+    th = np.arange(4097) * (np.pi / 4096)
+    bad = np.nonzero(~(_kb_r(cam, th)[1] > 0.0))[0]
+    lim = th[bad[0] - 1] if len(bad) else th[-1]
+    return float(lim), float(_kb_r(cam, lim)[0])
+
+
+def _kb_lift(cam, px):
+    """EquidistantCamera::liftProjective (:428-442) with backprojectSymmetric's root (:716-818) by Newton's method on the monotone
+    range; beyond it theta = r, the reference's fallback when it finds no root."""
+    with np.errstate(all="ignore"):
+        x, y = (px[..., 0] - cam["cx"]) / cam["fx"], (px[..., 1] - cam["cy"]) / cam["fy"]
+        r = np.hypot(x, y)
+        lim, r_lim = kb_monotone_limit(cam)
+        th = np.minimum(r, lim)
+        for _ in range(40):
+            f, fp = _kb_r(cam, th)
+            th = np.clip(th - (f - r) / fp, 0.0, lim)
+        th = np.where(r <= r_lim, th, r)
+        tiny = r < 1e-10
+        c, s = np.where(tiny, 1.0, x / np.where(tiny, 1.0, r)), np.where(tiny, 0.0, y / np.where(tiny, 1.0, r))
+        return np.stack([np.sin(th) * c, np.sin(th) * s, np.cos(th)], axis=-1)
+
+
+def _kb_space_to_plane(cam, P):
+    """EquidistantCamera::spaceToPlane (:450-470)."""
+    with np.errstate(all="ignore"):
+        th = np.arccos(P[..., 2] / np.linalg.norm(P, axis=-1))
+        phi = np.arctan2(P[..., 1], P[..., 0])
+        r = _kb_r(cam, th)[0]
+        return np.stack([cam["fx"] * (r * np.cos(phi)) + cam["cx"], cam["fy"] * (r * np.sin(phi)) + cam["cy"]], axis=-1)
+
+
 def camera_lift(cam, px):
-    """liftProjective of pixels px [..., 2] -> rays [..., 3], not normalised (PinholeCamera.cc:450-510, CataCamera.cc:556-626)."""
+    """liftProjective of pixels px [..., 2] -> rays [..., 3], not normalised (PinholeCamera.cc:450-510, CataCamera.cc:556-626;
+    KANNALA_BRANDT: _kb_lift)."""
     px = np.asarray(px, np.float64)
+    if cam["model"] == CAM_KANNALA_BRANDT:
+        return _kb_lift(cam, px)
     if cam["model"] not in (CAM_PINHOLE, CAM_MEI):
         raise ValueError("camera_lift: a PINHOLE or MEI camera")
     with np.errstate(all="ignore"):
@@ -360,6 +407,8 @@ def camera_lift(cam, px):
 def camera_space_to_plane(cam, P):
     """spaceToPlane of rays P [..., 3] -> pixels [..., 2] (PinholeCamera.cc:520-550, CataCamera.cc:636-659)."""
     P = np.asarray(P, np.float64)
+    if cam["model"] == CAM_KANNALA_BRANDT:
+        return _kb_space_to_plane(cam, P)
     if cam["model"] not in (CAM_PINHOLE, CAM_MEI):
         raise ValueError("camera_space_to_plane: a PINHOLE or MEI camera")
     with np.errstate(all="ignore"):

@@ -329,7 +329,7 @@ def make_image_stream(path, seed=0, n_frames=36, scale=4, cam_offset=0.0023, boo
     proportional to the wavelength, standard deviation `contrast` grey levels around 127.5), evaluated where the ray hits the wall,
     so it has no seams at the edges.  Pixels outside the 40-120 degree annulus are black; the matching base mask is the annulus of
     image_camera.
-    camera = (camera dict, width, height): a PINHOLE or MEI camera (Engine.camera) in place of image_camera(scale), which `scale`
+    camera = (camera dict, width, height): a PINHOLE, MEI or KANNALA_BRANDT camera (Engine.camera) in place of image_camera(scale), which `scale`
     then does not touch.  The pixels' rays are synth.camera_lift's, every pixel with a finite ray is lit, and the base mask is all
     255: the returned annulus is None and `mask` [height, width] is that mask.
 
