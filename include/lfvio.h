@@ -823,7 +823,9 @@ int lfvio_image_gray(lfvio_ctx *ctx, const LfvioImageFormat *fmt, int width, int
  *             z += p * poly[i], p *= phi; P = (xa, ya, -z) (the sign is the reference's, :644).
  *   the norm  n = sqrt((P.x P.x + P.y P.y) + P.z P.z), left to right.  Eigen's own reduction may order the three terms differently
  *             and differ in the last bit; the reference does not build without Eigen and OpenCV, so the two were never compared.
- * tests/track_ref.py restates both calls in numpy and is the specification; the device gives its bits.
+ * tests/track_ref.py restates both calls in numpy and is the specification; the device gives its bits.  The C++ of
+ * every lift below, the norm, P / n and the float casts of lfvio_track_undistort is lf-vio_amd/csrc/camera_models.h (with camera_kb.h),
+ * one text that the kernels and the host compile.
  *   the lift of LFVIO_CAM_PINHOLE and LFVIO_CAM_MEI (PinholeCamera.cc:450-510, CataCamera.cc:556-626), in double,
  *             every operation rounded on its own, grouped as written here:
  *             host, once: inv11 = 1.0 / fx, inv13 = -cx / fx, inv22 = 1.0 / fy, inv23 = -cy / fy,

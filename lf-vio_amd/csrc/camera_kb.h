@@ -1,10 +1,11 @@
 // camera_kb.h — the KANNALA_BRANDT camera model (LFVIO_CAM_KANNALA_BRANDT, include/lfvio.h): EquidistantCamera::liftProjective
 // (camera_model/src/camera_models/EquidistantCamera.cc:428-442) over backprojectSymmetric (:716-818), restated in operations IEEE 754
 // defines (+ - * / sqrt floor and comparisons), each rounded on its own: every user compiles this with -ffp-contract=off.  The
-// per-pixel functions are host-and-device functions that the kernels (kernels_track.h: trk_lift_kb) and the host compile, as
-// image_format.h's pixel conversions are; the once-per-camera constants are formed on the host (track_plan.h: track_cam).  It includes
-// nothing from HIP when compiled for the host: tests/test_kb_ref.py compiles it with g++ and holds it to tests/kb_ref.py, the numpy
-// text of the same specification, bit for bit, and tests/tools/camera_kb_walk.cpp walks it under the CPU sanitizers.
+// per-pixel functions are host-and-device functions that the kernels and the host compile, as image_format.h's pixel conversions
+// are; camera_models.h, which holds the other three models, includes this file, calls kb_lift_pixel from cam_lift and forms the
+// once-per-camera constants on the host in track_cam.  It includes nothing from HIP when compiled for the host: tests/test_kb_ref.py
+// compiles it with g++ and holds it to tests/kb_ref.py, the numpy text of the same specification, bit for bit, and
+// tests/tools/camera_kb_walk.cpp walks it under the CPU sanitizers.
 //
 // The model: a pixel (px, py) lies at x = inv11 px + inv13, y = inv22 py + inv23 of the normalised plane (:432-433), at the radius
 // r = sqrt(x x + y y); theta is the smallest non-negative real root of

@@ -1,0 +1,147 @@
+// camera_models.h — everything about a camera model, in one header that the host and the device both compile: the camera as the
+// kernels take it (TrackCam, formed by track_cam on the host), the argument check of an LfvioCamera (track_camera_check) and the lift
+// of a pixel for the four models of include/lfvio.h:
+//   LFVIO_CAM_OCAM             OCAMCamera::liftProjective (camera_model/src/camera_models/ScaramuzzaCamera.cc:623-645)
+//   LFVIO_CAM_PINHOLE          PinholeCamera::liftProjective (PinholeCamera.cc:450-510)
+//   LFVIO_CAM_MEI              CataCamera::liftProjective (CataCamera.cc:556-626)
+//   LFVIO_CAM_KANNALA_BRANDT   EquidistantCamera::liftProjective (EquidistantCamera.cc:428-442), restated in camera_kb.h
+// and what every model shares behind the lift: the norm, the unit bearing of rejectWithF and the two float outputs of
+// undistortedPoints.  The specification is in include/lfvio.h and, as numpy, in tests/track_ref.py (OCam), tests/camera_ref.py
+// (PINHOLE, MEI) and tests/kb_ref.py (KANNALA_BRANDT).
+//
+// Plain C++ when compiled without hipcc (nothing from HIP, dev_math.h or kernels_twoview.h); under hipcc the per-pixel functions are
+// __host__ __device__ (KB_HD of camera_kb.h), as image_format.h's pixel conversions are.  kernels_track.h calls them from the kernels,
+// track_plan.h includes this file for the host side, and tests/test_camera_lift.py compiles it alone with g++ and holds every lift to
+// its numpy text bit for bit; tests/tools/camera_models_walk.cpp walks it under the CPU sanitizers.
+//
+// Every lift is written operation by operation and every user compiles with -ffp-contract=off: each product and sum is rounded on
+// its own, grouped as include/lfvio.h states it.  The norm is sqrt((x x + y y) + z z), left to right as tv_residual forms its norms;
+// Eigen's own reduction may order the terms differently (the reference does not build here, so the two were never compared).  A
+// camera's model is the same in every thread of a workgroup (a kernel argument, or the slot's camera in the batched route), so the
+// branches on it are uniform, and no trip count depends on a pixel.
+#pragma once
+#include <cmath>
+
+#include "../../include/lfvio.h"
+#include "camera_kb.h"
+
+struct TrackCam {  // a kernel argument, by value; the members a model does not use are zero
+  double cx, cy, c, d, e, inv_scale, poly[5];          // OCam
+  double inv11, inv13, inv22, inv23, k1, k2, p1, p2, xi;  // PINHOLE and MEI (xi: MEI), PinholeCamera.cc:281-289
+  int model, no_distortion;
+  double theta_lim, r_lim;  // KANNALA_BRANDT (camera_kb.h), with inv11 .. inv23 and k2 .. k5 in poly[0 .. 3]
+};
+
+// On the host, in double, once per call (inv_scale: ScaramuzzaCamera.cc:197).  LfvioCamera's fx .. xi are read only for PINHOLE and
+// MEI, its c, d, e, poly only for OCam; KANNALA_BRANDT reads cx, cy, fx, fy and poly[0 .. 3]: callers may leave the others indeterminate.
+// kb: where a KANNALA_BRANDT camera's constants are kept from one call to the next (nullptr: formed anew); no other model looks at it.
+inline TrackCam track_cam(const LfvioCamera &k, KbCache *kb = nullptr) {
+  TrackCam t = {};
+  t.model = k.model, t.cx = k.cx, t.cy = k.cy;
+  if (k.model == LFVIO_CAM_OCAM) {
+    t.c = k.c, t.d = k.d, t.e = k.e;
+    t.inv_scale = 1.0 / (k.c - k.d * k.e);
+    for (int i = 0; i < 5; i++) t.poly[i] = k.poly[i];
+    return t;
+  }
+  t.inv11 = 1.0 / k.fx, t.inv13 = -k.cx / k.fx, t.inv22 = 1.0 / k.fy, t.inv23 = -k.cy / k.fy;
+  if (k.model == LFVIO_CAM_KANNALA_BRANDT) {
+    const double key[8] = {k.cx, k.cy, k.fx, k.fy, k.poly[0], k.poly[1], k.poly[2], k.poly[3]};
+    KbCache once;
+    const KbConstants &c = (kb ? *kb : once).get(key);
+    for (int i = 0; i < 4; i++) t.poly[i] = k.poly[i];
+    t.theta_lim = c.theta_lim, t.r_lim = c.r_lim;
+    return t;
+  }
+  t.k1 = k.k1, t.k2 = k.k2, t.p1 = k.p1, t.p2 = k.p2;
+  t.no_distortion = k.k1 == 0.0 && k.k2 == 0.0 && k.p1 == 0.0 && k.p2 == 0.0;
+  if (k.model == LFVIO_CAM_MEI) t.xi = k.xi;
+  return t;
+}
+
+// nullptr, or what is wrong with the camera.  v: the fields the model reads besides MEI's xi (OCam's are not judged)
+inline const char *track_camera_check(const LfvioCamera *cam) {
+  if (!cam) return "lfvio_track: null camera";
+  if (cam->model != LFVIO_CAM_OCAM && cam->model != LFVIO_CAM_PINHOLE && cam->model != LFVIO_CAM_MEI && cam->model != LFVIO_CAM_KANNALA_BRANDT)
+    return "lfvio_track: a camera model other than LFVIO_CAM_OCAM, LFVIO_CAM_PINHOLE, LFVIO_CAM_MEI and LFVIO_CAM_KANNALA_BRANDT";
+  if (cam->model == LFVIO_CAM_OCAM) return nullptr;
+  const bool kb = cam->model == LFVIO_CAM_KANNALA_BRANDT;
+  const double v[8] = {cam->cx, cam->cy, cam->fx, cam->fy, kb ? cam->poly[0] : cam->k1, kb ? cam->poly[1] : cam->k2,
+                       kb ? cam->poly[2] : cam->p1, kb ? cam->poly[3] : cam->p2};
+  for (double x : v)
+    if (!std::isfinite(x)) return "lfvio_track: a non-finite camera parameter";
+  if (cam->fx == 0.0 || cam->fy == 0.0) return "lfvio_track: fx or fy is zero";
+  if (cam->model == LFVIO_CAM_MEI && !std::isfinite(cam->xi)) return "lfvio_track: a non-finite xi";
+  return nullptr;
+}
+
+// ---- per pixel
+struct CamRay { double x, y, z; };
+
+// PinholeCamera::distortion (PinholeCamera.cc:646-662; CataCamera's is the same text): grouped as include/lfvio.h states it
+KB_HD void cam_distortion(const TrackCam &cam, double x, double y, double &dx, double &dy) {
+  const double mx2 = x * x, my2 = y * y, mxy = x * y, rho2 = mx2 + my2;
+  const double rad = cam.k1 * rho2 + (cam.k2 * rho2) * rho2;
+  dx = (x * rad + (2.0 * cam.p1) * mxy) + cam.p2 * (rho2 + 2.0 * mx2);
+  dy = (y * rad + (2.0 * cam.p2) * mxy) + cam.p1 * (rho2 + 2.0 * my2);
+}
+
+// PinholeCamera::liftProjective (:450-510): the normalised plane and the recursive distortion model, n = 8 evaluations, and z = 1.
+// CataCamera's (CataCamera.cc:562-612) is the same text up to its z.
+KB_HD CamRay cam_lift_pinhole(const TrackCam &cam, float px, float py) {
+  const double mx_d = cam.inv11 * (double)px + cam.inv13, my_d = cam.inv22 * (double)py + cam.inv23;
+  if (cam.no_distortion) return {mx_d, my_d, 1.0};
+  double mx_u = mx_d, my_u = my_d;
+  for (int i = 0; i < 8; i++) {
+    double dx, dy;
+    cam_distortion(cam, mx_u, my_u, dx, dy);
+    mx_u = mx_d - dx, my_u = my_d - dy;
+  }
+  return {mx_u, my_u, 1.0};
+}
+
+// CataCamera::liftProjective (:556-626)
+KB_HD CamRay cam_lift_mei(const TrackCam &cam, float px, float py) {
+  const CamRay P = cam_lift_pinhole(cam, px, py);
+  const double mx_u = P.x, my_u = P.y;
+  if (cam.xi == 1.0) return {mx_u, my_u, ((1.0 - mx_u * mx_u) - my_u * my_u) / 2.0};  // :618
+  const double rho2 = mx_u * mx_u + my_u * my_u;
+  return {mx_u, my_u, 1.0 - (cam.xi * (rho2 + 1.0)) / (cam.xi + sqrt(1.0 + (1.0 - cam.xi * cam.xi) * rho2))};  // :624
+}
+
+// liftProjective of the pixel (px, py).  KANNALA_BRANDT: as camera_kb.h restates it; OCAMCamera::liftProjective (:623-645):
+KB_HD CamRay cam_lift(const TrackCam &cam, float px, float py) {
+  if (cam.model == LFVIO_CAM_PINHOLE) return cam_lift_pinhole(cam, px, py);
+  if (cam.model == LFVIO_CAM_MEI) return cam_lift_mei(cam, px, py);
+  if (cam.model == LFVIO_CAM_KANNALA_BRANDT) {
+    CamRay P;
+    kb_lift_pixel(cam.inv11, cam.inv13, cam.inv22, cam.inv23, cam.poly, cam.theta_lim, cam.r_lim, px, py, P.x, P.y, P.z);
+    return P;
+  }
+  const double x = (double)px - cam.cx, y = (double)py - cam.cy;  // :627
+  const double xa = cam.inv_scale * (x - cam.d * y), ya = cam.inv_scale * (-cam.e * x + cam.c * y);  // :631-632
+  const double phi = sqrt(xa * xa + ya * ya);
+  double p = 1.0, z = 0.0;
+  for (int i = 0; i < 5; i++) {  // :638-642
+    z += p * cam.poly[i];
+    p *= phi;
+  }
+  return {xa, ya, -z};  // :644
+}
+
+KB_HD double cam_norm(CamRay P) { return sqrt((P.x * P.x + P.y * P.y) + P.z * P.z); }
+
+// rejectWithF's unit bearing of a pixel (feature_tracker.cpp:343, :353), three doubles
+KB_HD void cam_bearing(const TrackCam &cam, float px, float py, double *b) {
+  const CamRay P = cam_lift(cam, px, py);
+  const double n = cam_norm(P);
+  b[0] = P.x / n, b[1] = P.y / n, b[2] = P.z / n;
+}
+
+// undistortedPoints' two outputs for a pixel: un_pts (:454) and un_pts_3d (:455), the quotients in double, rounded to float once
+struct CamUndistorted { float ux, uy, bx, by, bz; };
+KB_HD CamUndistorted cam_undistorted(const TrackCam &cam, float px, float py) {
+  const CamRay Q = cam_lift(cam, px, py);
+  const double n = cam_norm(Q);
+  return {(float)(Q.x / Q.z), (float)(Q.y / Q.z), (float)(Q.x / n), (float)(Q.y / n), (float)(Q.z / n)};
+}

@@ -1,4 +1,4 @@
-"""The PINHOLE and MEI camera models on the device (trk_lift_pinhole / trk_lift_mei behind trk_lift, kernels_track.h) through every route
+"""The PINHOLE and MEI camera models on the device (cam_lift_pinhole / cam_lift_mei behind cam_lift, camera_models.h) through every route
 that takes an LfvioCamera, bit for bit unless said, against tests/camera_ref.py and against the library's own other routes.
 
   1  the lift: bearing_cur / bearing_forw equal camera_ref.bearings on every fixture case and on 2 x 1031 pixels over and 50 px beyond

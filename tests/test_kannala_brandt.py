@@ -1,4 +1,4 @@
-"""The KANNALA_BRANDT camera model on the device (trk_lift_kb behind trk_lift, kernels_track.h, over camera_kb.h) through every route that
+"""The KANNALA_BRANDT camera model on the device (kb_lift_pixel behind cam_lift, camera_models.h over camera_kb.h) through every route that
 takes an LfvioCamera, bit for bit unless said, against tests/kb_ref.py and against the library's own other routes.  Every test here
 fails on a library that answers LFVIO_ERR_ARG for model 5.
 
