@@ -40,7 +40,8 @@ int lfvio_debug_configure(lfvio_ctx *ctx, const char *key, double value);
  *   "marg_ahead"    {calls that started workers, priors a worker delivered} since the context was created
  *   "upload_times"  microseconds of the last upload: host packing | collecting a chained prior | prior + copies enqueued | final wait
  *   "sweep_kernel"  in out[0]: a count of resident slots; out[0]: the kernel that linearizes a launch over them — 0 k_lin (+ k_sum),
- *                   1 k_linw (a resident batch), 2 k_linb (+ k_sumb: a large single window) */
+ *                   1 k_linw (a resident batch), 2 k_linb (+ k_sumb: a large single window); out[1] (n >= 2): 1 where k_lin goes out
+ *                   role by role (k_lin<LIN_ROLE_LM>, <LIN_ROLE_GRAM>, k_imu_raw + k_lin<LIN_ROLE_POSE_RAW>), 0 where it is one grid */
 int lfvio_debug_query(lfvio_ctx *ctx, const char *key, double *out, int n);
 /* Gauss-Newton blocks at the window's state, caller landmark order:
  * Hpp 172x172 row-major, gp 172, a/b N, W N x 73, cost. */

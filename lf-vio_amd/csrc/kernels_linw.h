@@ -141,7 +141,9 @@ DEV void linw_strips(Slot *S, const LinView &lv, const LinwArgs &A, int cur, int
   //   prim[r]   where Q[kq + 4 r][ii] itself goes (upper triangle, < 14);
   //   extra[.]  for r = 0 and a jP row: the Pj copies (negated against other columns; (Pj, Pj) and the two (Pi, Pj) entries when
   //             the column is a jP column too);
-  //   the tic columns are Kt jP, Kt = M3^T M1 (M1 is orthogonal): lane e < 57 forms ONE entry (tic_a, u) = sum_k Kt[a][k] Q[k][u]
+  //   the tic columns are Kt jP, Kt = M3^T M1^-T — M3^T M1 where M1 = ric^T Rj^T is orthogonal, which it is unless the quaternion of
+  //             frame j or of the extrinsic is off the unit sphere (struct Tab: the pair then takes the inverse):
+  //             lane e < 57 forms ONE entry (tic_a, u) = sum_k Kt[a][k] Q[k][u]
   //             — or (tic_a, tic_b) — from rows 0 .. 2 of Q, which go through LDS for that.
   const int kq = lane >> 4, ii = lane & 15, privb = LW_PRIV0 + wv * (BIG ? LB_PRIVSZ : LW_PRIV), off0 = BIG ? privb + LW_PRIV : LW_OFF0;
   const size_t wld = BIG ? (size_t)A.wt_ld : (size_t)SPEC_MAX_LM;
@@ -302,13 +304,16 @@ DEV void linw_strips(Slot *S, const LinView &lv, const LinwArgs &A, int cur, int
       auto at = [&](int d) { return lw + ((d & 0xffff) + ((d >> 16) & 63) * s + ((d >> 22) & 63) * j + ((d & (1 << 28)) ? offp : 0)); };
       double tval = 0.0;
       if (tic_desc & LWD_VALID) {
-        // Kt = M3^T M1: Kt[a][k] = sum_m M3[m][a] M1[m][k] (uniform; this lane needs row a — and row b for a tic-tic entry)
+        // Kt = M3^T M1^-T: Kt[a][k] = sum_m M3[m][a] N1[m][k], N1 = M1 on the sphere (uniform; this lane needs row a — and row b for a
+        // tic-tic entry)
+        m33 N1 = M1;
+        if (OFFS && u.offc) N1 = tr(inv33(M1));  // (wave-uniform; a start point's newest frame)
         double ka[3], kb[3];
 #pragma unroll
         for (int k = 0; k < 3; k++) {
           double ra[3];
 #pragma unroll
-          for (int a2 = 0; a2 < 3; a2++) ra[a2] = fma(M3.a[6 + a2], M1.a[6 + k], fma(M3.a[3 + a2], M1.a[3 + k], M3.a[a2] * M1.a[k]));
+          for (int a2 = 0; a2 < 3; a2++) ra[a2] = fma(M3.a[6 + a2], N1.a[6 + k], fma(M3.a[3 + a2], N1.a[3 + k], M3.a[a2] * N1.a[k]));
           ka[k] = lw_sel3(tic_a, ra[0], ra[1], ra[2]);
           kb[k] = lw_sel3(tic_b < 0 ? 0 : tic_b, ra[0], ra[1], ra[2]);
         }

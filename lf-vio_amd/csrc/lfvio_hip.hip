@@ -2152,9 +2152,9 @@ int lfvio_debug_query(lfvio_ctx *c, const char *key, double *out, int n) {
   if (k == "marg_ahead") return put({(double)c->stat_ahead_calls, (double)c->stat_ahead_hits});
   if (k == "upload_times") return put({c->up_us[0], c->up_us[1], c->up_us[2], c->up_us[3]});
   if (k == "sweep_kernel") {  // out[0] in: the number of resident slots the launch would cover
-    const int r = sweep_kernel_of(c, (int)out[0]);
+    const int count = (int)out[0], r = sweep_kernel_of(c, count);
     if (r < 0) return r;
-    return put({(double)r});
+    return put({(double)r, route_for(c, count, MODE_SOLVE).split ? 1.0 : 0.0});
   }
   c->err = "lfvio_debug_query: unknown key '" + k + "'";
   return LFVIO_ERR_ARG;

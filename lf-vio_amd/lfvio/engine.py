@@ -894,6 +894,11 @@ class Engine:
         """Which kernel linearizes a launch over the resident slots [0, count): 0 k_lin (+ k_sum), 1 k_linw, 2 k_linb (+ k_sumb)."""
         return int(self.query("sweep_kernel", 1, float(count))[0])
 
+    def sweep_route(self, count):
+        """(the kernel as sweep_kernel gives it, whether k_lin goes out role by role) for a launch over `count` resident slots"""
+        q = self.query("sweep_kernel", 2, float(count))
+        return int(q[0]), bool(q[1])
+
     # ---- landmark-sharded API (multi-GPU)
     def shard_begin(self, win, lm_begin, lm_end, add_pose_side):
         self._shard_win = win  # keep the arrays alive

@@ -2,7 +2,9 @@
 the CPU oracle on the same seeded inputs and against the committed golden fixtures.
 
 Tolerances (FP64, sums re-ordered on the device):
-  * Gauss-Newton blocks (H_pp, g, a, b, W), cost            1e-10 relative to the block scale
+  * Gauss-Newton blocks (H_pp, g, a, b, W), cost            1e-10 relative to the block scale — of each whole array: beside the
+    1e10 of the IMU information roots that pins the ex / td rows, distant pose pairs and a single landmark's row only weakly.
+    What holds every block to the truth is tests/test_lin_hp.py (a 50-digit statement, per block, on every route)
   * trust-region trace: same accept/reject pattern, radii    1e-6, costs 1e-7 relative
   * final state (pose deltas)                                1e-6 relative   (north_star)
   * marginalization prior: structure exact; A', b', J0^T J0, J0^T r0   1e-6 relative; kept eigen-directions equal up to the

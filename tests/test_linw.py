@@ -4,7 +4,9 @@ and over whole optimization() calls, and against the oracle.
 
 Tolerances: the two device paths run the same per-observation arithmetic and associate the sums differently (one lane per
 track in frame order instead of four lanes + quad sum; private accumulators in wave order instead of k_sum's gather order)
-  * linearization outputs (g_p, Schur sums, a, b, landmark scalars, cost)      1e-11 relative to the array's largest entry
+  * linearization outputs (g_p, Schur sums, a, b, landmark scalars, cost)      1e-11 relative to the array's largest entry — a
+    path-against-path bar that never looks at W.  What holds k_linw's blocks (W, the visual part of H_pp, imu_out, prior_A) to
+    the truth is tests/test_lin_hp.py (a 50-digit statement, per block)
   * the dense solve behind them (pose-side Gauss-Newton step, q[])              1e-6 (the reduced system's conditioning) — a
     path-against-path bar: both paths share the Cholesky.  What holds the step and q[] to the truth is tests/test_solve_hp.py
     (a 50-digit reference on the solve's own inputs, bars in eps and eps kappa_2(S))
