@@ -12,7 +12,9 @@ extern "C" {
  *   "graph"              0: launch kernels directly, 1 (default): replay the captured hipGraphs
  *   "first_passes"       n > 0: every first graph of the synchronous entry points carries n passes instead of the most any of the last
  *                        four calls needed; 0: adaptive again
- *   "spec_count"         n > 0: a fixed number of speculative candidates per pass (1 .. 4); 0: from the call before (3, or 4)
+ *   "spec_count"         n > 0: a fixed number of speculative candidates per pass (1 .. 4); 0: from the call before (3, or 4).  The
+ *                        answer of a call — state, inverse depths, summary, trace, prior — is the same bytes for every value, and so
+ *                        for every history of a context (tests/test_spec_candidates.py); only the passes a call takes differ
  *   "function_tolerance" Solver::Options::function_tolerance of the windows uploaded from now on (Ceres' default 1e-6, which
  *                        estimator.cpp:810-822 leaves alone); 0 makes the loop run to its iteration cap or another criterion
  *   "initial_radius"     Solver::Options::initial_trust_region_radius of the windows uploaded from now on (Ceres' default 1e4; <= 0
@@ -36,7 +38,8 @@ extern "C" {
 int lfvio_debug_configure(lfvio_ctx *ctx, const char *key, double value);
 /* What the last calls left, as doubles into out[0 .. n).
  *   "last_call"     {passes of the trust-region loop the slowest window of the last synchronous call used, iterations they covered,
- *                   graph launches of that call (1: everything ran in the first graph), speculative candidates the next call prepares}
+ *                   graph launches of that call (1: everything ran in the first graph), speculative candidates per pass: the fixed number, or what the
+ *                   last call that speculated chose from the two counts of the call before it}
  *   "marg_ahead"    {calls that started workers, priors a worker delivered} since the context was created
  *   "upload_times"  microseconds of the last upload: host packing | collecting a chained prior | prior + copies enqueued | final wait
  *   "sweep_kernel"  in out[0]: a count of resident slots; out[0]: the kernel that linearizes a launch over them — 0 k_lin (+ k_sum),

@@ -1223,6 +1223,14 @@ int adaptive_loop(lfvio_ctx *c, const Route &r, const CallPlan &p, int passes, b
       break;
     }
   }
+  if (count == 1 && !*tail_done) {
+    // the window was still open behind the first graph: the iters_done that graph copied is the upload's zero, and the tail graph that
+    // sets it copies nothing back.  The count is final in the header (stream 0 is idle here); without it the next call would choose
+    // its candidates from "no iterations" (loop_graphs) and "last_call" would report none (tests/test_spec_candidates.py).
+    int it = 0;
+    HIPCHK(c, hipMemcpy(&it, c->d_base + offsetof(Slot, tr) + offsetof(TRState, iteration), sizeof it, hipMemcpyDeviceToHost));
+    c->last_iters = it;
+  }
   record_call(c, c->h_pending->passes, c->last_iters, c->call.loop_ended());  // passes the slowest window has used
   HIPCHK(c, hipGetLastError());
   // (a call that ended inside its first graph: the prior may be on its way from a worker; one that continues with a tail graph

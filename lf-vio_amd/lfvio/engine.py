@@ -204,6 +204,16 @@ class Engine:
         """Debug: > 0 sizes every first graph of the synchronous calls with this many passes (0: from the recent calls again)."""
         self.configure("first_passes", int(n))
 
+    def set_spec_count(self, n):
+        """Debug: 1 .. 4 fixes the speculative candidates a pass of a small window prepares (0: from the call before again, 3 or 4).
+        The answer is the same bytes for every value (tests/test_spec_candidates.py)."""
+        self.configure("spec_count", int(n))
+
+    def last_call(self):
+        """(passes the slowest window of the last synchronous call used, iterations they covered, graph launches of that call,
+        candidates per pass of the last call that speculated) — lfvio_debug_query "last_call"."""
+        return tuple(int(v) for v in self.query("last_call", 4))
+
     def batch_upload_chained_device(self, slot, win, marshalled=None):
         """The next window of the same estimator, its prior taken over ON THE DEVICE from the call still in flight (no wait, no
         copy of the prior in either direction); win.prior is ignored."""
