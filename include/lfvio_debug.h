@@ -1,6 +1,6 @@
 /*
  * lfvio_debug.h — parity / inspection hooks of liblfvio_hip.so used by tests/, tools/ and bench.py only.
- * Not part of the drop-in boundary (include/lfvio.h).  Ten entry points: two that take a key, eight that look inside.
+ * Not part of the drop-in boundary (include/lfvio.h).  Eleven entry points: two that take a key, nine that look inside.
  */
 #ifndef LFVIO_DEBUG_H
 #define LFVIO_DEBUG_H
@@ -93,6 +93,42 @@ typedef struct LfvioPassIO {
   int chol_fail, prior_n, est_ex, est_td, num_landmarks;
 } LfvioPassIO;
 int lfvio_debug_pass_io(lfvio_ctx *ctx, int count, int slot, double mu, LfvioPassIO *io);
+/* The step half of the same pass — landmark back-substitution, dogleg, candidates, their cost at every factor, bookkeeping — for
+ * tests/test_step_hp.py.  Launches exactly what lfvio_debug_pass_io launches (mu > 0 replaces tr.mu and radius > 0 tr.radius of every slot
+ * between k_setup and the sweep), then the step half through the very function the loop's passes go through, by the route that launch takes:
+ * k_step | k_backsub / k_backsub_wt + k_dogleg + k_cost (+ k_cost_imu) + k_decide | k_stepw.  `spec`: candidates per pass, 1 .. 4 where the
+ * route speculates (here: count = 1 and at most 320 landmarks), 1 otherwise (LFVIO_ERR_ARG if not).  The bookkeeping is k_decide, the form behind
+ * the last pass of a sequence, except in k_stepw, which carries it.  Adds no kernel and no kernel argument.  On the routes with a k_decide of
+ * their own the stream is joined in front of it and `head`, the candidates and their sums are copied then (head_valid 1); behind k_stepw
+ * `head` is the header in front of the step half, with the totals the step half wrote (gn_sq_total, grad_gn_total, gmax_pose, spec_n) taken
+ * from the copy after it, as the candidates are: its bookkeeping leaves them alone (head_valid 0).  Every pointer may be NULL.  Returns the sweep kernel as lfvio_debug_pass_io does, < 0 on error.
+ *   LFVIO_STATE_DOUBLES   a state: pose [11][7] | speed/bias [11][9] | ex [7] | td
+ *   read by the step half   pass: everything of LfvioPassIO; scale_l, diag_l, grad_l, einv_l, lam [N] (device landmark order; lam = lam[cur]),
+ *                           x [LFVIO_STATE_DOUBLES] = x[cur], head: the header in front of the bookkeeping
+ *   written                 gn_l, d1, d2 [N], step_p [172]; per candidate z < spec (slot z of every array): coef [4][5] = cg, cn,
+ *                           dogleg_step_norm, step_sq_pose, xn2_pose_cand; cand_x [4][LFVIO_STATE_DOUBLES]; cand_lam [4][N]; block_sums
+ *                           [4][num_blocks][5] = cost, mlin, mquad, dn, xn of every landmark block (behind k_stepw the window's totals in
+ *                           block 0); pose_cost [4][11]: IMU factors 0 .. 9 and the prior; cand_tab [4][tab_bytes]: the pair table
+ *   after the bookkeeping   after (the header), trace [LFVIO_MAX_TRACE] (entries head.trace_len .. after.trace_len - 1 are this pass's),
+ *                           x_after, lam_after [N], tab_after [tab_bytes]: x / lam / tab [after.cur] */
+#define LFVIO_STATE_DOUBLES (11 * 7 + 11 * 9 + 7 + 1)
+typedef struct LfvioStepHeader {
+  double radius, mu, x_cost, x_norm, cand_cost, model_cost_change, alpha, grad_sq_total, gn_sq_total, grad_gn_total, gmax_pose, function_tolerance;
+  double q[16];
+  int iteration, cur, do_lin, do_schur, done, termination, chol_fail, num_succ, num_unsucc, consec_invalid, trace_len, skip_step, spec_n, max_iter;
+} LfvioStepHeader;
+typedef struct LfvioStepIO {
+  LfvioPassIO pass;
+  double *scale_l, *diag_l, *grad_l, *einv_l, *lam, *x;
+  double *gn_l, *d1, *d2, *step_p;
+  double *coef, *cand_x, *cand_lam, *block_sums, *pose_cost;
+  unsigned char *cand_tab, *tab_after;
+  double *x_after, *lam_after;
+  LfvioIterationSummary *trace;
+  LfvioStepHeader head, after;
+  int head_valid, num_blocks, tab_bytes, spec, stepw; /* head was copied in front of the bookkeeping | landmark blocks | sizeof the pair table | candidates | 1: k_stepw ran */
+} LfvioStepIO;
+int lfvio_debug_step_io(lfvio_ctx *ctx, int count, int slot, double mu, double radius, int spec, LfvioStepIO *io);
 /* tests: the local context `local_ctx` of the group reports a failure when it enqueues phase `phase` (0 the sweep, 4 solve ..
  * candidate cost, 3 bookkeeping) of pass `pass` of the next lfvio_group_optimize(); local_ctx < 0 clears it.
  * The call must still issue every collective of its sequence (the peers of a real group are waiting in them), end the loops of all

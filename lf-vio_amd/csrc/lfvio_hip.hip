@@ -946,54 +946,72 @@ struct Pass {
   bool publish = false;            // ... and hands the state over early (CallPlan::publish)
   bool offs = true;                // see with_offs
 };
-// r: route_for(c, count, mode)
-bool launch_iteration(lfvio_ctx *c, const Route &r, int mode, const Pass &ps) {
+// The bookkeeping of a pass of the loop rides in the prologue of the next pass's k_lin
+// (latency of few windows only: in a resident batch every workgroup of k_lin repeating the decision costs more of the
+// GPU than the launch it saves)
+static bool pass_merges(const Route &r) { return r.sweep != Route::LINW && r.g.lm <= DOGLEG_INLINE_BLOCKS && r.role_wgs <= LIN_SPLIT_WGS; }
+
+// The step half of a pass behind its dense solve: landmark back-substitution, dogleg, candidates, their cost at every factor and — where it
+// does not ride in the next pass's k_lin (merge) — the bookkeeping.  spec_count: candidates a speculating pass prepares.  before_decide() is
+// called in front of a bookkeeping kernel of its own (not k_stepw, which carries it): nothing for the loop; lfvio_debug_step_io joins the
+// stream there and copies what the bookkeeping is about to read.  Returns true if the gated gauge fix went out with the bookkeeping.
+template <class F>
+bool launch_step_half(lfvio_ctx *c, const Route &r, const Pass &ps, bool merge, int spec_count, F &&before_decide) {
   const int count = r.count;
   const Grid &g = r.g;
   const size_t st = c->L.total;
-  const bool solve = (mode & (MODE_GATED - 1)) == MODE_SOLVE && !(mode & MODE_GATED);
-  // (latency of few windows only: in a resident batch every workgroup of k_lin repeating the decision costs more of the
-  // GPU than the launch it saves)
   const bool lw = r.sweep == Route::LINW, lb = r.sweep == Route::LINB;
-  const bool merge = solve && !lw && g.lm <= DOGLEG_INLINE_BLOCKS && r.role_wgs <= LIN_SPLIT_WGS;
+  // small windows: the landmark back-substitution rides inside k_dogleg (one launch less per pass)
+  const bool inl = g.lm <= DOGLEG_INLINE_BLOCKS;
+  const int spec = ps.speculate && inl ? spec_count : 1;
+  const int nb = g.lm + LFVIO_WINDOW_SIZE + 1;
+  // few small windows: the step and the cost of its candidates in one launch (k_step)
+  const bool split = r.split || lw;
+  const bool fuse = inl && !split && !c->shard_active && (size_t)count * nb <= 2048;
+  // a resident batch on the window-resident path: step, candidate cost and bookkeeping as ONE launch, one workgroup per window
+  const bool stepw = lw && inl && spec == 1;
+  if (stepw) {
+    hipLaunchKernelGGL(k_stepw, dim3(1, count), dim3(STEPW_LAUNCH_THREADS), 0, c->stream, c->d_base, st);
+    return false;
+  }
+  if (!inl && lb) hipLaunchKernelGGL(k_backsub_wt, dim3(g.lm, count), dim3(64), 0, c->stream, c->d_base, st, c->L.capLmBlocks * LM_BLOCK);
+  else if (!inl) hipLaunchKernelGGL(k_backsub, dim3(g.lm, count), dim3(64), 0, c->stream, c->d_base, st);
+  if (fuse) hipLaunchKernelGGL(k_step, dim3(spec * nb, count), dim3(DOGLEG_INLINE_THREADS), 0, c->stream, c->d_base, st, g.lm, spec);
+  else {
+    if (inl && (!split || lw)) hipLaunchKernelGGL((k_dogleg<true, true>), dim3(spec, count), dim3(DOGLEG_INLINE_THREADS), 0, c->stream, c->d_base, st, spec);
+    else if (inl) hipLaunchKernelGGL((k_dogleg<true, false>), dim3(spec, count), dim3(DOGLEG_INLINE_THREADS), 0, c->stream, c->d_base, st, spec);
+    else hipLaunchKernelGGL(k_dogleg<false>, dim3(spec, count), dim3(128), 0, c->stream, c->d_base, st, spec);
+  }
+  // four lanes per track while the GPU has room for the extra waves (latency of few windows), one when a batch fills it
+  if (fuse) {
+  } else if ((size_t)count * nb <= 2048)  // (four waves per workgroup: 8 192 waves = eight per SIMD)
+    hipLaunchKernelGGL(k_cost<4>, dim3(spec * nb, count), dim3(256), 0, c->stream, c->d_base, st, g.lm, spec);
+  else if (spec == 1 && !c->shard_active) {
+    hipLaunchKernelGGL((k_cost<1, false>), dim3(g.lm + 1, count), dim3(64), 0, c->stream, c->d_base, st, g.lm, 1);
+    hipLaunchKernelGGL(k_cost_imu, dim3((count * LFVIO_WINDOW_SIZE + 63) / 64), dim3(64), 0, c->stream, c->d_base, st, count);
+  } else
+    hipLaunchKernelGGL(k_cost<1>, dim3(spec * nb, count), dim3(64), 0, c->stream, c->d_base, st, g.lm, spec);
+  if (merge && ps.last && ps.gauge) {
+    before_decide();
+    hipLaunchKernelGGL(k_decide_gauge, dim3(1, count), dim3(128), 0, c->stream, c->d_base, st, ps.publish ? 1 : 0);
+    return true;
+  }
+  if (!merge || ps.last) {
+    before_decide();
+    hipLaunchKernelGGL(k_decide, dim3(1, count), dim3(64), 0, c->stream, c->d_base, st);
+  }
+  return false;
+}
+
+// r: route_for(c, count, mode)
+bool launch_iteration(lfvio_ctx *c, const Route &r, int mode, const Pass &ps) {
+  const bool solve = (mode & (MODE_GATED - 1)) == MODE_SOLVE && !(mode & MODE_GATED);
+  const bool lw = r.sweep == Route::LINW;
+  const bool merge = solve && pass_merges(r);
   launch_sweep(c, r, mode, ps.offs, merge && !ps.first);
   if ((mode & (MODE_GATED - 1)) == MODE_SOLVE) {
-    launch_solve(c, count, lw);  // (k_sumb leaves the complete matrix)
-    // small windows: the landmark back-substitution rides inside k_dogleg (one launch less per pass)
-    const bool inl = g.lm <= DOGLEG_INLINE_BLOCKS;
-    const int spec = ps.speculate && inl ? c->spec_count : 1;
-    const int nb = g.lm + LFVIO_WINDOW_SIZE + 1;
-    // few small windows: the step and the cost of its candidates in one launch (k_step)
-    const bool split = r.split || lw;
-    const bool fuse = inl && !split && !c->shard_active && (size_t)count * nb <= 2048;
-    // a resident batch on the window-resident path: step, candidate cost and bookkeeping as ONE launch, one workgroup per window
-    const bool stepw = lw && inl && spec == 1;
-    if (stepw) {
-      hipLaunchKernelGGL(k_stepw, dim3(1, count), dim3(STEPW_LAUNCH_THREADS), 0, c->stream, c->d_base, st);
-      return false;
-    }
-    if (!inl && lb) hipLaunchKernelGGL(k_backsub_wt, dim3(g.lm, count), dim3(64), 0, c->stream, c->d_base, st, c->L.capLmBlocks * LM_BLOCK);
-    else if (!inl) hipLaunchKernelGGL(k_backsub, dim3(g.lm, count), dim3(64), 0, c->stream, c->d_base, st);
-    if (fuse) hipLaunchKernelGGL(k_step, dim3(spec * nb, count), dim3(DOGLEG_INLINE_THREADS), 0, c->stream, c->d_base, st, g.lm, spec);
-    else {
-      if (inl && (!split || lw)) hipLaunchKernelGGL((k_dogleg<true, true>), dim3(spec, count), dim3(DOGLEG_INLINE_THREADS), 0, c->stream, c->d_base, st, spec);
-      else if (inl) hipLaunchKernelGGL((k_dogleg<true, false>), dim3(spec, count), dim3(DOGLEG_INLINE_THREADS), 0, c->stream, c->d_base, st, spec);
-      else hipLaunchKernelGGL(k_dogleg<false>, dim3(spec, count), dim3(128), 0, c->stream, c->d_base, st, spec);
-    }
-    // four lanes per track while the GPU has room for the extra waves (latency of few windows), one when a batch fills it
-    if (fuse) {
-    } else if ((size_t)count * nb <= 2048)  // (four waves per workgroup: 8 192 waves = eight per SIMD)
-      hipLaunchKernelGGL(k_cost<4>, dim3(spec * nb, count), dim3(256), 0, c->stream, c->d_base, st, g.lm, spec);
-    else if (spec == 1 && !c->shard_active) {
-      hipLaunchKernelGGL((k_cost<1, false>), dim3(g.lm + 1, count), dim3(64), 0, c->stream, c->d_base, st, g.lm, 1);
-      hipLaunchKernelGGL(k_cost_imu, dim3((count * LFVIO_WINDOW_SIZE + 63) / 64), dim3(64), 0, c->stream, c->d_base, st, count);
-    } else
-      hipLaunchKernelGGL(k_cost<1>, dim3(spec * nb, count), dim3(64), 0, c->stream, c->d_base, st, g.lm, spec);
-    if (merge && ps.last && ps.gauge) {
-      hipLaunchKernelGGL(k_decide_gauge, dim3(1, count), dim3(128), 0, c->stream, c->d_base, st, ps.publish ? 1 : 0);
-      return true;
-    }
-    if (!merge || ps.last) hipLaunchKernelGGL(k_decide, dim3(1, count), dim3(64), 0, c->stream, c->d_base, st);
+    launch_solve(c, r.count, lw);  // (k_sumb leaves the complete matrix)
+    return launch_step_half(c, r, ps, merge, c->spec_count, [] {});
   }
   return false;
 }
@@ -2019,26 +2037,35 @@ int lfvio_debug_resident_pass(lfvio_ctx *c, int count, int slot, double *gp, dou
 
 // The same pass as lfvio_debug_resident_pass — at the caller's mu where it gives one — and everything k_solve_dense read and wrote in slot
 // `slot` (include/lfvio_debug.h): plain copies of what the pass leaves.  tests/test_solve_hp.py holds the solve to a 50-digit reference
-// formed from these very inputs.
-int lfvio_debug_pass_io(lfvio_ctx *c, int count, int slot, double mu, LfvioPassIO *io) {
-  if (!c || !c->d_base || !io || count <= 0 || count > c->batch || slot < 0 || slot >= count) return LFVIO_ERR_ARG;
+// formed from these very inputs.  In two halves, which lfvio_debug_step_io shares:
+// k_setup, the header's mu (and radius) where the caller gives one, the sweep and the solve of the launch's own route: the first half of a pass
+static int debug_pass_launch(lfvio_ctx *c, const Route &r, int count, int slot, double mu, double radius) {
+  if (!c || !c->d_base || count <= 0 || count > c->batch || slot < 0 || slot >= count) return LFVIO_ERR_ARG;
   (void)hipSetDevice(c->device);
   if (int rc = join_inflight(c)) return rc;
   for (int s = 0; s < count; s++)
     if (!c->info[s].resident) return LFVIO_ERR_ARG;
   const size_t st = c->L.total;
-  const Layout &L = c->L;
-  const Route r = route_for(c, count, MODE_SOLVE);
   launch_setup(c, r, MODE_SOLVE);
   if (mu > 0.0) {  // (k_setup arms the header with Ceres' initial mu: the caller's replaces it before the sweep weighs the landmarks with it)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (int s = 0; s < count; s++)
       HIPCHK(c, hipMemcpy(c->d_base + (size_t)s * st + offsetof(Slot, tr) + offsetof(TRState, mu), &mu, sizeof mu, hipMemcpyHostToDevice));
   }
+  if (radius > 0.0) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int s = 0; s < count; s++)
+      HIPCHK(c, hipMemcpy(c->d_base + (size_t)s * st + offsetof(Slot, tr) + offsetof(TRState, radius), &radius, sizeof radius, hipMemcpyHostToDevice));
+  }
   launch_sweep(c, r, MODE_SOLVE, true);
   launch_solve(c, count, r.sweep == Route::LINW);
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return LFVIO_OK;
+}
+// what that half left in slot `slot`
+static int debug_pass_copy(lfvio_ctx *c, const Route &r, int slot, LfvioPassIO *io) {
+  const size_t st = c->L.total;
+  const Layout &L = c->L;
   const char *d = c->d_base + (size_t)slot * st;
   const int N = c->info[slot].N;
   auto get = [&](void *dst, size_t off, size_t bytes) { return !dst || !bytes ? hipSuccess : hipMemcpy(dst, d + off, bytes, hipMemcpyDeviceToHost); };
@@ -2096,7 +2123,115 @@ int lfvio_debug_pass_io(lfvio_ctx *c, int count, int slot, double mu, LfvioPassI
   io->alpha = th.alpha, io->grad_sq_total = th.grad_sq_total, io->x_cost = th.x_cost, io->mu = th.mu, io->chol_fail = th.chol_fail;
   return r.sweep;
 }
+int lfvio_debug_pass_io(lfvio_ctx *c, int count, int slot, double mu, LfvioPassIO *io) {
+  if (!c || !c->d_base || !io || count <= 0 || count > c->batch) return LFVIO_ERR_ARG;
+  const Route r = route_for(c, count, MODE_SOLVE);
+  if (int rc = debug_pass_launch(c, r, count, slot, mu, 0.0)) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return debug_pass_copy(c, r, slot, io);
+}
 
+// The whole pass: the half above, then the step half through launch_step_half — the function the loop's passes go through — and what it
+// read and wrote in slot `slot` (include/lfvio_debug.h).  tests/test_step_hp.py holds every stage to a 50-digit reference formed from these
+// very inputs.
+static void step_header_from(LfvioStepHeader &h, const TRHead &t, int max_iter) {
+  h.radius = t.radius, h.mu = t.mu, h.x_cost = t.x_cost, h.x_norm = t.x_norm, h.cand_cost = t.cand_cost, h.model_cost_change = t.model_cost_change;
+  h.alpha = t.alpha, h.grad_sq_total = t.grad_sq_total, h.gn_sq_total = t.gn_sq_total, h.grad_gn_total = t.grad_gn_total, h.gmax_pose = t.gmax_pose;
+  h.function_tolerance = t.function_tolerance;
+  std::copy(t.q, t.q + Q_COUNT, h.q);
+  h.iteration = t.iteration, h.cur = t.cur, h.do_lin = t.do_lin, h.do_schur = t.do_schur, h.done = t.done, h.termination = t.termination;
+  h.chol_fail = t.chol_fail, h.num_succ = t.num_succ, h.num_unsucc = t.num_unsucc, h.consec_invalid = t.consec_invalid, h.trace_len = t.trace_len;
+  h.skip_step = t.skip_step, h.spec_n = t.spec_n, h.max_iter = max_iter;
+}
+int lfvio_debug_step_io(lfvio_ctx *c, int count, int slot, double mu, double radius, int spec, LfvioStepIO *io) {
+  if (!c || !c->d_base || !io || count <= 0 || count > c->batch || slot < 0 || slot >= count) return LFVIO_ERR_ARG;
+  const Route r = route_for(c, count, MODE_SOLVE);
+  // (more than one candidate only where the loop itself always speculates: one window whose back-substitution rides in the dogleg)
+  const bool speculates = count == 1 && r.g.lm <= DOGLEG_INLINE_BLOCKS;
+  if (spec < 1 || spec > 1 + SPEC_EXTRA || (spec > 1 && !speculates)) return LFVIO_ERR_ARG;
+  static_assert(sizeof(FrameState) == LFVIO_STATE_DOUBLES * sizeof(double), "LFVIO_STATE_DOUBLES is a FrameState");
+  if (int rc = debug_pass_launch(c, r, count, slot, mu, radius)) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (int rc = debug_pass_copy(c, r, slot, &io->pass); rc < 0) return rc;
+  const size_t st = c->L.total;
+  const Layout &L = c->L;
+  const char *d = c->d_base + (size_t)slot * st;
+  const int N = c->info[slot].N;
+  auto get = [&](void *dst, size_t off, size_t bytes) { return !dst || !bytes ? hipSuccess : hipMemcpy(dst, d + off, bytes, hipMemcpyDeviceToHost); };
+  int nblk = 0, max_iter = 0;
+  HIPCHK(c, get(&nblk, offsetof(Slot, nLmBlocks), sizeof nblk));
+  HIPCHK(c, get(&max_iter, offsetof(Slot, max_iter), sizeof max_iter));
+  if (nblk < 0 || nblk > L.capLmBlocks) return LFVIO_ERR_ARG;
+  io->num_blocks = nblk, io->tab_bytes = (int)sizeof(Tab), io->spec = spec, io->head_valid = 0, io->stepw = 0;
+  TRHead th;
+  HIPCHK(c, get(&th, offsetof(Slot, tr), sizeof th));
+  const int cur = th.cur & 1;
+  step_header_from(io->head, th, max_iter);
+  // read by the step half (the solve is behind us, nothing of this is written by the step half)
+  HIPCHK(c, get(io->scale_l, L.scale_l, (size_t)N * 8));
+  HIPCHK(c, get(io->diag_l, L.diag_l, (size_t)N * 8));
+  HIPCHK(c, get(io->grad_l, L.grad_l, (size_t)N * 8));
+  HIPCHK(c, get(io->einv_l, L.einv_l, (size_t)N * 8));
+  HIPCHK(c, get(io->lam, L.lam[cur], (size_t)N * 8));
+  HIPCHK(c, get(io->x, offsetof(Slot, x) + (size_t)cur * sizeof(FrameState), sizeof(FrameState)));
+  // what the bookkeeping reads: copied in front of it, where it is a kernel of its own (an accepted speculative candidate is copied
+  // over candidate 0 by it), behind k_stepw otherwise (one candidate, which its bookkeeping leaves where it is)
+  int crc = LFVIO_OK;
+  auto copy_candidates = [&]() -> int {
+    TRHead t;
+    HIPCHK(c, get(&t, offsetof(Slot, tr), sizeof t));
+    if (io->head_valid) step_header_from(io->head, t, max_iter);
+    else io->head.gn_sq_total = t.gn_sq_total, io->head.grad_gn_total = t.grad_gn_total, io->head.gmax_pose = t.gmax_pose, io->head.spec_n = t.spec_n;
+    HIPCHK(c, get(io->gn_l, L.gn_l, (size_t)N * 8));
+    HIPCHK(c, get(io->d1, L.d1, (size_t)N * 8));
+    HIPCHK(c, get(io->d2, L.d2, (size_t)N * 8));
+    HIPCHK(c, get(io->step_p, offsetof(Slot, step_p), KP * 8));
+    std::vector<double> part;
+    for (int z = 0; z < spec; z++) {
+      if (io->coef) {
+        double *o = io->coef + 5 * z;
+        o[0] = z ? t.cgE[z - 1] : t.cg, o[1] = z ? t.cnE[z - 1] : t.cn, o[2] = z ? t.snE[z - 1] : t.dogleg_step_norm;
+        o[3] = z ? t.step_sqE[z - 1] : t.step_sq_pose, o[4] = z ? t.xn2E[z - 1] : t.xn2_pose_cand;
+      }
+      const size_t xo = z ? offsetof(Slot, xE) + (size_t)(z - 1) * sizeof(FrameState) : offsetof(Slot, x) + (size_t)(cur ^ 1) * sizeof(FrameState);
+      const size_t to = z ? offsetof(Slot, tabE) + (size_t)(z - 1) * sizeof(Tab) : offsetof(Slot, tab) + (size_t)(cur ^ 1) * sizeof(Tab);
+      HIPCHK(c, get(io->cand_x ? io->cand_x + (size_t)z * LFVIO_STATE_DOUBLES : nullptr, xo, sizeof(FrameState)));
+      HIPCHK(c, get(io->cand_tab ? io->cand_tab + (size_t)z * sizeof(Tab) : nullptr, to, sizeof(Tab)));
+      HIPCHK(c, get(io->cand_lam ? io->cand_lam + (size_t)z * N : nullptr, z ? L.lamE[z - 1] : L.lam[cur ^ 1], (size_t)N * 8));
+      HIPCHK(c, get(io->pose_cost ? io->pose_cost + 11 * z : nullptr, z ? offsetof(Slot, pose_costE) + (size_t)(z - 1) * 16 * 8 : offsetof(Slot, pose_cost), 11 * 8));
+      if (io->block_sums && nblk) {
+        // (candidates 1 .. hold the blocks of windows of at most SPEC_MAX_LM landmarks: the only ones that speculate)
+        if (z && nblk > SPEC_MAX_LM / 64) return LFVIO_ERR_ARG;
+        part.resize((size_t)nblk * LMS);
+        HIPCHK(c, get(part.data(), z ? L.cost_partE + (size_t)(z - 1) * (SPEC_MAX_LM / 64) * LMS * 8 : L.cost_part, part.size() * 8));
+        for (int b = 0; b < nblk; b++) std::copy(part.begin() + (size_t)b * LMS, part.begin() + (size_t)b * LMS + 5, io->block_sums + ((size_t)z * nblk + b) * 5);
+      }
+    }
+    return LFVIO_OK;
+  };
+  Pass ps;
+  ps.speculate = spec > 1;  // (first and last: the bookkeeping is k_decide, the form behind the last pass of a sequence)
+  launch_step_half(c, r, ps, pass_merges(r), spec, [&] {
+    io->head_valid = 1;
+    const hipError_t e = hipStreamSynchronize(c->stream);
+    crc = e != hipSuccess ? LFVIO_ERR_DEVICE : copy_candidates();
+  });
+  if (crc) return crc;
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (!io->head_valid) {
+    io->stepw = 1;
+    if (int rc = copy_candidates()) return rc;
+  }
+  HIPCHK(c, get(&th, offsetof(Slot, tr), sizeof th));
+  step_header_from(io->after, th, max_iter);
+  const int ncur = th.cur & 1;
+  HIPCHK(c, get(io->trace, offsetof(Slot, tr) + offsetof(TRState, trace), sizeof(LfvioIterationSummary) * LFVIO_MAX_TRACE));
+  HIPCHK(c, get(io->x_after, offsetof(Slot, x) + (size_t)ncur * sizeof(FrameState), sizeof(FrameState)));
+  HIPCHK(c, get(io->lam_after, L.lam[ncur], (size_t)N * 8));
+  HIPCHK(c, get(io->tab_after, offsetof(Slot, tab) + (size_t)ncur * sizeof(Tab), sizeof(Tab)));
+  return r.sweep;
+}
 // Every switch of the debug interface in one call (include/lfvio_debug.h).  The product entry points read no environment: a tool
 // that wants LFVIO_DEBUG="key=value,key=value" honoured asks for it with the key "env".
 int lfvio_debug_configure(lfvio_ctx *c, const char *key, double value) {

@@ -123,6 +123,89 @@ class Engine:
             out[k] = getattr(io, k)
         return out
 
+    STATE_DOUBLES = 11 * 7 + 11 * 9 + 7 + 1  # LFVIO_STATE_DOUBLES: pose [11][7] | speed/bias [11][9] | ex [7] | td
+
+    class _StepHeader(C.Structure):  # LfvioStepHeader of include/lfvio_debug.h
+        _DOUBLES = ("radius", "mu", "x_cost", "x_norm", "cand_cost", "model_cost_change", "alpha", "grad_sq_total", "gn_sq_total",
+                    "grad_gn_total", "gmax_pose", "function_tolerance")
+        _INTS = ("iteration", "cur", "do_lin", "do_schur", "done", "termination", "chol_fail", "num_succ", "num_unsucc", "consec_invalid",
+                 "trace_len", "skip_step", "spec_n", "max_iter")
+        _fields_ = [(k, C.c_double) for k in _DOUBLES] + [("q", C.c_double * 16)] + [(k, C.c_int) for k in _INTS]
+
+        def as_dict(self):
+            d = {k: getattr(self, k) for k in self._DOUBLES + self._INTS}
+            d["q"] = np.array(self.q[:])
+            return d
+
+    class _StepIO(C.Structure):  # LfvioStepIO
+        _DOUBLE_ARRAYS = ("scale_l", "diag_l", "grad_l", "einv_l", "lam", "x", "gn_l", "d1", "d2", "step_p", "coef", "cand_x", "cand_lam",
+                          "block_sums", "pose_cost")
+        _BYTE_ARRAYS = ("cand_tab", "tab_after")
+
+    _StepIO._fields_ = ([("pass_", _PassIO)] + [(k, _dp) for k in _StepIO._DOUBLE_ARRAYS] + [(k, C.POINTER(C.c_ubyte)) for k in _StepIO._BYTE_ARRAYS]
+                        + [("x_after", _dp), ("lam_after", _dp), ("trace", C.POINTER(abi.IterationSummary)), ("head", _StepHeader),
+                           ("after", _StepHeader)] + [(k, C.c_int) for k in ("head_valid", "num_blocks", "tab_bytes", "spec", "stepw")])
+
+    @staticmethod
+    def state_dict(v):
+        """A state of LFVIO_STATE_DOUBLES doubles as pose [11, 7], sb [11, 9], ex [7], td."""
+        v = np.asarray(v, dtype=np.float64)
+        return dict(pose=v[:77].reshape(11, 7).copy(), sb=v[77:176].reshape(11, 9).copy(), ex=v[176:183].copy(), td=float(v[183]))
+
+    def step_io(self, count, slot, n_landmarks, mu=0.0, radius=0.0, spec=1, tabs=False):
+        """One whole pass of the resident slots [0, count) at `mu` and `radius` (0: what the setup leaves) with `spec` candidates:
+        everything the step half of `slot` read and wrote, as a dict (lfvio_debug_step_io; the first half under the names of
+        pass_io).  Landmarks in device order; the per-candidate arrays have `spec` leading entries; head / after are dicts of the
+        header's fields, trace the list of the entries this pass pushed.  tabs: the pair tables too (cand_tab [spec, tab_bytes],
+        tab_after [tab_bytes] as uint8)."""
+        N, KP, SD = n_landmarks, abi.KP, Engine.STATE_DOUBLES
+        n1, nb = max(N, 1), max((N + 63) // 64, 1)
+        out = dict(H=np.zeros(KP * (KP + 1) // 2), gp=np.zeros(KP), schur=np.zeros(15 * 256), lm_sum=np.zeros(16), imu_out=np.zeros((10, 932)),
+                   prior_A=np.zeros(KP * KP), prior_cmap=np.zeros(KP, np.int32), a=np.zeros(n1), b=np.zeros(n1),
+                   W=np.zeros((n1, abi.KC)), scale_p=np.zeros(KP), diag_p=np.zeros(KP), grad_p=np.zeros(KP), gn_p=np.zeros(KP),
+                   uc_grad=np.zeros(80), uc_gn=np.zeros(80), q=np.zeros(16))
+        io = Engine._StepIO()
+        for k in Engine._PassIO._ARRAYS:
+            setattr(io.pass_, k, out[k].ctypes.data_as(C.POINTER(C.c_int) if k == "prior_cmap" else _dp))
+        more = dict(scale_l=np.zeros(n1), diag_l=np.zeros(n1), grad_l=np.zeros(n1), einv_l=np.zeros(n1), lam=np.zeros(n1), x=np.zeros(SD),
+                    gn_l=np.zeros(n1), d1=np.zeros(n1), d2=np.zeros(n1), step_p=np.zeros(KP), coef=np.zeros((4, 5)), cand_x=np.zeros((4, SD)),
+                    cand_lam=np.zeros((4, n1)), block_sums=np.zeros((4, nb, 5)), pose_cost=np.zeros((4, 11)), x_after=np.zeros(SD),
+                    lam_after=np.zeros(n1))
+        for k, a in more.items():
+            setattr(io, k, _p(a))
+        tab_cap = 32768  # (room for the table: the library reports its size)
+        if tabs:
+            more.update(cand_tab=np.zeros(4 * tab_cap, np.uint8), tab_after=np.zeros(tab_cap, np.uint8))
+            io.cand_tab = more["cand_tab"].ctypes.data_as(C.POINTER(C.c_ubyte))
+            io.tab_after = more["tab_after"].ctypes.data_as(C.POINTER(C.c_ubyte))
+        trace = (abi.IterationSummary * abi.MAX_TRACE)()
+        io.trace = trace
+        self.lib.lfvio_debug_step_io.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.POINTER(Engine._StepIO)]
+        rc = self.lib.lfvio_debug_step_io(self.ctx, count, slot, float(mu), float(radius), int(spec), C.byref(io))
+        if rc < 0:
+            self._check(rc, "step_io")
+        ps = io.pass_
+        assert ps.num_landmarks == N and io.num_blocks == (N + 63) // 64, (ps.num_landmarks, io.num_blocks, N)
+        assert 0 < io.tab_bytes <= tab_cap, io.tab_bytes
+        n = ps.prior_n
+        out.update(a=out["a"][:N], b=out["b"][:N], W=out["W"][:N], prior_A=out["prior_A"][:n * n].reshape(n, n).copy(),
+                   prior_cmap=out["prior_cmap"][:n].copy(), linw=rc)
+        for k in ("alpha", "grad_sq_total", "x_cost", "mu", "prior_cost", "chol_fail", "prior_n", "est_ex", "est_td"):
+            out[k] = getattr(ps, k)
+        for k in ("scale_l", "diag_l", "grad_l", "einv_l", "lam", "gn_l", "d1", "d2", "lam_after"):
+            more[k] = more[k][:N]
+        more.update(coef=more["coef"][:spec], cand_x=more["cand_x"][:spec], cand_lam=more["cand_lam"][:spec, :N],
+                    block_sums=more["block_sums"][:spec, :io.num_blocks], pose_cost=more["pose_cost"][:spec])
+        if tabs:
+            more.update(cand_tab=more["cand_tab"][:spec * io.tab_bytes].reshape(spec, io.tab_bytes), tab_after=more["tab_after"][:io.tab_bytes])
+        out.update(more)
+        out.update(head=io.head.as_dict(), after=io.after.as_dict(), head_valid=io.head_valid, num_blocks=io.num_blocks, tab_bytes=io.tab_bytes,
+                   spec=io.spec, stepw=io.stepw)
+        fields = ("cost", "cost_change", "gradient_max_norm", "step_norm", "relative_decrease", "trust_region_radius", "step_is_valid",
+                  "step_is_successful")
+        out["trace"] = [{f: getattr(trace[i], f) for f in fields} for i in range(io.head.trace_len, io.after.trace_len)]
+        return out
+
     def set_function_tolerance(self, tol):
         """Solver::Options::function_tolerance of the windows uploaded from now on (Ceres' default 1e-6)."""
         self.configure("function_tolerance", float(tol))
