@@ -1,6 +1,6 @@
 /*
  * lfvio_debug.h — parity / inspection hooks of liblfvio_hip.so used by tests/, tools/ and bench.py only.
- * Not part of the drop-in boundary (include/lfvio.h).  Eleven entry points: two that take a key, nine that look inside.
+ * Not part of the drop-in boundary (include/lfvio.h).  Ten entry points: two that take a key, eight that look inside.
  */
 #ifndef LFVIO_DEBUG_H
 #define LFVIO_DEBUG_H
@@ -62,17 +62,11 @@ int lfvio_debug_read_clocks(lfvio_ctx *ctx, long long *out32);
  * 4 .. 7 k_setup by role, 8 .. 10 k_lin by role; a resident batch on the strip sweep: 12 k_linw, 13 k_solve_dense<true>, 14 k_stepw;
  * a large window group by group: 15 k_linb, 16 k_sumb, 17 k_backsub_wt (an error where the launch does not take that path). */
 int lfvio_debug_time_kernel(lfvio_ctx *ctx, int which, int count, int reps, double *avg_ms);
-/* One linearization + dense solve of the resident slots [0, count) by the path the launch takes; then, of slot `slot`: g_p[172],
- * the Schur sums (15 x 256, tile layout), lm_sum[5], a[N], b[N] (device landmark order), the pose-side Gauss-Newton step [172], the
- * dogleg model's quadratic forms [16], the cost.  Any output may be NULL.  Returns 1 if k_linw ran, 2 if k_linb + k_sumb, 0 if k_lin + k_sum,
- * < 0 on error. */
-int lfvio_debug_resident_pass(lfvio_ctx *ctx, int count, int slot, double *gp, double *schur, double *lm_sum, double *a, double *b, double *gn_p, double *q,
-                              double *x_cost);
-/* What the dense solve (k_solve_dense, csrc/kernels_solve.h) read and what it wrote, for tests/test_solve_hp.py.  Launches exactly what
- * lfvio_debug_resident_pass launches on the resident slots [0, count) — k_setup, the sweep and the solve of the launch's own route; with
- * mu > 0, tr.mu of every slot's header is set to it between k_setup and the sweep (mu <= 0: the 1e-8 k_setup leaves) — adds no kernel and
- * no kernel argument, and copies down memory the pass leaves in slot `slot`.  Every pointer of `io` may be NULL.  Returns the sweep
- * kernel as lfvio_debug_resident_pass does, < 0 on error.
+/* What the dense solve (k_solve_dense, csrc/kernels_solve.h) read and what it wrote, for tests/test_solve_hp.py.  One linearization +
+ * dense solve of the resident slots [0, count) from their uploaded state, by the path the launch takes — k_setup, the sweep and the solve
+ * of the launch's own route; with mu > 0, tr.mu of every slot's header is set to it between k_setup and the sweep (mu <= 0: the 1e-8
+ * k_setup leaves) — adds no kernel and no kernel argument, and copies down memory the pass leaves in slot `slot`.  Every pointer of `io`
+ * may be NULL.  Returns the sweep kernel: 1 if k_linw ran, 2 if k_linb + k_sumb, 0 if k_lin + k_sum; < 0 on error.
  *   read by the solve    H        the H region of the exchange buffer, 14 878 packed doubles (lower triangle, entry (i, j <= i) at
  *                                 i (i + 1) / 2 + j): complete H_pp behind k_sum / k_sumb; behind k_linw only the visual terms of the camera
  *                                 rows (i < 73), the rest of it is whatever an earlier pass left

@@ -28,6 +28,9 @@ class Engine:
         self.lib.lfvio_debug_configure.argtypes = [C.c_void_p, C.c_char_p, C.c_double]
         self.lib.lfvio_debug_query.argtypes = [C.c_void_p, C.c_char_p, _dp, C.c_int]
         self.lib.lfvio_debug_time_kernel.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp]
+        self.lib.lfvio_debug_pass_io.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.POINTER(Engine._PassIO)]
+        self.lib.lfvio_debug_step_io.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.POINTER(Engine._StepIO)]
+        self.lib.lfvio_debug_schur_repeat.argtypes = [C.c_void_p, C.POINTER(abi.WindowC), C.c_double, _dp]
         self.ctx = self.lib.lfvio_create(device)
         if not self.ctx:
             raise RuntimeError("lfvio_create failed: no usable HIP device (there is no CPU fallback)")
@@ -82,16 +85,9 @@ class Engine:
         self.configure("linw", int(mode))
 
     def resident_pass(self, count, slot, n_landmarks):
-        """One linearization + dense solve of the resident slots; what it left in `slot` (lfvio_debug_resident_pass)."""
-        out = dict(gp=np.zeros(abi.KP), schur=np.zeros(15 * 256), lm_sum=np.zeros(5), a=np.zeros(max(n_landmarks, 1)),
-                   b=np.zeros(max(n_landmarks, 1)), gn_p=np.zeros(abi.KP), q=np.zeros(16), x_cost=np.zeros(1))
-        dp = C.POINTER(C.c_double)
-        self.lib.lfvio_debug_resident_pass.argtypes = [C.c_void_p, C.c_int, C.c_int] + [dp] * 8
-        rc = self.lib.lfvio_debug_resident_pass(self.ctx, count, slot, *[_p(out[k]) for k in ("gp", "schur", "lm_sum", "a", "b", "gn_p", "q", "x_cost")])
-        if rc < 0:
-            self._check(rc, "resident_pass")
-        out["a"], out["b"], out["linw"] = out["a"][:n_landmarks], out["b"][:n_landmarks], rc
-        return out
+        """One linearization + dense solve of the resident slots; what it left in `slot`: a view on pass_io (lm_sum: its first 5)."""
+        io = self.pass_io(count, slot, n_landmarks)
+        return dict({k: io[k] for k in ("gp", "schur", "a", "b", "gn_p", "q", "linw")}, lm_sum=io["lm_sum"][:5], x_cost=np.array([io["x_cost"]]))
 
     class _PassIO(C.Structure):  # LfvioPassIO of include/lfvio_debug.h
         _ARRAYS = ("H", "gp", "schur", "lm_sum", "imu_out", "prior_A", "prior_cmap", "a", "b", "W",
@@ -100,28 +96,40 @@ class Engine:
                     + [(k, C.c_double) for k in ("alpha", "grad_sq_total", "x_cost", "mu", "prior_cost")]
                     + [(k, C.c_int) for k in ("chol_fail", "prior_n", "est_ex", "est_td", "num_landmarks")])
 
+    @staticmethod
+    def _pass_buffers(N):
+        """The seventeen arrays of LfvioPassIO for a slot of N landmarks."""
+        KP, n1 = abi.KP, max(N, 1)
+        return dict(H=np.zeros(KP * (KP + 1) // 2), gp=np.zeros(KP), schur=np.zeros(15 * 256), lm_sum=np.zeros(16), imu_out=np.zeros((10, 932)),
+                    prior_A=np.zeros(KP * KP), prior_cmap=np.zeros(KP, np.int32), a=np.zeros(n1), b=np.zeros(n1),
+                    W=np.zeros((n1, abi.KC)), scale_p=np.zeros(KP), diag_p=np.zeros(KP), grad_p=np.zeros(KP), gn_p=np.zeros(KP),
+                    uc_grad=np.zeros(80), uc_gn=np.zeros(80), q=np.zeros(16))
+
+    @staticmethod
+    def _bind_pass(io_struct, out):
+        for k in Engine._PassIO._ARRAYS:
+            setattr(io_struct, k, out[k].ctypes.data_as(C.POINTER(C.c_int) if k == "prior_cmap" else _dp))
+
+    @staticmethod
+    def _pass_result(ps, out, N, rc):
+        """`out` trimmed to the sizes the library reports in `ps` (a _PassIO), with its scalars and the sweep kernel `rc`."""
+        n = ps.prior_n
+        out.update(a=out["a"][:N], b=out["b"][:N], W=out["W"][:N], prior_A=out["prior_A"][:n * n].reshape(n, n).copy(),
+                   prior_cmap=out["prior_cmap"][:n].copy(), linw=rc)
+        for k in ("alpha", "grad_sq_total", "x_cost", "mu", "prior_cost", "chol_fail", "prior_n", "est_ex", "est_td"):
+            out[k] = getattr(ps, k)
+        return out
+
     def pass_io(self, count, slot, n_landmarks, mu=0.0):
         """One linearization + dense solve of the resident slots [0, count) at `mu` (0: the 1e-8 the setup leaves): everything the
         solve of `slot` read and wrote, as a dict (lfvio_debug_pass_io).  W is [N, 73] in device landmark order, prior_A [n, n]."""
-        N, KP = n_landmarks, abi.KP
-        out = dict(H=np.zeros(KP * (KP + 1) // 2), gp=np.zeros(KP), schur=np.zeros(15 * 256), lm_sum=np.zeros(16), imu_out=np.zeros((10, 932)),
-                   prior_A=np.zeros(KP * KP), prior_cmap=np.zeros(KP, np.int32), a=np.zeros(max(N, 1)), b=np.zeros(max(N, 1)),
-                   W=np.zeros((max(N, 1), abi.KC)), scale_p=np.zeros(KP), diag_p=np.zeros(KP), grad_p=np.zeros(KP), gn_p=np.zeros(KP),
-                   uc_grad=np.zeros(80), uc_gn=np.zeros(80), q=np.zeros(16))
-        io = Engine._PassIO()
-        for k in Engine._PassIO._ARRAYS:
-            setattr(io, k, out[k].ctypes.data_as(C.POINTER(C.c_int) if k == "prior_cmap" else _dp))
-        self.lib.lfvio_debug_pass_io.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.POINTER(Engine._PassIO)]
+        N, out, io = n_landmarks, Engine._pass_buffers(n_landmarks), Engine._PassIO()
+        Engine._bind_pass(io, out)
         rc = self.lib.lfvio_debug_pass_io(self.ctx, count, slot, float(mu), C.byref(io))
         if rc < 0:
             self._check(rc, "pass_io")
         assert io.num_landmarks == N, (io.num_landmarks, N)
-        n = io.prior_n
-        out.update(a=out["a"][:N], b=out["b"][:N], W=out["W"][:N], prior_A=out["prior_A"][:n * n].reshape(n, n).copy(),
-                   prior_cmap=out["prior_cmap"][:n].copy(), linw=rc)
-        for k in ("alpha", "grad_sq_total", "x_cost", "mu", "prior_cost", "chol_fail", "prior_n", "est_ex", "est_td"):
-            out[k] = getattr(io, k)
-        return out
+        return Engine._pass_result(io, out, N, rc)
 
     STATE_DOUBLES = 11 * 7 + 11 * 9 + 7 + 1  # LFVIO_STATE_DOUBLES: pose [11][7] | speed/bias [11][9] | ex [7] | td
 
@@ -160,13 +168,9 @@ class Engine:
         tab_after [tab_bytes] as uint8)."""
         N, KP, SD = n_landmarks, abi.KP, Engine.STATE_DOUBLES
         n1, nb = max(N, 1), max((N + 63) // 64, 1)
-        out = dict(H=np.zeros(KP * (KP + 1) // 2), gp=np.zeros(KP), schur=np.zeros(15 * 256), lm_sum=np.zeros(16), imu_out=np.zeros((10, 932)),
-                   prior_A=np.zeros(KP * KP), prior_cmap=np.zeros(KP, np.int32), a=np.zeros(n1), b=np.zeros(n1),
-                   W=np.zeros((n1, abi.KC)), scale_p=np.zeros(KP), diag_p=np.zeros(KP), grad_p=np.zeros(KP), gn_p=np.zeros(KP),
-                   uc_grad=np.zeros(80), uc_gn=np.zeros(80), q=np.zeros(16))
+        out = Engine._pass_buffers(N)
         io = Engine._StepIO()
-        for k in Engine._PassIO._ARRAYS:
-            setattr(io.pass_, k, out[k].ctypes.data_as(C.POINTER(C.c_int) if k == "prior_cmap" else _dp))
+        Engine._bind_pass(io.pass_, out)
         more = dict(scale_l=np.zeros(n1), diag_l=np.zeros(n1), grad_l=np.zeros(n1), einv_l=np.zeros(n1), lam=np.zeros(n1), x=np.zeros(SD),
                     gn_l=np.zeros(n1), d1=np.zeros(n1), d2=np.zeros(n1), step_p=np.zeros(KP), coef=np.zeros((4, 5)), cand_x=np.zeros((4, SD)),
                     cand_lam=np.zeros((4, n1)), block_sums=np.zeros((4, nb, 5)), pose_cost=np.zeros((4, 11)), x_after=np.zeros(SD),
@@ -180,18 +184,13 @@ class Engine:
             io.tab_after = more["tab_after"].ctypes.data_as(C.POINTER(C.c_ubyte))
         trace = (abi.IterationSummary * abi.MAX_TRACE)()
         io.trace = trace
-        self.lib.lfvio_debug_step_io.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.POINTER(Engine._StepIO)]
         rc = self.lib.lfvio_debug_step_io(self.ctx, count, slot, float(mu), float(radius), int(spec), C.byref(io))
         if rc < 0:
             self._check(rc, "step_io")
         ps = io.pass_
         assert ps.num_landmarks == N and io.num_blocks == (N + 63) // 64, (ps.num_landmarks, io.num_blocks, N)
         assert 0 < io.tab_bytes <= tab_cap, io.tab_bytes
-        n = ps.prior_n
-        out.update(a=out["a"][:N], b=out["b"][:N], W=out["W"][:N], prior_A=out["prior_A"][:n * n].reshape(n, n).copy(),
-                   prior_cmap=out["prior_cmap"][:n].copy(), linw=rc)
-        for k in ("alpha", "grad_sq_total", "x_cost", "mu", "prior_cost", "chol_fail", "prior_n", "est_ex", "est_td"):
-            out[k] = getattr(ps, k)
+        Engine._pass_result(ps, out, N, rc)
         for k in ("scale_l", "diag_l", "grad_l", "einv_l", "lam", "gn_l", "d1", "d2", "lam_after"):
             more[k] = more[k][:N]
         more.update(coef=more["coef"][:spec], cand_x=more["cand_x"][:spec], cand_lam=more["cand_lam"][:spec, :N],
@@ -247,7 +246,6 @@ class Engine:
     def schur_repeat(self, win, mu):
         """Largest |difference| between the Schur sums of the mu-retry path and of a full re-linearization (expected 0)."""
         d = np.zeros(1)
-        self.lib.lfvio_debug_schur_repeat.argtypes = [C.c_void_p, C.POINTER(abi.WindowC), C.c_double, _dp]
         self._check(self.lib.lfvio_debug_schur_repeat(self.ctx, C.byref(win.c()), float(mu), _p(d)), "lfvio_debug_schur_repeat")
         return float(d[0])
 
