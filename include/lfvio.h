@@ -938,6 +938,82 @@ int lfvio_track_undistort(lfvio_ctx *ctx, const LfvioTrackUndistortIn *in, float
                           float *velocity_3d /* [N][3] */, int *matched /* [N]: index in the previous call, or -1; or NULL */);
 int lfvio_track_reset(lfvio_ctx *ctx);   /* forget the resident map and time */
 
+/* lfvio_cam_project / lfvio_remap_build / lfvio_remap_apply / lfvio_remap_reset: the camera models the other way — spaceToPlane of the
+ * four models on the device — and what the reference builds on it: the equirectangular expansion of the panoramic annular image
+ * (pointcloud_image_fusion: GetremapMat, pointcloud_image_fusion.cpp:83-114, once; cv::remap(show_img, equal_rectangle_img, remap_x,
+ * remap_y, 0) per BGR8 image, pointcloud_image_fusion_node.cpp:62-81) and OCAMCamera::initUndistortRectifyMap
+ * (ScaramuzzaCamera.cc:723-777), the same machinery with a perspective ray per output pixel.  DESIGN.md 3w.
+ *   the projection of a point P = (X, Y, Z), in double, every operation rounded on its own, grouped as written here; the C++ is
+ *             cam_project of lf-vio_amd/csrc/camera_models.h over camera_atan.h, tests/project_ref.py restates it in numpy and is the
+ *             specification, held to a 50-digit evaluation of the reference's definitions (tests/test_project_ref.py: OCAM to 7.98,
+ *             PINHOLE to 10.78, MEI to 21.64 and, where F' >= 0.1, KANNALA_BRANDT to 30.58 eps max(|u|, |v|, 1); atan to 1.412 ulp).
+ *   LFVIO_CAM_OCAM (ScaramuzzaCamera.cc:654-674): n = sqrt(X * X + Y * Y); theta = atan(-Z / n); rho = 0, t = 1, for i = 0 .. 19:
+ *             rho += t * inv_poly[i], t *= theta (the reference's loop over SCARAMUZZA_INV_POLY_SIZE, not Horner); inv = 1.0 / n;
+ *             xn = (X * inv) * rho, yn = (Y * inv) * rho; u = (xn * c + yn * d) + cx, v = (xn * e + yn) + cy.  atan(-Z / n) stands
+ *             for the reference's atan2(-Z, n), n >= 0; at n == 0 the reference's pixel is NaN either way (0 * inf), so this is a
+ *             deviation of the text, not of the value.
+ *   LFVIO_CAM_PINHOLE (PinholeCamera.cc:520-542): x = X / Z, y = Y / Z; unless no_distortion: (dx, dy) = dist(x, y) of the lift
+ *             above, x += dx, y += dy; u = fx * x + cx, v = fy * y + cy.
+ *   LFVIO_CAM_MEI (CataCamera.cc:636-659): the same with z = Z + xi * n3 in place of Z, n3 the norm of the lift above,
+ *             sqrt((X * X + Y * Y) + Z * Z).
+ *   LFVIO_CAM_KANNALA_BRANDT (EquidistantCamera.cc:451-461): the reference's MATHEMATICS (theta = acos(Z / |P|), phi = atan2(Y, X),
+ *             p = F(theta) (cos phi, sin phi)) in a text of this library's own: rxy = sqrt(X * X + Y * Y); q = rxy / Z, a = atan(q);
+ *             theta = a for Z > 0, pi_hi + (a + pi_lo) for Z < 0 (the two parts of pi), pi / 2 for Z == 0 and rxy > 0, and q — a NaN —
+ *             otherwise (the zero vector, a NaN); cphi = X / rxy, sphi = Y / rxy, and (1.0, 0.0) for rxy < 1e-10; r = F(theta);
+ *             u = fx * (r * cphi) + cx, v = fy * (r * sphi) + cy.  Stated deviations: theta from the arctangent of rxy / Z in place
+ *             of the arc cosine (the same angle), X / rxy, Y / rxy in place of cos(atan2(Y, X)), sin(atan2(Y, X)), and phi = 0 below
+ *             rxy = 1e-10 where the reference's atan2 still follows (X, Y) (there r F(theta) < 2e-10 of a focal length).
+ *   atan      s_atan.c's scheme of fdlibm in + - * /, comparisons and fabs (camera_atan.h): a = |x|; t = a below 7 / 16, (2.0 * a -
+ *             1.0) / (2.0 + a) below 11 / 16, (a - 1.0) / (a + 1.0) below 19 / 16, (a - 1.5) / (1.0 + 1.5 * a) below 39 / 16 and
+ *             -1.0 / a from there; z = t * t, w = z * z, s1 = z * (aT0 + w * (aT2 + .. w * aT10)), s2 = w * (aT1 + w * (aT3 + .. w *
+ *             aT9)); below 7 / 16 t - t * (s1 + s2), otherwise atanhi - ((t * (s1 + s2) - atanlo) - t); negated for x < 0; x itself
+ *             for a < 2^-29, +-(atanhi[3] + atanlo[3]) for a >= 2^66.  No libm call anywhere in the projection.
+ *
+ * lfvio_cam_project: px[k] = (u, v) of P[k], k < n.  LFVIO_ERR_ARG (px untouched): null ctx / proj / proj->camera, P or px null
+ * with n > 0, a camera refused above (lfvio_track_reject), for OCam a non-finite inv_poly entry, n outside [0, 1 << 20].
+ *
+ * lfvio_remap_build: the float maps of a width x height OUTPUT image, map_x = (float)u, map_y = (float)v of the ray of output pixel
+ * (i, j) (column, row), in double, grouped as written:
+ *   LFVIO_MAP_EQUIRECT     lon = ((double)i / (double)width - 0.5) * (2.0 * pi), lat = -(((double)j / (double)height - 0.5) * pi),
+ *                          P = (cos(lat) * sin(lon), cos(lat) * cos(lon), sin(lat)) (:93-101), sine and cosine as the KANNALA_BRANDT
+ *                          lift takes them (above; held to 2.716 ulp on [-pi, pi] as they are, so no symmetry is applied).
+ *   LFVIO_MAP_PERSPECTIVE  P = M (i, j, 1): P.k = (M[3k] * i + M[3k + 1] * j) + M[3k + 2].  A stated deviation: the reference forms
+ *                          R_inv * K_rect_inv and the ray in float (Matrix3f); here the caller supplies the product, in double.
+ * The maps stay resident in the context, in device memory of their own (allocated at the first build), until the next build or
+ * lfvio_remap_reset; map_x / map_y (both, or both NULL) receive them.  LFVIO_ERR_ARG (outputs and the resident maps untouched):
+ * null ctx / in / in->proj / camera, a projector refused above, an unknown kind, for PERSPECTIVE a non-finite M entry, width or
+ * height outside [16, 8192], exactly one of map_x and map_y null.
+ *
+ * lfvio_remap_apply: cv::remap(src, out, map_x, map_y, INTER_NEAREST) with BORDER_CONSTANT 0 through the resident maps.  Per output
+ * pixel sx = saturate_cast<short>(map_x), sy likewise: round to nearest, ties to even, clamped to [-32768, 32767]; a NaN counts as
+ * outside.  With 0 <= sx < src_width and 0 <= sy < src_height the source pixel's bytes are copied, otherwise zero bytes are
+ * written.  Bytes per pixel are fmt->encoding's (1, 3, 3, 4, 4, 2, 2 for LFVIO_IMG_MONO8 .. _MONO16_BE); fmt->step is the SOURCE's,
+ * the output's rows are contiguous (height * width * bytes per pixel bytes); nothing is converted.  fmt NULL: mono8, rows
+ * contiguous, as for lfvio_image_gray.  THIS LINE IS WRITTEN DOWN FROM MEMORY of OpenCV 3.3's RemapInvoker / remapNearest: no
+ * OpenCV was at hand and nobody has compared them (tests/project_ref.py is the specification).
+ * LFVIO_ERR_ARG (out untouched): null ctx / pixels / out, src_width or src_height outside [16, 8192], a format
+ * lfvio_image_format_set refuses, 0 < step < src_width * bytes per pixel; and, as lfvio_klt_level without a resident image, no
+ * resident map (before the first build, after lfvio_remap_reset).
+ * All four run on the feature stream like lfvio_klt_track: they do not wait for an optimization in flight, and they touch neither
+ * the resident image nor any setting of the tracker calls. */
+#define LFVIO_OCAM_INV_POLY_SIZE 20
+typedef struct {
+  const LfvioCamera *camera;
+  double inv_poly[LFVIO_OCAM_INV_POLY_SIZE];  /* OCam only (SCARAMUZZA_INV_POLY_SIZE); unused tail 0.0 */
+} LfvioProjector;
+int lfvio_cam_project(lfvio_ctx *ctx, const LfvioProjector *proj, int n, const double *P /* [n][3] */, double *px /* [n][2] */);
+#define LFVIO_MAP_EQUIRECT    0  /* GetremapMat */
+#define LFVIO_MAP_PERSPECTIVE 1  /* initUndistortRectifyMap */
+typedef struct {
+  const LfvioProjector *proj;
+  int kind, width, height;  /* width, height: of the OUTPUT image */
+  double M[9];              /* PERSPECTIVE only: ray = M (u, v, 1), row-major */
+} LfvioRemapIn;
+int lfvio_remap_build(lfvio_ctx *ctx, const LfvioRemapIn *in, float *map_x, float *map_y /* [height][width], or both NULL */);
+int lfvio_remap_apply(lfvio_ctx *ctx, const LfvioImageFormat *fmt, int src_width, int src_height, const unsigned char *pixels,
+                      unsigned char *out /* [height][width * bytes per pixel] of the resident map's size */);
+int lfvio_remap_reset(lfvio_ctx *ctx);   /* forget the resident maps */
+
 /* lfvio_track_frame / lfvio_track_frame_reset: one image through FeatureTracker::readImage (feature_tracker/src/feature_tracker.cpp:
  * 95-184) and the node's updateID loop (feature_tracker_node.cpp:102-111) in ONE call: one copy up ([sample_words | image]), the
  * stages below enqueued back to back, one copy down.  The track table (cur_pts, ids, track_cnt) is resident in the context, and so

@@ -7,7 +7,9 @@
 //   LFVIO_CAM_KANNALA_BRANDT   EquidistantCamera::liftProjective (EquidistantCamera.cc:428-442), restated in camera_kb.h
 // and what every model shares behind the lift: the norm, the unit bearing of rejectWithF and the two float outputs of
 // undistortedPoints.  The specification is in include/lfvio.h and, as numpy, in tests/track_ref.py (OCam), tests/camera_ref.py
-// (PINHOLE, MEI) and tests/kb_ref.py (KANNALA_BRANDT).
+// (PINHOLE, MEI) and tests/kb_ref.py (KANNALA_BRANDT).  The other way — spaceToPlane of the four models, cam_project over the
+// arctangent of camera_atan.h, with ProjCam / proj_cam / proj_check — is at the end of the file (numpy: tests/project_ref.py; held to
+// it by tests/test_camera_project.py; walked under the CPU sanitizers by tests/tools/remap_plan_walk.cpp).
 //
 // Plain C++ when compiled without hipcc (nothing from HIP, dev_math.h or kernels_twoview.h); under hipcc the per-pixel functions are
 // __host__ __device__ (KB_HD of camera_kb.h), as image_format.h's pixel conversions are.  kernels_track.h calls them from the kernels,
@@ -23,6 +25,7 @@
 #include <cmath>
 
 #include "../../include/lfvio.h"
+#include "camera_atan.h"
 #include "camera_kb.h"
 
 struct TrackCam {  // a kernel argument, by value; the members a model does not use are zero
@@ -144,4 +147,88 @@ KB_HD CamUndistorted cam_undistorted(const TrackCam &cam, float px, float py) {
   const CamRay Q = cam_lift(cam, px, py);
   const double n = cam_norm(Q);
   return {(float)(Q.x / Q.z), (float)(Q.y / Q.z), (float)(Q.x / n), (float)(Q.y / n), (float)(Q.z / n)};
+}
+
+// ---- the other way: spaceToPlane of the four models (include/lfvio.h, lfvio_cam_project)
+//   LFVIO_CAM_OCAM             OCAMCamera::spaceToPlane (ScaramuzzaCamera.cc:654-674)
+//   LFVIO_CAM_PINHOLE          PinholeCamera::spaceToPlane (PinholeCamera.cc:520-542)
+//   LFVIO_CAM_MEI              CataCamera::spaceToPlane (CataCamera.cc:636-659)
+//   LFVIO_CAM_KANNALA_BRANDT   EquidistantCamera::spaceToPlane (EquidistantCamera.cc:451-461), its mathematics in a text of this library's
+// The specification as numpy is tests/project_ref.py; tests/test_camera_project.py holds cam_project to it bit for bit.
+// ProjCam is the TrackCam of the lifts plus what only the projection reads; proj_cam forms it on the host.  TrackCam, track_cam
+// and the lifts above are what they were: the kernels that take them keep their instructions.
+constexpr int CAM_INV_POLY = LFVIO_OCAM_INV_POLY_SIZE;
+struct ProjCam {  // a kernel argument, by value
+  TrackCam t;
+  double fx, fy;                  // as given (PINHOLE, MEI, KANNALA_BRANDT); OCam: zero
+  double inv_poly[CAM_INV_POLY];  // OCam; the other models: zero
+};
+
+inline ProjCam proj_cam(const LfvioProjector &p, KbCache *kb = nullptr) {
+  ProjCam q = {};
+  q.t = track_cam(*p.camera, kb);
+  if (p.camera->model == LFVIO_CAM_OCAM)
+    for (int i = 0; i < CAM_INV_POLY; i++) q.inv_poly[i] = p.inv_poly[i];
+  else
+    q.fx = p.camera->fx, q.fy = p.camera->fy;
+  return q;
+}
+
+// nullptr, or what is wrong with the projector: its camera as track_camera_check judges it and, for OCam, a finite inverse polynomial
+inline const char *proj_check(const LfvioProjector *p) {
+  if (!p) return "lfvio_cam_project: null projector";
+  if (const char *why = track_camera_check(p->camera)) return why;
+  if (p->camera->model == LFVIO_CAM_OCAM)
+    for (double x : p->inv_poly)
+      if (!std::isfinite(x)) return "lfvio_cam_project: a non-finite inv_poly entry";
+  return nullptr;
+}
+
+struct CamPixel { double u, v; };
+
+// PINHOLE (:520-542) and, with z = Z + xi |P|, MEI (:636-659)
+KB_HD CamPixel cam_project_plane(const ProjCam &cam, double X, double Y, double z) {
+  double x = X / z, y = Y / z;
+  if (!cam.t.no_distortion) {
+    double dx, dy;
+    cam_distortion(cam.t, x, y, dx, dy);
+    x += dx, y += dy;
+  }
+  return {cam.fx * x + cam.t.cx, cam.fy * y + cam.t.cy};
+}
+
+// KANNALA_BRANDT: theta in [0, pi] with tangent rxy / Z from cam_atan, (cos phi, sin phi) = (X, Y) / rxy, r = F(theta).
+// Stated deviations from the reference's text (acos(Z / |P|), atan2(Y, X), cos, sin): theta from the arctangent of rxy / Z
+// (the same angle; better conditioned near the axis than the arc cosine); X / rxy, Y / rxy in place of cos(atan2(Y, X)),
+// sin(atan2(Y, X)); rxy < 1e-10 gives phi = 0 as the lift's r < 1e-10 does, where the reference's atan2 still follows (X, Y);
+// the zero vector is NaN here as there (0 / 0).
+KB_HD CamPixel cam_project_kb(const ProjCam &cam, double X, double Y, double Z) {
+  constexpr double PI_HI = 3.14159265358979311600e+00, PI_LO = 1.22464679914735317723e-16, PIO2 = 1.57079632679489655800e+00;
+  const double rxy = sqrt(X * X + Y * Y);
+  const double q = rxy / Z, a = cam_atan(q);
+  // Z > 0: atan(q); Z < 0: pi + atan(q), q < 0; Z == 0: pi / 2 off the axis, 0 / 0 = NaN on it; a NaN Z: NaN (q)
+  const double theta = Z > 0.0 ? a : Z < 0.0 ? PI_HI + (a + PI_LO) : (Z == 0.0 && rxy > 0.0) ? PIO2 : q;
+  const bool tiny = rxy < 1e-10;
+  const double cphi = tiny ? 1.0 : X / rxy, sphi = tiny ? 0.0 : Y / rxy;
+  const double r = kb_f(cam.t.poly, theta);
+  return {cam.fx * (r * cphi) + cam.t.cx, cam.fy * (r * sphi) + cam.t.cy};
+}
+
+// spaceToPlane of the point (X, Y, Z).  OCam (:654-674): theta = atan(-Z / n) stands for the reference's atan2(-Z, n), n >= 0 — at
+// n == 0 the reference's pixel is NaN too (0 * inf), so the deviation is of the text, not of the value — and the inverse polynomial
+// is the reference's running power over all SCARAMUZZA_INV_POLY_SIZE = 20 terms, not Horner.
+KB_HD CamPixel cam_project(const ProjCam &cam, double X, double Y, double Z) {
+  if (cam.t.model == LFVIO_CAM_PINHOLE) return cam_project_plane(cam, X, Y, Z);
+  if (cam.t.model == LFVIO_CAM_MEI) return cam_project_plane(cam, X, Y, Z + cam.t.xi * cam_norm({X, Y, Z}));
+  if (cam.t.model == LFVIO_CAM_KANNALA_BRANDT) return cam_project_kb(cam, X, Y, Z);
+  const double n = sqrt(X * X + Y * Y);
+  const double theta = cam_atan(-Z / n);
+  double rho = 0.0, t = 1.0;
+  for (int i = 0; i < CAM_INV_POLY; i++) {
+    rho += t * cam.inv_poly[i];
+    t *= theta;
+  }
+  const double inv = 1.0 / n;
+  const double xn = (X * inv) * rho, yn = (Y * inv) * rho;
+  return {(xn * cam.t.c + yn * cam.t.d) + cam.t.cx, (xn * cam.t.e + yn) + cam.t.cy};
 }

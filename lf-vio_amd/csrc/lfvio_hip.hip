@@ -52,6 +52,7 @@ constexpr ncclDataType_t ncclDouble = 8;
 #include "kernels_gft.h"
 #include "kernels_clahe.h"
 #include "kernels_imgfmt.h"
+#include "kernels_remap.h"
 #include "kernels_track.h"
 #include "kernels_trackframe.h"
 #include "kernels_trackbatch.h"
@@ -202,6 +203,15 @@ struct lfvio_ctx : CtxQueues {
     LfvioImageFormat f = {};
     const LfvioImageFormat *get() const { return on ? &f : nullptr; }
   } imgfmt;
+  // lfvio_remap_build / lfvio_remap_apply (remap.inc): what is resident (remap_plan.h), the two float maps [2][height][width] and the
+  // integer map [height][width] in device memory of their own, allocated at the first build; kb: the last KANNALA_BRANDT projector's
+  // monotone range.  No tracker call looks at any of it, and lfvio_klt_reset leaves it alone.
+  struct RemapState {
+    RemapResident r;
+    DevBuf<float> map;
+    DevBuf<int> index;
+    KbCache kb;
+  } remap;
   // lfvio_track_undistort (track.inc): the (id, un_pts_3d) pairs of the previous call — [4096 ints | 4096 x 3 floats] twice, allocated
   // at the first use; tstream.mcur holds the tstream.mcount resident pairs (0: the map is empty), tstream.time is that call's
   struct TrackState {
@@ -1812,6 +1822,8 @@ int lfvio_batch_optimize_pending(const lfvio_ctx *c) { return c && c->call.pendi
 #include "clahe.inc"
 
 #include "imgfmt.inc"
+
+#include "remap.inc"
 
 #include "klt.inc"
 

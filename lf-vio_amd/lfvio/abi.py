@@ -717,6 +717,29 @@ def camera_c(cam):
                    g("fx"), g("fy"), g("k1"), g("k2"), g("p1"), g("p2"), g("xi"))
 
 
+OCAM_INV_POLY_SIZE = 20  # LFVIO_OCAM_INV_POLY_SIZE
+MAP_EQUIRECT, MAP_PERSPECTIVE = 0, 1  # LFVIO_MAP_*
+CAM_PROJECT_MAX_POINTS = 1 << 20
+
+
+class ProjectorC(C.Structure):
+    """LfvioProjector (include/lfvio.h)."""
+    _fields_ = [("camera", C.POINTER(CameraC)), ("inv_poly", C.c_double * OCAM_INV_POLY_SIZE)]
+
+
+class RemapInC(C.Structure):
+    """LfvioRemapIn (include/lfvio.h)."""
+    _fields_ = [("proj", C.POINTER(ProjectorC)), ("kind", C.c_int), ("width", C.c_int), ("height", C.c_int), ("M", C.c_double * 9)]
+
+
+def projector_c(cam):
+    """(ProjectorC, CameraC) from a camera dict (camera_c); an OCam camera's `inv_poly` (up to 20 numbers) fills the inverse
+    polynomial, the tail is 0.0.  The CameraC is returned to keep it alive beside the pointer."""
+    cc = cam if isinstance(cam, CameraC) else camera_c(cam)
+    inv = [float(v) for v in (() if isinstance(cam, CameraC) else cam.get("inv_poly", ()))]
+    return ProjectorC(C.pointer(cc), (C.c_double * OCAM_INV_POLY_SIZE)(*inv)), cc
+
+
 class TrackFrameInC(C.Structure):
     """LfvioTrackFrameIn (include/lfvio.h)."""
     _fields_ = [
@@ -793,6 +816,7 @@ HIP_SYMBOLS = [
     "lfvio_clahe_set", "lfvio_clahe_apply", "lfvio_image_format_set", "lfvio_image_gray", "lfvio_track_batch_format",
     "lfvio_track_reject", "lfvio_track_undistort", "lfvio_track_reset", "lfvio_track_frame", "lfvio_track_frame_reset",
     "lfvio_track_frame_message",
+    "lfvio_cam_project", "lfvio_remap_build", "lfvio_remap_apply", "lfvio_remap_reset",
     "lfvio_track_batch_reserve", "lfvio_track_batch_set_mask", "lfvio_track_batch_clahe", "lfvio_track_batch_frame", "lfvio_track_batch_reset",
     "lfvio_group_create", "lfvio_group_unique_id", "lfvio_group_create_rank", "lfvio_group_create_local", "lfvio_group_destroy",
     "lfvio_group_last_error", "lfvio_group_size", "lfvio_group_local", "lfvio_group_rank", "lfvio_group_ctx", "lfvio_group_backend",
@@ -883,6 +907,11 @@ def load_hip_library(path=None):
         lib.lfvio_image_format_set.argtypes = [C.c_void_p, C.POINTER(ImageFormatC)]
         lib.lfvio_image_gray.argtypes = [C.c_void_p, C.POINTER(ImageFormatC), C.c_int, C.c_int] + [C.POINTER(C.c_ubyte)] * 2
         lib.lfvio_track_batch_format.argtypes = [C.c_void_p, C.POINTER(ImageFormatC)]
+    if hasattr(lib, "lfvio_cam_project"):
+        lib.lfvio_cam_project.argtypes = [C.c_void_p, C.POINTER(ProjectorC), C.c_int, _dp, _dp]
+        lib.lfvio_remap_build.argtypes = [C.c_void_p, C.POINTER(RemapInC), C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        lib.lfvio_remap_apply.argtypes = [C.c_void_p, C.POINTER(ImageFormatC), C.c_int, C.c_int] + [C.POINTER(C.c_ubyte)] * 2
+        lib.lfvio_remap_reset.argtypes = [C.c_void_p]
     if hasattr(lib, "lfvio_track_reject"):
         lib.lfvio_track_reject.argtypes = [C.c_void_p, C.POINTER(TrackRejectInC), C.POINTER(C.c_ubyte), C.POINTER(TrackRejectOutC), _dp, _dp]
         lib.lfvio_track_undistort.argtypes = [C.c_void_p, C.POINTER(TrackUndistortInC)] + [C.POINTER(C.c_float)] * 3 + [C.POINTER(C.c_int)]

@@ -686,6 +686,75 @@ class Engine:
         return out
 
     @staticmethod
+    def projector(cam):
+        """(ProjectorC or None, keep-alive) from a camera dict (an OCam camera's `inv_poly`: abi.projector_c); None: a null pointer."""
+        if cam is None:
+            return None, None
+        if isinstance(cam, abi.ProjectorC):
+            return cam, None
+        return abi.projector_c(cam)
+
+    def cam_project(self, cam, P, out=None, n=None, check=True):
+        """lfvio_cam_project: spaceToPlane of the points P [n, 3] float64 through `cam` (projector()), as px [n, 2] float64, a new array or
+        `out`.  n: the call's field whatever the array says, cam / P None: null pointers (tests of what a refused call leaves alone);
+        check=False returns (error code, out)."""
+        dp = C.POINTER(C.c_double)
+        pts = None if P is None else np.ascontiguousarray(P, dtype=np.float64).reshape(-1, 3)
+        n = n if n is not None else len(pts)
+        if out is None:
+            out = np.zeros((min(max(n, 1), abi.CAM_PROJECT_MAX_POINTS), 2), dtype=np.float64)
+        proj, keep = self.projector(cam)
+        rc = self.lib.lfvio_cam_project(self.ctx, None if proj is None else C.byref(proj), n, None if pts is None else pts.ctypes.data_as(dp),
+                                        out.ctypes.data_as(dp))
+        del keep
+        if not check:
+            return rc, out
+        self._check(rc, "lfvio_cam_project")
+        return out[:n]
+
+    def remap_build(self, cam, kind, width, height, M=None, want_maps=True, map_x=None, map_y=None, check=True):
+        """lfvio_remap_build: the resident map of a width x height output image through `cam` (projector()); kind abi.MAP_EQUIRECT or
+        abi.MAP_PERSPECTIVE with M [3, 3] (ray = M (u, v, 1)).  Returns (map_x, map_y) float32 [height, width], or None with
+        want_maps=False (both pointers null).  map_x / map_y: arrays to be written, or False: that pointer null whatever want_maps says;
+        cam None: a null projector; check=False returns (error code, map_x, map_y)."""
+        fp = C.POINTER(C.c_float)
+        proj, keep = self.projector(cam)
+        m = np.zeros(9) if M is None else np.ascontiguousarray(M, dtype=np.float64).reshape(9)
+        rin = abi.RemapInC(None if proj is None else C.pointer(proj), kind, width, height, (C.c_double * 9)(*m.tolist()))
+        shape = (min(max(height, 1), 8192), min(max(width, 1), 8192))
+        if map_x is None and want_maps:
+            map_x = np.zeros(shape, dtype=np.float32)
+        if map_y is None and want_maps:
+            map_y = np.zeros(shape, dtype=np.float32)
+        px = None if map_x is None or map_x is False else map_x.ctypes.data_as(fp)
+        py = None if map_y is None or map_y is False else map_y.ctypes.data_as(fp)
+        rc = self.lib.lfvio_remap_build(self.ctx, C.byref(rin), px, py)
+        del keep
+        if not check:
+            return rc, map_x, map_y
+        self._check(rc, "lfvio_remap_build")
+        return (map_x, map_y) if want_maps else None
+
+    def remap_apply(self, rows, src_width, src_height, out_shape, encoding=None, step=0, out=None, check=True):
+        """lfvio_remap_apply: `rows` (uint8, src_height * step bytes in `encoding`; None: a null pointer) through the resident map, as
+        uint8 [height, width * bytes per pixel] with out_shape = (width, height) of the resident map, a new array or `out`.  encoding
+        None: a null format (mono8, rows contiguous).  check=False returns (error code, out)."""
+        up = C.POINTER(C.c_ubyte)
+        px = None if rows is None else np.ascontiguousarray(rows, dtype=np.uint8)
+        if out is None:
+            out = np.zeros((out_shape[1], out_shape[0] * abi.IMG_BPP.get(encoding or 0, 4)), dtype=np.uint8)
+        rc = self.lib.lfvio_remap_apply(self.ctx, None if encoding is None else C.byref(abi.ImageFormatC(encoding, step)), src_width, src_height,
+                                        None if px is None else px.ctypes.data_as(up), out.ctypes.data_as(up))
+        if not check:
+            return rc, out
+        self._check(rc, "lfvio_remap_apply")
+        return out
+
+    def remap_reset(self):
+        """lfvio_remap_reset: forget the resident map."""
+        self._check(self.lib.lfvio_remap_reset(self.ctx), "lfvio_remap_reset")
+
+    @staticmethod
     def camera(cam):
         """A CameraC from a dict; None: a null pointer.  model (optional) LFVIO_CAM_OCAM: cx, cy, c, d, e, poly [5];
         LFVIO_CAM_PINHOLE: cx, cy, fx, fy, k1, k2, p1, p2; LFVIO_CAM_MEI: those (u0, v0, gamma1, gamma2 under cx, cy, fx, fy) and xi;
