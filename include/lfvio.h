@@ -1014,6 +1014,73 @@ int lfvio_remap_apply(lfvio_ctx *ctx, const LfvioImageFormat *fmt, int src_width
                       unsigned char *out /* [height][width * bytes per pixel] of the resident map's size */);
 int lfvio_remap_reset(lfvio_ctx *ctx);   /* forget the resident maps */
 
+/* lfvio_cloud_fuse: the other half of pointcloud_image_fusion — every point of a lidar scan taken into the camera frame, projected and
+ * marked in the expanded image (pointcloud_image_fusion_node.cpp:92-115, in comments as shipped; laserCloudIn is pointcloud_callback's,
+ * :121-125).  One copy up ([cloud | image]), the launches back to back, one copy down.  DESIGN.md 3x; tests/fuse_ref.py restates it
+ * in numpy and is the specification; the C++ is fuse_point of lf-vio_amd/csrc/fuse_plan.h.
+ *   the cloud   the raw `data` bytes of a sensor_msgs/PointCloud2: n points of point_step bytes, x / y / z float32 at the byte offsets
+ *               off_x / off_y / off_z of a point, of the byte order big_endian says.  No alignment is required of offsets or step.
+ *   per point   in double, every operation rounded on its own, grouped as written: x, y, z widened;
+ *               P.k = ((R[3k] * x + R[3k + 1] * y) + R[3k + 2] * z) + T[k] (camera_R_lidar, camera_T_lidar; R row-major);
+ *               r = sqrt((X * X + Y * Y) + Z * Z); the point passes the RANGE GATE iff r > 0 && r >= min_range && r <= max_range
+ *               && r < inf (a NaN or infinite coordinate fails, and so does an Ouster no-return (0, 0, 0)).
+ *   LFVIO_FUSE_EQUIRECT  the inverse of LFVIO_MAP_EQUIRECT: nxy = sqrt(X * X + Y * Y), dropped at nxy == 0 (the pole);
+ *               a = atan(X / Y) (the atan above); lon = a for Y > 0, pi_hi + (a + pi_lo) for Y < 0 and X >= 0, (a - pi_lo) - pi_hi
+ *               for Y < 0 and X < 0, +-pi / 2 by the sign of X for Y == 0: the angle of atan2(X, Y).  lat = atan(Z / nxy).
+ *               fx = width * (0.5 + lon / (2.0 * pi)), fy = height * (0.5 - lat / pi); col = (int)fx, row = (int)fy (truncation, as
+ *               the reference's int idx_x = ...; both >= 0); col == width (the seam lon = +pi) wraps to column 0, row == height
+ *               (lat = -pi / 2 as a double: |Z / nxy| beyond about 1e16) becomes height - 1.  Stated deviations: the reference
+ *               normalises and takes asin(z), the same angle (the treatment KANNALA_BRANDT's acos got); and at row == height the
+ *               reference writes outside its image.
+ *   LFVIO_FUSE_CAMERA    (u, v) = the projection above of P through proj; col, row = saturate_cast<short> of (float)u, (float)v
+ *               as lfvio_remap_apply rounds; kept iff 0 <= col < width and 0 <= row < height and, because a projection through the
+ *               centre otherwise yields plausible pixels, PINHOLE: Z > 0, MEI: Z + xi * r > 0.
+ *   the image   image_mode LFVIO_FUSE_IMAGE_NONE; _GIVEN: pixels is a width x height image of fmt (fmt->step its row's bytes);
+ *               _REMAP: pixels is a src_width x src_height image of fmt that goes through the RESIDENT maps first, exactly as
+ *               lfvio_remap_apply takes it (same integer map, same rebuild decision): a resident map of width x height is required.
+ *               fmt NULL: mono8, rows contiguous.  With paint_on nonzero the first bytes-per-pixel bytes of paint are written at
+ *               every marked pixel (the reference: (255, 0, 0) into bgr8).
+ * Outputs, each NULL or written: index[k] = row * width + col, or -1 for a dropped point; range = the smallest (float)r of the points
+ * on a pixel, +inf where there is none (an atomic minimum on the bit pattern: positive floats order as their bits, so the order of
+ * arrival does not show); colour[k] = the image's bytes at index[k] BEFORE anything is painted, zero bytes for -1; image_out = the
+ * (remapped) image, rows contiguous, painted when paint_on (sampling and painting are two launches in stream order); counts =
+ * (points kept, dropped by the range gate, dropped by the projection).
+ * LFVIO_ERR_ARG (every output untouched, the resident maps still serving the next lfvio_remap_apply): null ctx / in / out; n outside
+ * [0, 1 << 20] or a null cloud with n > 0; point_step outside [12, 1024]; an offset outside [0, point_step - 4] or two fields that
+ * overlap; big_endian not 0 or 1; a non-finite R or T entry; min_range negative or not finite, max_range below min_range or NaN; an
+ * unknown kind; width or height outside [16, 8192]; for CAMERA a projector lfvio_cam_project refuses; an unknown image_mode; with an
+ * image: null pixels, a format lfvio_image_format_set refuses, 0 < step < the row's bytes, for REMAP src_width or src_height outside
+ * [16, 8192]; colour or image_out without an image; REMAP without a resident map or with one of another size (as lfvio_remap_apply).
+ * Runs on the feature stream like lfvio_remap_apply: it does not wait for an optimization in flight and touches no tracker state. */
+#define LFVIO_FUSE_EQUIRECT 0
+#define LFVIO_FUSE_CAMERA   1
+#define LFVIO_FUSE_IMAGE_NONE  0
+#define LFVIO_FUSE_IMAGE_GIVEN 1
+#define LFVIO_FUSE_IMAGE_REMAP 2
+#define LFVIO_FUSE_MAX_POINTS (1 << 20)
+typedef struct {
+  const unsigned char *cloud;      /* n * point_step bytes */
+  int n, point_step, off_x, off_y, off_z, big_endian;
+  double R[9], T[3];               /* P = R p + T, R row-major */
+  double min_range, max_range;     /* max_range may be +inf */
+  int kind, width, height;         /* width, height: of the image the points are marked in */
+  const LfvioProjector *proj;      /* CAMERA only */
+  int image_mode;
+  const LfvioImageFormat *fmt;     /* NULL: mono8, rows contiguous */
+  int src_width, src_height;       /* REMAP only */
+  const unsigned char *pixels;     /* GIVEN: height rows; REMAP: src_height rows */
+  int paint_on;
+  unsigned char paint[4];
+} LfvioFuseIn;
+typedef struct {                   /* each NULL, or written */
+  int *index;                      /* [n] */
+  float *range;                    /* [height][width] */
+  unsigned char *colour;           /* [n][bytes per pixel] */
+  unsigned char *image_out;        /* [height][width * bytes per pixel] */
+  int *counts;                     /* [3]: kept, dropped by the gate, dropped by the projection */
+} LfvioFuseOut;
+int lfvio_cloud_fuse(lfvio_ctx *ctx, const LfvioFuseIn *in, LfvioFuseOut *out);
+
 /* lfvio_track_frame / lfvio_track_frame_reset: one image through FeatureTracker::readImage (feature_tracker/src/feature_tracker.cpp:
  * 95-184) and the node's updateID loop (feature_tracker_node.cpp:102-111) in ONE call: one copy up ([sample_words | image]), the
  * stages below enqueued back to back, one copy down.  The track table (cur_pts, ids, track_cnt) is resident in the context, and so

@@ -53,6 +53,7 @@ constexpr ncclDataType_t ncclDouble = 8;
 #include "kernels_clahe.h"
 #include "kernels_imgfmt.h"
 #include "kernels_remap.h"
+#include "kernels_fuse.h"
 #include "kernels_track.h"
 #include "kernels_trackframe.h"
 #include "kernels_trackbatch.h"
@@ -1824,6 +1825,8 @@ int lfvio_batch_optimize_pending(const lfvio_ctx *c) { return c && c->call.pendi
 #include "imgfmt.inc"
 
 #include "remap.inc"
+
+#include "fuse.inc"
 
 #include "klt.inc"
 

@@ -57,6 +57,24 @@ int lfvio_remap_build(lfvio_ctx *c, const LfvioRemapIn *in, float *map_x, float 
   return LFVIO_OK;
 }
 
+// The gather of a source image of geometry g, already on the device, through the RESIDENT maps (valid: the caller's check) into dst
+// [height][width * g.bpp]: the integer map is rebuilt first where remap_needs_index says so.  lfvio_remap_apply and lfvio_cloud_fuse
+// (fuse.inc) enqueue it on the feature stream fs.
+static int remap_gather(lfvio_ctx *c, hipStream_t fs, const RemapGeom &g, const unsigned char *src, unsigned char *dst) {
+  lfvio_ctx::RemapState &s = c->remap;
+  const size_t n = (size_t)s.r.width * s.r.height;
+  const float *mx = s.map.get(), *my = mx + n;
+  if (remap_needs_index(s.r, g)) {
+    s.r.indexed = false;
+    hipLaunchKernelGGL(k_remap_index, dim3((unsigned)((n + REMAP_THREADS - 1) / REMAP_THREADS)), dim3(REMAP_THREADS), 0, fs, g, n, mx, my, s.index.get());
+    HIPCHK(c, hipGetLastError());
+    s.r.geom = g, s.r.indexed = true;
+  }
+  remap_apply_launch(fs, g.bpp, s.index.get(), src, dst, n);
+  HIPCHK(c, hipGetLastError());
+  return LFVIO_OK;
+}
+
 int lfvio_remap_apply(lfvio_ctx *c, const LfvioImageFormat *fmt, int src_width, int src_height, const unsigned char *pixels, unsigned char *out) {
   if (!c) return LFVIO_ERR_ARG;
   if (const char *why = remap_apply_check(fmt, src_width, src_height, pixels, out)) {
@@ -77,17 +95,7 @@ int lfvio_remap_apply(lfvio_ctx *c, const LfvioImageFormat *fmt, int src_width, 
   if (int rc = st.reserve()) return rc;
   std::memcpy(st.h + oI, pixels, nI);
   if (int rc = st.up(in_end)) return rc;
-  const float *mx = s.map.get(), *my = mx + n;
-  if (remap_needs_index(s.r, g)) {
-    s.r.indexed = false;
-    hipLaunchKernelGGL(k_remap_index, dim3((unsigned)((n + REMAP_THREADS - 1) / REMAP_THREADS)), dim3(REMAP_THREADS), 0, st.fs, g, n, mx, my, s.index.get());
-    HIPCHK(c, hipGetLastError());
-    s.r.geom = g, s.r.indexed = true;
-  }
-  const unsigned char *src = (const unsigned char *)(st.d + oI);
-  unsigned char *dst = (unsigned char *)(st.d + oO);
-  remap_apply_launch(st.fs, g.bpp, s.index.get(), src, dst, n);
-  HIPCHK(c, hipGetLastError());
+  if (int rc = remap_gather(c, st.fs, g, (const unsigned char *)(st.d + oI), (unsigned char *)(st.d + oO))) return rc;
   if (int rc = st.down(oO, st.end)) return rc;
   std::memcpy(out, st.h + oO, nO);
   return LFVIO_OK;

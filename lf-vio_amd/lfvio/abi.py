@@ -740,6 +740,26 @@ def projector_c(cam):
     return ProjectorC(C.pointer(cc), (C.c_double * OCAM_INV_POLY_SIZE)(*inv)), cc
 
 
+FUSE_EQUIRECT, FUSE_CAMERA = 0, 1  # LFVIO_FUSE_*
+FUSE_IMAGE_NONE, FUSE_IMAGE_GIVEN, FUSE_IMAGE_REMAP = 0, 1, 2  # LFVIO_FUSE_IMAGE_*
+FUSE_MAX_POINTS = 1 << 20
+
+
+class FuseInC(C.Structure):
+    """LfvioFuseIn (include/lfvio.h)."""
+    _fields_ = [("cloud", C.POINTER(C.c_ubyte)), ("n", C.c_int), ("point_step", C.c_int), ("off_x", C.c_int), ("off_y", C.c_int), ("off_z", C.c_int),
+                ("big_endian", C.c_int), ("R", C.c_double * 9), ("T", C.c_double * 3), ("min_range", C.c_double), ("max_range", C.c_double),
+                ("kind", C.c_int), ("width", C.c_int), ("height", C.c_int), ("proj", C.POINTER(ProjectorC)), ("image_mode", C.c_int),
+                ("fmt", C.POINTER(ImageFormatC)), ("src_width", C.c_int), ("src_height", C.c_int), ("pixels", C.POINTER(C.c_ubyte)),
+                ("paint_on", C.c_int), ("paint", C.c_ubyte * 4)]
+
+
+class FuseOutC(C.Structure):
+    """LfvioFuseOut (include/lfvio.h): each pointer null, or written."""
+    _fields_ = [("index", C.POINTER(C.c_int)), ("range", C.POINTER(C.c_float)), ("colour", C.POINTER(C.c_ubyte)), ("image_out", C.POINTER(C.c_ubyte)),
+                ("counts", C.POINTER(C.c_int))]
+
+
 class TrackFrameInC(C.Structure):
     """LfvioTrackFrameIn (include/lfvio.h)."""
     _fields_ = [
@@ -816,7 +836,7 @@ HIP_SYMBOLS = [
     "lfvio_clahe_set", "lfvio_clahe_apply", "lfvio_image_format_set", "lfvio_image_gray", "lfvio_track_batch_format",
     "lfvio_track_reject", "lfvio_track_undistort", "lfvio_track_reset", "lfvio_track_frame", "lfvio_track_frame_reset",
     "lfvio_track_frame_message",
-    "lfvio_cam_project", "lfvio_remap_build", "lfvio_remap_apply", "lfvio_remap_reset",
+    "lfvio_cam_project", "lfvio_remap_build", "lfvio_remap_apply", "lfvio_remap_reset", "lfvio_cloud_fuse",
     "lfvio_track_batch_reserve", "lfvio_track_batch_set_mask", "lfvio_track_batch_clahe", "lfvio_track_batch_frame", "lfvio_track_batch_reset",
     "lfvio_group_create", "lfvio_group_unique_id", "lfvio_group_create_rank", "lfvio_group_create_local", "lfvio_group_destroy",
     "lfvio_group_last_error", "lfvio_group_size", "lfvio_group_local", "lfvio_group_rank", "lfvio_group_ctx", "lfvio_group_backend",
@@ -912,6 +932,8 @@ def load_hip_library(path=None):
         lib.lfvio_remap_build.argtypes = [C.c_void_p, C.POINTER(RemapInC), C.POINTER(C.c_float), C.POINTER(C.c_float)]
         lib.lfvio_remap_apply.argtypes = [C.c_void_p, C.POINTER(ImageFormatC), C.c_int, C.c_int] + [C.POINTER(C.c_ubyte)] * 2
         lib.lfvio_remap_reset.argtypes = [C.c_void_p]
+    if hasattr(lib, "lfvio_cloud_fuse"):
+        lib.lfvio_cloud_fuse.argtypes = [C.c_void_p, C.POINTER(FuseInC), C.POINTER(FuseOutC)]
     if hasattr(lib, "lfvio_track_reject"):
         lib.lfvio_track_reject.argtypes = [C.c_void_p, C.POINTER(TrackRejectInC), C.POINTER(C.c_ubyte), C.POINTER(TrackRejectOutC), _dp, _dp]
         lib.lfvio_track_undistort.argtypes = [C.c_void_p, C.POINTER(TrackUndistortInC)] + [C.POINTER(C.c_float)] * 3 + [C.POINTER(C.c_int)]

@@ -754,6 +754,52 @@ class Engine:
         """lfvio_remap_reset: forget the resident map."""
         self._check(self.lib.lfvio_remap_reset(self.ctx), "lfvio_remap_reset")
 
+    FUSE_OUTPUTS = ("index", "range", "colour", "image_out", "counts")
+
+    def cloud_fuse(self, cloud, n, point_step, offs, width, height, kind=abi.FUSE_EQUIRECT, big_endian=0, R=None, T=None, min_range=0.0,
+                   max_range=float("inf"), cam=None, image=None, image_mode=None, encoding=None, step=0, src_size=(0, 0), paint=None,
+                   want=("index", "range", "counts"), out=None, check=True):
+        """lfvio_cloud_fuse: the n points of `cloud` (uint8, n * point_step bytes: a PointCloud2's data; None: a null pointer) with their
+        float32 fields at the byte offsets offs = (off_x, off_y, off_z), through P = R p + T (defaults: the identity) and the range gate,
+        onto a width x height image: kind abi.FUSE_EQUIRECT, or abi.FUSE_CAMERA through `cam` (projector()).  image (uint8; None: a null
+        pointer): with image_mode abi.FUSE_IMAGE_GIVEN (the default where there is one) the width x height image itself, with
+        abi.FUSE_IMAGE_REMAP a src_size = (src_width, src_height) source that goes through the resident map first; encoding None: a null
+        format (mono8).  paint: None, or up to four bytes written at every marked pixel.  want: the outputs brought down, of
+        FUSE_OUTPUTS; out: {name: array to be written}, taken as they are.  Returns {name: array}; check=False returns (error code, that)."""
+        up = C.POINTER(C.c_ubyte)
+        data = None if cloud is None else np.ascontiguousarray(cloud, dtype=np.uint8)
+        px = None if image is None else np.ascontiguousarray(image, dtype=np.uint8)
+        if image_mode is None:
+            image_mode = abi.FUSE_IMAGE_NONE if image is None else abi.FUSE_IMAGE_GIVEN
+        proj, keep = self.projector(cam)
+        fmt = None if encoding is None else abi.ImageFormatC(encoding, step)
+        r = np.eye(3).reshape(9) if R is None else np.ascontiguousarray(R, dtype=np.float64).reshape(9)
+        t = np.zeros(3) if T is None else np.ascontiguousarray(T, dtype=np.float64).reshape(3)
+        pb = [int(v) for v in (paint if paint is not None else ())] + [0] * 4
+        fin = abi.FuseInC(None if data is None else data.ctypes.data_as(up), n, point_step, offs[0], offs[1], offs[2], big_endian, (C.c_double * 9)(*r.tolist()),
+                          (C.c_double * 3)(*t.tolist()), min_range, max_range, kind, width, height, None if proj is None else C.pointer(proj), image_mode,
+                          None if fmt is None else C.pointer(fmt), src_size[0], src_size[1], None if px is None else px.ctypes.data_as(up),
+                          0 if paint is None else 1, (C.c_ubyte * 4)(*pb[:4]))
+        bpp = abi.IMG_BPP.get(encoding or 0, 4)
+        nn, w, h = min(max(n, 1), abi.FUSE_MAX_POINTS), min(max(width, 1), 8192), min(max(height, 1), 8192)
+        shapes = dict(index=((nn,), np.int32), range=((h, w), np.float32), colour=((nn, bpp), np.uint8), image_out=((h, w * bpp), np.uint8), counts=((3,), np.int32))
+        res = dict(out or {})
+        for name in want:
+            if name not in res:
+                res[name] = np.zeros(*shapes[name])
+        types = dict(index=C.c_int, range=C.c_float, colour=C.c_ubyte, image_out=C.c_ubyte, counts=C.c_int)
+        ptr = {k: res[k].ctypes.data_as(C.POINTER(types[k])) if k in res else None for k in self.FUSE_OUTPUTS}
+        fout = abi.FuseOutC(ptr["index"], ptr["range"], ptr["colour"], ptr["image_out"], ptr["counts"])
+        rc = self.lib.lfvio_cloud_fuse(self.ctx, C.byref(fin), C.byref(fout))
+        del keep
+        if not check:
+            return rc, res
+        self._check(rc, "lfvio_cloud_fuse")
+        for name in ("index", "colour"):
+            if name in res:
+                res[name] = res[name][:n]
+        return res
+
     @staticmethod
     def camera(cam):
         """A CameraC from a dict; None: a null pointer.  model (optional) LFVIO_CAM_OCAM: cx, cy, c, d, e, poly [5];

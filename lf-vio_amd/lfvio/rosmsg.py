@@ -9,6 +9,9 @@ tools/bag_to_lfvt.py.  Message layouts are the published ROS 1 serialization of
                            (feature_tracker_node.cpp:113-178 -> estimator_node.cpp:292-312)
   sensor_msgs/Image        header, u32 height, u32 width, string encoding, u8 is_bigendian, u32 step, u8[] data — the camera topic
                            img_callback takes (feature_tracker_node.cpp:28-78), for recordings with raw images (record type 10)
+  sensor_msgs/PointCloud2  header, u32 height, u32 width, fields[] (u32 m, each: string name, u32 offset, u8 datatype, u32 count),
+                           u8 is_bigendian, u32 point_step, u32 row_step, u8[] data, u8 is_dense — the lidar topic of
+                           pointcloud_image_fusion (pointcloud_callback, pointcloud_image_fusion_node.cpp:121-125), for lfvio_cloud_fuse
   std_msgs/Bool            u8                                                       (restart_callback, :187-204)
   std_msgs/Float64MultiArray  layout (dim[], data_offset), f64[] data — the bootstrap record the dump hook of
                            INTEGRATION.md section 3 publishes (247 doubles + the stamp of Headers[WINDOW_SIZE])
@@ -185,6 +188,58 @@ def de_image_any(buf):
     return stamp, np.frombuffer(buf, dtype=np.uint8, count=n, offset=o + 9).reshape(h, step).copy(), w, step, code
 
 
+POINTFIELD_FLOAT32 = 7  # sensor_msgs/PointField: INT8 1, UINT8 2, INT16 3, UINT16 4, INT32 5, UINT32 6, FLOAT32 7, FLOAT64 8
+
+
+def ser_pointcloud2(seq, stamp, data, fields, point_step, width, height=1, is_bigendian=0, is_dense=1, row_step=None, frame_id=b"lidar"):
+    """sensor_msgs/PointCloud2 from its data bytes as they are.  fields: [(name bytes, offset, datatype, count)]; row_step: default
+    width * point_step.  Nothing is checked: the tests write refused messages with it too."""
+    d = np.ascontiguousarray(data, dtype=np.uint8).tobytes()
+    out = _header(seq, stamp, frame_id) + struct.pack("<II", height, width) + struct.pack("<I", len(fields))
+    for name, offset, datatype, count in fields:
+        out += _string(name) + struct.pack("<IBI", offset, datatype, count)
+    row_step = width * point_step if row_step is None else row_step
+    return out + struct.pack("<BII", is_bigendian, point_step, row_step) + struct.pack("<I", len(d)) + d + struct.pack("<B", is_dense)
+
+
+def de_pointcloud2(buf):
+    """-> (stamp, dict(height, width, fields [(name, offset, datatype, count)], is_bigendian, point_step, row_step, data uint8 [n *
+    point_step], is_dense)) of a sensor_msgs/PointCloud2 whose height * width points lie one behind the other: row_step == width *
+    point_step and height * row_step data bytes.  Anything else raises ValueError."""
+    stamp, o = _read_header(buf, 0)
+    height, width, m = struct.unpack_from("<III", buf, o)
+    o += 12
+    fields = []
+    for _ in range(m):
+        (ln,) = struct.unpack_from("<I", buf, o)
+        name = bytes(buf[o + 4:o + 4 + ln])
+        offset, datatype, count = struct.unpack_from("<IBI", buf, o + 4 + ln)
+        fields.append((name, offset, datatype, count))
+        o += 4 + ln + 9
+    big, point_step, row_step = struct.unpack_from("<BII", buf, o)
+    (n,) = struct.unpack_from("<I", buf, o + 9)
+    if row_step != width * point_step or n != height * row_step:
+        raise ValueError(f"sensor_msgs/PointCloud2: {n} bytes in rows of {row_step} are not {height} x {width} points of {point_step} bytes")
+    data = np.frombuffer(buf, dtype=np.uint8, count=n, offset=o + 13).copy()
+    return stamp, dict(height=height, width=width, fields=fields, is_bigendian=big, point_step=point_step, row_step=row_step, data=data,
+                       is_dense=buf[o + 13 + n])
+
+
+def pointcloud2_xyz(msg):
+    """(point_step, off_x, off_y, off_z, big_endian) of a de_pointcloud2 message: what lfvio_cloud_fuse takes beside the data bytes.  The
+    fields named x, y and z must each be one FLOAT32; a message without one of them raises ValueError."""
+    off = {}
+    for name, offset, datatype, count in msg["fields"]:
+        if name in (b"x", b"y", b"z"):
+            if datatype != POINTFIELD_FLOAT32 or count != 1:
+                raise ValueError(f"sensor_msgs/PointCloud2: field {name.decode()} is not one FLOAT32")
+            off[name] = offset
+    missing = [k.decode() for k in (b"x", b"y", b"z") if k not in off]
+    if missing:
+        raise ValueError(f"sensor_msgs/PointCloud2: no field {', '.join(missing)}")
+    return msg["point_step"], off[b"x"], off[b"y"], off[b"z"], 1 if msg["is_bigendian"] else 0
+
+
 def ser_bool(v):
     return struct.pack("<B", 1 if v else 0)
 
@@ -215,6 +270,7 @@ TYPES = {
     "std_msgs/Bool": "8b94c1b53db61fb6aed406028ad6332a",
     "std_msgs/Float64MultiArray": "4b7d974086d4060e7db4613a7e6c3ba4",
     "sensor_msgs/Image": "060021388200f6f0f447d0fcd9c64743",
+    "sensor_msgs/PointCloud2": "1158d486dd51d683ce2f1be655c3c181",
 }
 
 
