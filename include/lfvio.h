@@ -867,7 +867,17 @@ int lfvio_image_gray(lfvio_ctx *ctx, const LfvioImageFormat *fmt, int width, int
  *             and the grid can miss a dip of F' narrower than a step.  tests/kb_ref.py restates this lift and holds it to a
  *             50-digit evaluation of the reference's definition (tests/test_kb_ref.py: the root to 3.6 eps where F' >= 0.1, sin and
  *             cos to 5.4 ulp, the bearing to 25.6 eps where F' >= 0.1); the device gives the restatement's bits.
- *   the camera LFVIO_ERR_ARG of every call that takes an LfvioCamera: models 1 and 4 and any model outside {0, 2, 3, 5}; for PINHOLE
+ *   the lift of LFVIO_CAM_EQUIRECT: the camera of the EXPANDED image that lfvio_remap_build's LFVIO_MAP_EQUIRECT map
+ *             writes — GetremapMat's ray (pointcloud_image_fusion.cpp:93-101) with the float pixel in place of the integer one.
+ *             fx, fy carry that image's width and height (finite, integral, in [16, 8192]); no other field is read.  In double,
+ *             grouped as written: lon = ((double)px / fx - 0.5) * (2.0 * pi), lat = -(((double)py / fy - 0.5) * pi),
+ *             P = (cos(lat) * sin(lon), cos(lat) * cos(lon), sin(lat)), sine and cosine as the KANNALA_BRANDT lift takes them.  At an
+ *             integer pixel this is the map's own ray bit for bit, so tracked bearings are in the frame the map was built in.  The
+ *             lift ONLY: lfvio_cam_project, lfvio_remap_build and lfvio_cloud_fuse with LFVIO_FUSE_CAMERA refuse the model (the
+ *             projection exists as LFVIO_FUSE_EQUIRECT).  tests/equirect_ref.py restates it and holds it to a 50-digit evaluation on
+ *             [0, width] x [0, height] (tests/test_equirect_lift.py: to 5.438 eps max(|P|, 1), twice the 2.719 measured).
+ *   the camera LFVIO_ERR_ARG of every call that takes an LfvioCamera: models 1 and 4 and any model outside {0, 2, 3, 5, 6}; for
+ *             EQUIRECT fx or fy non-finite, non-integral or outside [16, 8192]; for PINHOLE
  *             and MEI a non-finite value among cx, cy, fx, fy, k1, k2, p1, p2, fx == 0 or fy == 0, and for MEI a non-finite xi; for
  *             KANNALA_BRANDT a non-finite value among cx, cy, fx, fy, poly[0 .. 3], fx == 0 or fy == 0.  An OCam camera's fx .. xi are
  *             not read, a PINHOLE or MEI camera's c, d, e, poly are not, a KANNALA_BRANDT camera's c, d, e, poly[4], k1 .. xi are
@@ -904,15 +914,16 @@ int lfvio_image_gray(lfvio_ctx *ctx, const LfvioImageFormat *fmt, int width, int
  * device memory of their own (2 x 64 KiB, allocated at the first use), not in the feature calls' staging block. */
 #define LFVIO_CAM_OCAM 0
 #define LFVIO_CAM_PINHOLE 2
-#define LFVIO_CAM_MEI     3   /* 1 and 4 are refused, like every model outside {0, 2, 3, 5} */
+#define LFVIO_CAM_MEI     3   /* 1 and 4 are refused, like every model outside {0, 2, 3, 5, 6} */
 #define LFVIO_CAM_KANNALA_BRANDT 5
+#define LFVIO_CAM_EQUIRECT 6  /* the lift only: the expanded image of LFVIO_MAP_EQUIRECT; fx, fy = its width, height */
 #define LFVIO_TRACK_MAX_POINTS 4096
 typedef struct {
-  int model;             /* LFVIO_CAM_OCAM, _PINHOLE, _MEI or _KANNALA_BRANDT; anything else: LFVIO_ERR_ARG */
+  int model;             /* LFVIO_CAM_OCAM, _PINHOLE, _MEI, _KANNALA_BRANDT or _EQUIRECT; anything else: LFVIO_ERR_ARG */
   double cx, cy;         /* OCam: center_x, center_y; PINHOLE: cx, cy; MEI and KANNALA_BRANDT: u0, v0 */
   double c, d, e;        /* OCam only: the affine part; inv_scale = 1.0 / (c - d * e) */
   double poly[5];        /* OCam: SCARAMUZZA_POLY_SIZE; KANNALA_BRANDT: poly[0 .. 3] = k2, k3, k4, k5 (NOT the k1, k2 below) */
-  double fx, fy;         /* PINHOLE: fx, fy; MEI: gamma1, gamma2; KANNALA_BRANDT: mu, mv.  Not read for OCam, like everything below */
+  double fx, fy;         /* PINHOLE: fx, fy; MEI: gamma1, gamma2; KANNALA_BRANDT: mu, mv; EQUIRECT: width, height.  Not read for OCam, like everything below */
   double k1, k2, p1, p2; /* PINHOLE and MEI: distortion_parameters */
   double xi;             /* MEI: mirror_parameters.xi */
 } LfvioCamera;
@@ -1013,6 +1024,28 @@ int lfvio_remap_build(lfvio_ctx *ctx, const LfvioRemapIn *in, float *map_x, floa
 int lfvio_remap_apply(lfvio_ctx *ctx, const LfvioImageFormat *fmt, int src_width, int src_height, const unsigned char *pixels,
                       unsigned char *out /* [height][width * bytes per pixel] of the resident map's size */);
 int lfvio_remap_reset(lfvio_ctx *ctx);   /* forget the resident maps */
+
+/* lfvio_track_source_set: track on the EXPANDED image — level 0 of the fresh pyramid gathered through the resident map.
+ * All three of the reference's launch files that carry the expansion node remap its equal_rectangle_img onto /camera/image_raw
+ * (mindvision.launch:28-32), so its tracker can be fed the expanded image; here the raw source image goes up once and never comes down.
+ * src != NULL: `image` of every later lfvio_klt_track, lfvio_track_frame and lfvio_track_frame_message is the SOURCE image: src_height
+ * rows of src_width pixels in the encoding and step of lfvio_image_format_set (mono8 with contiguous rows while that is off), and
+ * in->width, in->height stay the size of the image that is TRACKED, which must be the resident map's (lfvio_remap_build).  Level 0 is
+ * the grey value above of the pixel lfvio_remap_apply would have written (for an outside entry the grey value of a zero pixel), in
+ * one kernel (k_remap_gray, csrc/kernels_tracksource.h); the bytes that go up are src_height * step.  The contract: every output array
+ * of the three calls, and lfvio_klt_level afterwards, is bit for bit what a second context gives that is fed lfvio_remap_apply's
+ * output under lfvio_image_format_set({the same encoding, step 0}).  CLAHE, the mask, detection, the table and the message see an image
+ * of in->width x in->height.  The camera of such a call is the TRACKED image's: LFVIO_CAM_EQUIRECT for an LFVIO_MAP_EQUIRECT map, a
+ * distortion-free LFVIO_CAM_PINHOLE for an LFVIO_MAP_PERSPECTIVE one.  The integer map is shared with lfvio_remap_apply and
+ * lfvio_cloud_fuse: each rebuilds it when it finds it written for another source geometry, so they may alternate.
+ * src == NULL: off.  Off after lfvio_create; survives lfvio_klt_reset, lfvio_track_frame_reset and lfvio_remap_reset.  The batched
+ * route (lfvio_track_batch_*) does not look at the setting: its images are the tracked images (a map per slot is a later step).
+ * LFVIO_ERR_ARG: at the set call (the setting untouched) src_width or src_height outside [16, 8192]; at the tracker call, before
+ * anything is touched (the resident pyramid, the track table, the maps and the stream as they were): no resident map (never built, or
+ * after lfvio_remap_reset), a resident map of another size than in->width x in->height, and what lfvio_image_format_set's check
+ * refuses beside src_width x src_height (0 < step < src_width * bytes per pixel). */
+typedef struct { int src_width, src_height; } LfvioTrackSource;
+int lfvio_track_source_set(lfvio_ctx *ctx, const LfvioTrackSource *src /* NULL: off */);
 
 /* lfvio_cloud_fuse: the other half of pointcloud_image_fusion — every point of a lidar scan taken into the camera frame, projected and
  * marked in the expanded image (pointcloud_image_fusion_node.cpp:92-115, in comments as shipped; laserCloudIn is pointcloud_callback's,

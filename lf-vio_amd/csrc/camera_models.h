@@ -5,6 +5,8 @@
 //   LFVIO_CAM_PINHOLE          PinholeCamera::liftProjective (PinholeCamera.cc:450-510)
 //   LFVIO_CAM_MEI              CataCamera::liftProjective (CataCamera.cc:556-626)
 //   LFVIO_CAM_KANNALA_BRANDT   EquidistantCamera::liftProjective (EquidistantCamera.cc:428-442), restated in camera_kb.h
+//   LFVIO_CAM_EQUIRECT         the expanded image of LFVIO_MAP_EQUIRECT: GetremapMat's ray (pointcloud_image_fusion.cpp:93-101) at a float
+//                              pixel — the lift only (proj_check refuses it); numpy: tests/equirect_ref.py
 // and what every model shares behind the lift: the norm, the unit bearing of rejectWithF and the two float outputs of
 // undistortedPoints.  The specification is in include/lfvio.h and, as numpy, in tests/track_ref.py (OCam), tests/camera_ref.py
 // (PINHOLE, MEI) and tests/kb_ref.py (KANNALA_BRANDT).  The other way — spaceToPlane of the four models, cam_project over the
@@ -33,14 +35,21 @@ struct TrackCam {  // a kernel argument, by value; the members a model does not 
   double inv11, inv13, inv22, inv23, k1, k2, p1, p2, xi;  // PINHOLE and MEI (xi: MEI), PinholeCamera.cc:281-289
   int model, no_distortion;
   double theta_lim, r_lim;  // KANNALA_BRANDT (camera_kb.h), with inv11 .. inv23 and k2 .. k5 in poly[0 .. 3]
+  // EQUIRECT: the expanded image's width and height in cx and cy, nothing else
 };
 
 // On the host, in double, once per call (inv_scale: ScaramuzzaCamera.cc:197).  LfvioCamera's fx .. xi are read only for PINHOLE and
-// MEI, its c, d, e, poly only for OCam; KANNALA_BRANDT reads cx, cy, fx, fy and poly[0 .. 3]: callers may leave the others indeterminate.
+// MEI, its c, d, e, poly only for OCam; KANNALA_BRANDT reads cx, cy, fx, fy and poly[0 .. 3], EQUIRECT fx and fy: callers may leave the
+// others indeterminate.
 // kb: where a KANNALA_BRANDT camera's constants are kept from one call to the next (nullptr: formed anew); no other model looks at it.
 inline TrackCam track_cam(const LfvioCamera &k, KbCache *kb = nullptr) {
   TrackCam t = {};
-  t.model = k.model, t.cx = k.cx, t.cy = k.cy;
+  t.model = k.model;
+  if (k.model == LFVIO_CAM_EQUIRECT) {
+    t.cx = k.fx, t.cy = k.fy;
+    return t;
+  }
+  t.cx = k.cx, t.cy = k.cy;
   if (k.model == LFVIO_CAM_OCAM) {
     t.c = k.c, t.d = k.d, t.e = k.e;
     t.inv_scale = 1.0 / (k.c - k.d * k.e);
@@ -62,12 +71,22 @@ inline TrackCam track_cam(const LfvioCamera &k, KbCache *kb = nullptr) {
   return t;
 }
 
+constexpr int CAM_EQUIRECT_MIN_SIDE = 16, CAM_EQUIRECT_MAX_SIDE = 8192;  // (IMGFMT_MIN_SIDE, IMGFMT_MAX_SIDE of image_format.h)
+
 // nullptr, or what is wrong with the camera.  v: the fields the model reads besides MEI's xi (OCam's are not judged)
 inline const char *track_camera_check(const LfvioCamera *cam) {
   if (!cam) return "lfvio_track: null camera";
-  if (cam->model != LFVIO_CAM_OCAM && cam->model != LFVIO_CAM_PINHOLE && cam->model != LFVIO_CAM_MEI && cam->model != LFVIO_CAM_KANNALA_BRANDT)
-    return "lfvio_track: a camera model other than LFVIO_CAM_OCAM, LFVIO_CAM_PINHOLE, LFVIO_CAM_MEI and LFVIO_CAM_KANNALA_BRANDT";
+  if (cam->model != LFVIO_CAM_OCAM && cam->model != LFVIO_CAM_PINHOLE && cam->model != LFVIO_CAM_MEI && cam->model != LFVIO_CAM_KANNALA_BRANDT &&
+      cam->model != LFVIO_CAM_EQUIRECT)
+    return "lfvio_track: a camera model other than LFVIO_CAM_OCAM, LFVIO_CAM_PINHOLE, LFVIO_CAM_MEI, LFVIO_CAM_KANNALA_BRANDT and LFVIO_CAM_EQUIRECT";
   if (cam->model == LFVIO_CAM_OCAM) return nullptr;
+  if (cam->model == LFVIO_CAM_EQUIRECT) {  // fx, fy: the expanded image's width and height (a NaN fails every comparison)
+    const double side[2] = {cam->fx, cam->fy};
+    for (double x : side)
+      if (!(x >= (double)CAM_EQUIRECT_MIN_SIDE && x <= (double)CAM_EQUIRECT_MAX_SIDE) || x != std::floor(x))
+        return "lfvio_track: LFVIO_CAM_EQUIRECT with fx or fy (the image's width and height) not an integer in [16, 8192]";
+    return nullptr;
+  }
   const bool kb = cam->model == LFVIO_CAM_KANNALA_BRANDT;
   const double v[8] = {cam->cx, cam->cy, cam->fx, cam->fy, kb ? cam->poly[0] : cam->k1, kb ? cam->poly[1] : cam->k2,
                        kb ? cam->poly[2] : cam->p1, kb ? cam->poly[3] : cam->p2};
@@ -112,6 +131,17 @@ KB_HD CamRay cam_lift_mei(const TrackCam &cam, float px, float py) {
   return {mx_u, my_u, 1.0 - (cam.xi * (rho2 + 1.0)) / (cam.xi + sqrt(1.0 + (1.0 - cam.xi * cam.xi) * rho2))};  // :624
 }
 
+// LFVIO_CAM_EQUIRECT: remap_ray's text (remap_plan.h, LFVIO_MAP_EQUIRECT) with the float pixel in place of (i, j); cx, cy: width, height
+KB_HD CamRay cam_lift_equirect(const TrackCam &cam, float px, float py) {
+  constexpr double PI = 3.14159265358979323846;
+  const double lon = ((double)px / cam.cx - 0.5) * (2.0 * PI);
+  const double lat = -(((double)py / cam.cy - 0.5) * PI);
+  double slon, clon, slat, clat;
+  kb_sincos(lon, slon, clon);
+  kb_sincos(lat, slat, clat);
+  return {clat * slon, clat * clon, slat};
+}
+
 // liftProjective of the pixel (px, py).  KANNALA_BRANDT: as camera_kb.h restates it; OCAMCamera::liftProjective (:623-645):
 KB_HD CamRay cam_lift(const TrackCam &cam, float px, float py) {
   if (cam.model == LFVIO_CAM_PINHOLE) return cam_lift_pinhole(cam, px, py);
@@ -121,6 +151,7 @@ KB_HD CamRay cam_lift(const TrackCam &cam, float px, float py) {
     kb_lift_pixel(cam.inv11, cam.inv13, cam.inv22, cam.inv23, cam.poly, cam.theta_lim, cam.r_lim, px, py, P.x, P.y, P.z);
     return P;
   }
+  if (cam.model == LFVIO_CAM_EQUIRECT) return cam_lift_equirect(cam, px, py);
   const double x = (double)px - cam.cx, y = (double)py - cam.cy;  // :627
   const double xa = cam.inv_scale * (x - cam.d * y), ya = cam.inv_scale * (-cam.e * x + cam.c * y);  // :631-632
   const double phi = sqrt(xa * xa + ya * ya);
@@ -174,10 +205,13 @@ inline ProjCam proj_cam(const LfvioProjector &p, KbCache *kb = nullptr) {
   return q;
 }
 
-// nullptr, or what is wrong with the projector: its camera as track_camera_check judges it and, for OCam, a finite inverse polynomial
+// nullptr, or what is wrong with the projector: its camera as track_camera_check judges it — but no LFVIO_CAM_EQUIRECT, which has no
+// projection here — and, for OCam, a finite inverse polynomial
 inline const char *proj_check(const LfvioProjector *p) {
   if (!p) return "lfvio_cam_project: null projector";
   if (const char *why = track_camera_check(p->camera)) return why;
+  if (p->camera->model == LFVIO_CAM_EQUIRECT)  // (cam_project would fall through to the OCam branch)
+    return "lfvio_cam_project: LFVIO_CAM_EQUIRECT has the lift only (the projection is LFVIO_FUSE_EQUIRECT of lfvio_cloud_fuse)";
   if (p->camera->model == LFVIO_CAM_OCAM)
     for (double x : p->inv_poly)
       if (!std::isfinite(x)) return "lfvio_cam_project: a non-finite inv_poly entry";

@@ -3,7 +3,8 @@
 // lfvio_hip.hip inside its extern "C" block.
 //
 // One call: validate and plan (klt_plan.h), pack [points | image] into the staging block of feat.inc, one copy up, the image into the
-// context's other pyramid buffer (a copy — k_img_gray of imgfmt.inc instead while lfvio_image_format_set names another encoding — or
+// context's other pyramid buffer (a copy — k_img_gray of imgfmt.inc instead while lfvio_image_format_set names another encoding,
+// k_remap_gray of tracksource.inc instead of both while lfvio_track_source_set is on — or
 // the three CLAHE launches of clahe.inc while lfvio_clahe_set is on), k_klt_down per level,
 // k_klt_track (grid N) from the resident pyramid into the new one, one copy down of [next | status | iterations]; then the new pyramid
 // is the resident one.  The pyramid buffers are the context's own: the
@@ -19,23 +20,28 @@ static int klt_build(lfvio_ctx *c, hipStream_t fs, unsigned char *pyr, const Klt
   return LFVIO_OK;
 }
 
-// The image at d_image (device, W x H as `im` describes it) into the context's other pyramid buffer — a copy or the conversion to
-// grey, then CLAHE while it is on: in place behind a conversion, since clahe_map_body reads and writes the same pixel and nothing
-// else and the histograms are a launch earlier — with the levels
+// The image at d_image (device, W x H as `ti.im` describes it — or the source image `ti.src` describes, gathered through the resident
+// map) into the context's other pyramid buffer — a copy, the conversion to grey or that gather, then CLAHE while it is on: in place
+// behind a conversion or a gather, since clahe_map_body reads and writes the same pixel and nothing else and the histograms are a
+// launch earlier — with the levels
 // 1 .. LU, and the levels of the resident pyramid that an earlier call did not build.  *prev: the pyramid to track from (the new one
 // when none of this size is resident, :111-114).  Returns the new pyramid, which the caller makes resident with a commit of the stream once the
 // call has succeeded.  (Every earlier call on the feature stream has been waited for: nobody reads the other buffer.)
-static int klt_pyramid(lfvio_ctx *c, hipStream_t fs, const unsigned char *d_image, const ImgfmtPlan &im, int W, int H, const KltPlan &full, int LU,
+static int klt_pyramid(lfvio_ctx *c, hipStream_t fs, const unsigned char *d_image, const TrackImage &ti, int W, int H, const KltPlan &full, int LU,
                        const unsigned char **prev, unsigned char **fresh_out) {
   TrackStream &s = c->tstream;
   unsigned char *fresh = c->klt.d[1 - s.pcur], *resident = c->klt.d[s.pcur];
-  if (im.convert) {  // level 0 is the grey image; CLAHE, if on, reads it there
-    if (int rc = imgfmt_run(c, fs, im, W, H, d_image, fresh)) return rc;
+  const bool written = ti.source || ti.im.convert;  // level 0 is written by a kernel of its own; CLAHE, if on, reads it there
+  if (ti.source) {  // d_image is the SOURCE image: level 0 is gathered through the resident map (tracksource.inc)
+    if (int rc = tracksource_run(c, fs, ti.src, W, H, d_image, fresh)) return rc;
+    d_image = fresh;
+  } else if (ti.im.convert) {  // level 0 is the grey image
+    if (int rc = imgfmt_run(c, fs, ti.im, W, H, d_image, fresh)) return rc;
     d_image = fresh;
   }
   if (c->clahe.on) {  // the equalized image is the image: k_clahe_map writes level 0 (clahe.inc)
     if (int rc = clahe_run(c, fs, c->clahe.cfg, W, H, d_image, fresh, nullptr)) return rc;
-  } else if (!im.convert) {
+  } else if (!written) {
     HIPCHK(c, hipMemcpyAsync(fresh, d_image, (size_t)W * H, hipMemcpyDeviceToDevice, fs));
   }
   if (int rc = klt_build(c, fs, fresh, full, 0, LU)) return rc;
@@ -61,15 +67,15 @@ int lfvio_klt_track(lfvio_ctx *c, const LfvioKltIn *in, float *next_pts, unsigne
     return LFVIO_ERR_ARG;
   }
   const int N = in->num_points, W = in->width, H = in->height, ML = in->max_level;
-  if (const char *why = imgfmt_call_check(c->imgfmt, W, H)) {
+  TrackImage im;  // what goes up: the image, or under lfvio_track_source_set the source image
+  if (const char *why = track_image_plan(c, W, H, &im)) {
     c->err = why;
     return LFVIO_ERR_ARG;
   }
-  const ImgfmtPlan im = imgfmt_plan(c->imgfmt.get(), W, H);
   const KltPlan p = klt_plan(W, H, in->win_size, ML), full = klt_plan(W, H, 0, LFVIO_KLT_MAX_LEVEL);
   const int LU = p.levels_used;
   FeatStage st(c);
-  const size_t nI = im.bytes, nT = (size_t)N * (ML + 1) * 4;
+  const size_t nI = im.bytes(), nT = (size_t)N * (ML + 1) * 4;
   const size_t oP = st.take((size_t)N * 8), oI = st.take(nI), in_end = st.end;
   const size_t oN = st.take((size_t)N * 8), oS = st.take((size_t)N), oT = st.take(nT);
   if (int rc = st.reserve()) return rc;

@@ -53,6 +53,8 @@ constexpr ncclDataType_t ncclDouble = 8;
 #include "kernels_clahe.h"
 #include "kernels_imgfmt.h"
 #include "kernels_remap.h"
+#include "kernels_tracksource.h"
+#include "tracksource_plan.h"
 #include "kernels_fuse.h"
 #include "kernels_track.h"
 #include "kernels_trackframe.h"
@@ -206,13 +208,16 @@ struct lfvio_ctx : CtxQueues {
   } imgfmt;
   // lfvio_remap_build / lfvio_remap_apply (remap.inc): what is resident (remap_plan.h), the two float maps [2][height][width] and the
   // integer map [height][width] in device memory of their own, allocated at the first build; kb: the last KANNALA_BRANDT projector's
-  // monotone range.  No tracker call looks at any of it, and lfvio_klt_reset leaves it alone.
+  // monotone range.  No tracker call looks at any of it unless lfvio_track_source_set is on, and lfvio_klt_reset leaves it alone.
   struct RemapState {
     RemapResident r;
     DevBuf<float> map;
     DevBuf<int> index;
     KbCache kb;
   } remap;
+  // lfvio_track_source_set (tracksource.inc): the single route's tracker calls take the SOURCE image and fill level 0 through the
+  // resident map above (off after lfvio_create; survives lfvio_klt_reset, lfvio_track_frame_reset and lfvio_remap_reset)
+  TrackSourceState tsource;
   // lfvio_track_undistort (track.inc): the (id, un_pts_3d) pairs of the previous call — [4096 ints | 4096 x 3 floats] twice, allocated
   // at the first use; tstream.mcur holds the tstream.mcount resident pairs (0: the map is empty), tstream.time is that call's
   struct TrackState {
@@ -1827,6 +1832,8 @@ int lfvio_batch_optimize_pending(const lfvio_ctx *c) { return c && c->call.pendi
 #include "remap.inc"
 
 #include "fuse.inc"
+
+#include "tracksource.inc"
 
 #include "klt.inc"
 

@@ -57,19 +57,29 @@ int lfvio_remap_build(lfvio_ctx *c, const LfvioRemapIn *in, float *map_x, float 
   return LFVIO_OK;
 }
 
+// The integer map of the RESIDENT maps (valid: the caller's check) made the one of a source of geometry g, on fs: rebuilt from the
+// float maps where remap_needs_index says so, and only there.  Everyone who reads the integer map — remap_gather below and the
+// tracker calls under lfvio_track_source_set (tracksource.inc) — comes through here first, so whoever finds it written for another
+// geometry rebuilds it and the one RemapResident says whose it is.
+static int remap_index_for(lfvio_ctx *c, hipStream_t fs, const RemapGeom &g) {
+  lfvio_ctx::RemapState &s = c->remap;
+  if (!remap_needs_index(s.r, g)) return LFVIO_OK;
+  const size_t n = (size_t)s.r.width * s.r.height;
+  const float *mx = s.map.get(), *my = mx + n;
+  s.r.indexed = false;
+  hipLaunchKernelGGL(k_remap_index, dim3((unsigned)((n + REMAP_THREADS - 1) / REMAP_THREADS)), dim3(REMAP_THREADS), 0, fs, g, n, mx, my, s.index.get());
+  HIPCHK(c, hipGetLastError());
+  s.r.geom = g, s.r.indexed = true;
+  return LFVIO_OK;
+}
+
 // The gather of a source image of geometry g, already on the device, through the RESIDENT maps (valid: the caller's check) into dst
-// [height][width * g.bpp]: the integer map is rebuilt first where remap_needs_index says so.  lfvio_remap_apply and lfvio_cloud_fuse
-// (fuse.inc) enqueue it on the feature stream fs.
+// [height][width * g.bpp], behind remap_index_for.  lfvio_remap_apply and lfvio_cloud_fuse (fuse.inc) enqueue it on the feature
+// stream fs.
 static int remap_gather(lfvio_ctx *c, hipStream_t fs, const RemapGeom &g, const unsigned char *src, unsigned char *dst) {
   lfvio_ctx::RemapState &s = c->remap;
   const size_t n = (size_t)s.r.width * s.r.height;
-  const float *mx = s.map.get(), *my = mx + n;
-  if (remap_needs_index(s.r, g)) {
-    s.r.indexed = false;
-    hipLaunchKernelGGL(k_remap_index, dim3((unsigned)((n + REMAP_THREADS - 1) / REMAP_THREADS)), dim3(REMAP_THREADS), 0, fs, g, n, mx, my, s.index.get());
-    HIPCHK(c, hipGetLastError());
-    s.r.geom = g, s.r.indexed = true;
-  }
+  if (int rc = remap_index_for(c, fs, g)) return rc;
   remap_apply_launch(fs, g.bpp, s.index.get(), src, dst, n);
   HIPCHK(c, hipGetLastError());
   return LFVIO_OK;

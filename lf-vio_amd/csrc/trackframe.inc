@@ -22,11 +22,11 @@ static int track_frame_run(lfvio_ctx *c, const LfvioTrackFrameIn *in, LfvioTrack
     return LFVIO_ERR_ARG;
   }
   const int W = in->width, H = in->height, S = in->num_samples, MC = in->max_count, n0 = s.count;
-  if (const char *why = imgfmt_call_check(c->imgfmt, W, H)) {
+  TrackImage im;  // what goes up: the image, or under lfvio_track_source_set the source image
+  if (const char *why = track_image_plan(c, W, H, &im)) {
     c->err = why;
     return LFVIO_ERR_ARG;
   }
-  const ImgfmtPlan im = imgfmt_plan(c->imgfmt.get(), W, H);
   const bool pub = in->publish != 0;
   if (!trackframe_out_check(out, nullptr) || (pub && !s.mask_fits(W, H))) {  // (a message's rows: lfvio_track_frame_message's check)
     c->err = "lfvio_track_frame: a null array in out, or a base mask that is not the image's size";
@@ -38,7 +38,7 @@ static int track_frame_run(lfvio_ctx *c, const LfvioTrackFrameIn *in, LfvioTrack
   const int LU = klt_plan(W, H, in->win_size, in->max_level).levels_used;
   const TrackCam cam = track_cam(*in->camera, &c->track_kb);
   const GftWork wk = gft_work(W, H);
-  const size_t B = (size_t)trackframe_bound(n0, MC, pub), N0 = (size_t)n0, nI = im.bytes;
+  const size_t B = (size_t)trackframe_bound(n0, MC, pub), N0 = (size_t)n0, nI = im.bytes();
   FeatStage st(c);
   // up
   const size_t oW = st.take(pub ? (size_t)S * 32 : 0), oI = st.take(nI), in_end = st.end;

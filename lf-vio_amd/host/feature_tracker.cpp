@@ -55,19 +55,23 @@ int FeatureTracker::onImage(double stamp, int width, int height, int step, int e
   const ImageGate::Stamp what = gate.onStamp(stamp);  // feature_tracker_node.cpp:30-62
   if (what == ImageGate::DROP) return DROPPED;
   if (what == ImageGate::RESTART) return RESTART;
+  // the image that is tracked: the record's, or the expanded one that the device gathers from it
+  const TrackerConfig::Expand &ex = cfg_.expand;
+  const int tw = ex.on ? ex.width : width, th = ex.on ? ex.height : height;
+  const LfvioTrackSource source = {width, height};
   if (!ready_) {  // the base mask (feature_tracker.cpp:53-56) and EQUALIZE (:101-107), once
     int rc = LFVIO_OK;
     if (!cfg_.mask.empty()) {
       rc = lfvio_gft_set_mask(ctx_, cfg_.mask_width, cfg_.mask_height, cfg_.mask.data());
     } else if (cfg_.annulus) {
-      std::vector<unsigned char> m((size_t)width * height);
+      std::vector<unsigned char> m((size_t)tw * th);
       const double hi = cfg_.max_r * cfg_.max_r, lo = cfg_.min_r * cfg_.min_r;
-      for (int y = 0; y < height; y++)
-        for (int x = 0; x < width; x++) {
+      for (int y = 0; y < th; y++)
+        for (int x = 0; x < tw; x++) {
           const double dx = x - cfg_.center_x, dy = y - cfg_.center_y, d2 = dx * dx + dy * dy;
-          m[(size_t)y * width + x] = d2 <= hi && d2 > lo ? 255 : 0;
+          m[(size_t)y * tw + x] = d2 <= hi && d2 > lo ? 255 : 0;
         }
-      rc = lfvio_gft_set_mask(ctx_, width, height, m.data());
+      rc = lfvio_gft_set_mask(ctx_, tw, th, m.data());
     } else {
       rc = lfvio_gft_set_mask(ctx_, 0, 0, nullptr);
     }
@@ -76,14 +80,28 @@ int FeatureTracker::onImage(double stamp, int width, int height, int step, int e
       rc = lfvio_clahe_set(ctx_, cfg_.equalize ? &clahe : nullptr);
     }
     if (rc == LFVIO_OK) rc = lfvio_image_format_set(ctx_, &format);  // (mono8 with step == width: the same as none)
+    if (rc == LFVIO_OK && ex.on) {  // the map of the expanded image through the source camera, resident from here on
+      LfvioProjector proj = {};
+      proj.camera = &ex.src_camera;
+      std::memcpy(proj.inv_poly, ex.inv_poly, sizeof proj.inv_poly);
+      LfvioRemapIn rin = {};
+      rin.proj = &proj, rin.kind = ex.kind, rin.width = ex.width, rin.height = ex.height;
+      std::memcpy(rin.M, ex.M, sizeof rin.M);
+      rc = lfvio_remap_build(ctx_, &rin, nullptr, nullptr);
+    }
+    if (rc == LFVIO_OK) rc = lfvio_track_source_set(ctx_, ex.on ? &source : nullptr);  // (off: whatever an earlier tracker left on the context)
     if (rc != LFVIO_OK) return status = rc;
-    format_ = format, ready_ = true;
+    format_ = format, source_ = source, ready_ = true;
+  }
+  if (ex.on && (source.src_width != source_.src_width || source.src_height != source_.src_height)) {  // a driver that changes its size
+    if (int rc = lfvio_track_source_set(ctx_, &source)) return status = rc;
+    source_ = source;
   }
   if (format.encoding != format_.encoding || format.step != format_.step) {  // a driver that changes its rows
     if (int rc = lfvio_image_format_set(ctx_, &format)) return status = rc;
     format_ = format;
   }
-  const unsigned char *image = pixels;  // height rows of step bytes: no repacking on the host
+  const unsigned char *image = pixels;  // height rows of step bytes: no repacking on the host (with expand: the SOURCE image)
   const bool pub = gate.publish;
   const int S = cfg_.num_samples;
   if (pub) {  // num_samples x 8 raw outputs of the generator, row-major; nothing is drawn for a frame that is only tracked
@@ -91,7 +109,7 @@ int FeatureTracker::onImage(double stamp, int width, int height, int step, int e
     for (unsigned &w : words_) w = (unsigned)rng_();
   }
   LfvioTrackFrameIn in = {};
-  in.width = width, in.height = height, in.image = image, in.time = stamp, in.publish = pub ? 1 : 0, in.camera = &cfg_.camera;
+  in.width = tw, in.height = th, in.image = image, in.time = stamp, in.publish = pub ? 1 : 0, in.camera = &cfg_.camera;
   in.win_size = 41, in.max_level = 3, in.max_iterations = 30, in.epsilon = 0.01, in.min_eig_threshold = 1e-4, in.border = 1;  // feature_tracker.cpp:127
   in.max_count = cfg_.max_cnt, in.quality_level = 0.01, in.min_distance = cfg_.min_dist, in.mask_radius = cfg_.min_dist;  // :60-75, :157
   in.num_samples = S, in.sample_words = pub ? words_.data() : nullptr, in.capacity = LFVIO_TRACK_MAX_POINTS;

@@ -2,7 +2,8 @@
 // device call per image, lfvio_track_frame_message (include/lfvio.h), which runs readImage, updateID and the feature message on a
 // track table resident in the context.  What is left here is the node's bookkeeping (image_gate.h), the base mask, the CLAHE setting and
 // the image format (lfvio_image_format_set: the record's rows go up as they are, padded, colour or 16-bit, and the device makes grey
-// of them) at the first use, and the generator of rejectWithF's sample sets.
+// of them) at the first use, where asked for the map of the expanded image and lfvio_track_source_set beside them, and the generator
+// of rejectWithF's sample sets.
 // Not compiled into the test suite's CPU build of the host sources (oracle/Makefile): only host/Makefile builds it.
 #pragma once
 #include <random>
@@ -29,6 +30,17 @@ struct TrackerConfig {
   double center_x = 0, center_y = 0, max_r = 0, min_r = 0;
   int num_samples = 100;     // rejectWithF's sample sets
   unsigned ransac_seed = 0;  // 0: seeded from std::random_device, as Config::ransac_seed
+  // Track on the EXPANDED image (the launch files' remap of pointcloud_image_fusion's equal_rectangle_img onto /camera/image_raw;
+  // lfvio_track_source_set): the records stay the raw source images, the map through the SOURCE camera is built at the first image,
+  // and `camera` above is then the camera of the width x height image that is tracked — LFVIO_CAM_EQUIRECT for kind
+  // LFVIO_MAP_EQUIRECT, a distortion-free LFVIO_CAM_PINHOLE for LFVIO_MAP_PERSPECTIVE — whose size the base mask has too
+  struct Expand {
+    bool on = false;
+    int kind = LFVIO_MAP_EQUIRECT, width = 0, height = 0;
+    double M[9] = {};                                  // PERSPECTIVE only
+    LfvioCamera src_camera = {};                       // the source camera's LfvioProjector values
+    double inv_poly[LFVIO_OCAM_INV_POLY_SIZE] = {};
+  } expand;
 };
 
 class FeatureTracker {
@@ -58,6 +70,7 @@ class FeatureTracker {
   bool own_ = false, ready_ = false;
   std::mt19937 rng_;
   LfvioImageFormat format_ = {LFVIO_IMG_MONO8, 0};  // what the context's format was last set to (ready_)
+  LfvioTrackSource source_ = {0, 0};                // ... and, with cfg_.expand.on, its source
   std::vector<unsigned> words_;
   std::vector<float> pts_, un_pts_, un_pts_3d_, velocity_3d_, rows_;
   std::vector<int> ids_, track_cnt_;

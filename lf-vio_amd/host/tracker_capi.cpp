@@ -40,6 +40,19 @@ void lfvio_host_track_config(const LfvioCamera *camera, const int *iv, const dou
   }
 }
 
+// Track on the expanded image (TrackerConfig::expand, feature_tracker.h): src: the SOURCE camera's projector, or null: off; kind
+// LFVIO_MAP_EQUIRECT or LFVIO_MAP_PERSPECTIVE with M[9] (null: zeros); width x height: the image that is tracked, whose camera and
+// base mask lfvio_host_track_config then names.  Call it BEHIND lfvio_host_track_config, which starts from a fresh TrackerConfig.
+void lfvio_host_track_expand(const LfvioProjector *src, int kind, int width, int height, const double *M) {
+  TrackerConfig::Expand &x = trackerConfig().expand;
+  x = TrackerConfig::Expand();
+  if (!src || !src->camera) return;
+  x.on = true, x.kind = kind, x.width = width, x.height = height;
+  if (M) std::memcpy(x.M, M, sizeof x.M);
+  x.src_camera = *src->camera;
+  std::memcpy(x.inv_poly, src->inv_poly, sizeof x.inv_poly);
+}
+
 // "Pre-track a bag": the recording in_path with every raw image (record type 10) replaced by what a fresh FeatureTracker on the
 // estimator's context emitted for it, every other record copied.  track_stats[7] (or null) = {raw images, dropped, restarts, tracked
 // only, published, rows in total, milliseconds in the tracker}.  0; -1 cannot write; -2 a device call failed; -3 unreadable or refused.

@@ -702,15 +702,18 @@ class TrackUndistortInC(C.Structure):
 CAM_OCAM, TRACK_MAX_POINTS = 0, 4096  # LFVIO_CAM_OCAM, LFVIO_TRACK_MAX_POINTS
 CAM_PINHOLE, CAM_MEI = 2, 3  # LFVIO_CAM_PINHOLE, LFVIO_CAM_MEI
 CAM_KANNALA_BRANDT = 5  # LFVIO_CAM_KANNALA_BRANDT
+CAM_EQUIRECT = 6  # LFVIO_CAM_EQUIRECT: the lift only; fx, fy = the expanded image's width, height
 
 
 def camera_c(cam):
     """A CameraC from a camera dict.  model (optional) LFVIO_CAM_OCAM: cx, cy, c, d, e, poly [5]; LFVIO_CAM_PINHOLE: cx, cy, fx, fy,
     k1, k2, p1, p2; LFVIO_CAM_MEI: those (u0, v0, gamma1, gamma2 under cx, cy, fx, fy) and xi; LFVIO_CAM_KANNALA_BRANDT: cx, cy, fx, fy
-    (u0, v0, mu, mv) and k2, k3, k4, k5, which go into poly[0 .. 3] and NOT into the struct's k1, k2.  The fields of the other
-    models may be left out (zero)."""
+    (u0, v0, mu, mv) and k2, k3, k4, k5, which go into poly[0 .. 3] and NOT into the struct's k1, k2; LFVIO_CAM_EQUIRECT: fx, fy, the
+    expanded image's width and height.  The fields of the other models may be left out (zero)."""
     g = lambda k: float(cam.get(k, 0.0))
     model = int(cam.get("model", CAM_OCAM))
+    if model == CAM_EQUIRECT:  # fx, fy (the image's width and height) alone
+        return CameraC(model, g("cx"), g("cy"), 0.0, 0.0, 0.0, (C.c_double * 5)(), g("fx"), g("fy"))
     if model == CAM_KANNALA_BRANDT:
         return CameraC(model, cam["cx"], cam["cy"], 0.0, 0.0, 0.0, (C.c_double * 5)(g("k2"), g("k3"), g("k4"), g("k5"), 0.0), g("fx"), g("fy"))
     return CameraC(model, cam["cx"], cam["cy"], g("c"), g("d"), g("e"), (C.c_double * 5)(*[float(v) for v in cam.get("poly", (0.0,) * 5)]),
@@ -738,6 +741,11 @@ def projector_c(cam):
     cc = cam if isinstance(cam, CameraC) else camera_c(cam)
     inv = [float(v) for v in (() if isinstance(cam, CameraC) else cam.get("inv_poly", ()))]
     return ProjectorC(C.pointer(cc), (C.c_double * OCAM_INV_POLY_SIZE)(*inv)), cc
+
+
+class TrackSourceC(C.Structure):
+    """LfvioTrackSource (include/lfvio.h)."""
+    _fields_ = [("src_width", C.c_int), ("src_height", C.c_int)]
 
 
 FUSE_EQUIRECT, FUSE_CAMERA = 0, 1  # LFVIO_FUSE_*
@@ -837,6 +845,7 @@ HIP_SYMBOLS = [
     "lfvio_track_reject", "lfvio_track_undistort", "lfvio_track_reset", "lfvio_track_frame", "lfvio_track_frame_reset",
     "lfvio_track_frame_message",
     "lfvio_cam_project", "lfvio_remap_build", "lfvio_remap_apply", "lfvio_remap_reset", "lfvio_cloud_fuse",
+    "lfvio_track_source_set",
     "lfvio_track_batch_reserve", "lfvio_track_batch_set_mask", "lfvio_track_batch_clahe", "lfvio_track_batch_frame", "lfvio_track_batch_reset",
     "lfvio_group_create", "lfvio_group_unique_id", "lfvio_group_create_rank", "lfvio_group_create_local", "lfvio_group_destroy",
     "lfvio_group_last_error", "lfvio_group_size", "lfvio_group_local", "lfvio_group_rank", "lfvio_group_ctx", "lfvio_group_backend",
@@ -932,6 +941,8 @@ def load_hip_library(path=None):
         lib.lfvio_remap_build.argtypes = [C.c_void_p, C.POINTER(RemapInC), C.POINTER(C.c_float), C.POINTER(C.c_float)]
         lib.lfvio_remap_apply.argtypes = [C.c_void_p, C.POINTER(ImageFormatC), C.c_int, C.c_int] + [C.POINTER(C.c_ubyte)] * 2
         lib.lfvio_remap_reset.argtypes = [C.c_void_p]
+    if hasattr(lib, "lfvio_track_source_set"):
+        lib.lfvio_track_source_set.argtypes = [C.c_void_p, C.POINTER(TrackSourceC)]
     if hasattr(lib, "lfvio_cloud_fuse"):
         lib.lfvio_cloud_fuse.argtypes = [C.c_void_p, C.POINTER(FuseInC), C.POINTER(FuseOutC)]
     if hasattr(lib, "lfvio_track_reject"):

@@ -754,6 +754,16 @@ class Engine:
         """lfvio_remap_reset: forget the resident map."""
         self._check(self.lib.lfvio_remap_reset(self.ctx), "lfvio_remap_reset")
 
+    def track_source(self, src_width=None, src_height=None, check=True):
+        """lfvio_track_source_set: the image of every later klt_track / track_frame / track_frame_message is the SOURCE image —
+        src_height rows of src_width pixels in the encoding and step of image_format(), a uint8 array [src_height, step] — and level 0
+        is gathered from it through the resident map of remap_build, whose size the calls' size / params width and height must name.
+        track_source(None): off, the state of a fresh context.  Returns the error code."""
+        rc = self.lib.lfvio_track_source_set(self.ctx, None if src_width is None else C.byref(abi.TrackSourceC(src_width, src_height)))
+        if check:
+            self._check(rc, "lfvio_track_source_set")
+        return rc
+
     FUSE_OUTPUTS = ("index", "range", "colour", "image_out", "counts")
 
     def cloud_fuse(self, cloud, n, point_step, offs, width, height, kind=abi.FUSE_EQUIRECT, big_endian=0, R=None, T=None, min_range=0.0,
@@ -804,7 +814,7 @@ class Engine:
     def camera(cam):
         """A CameraC from a dict; None: a null pointer.  model (optional) LFVIO_CAM_OCAM: cx, cy, c, d, e, poly [5];
         LFVIO_CAM_PINHOLE: cx, cy, fx, fy, k1, k2, p1, p2; LFVIO_CAM_MEI: those (u0, v0, gamma1, gamma2 under cx, cy, fx, fy) and xi;
-        LFVIO_CAM_KANNALA_BRANDT: cx, cy, fx, fy (u0, v0, mu, mv), k2, k3, k4, k5 (abi.camera_c).
+        LFVIO_CAM_KANNALA_BRANDT: cx, cy, fx, fy (u0, v0, mu, mv), k2, k3, k4, k5; LFVIO_CAM_EQUIRECT: fx, fy (abi.camera_c).
         The fields of the other models may be left out (zero)."""
         if cam is None or isinstance(cam, abi.CameraC):
             return cam

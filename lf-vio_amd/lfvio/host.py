@@ -82,6 +82,9 @@ class HostEstimator:
         if self.has_tracker:
             L.lfvio_host_track_config.argtypes = [C.POINTER(abi.CameraC), ip, _dp, C.c_int, C.c_int, C.POINTER(C.c_ubyte)]
             L.lfvio_host_track_config.restype = None
+            if hasattr(L, "lfvio_host_track_expand"):
+                L.lfvio_host_track_expand.argtypes = [C.POINTER(abi.ProjectorC), C.c_int, C.c_int, C.c_int, _dp]
+                L.lfvio_host_track_expand.restype = None
             L.lfvio_host_track_trace.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, _dp]
             L.lfvio_host_replay_images.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_int, ip, _dp]
             L.lfvio_host_trace_raw_images.argtypes = [C.c_char_p, C.c_int, _dp, C.c_char_p, C.c_int]
@@ -231,6 +234,20 @@ class HostEstimator:
         self.L.lfvio_host_track_config(C.byref(camc), iv.ctypes.data_as(C.POINTER(C.c_int)), None if an is None else _p(an),
                                        0 if m is None else m.shape[1], 0 if m is None else m.shape[0],
                                        None if m is None else m.ctypes.data_as(C.POINTER(C.c_ubyte)))
+
+    def track_expand(self, src_cam, kind=abi.MAP_EQUIRECT, width=0, height=0, M=None):
+        """lfvio_host_track_expand, BEHIND track_config: the next track_trace / replay_images tracks on the width x height image expanded
+        from the records' raw images through the SOURCE camera src_cam (a dict as Engine.projector takes: an OCam camera with its
+        inv_poly) — kind abi.MAP_EQUIRECT, or abi.MAP_PERSPECTIVE with M [3, 3].  track_config's camera is then the expanded image's
+        (abi.CAM_EQUIRECT with fx, fy = width, height for MAP_EQUIRECT) and its mask of that size.  src_cam None: off."""
+        self._tracker()
+        if src_cam is None:
+            self.L.lfvio_host_track_expand(None, 0, 0, 0, None)
+            return
+        proj, keep = abi.projector_c(src_cam)
+        m = None if M is None else _f(np.asarray(M, dtype=np.float64).reshape(9))
+        self.L.lfvio_host_track_expand(C.byref(proj), int(kind), int(width), int(height), None if m is None else _p(m))
+        del keep
 
     def track_trace(self, in_path, out_path):
         """lfvio_host_track_trace: the recording with its raw images (type 10) replaced by what the tracker published for them.
