@@ -1039,7 +1039,8 @@ int lfvio_remap_reset(lfvio_ctx *ctx);   /* forget the resident maps */
  * distortion-free LFVIO_CAM_PINHOLE for an LFVIO_MAP_PERSPECTIVE one.  The integer map is shared with lfvio_remap_apply and
  * lfvio_cloud_fuse: each rebuilds it when it finds it written for another source geometry, so they may alternate.
  * src == NULL: off.  Off after lfvio_create; survives lfvio_klt_reset, lfvio_track_frame_reset and lfvio_remap_reset.  The batched
- * route (lfvio_track_batch_*) does not look at the setting: its images are the tracked images (a map per slot is a later step).
+ * route (lfvio_track_batch_*) does not look at this setting or at the resident map: it has a setting of its own
+ * (lfvio_track_batch_source) and a map per slot (lfvio_track_batch_map), below.
  * LFVIO_ERR_ARG: at the set call (the setting untouched) src_width or src_height outside [16, 8192]; at the tracker call, before
  * anything is touched (the resident pyramid, the track table, the maps and the stream as they were): no resident map (never built, or
  * after lfvio_remap_reset), a resident map of another size than in->width x in->height, and what lfvio_image_format_set's check
@@ -1226,7 +1227,32 @@ int lfvio_track_frame_message(lfvio_ctx *ctx, const LfvioTrackFrameIn *in, Lfvio
  *                               ATOMIC over the batch: a refused call (LFVIO_ERR_ARG), a call that fails later and a call that
  *                               reads a count from the device beyond its bound leave every out, every msg and every slot untouched;
  *                               the double buffers of all active slots are swapped only after the one download has been checked.
- *   lfvio_track_batch_reset     lfvio_track_frame_reset for one slot, or for every slot with slot = -1 (the base masks stay).
+ *   lfvio_track_batch_reset     lfvio_track_frame_reset for one slot, or for every slot with slot = -1 (the base masks and the maps
+ *                               stay).
+ *   lfvio_track_batch_map       lfvio_remap_build for one slot, or for every slot with slot = -1 (the same recipe in each, one launch):
+ *                               the slot's resident remap, built on the device, with lfvio_remap_build's checks.  The maps are the
+ *                               batch's own: no batch call reads or writes the context's resident map, and lfvio_remap_*,
+ *                               lfvio_cloud_fuse and the single route never touch a slot's.  Slots may hold maps of different kinds,
+ *                               cameras, M and sizes.  in NULL: the slot's map (or every map) is forgotten.  After
+ *                               lfvio_track_batch_reserve no slot has a map.  12 bytes per output pixel and slot, every slot with the
+ *                               capacity of the largest map built; an allocation that fails is LFVIO_ERR_DEVICE and leaves the
+ *                               previous maps usable.
+ *   lfvio_track_batch_source    lfvio_track_source_set for the batch: one setting for every slot; it survives reserve and reset.
+ *                               NULL: off.  src_width or src_height outside [16, 8192]: LFVIO_ERR_ARG, the setting untouched.  While
+ *                               it is on, every active in[i].image of lfvio_track_batch_frame is the SOURCE image — src_height rows
+ *                               of `step` bytes in the encoding of lfvio_track_batch_format (mono8 with contiguous rows while that is
+ *                               off) — and level 0 of slot i's fresh pyramid is gathered from it through slot i's own map, all slots
+ *                               in one launch (k_remap_gray_b); width and height stay the size that is TRACKED and stay under the
+ *                               agreement rule.  THE CONTRACT then reads: slot i equals, bit for bit (outputs, message and every
+ *                               pyramid level), a fresh context given lfvio_remap_build with slot i's recipe, lfvio_image_format_set
+ *                               and lfvio_track_source_set with the batch's settings, and slot i's active frames.  The frame call
+ *                               is refused (LFVIO_ERR_ARG, atomically as above: every out, msg, slot and map as it was) when an
+ *                               active slot has no map, when an active slot's map is of another size than width x height, and for
+ *                               what lfvio_track_batch_format's check refuses beside src_width x src_height (0 < step < src_width *
+ *                               bytes per pixel).  Idle slots need no map.  The source geometry (width, height, step, bytes per
+ *                               pixel) is the batch's: a frame call of another geometry than the last rewrites the integer maps of
+ *                               all mapped slots in one launch first; a steady stream never does.
+ *   lfvio_track_batch_level     lfvio_klt_level for one slot: level `level` of slot's resident pyramid.
  * LFVIO_ERR_ARG besides: a slot index outside [-1, slots), any call but reserve with no slots reserved.  The calls run on the feature
  * stream like lfvio_track_frame: they do not wait for an optimization in flight.   */
 #define LFVIO_TRACK_BATCH_MAX_SLOTS 64
@@ -1237,6 +1263,9 @@ int lfvio_track_batch_format(lfvio_ctx *ctx, const LfvioImageFormat *fmt /* NULL
 int lfvio_track_batch_frame(lfvio_ctx *ctx, int count, const LfvioTrackFrameIn *in /* [count] */, LfvioTrackFrameOut *out /* [count] */,
                             LfvioTrackMessage *msg /* [count], or NULL */);
 int lfvio_track_batch_reset(lfvio_ctx *ctx, int slot /* -1: every slot */);
+int lfvio_track_batch_map(lfvio_ctx *ctx, int slot /* -1: every slot */, const LfvioRemapIn *in /* NULL: forget */);
+int lfvio_track_batch_source(lfvio_ctx *ctx, const LfvioTrackSource *src /* NULL: off */);
+int lfvio_track_batch_level(lfvio_ctx *ctx, int slot, int level, int *width, int *height, unsigned char *pixels /* or NULL: the size alone */);
 
 /* ---- landmark-sharded API (multi-GPU) ------------------------
  * Every rank passes the same window but linearizes only landmarks [lm_begin, lm_end) (caller order);

@@ -35,7 +35,9 @@ struct RemapBuildArgs {  // by value
   RemapGeom g;  // bpp 0: no integer map yet
 };
 
-__global__ __launch_bounds__(REMAP_THREADS) void k_remap_build(RemapBuildArgs a, float *__restrict__ map_x, float *__restrict__ map_y, int *__restrict__ imap) {
+// The bodies of k_remap_build and k_remap_index: the kernels below and their *_b entries (kernels_trackbatch.h: a slot of the batched
+// route in blockIdx.z) run them.
+DEV void remap_build_body(const RemapBuildArgs &a, float *__restrict__ map_x, float *__restrict__ map_y, int *__restrict__ imap) {
   const int i = blockIdx.x * REMAP_TILE_W + (threadIdx.x % REMAP_TILE_W), j = blockIdx.y * REMAP_TILE_H + (threadIdx.x / REMAP_TILE_W);
   if (i >= a.width || j >= a.height) return;
   const RemapEntry e = remap_entry(a.cam, a.kind, a.width, a.height, a.M, i, j);
@@ -43,12 +45,19 @@ __global__ __launch_bounds__(REMAP_THREADS) void k_remap_build(RemapBuildArgs a,
   map_x[p] = e.x, map_y[p] = e.y;
   if (a.g.bpp) imap[p] = remap_offset(e.x, e.y, a.g);
 }
-
-__global__ __launch_bounds__(REMAP_THREADS) void k_remap_index(RemapGeom g, size_t pixels, const float *__restrict__ map_x, const float *__restrict__ map_y,
-                                                               int *__restrict__ imap) {
+DEV void remap_index_body(const RemapGeom &g, size_t pixels, const float *__restrict__ map_x, const float *__restrict__ map_y, int *__restrict__ imap) {
   const size_t p = (size_t)blockIdx.x * REMAP_THREADS + threadIdx.x;
   if (p >= pixels) return;
   imap[p] = remap_offset(map_x[p], map_y[p], g);
+}
+
+__global__ __launch_bounds__(REMAP_THREADS) void k_remap_build(RemapBuildArgs a, float *__restrict__ map_x, float *__restrict__ map_y, int *__restrict__ imap) {
+  remap_build_body(a, map_x, map_y, imap);
+}
+
+__global__ __launch_bounds__(REMAP_THREADS) void k_remap_index(RemapGeom g, size_t pixels, const float *__restrict__ map_x, const float *__restrict__ map_y,
+                                                               int *__restrict__ imap) {
+  remap_index_body(g, pixels, map_x, map_y, imap);
 }
 
 template <int BPP>

@@ -17,8 +17,10 @@
 #pragma once
 #include "kernels_clahe.h"
 #include "kernels_imgfmt.h"
+#include "kernels_remap.h"
 #include "kernels_trackframe.h"
-#include "trackbatch_plan.h"
+#include "kernels_tracksource.h"
+#include "trackbatch_source_plan.h"
 
 constexpr int TB_COPY_THREADS = 256, TB_COPY_BYTES = TB_COPY_THREADS * 16;
 
@@ -79,7 +81,46 @@ __global__ __launch_bounds__(IMG_THREADS) void k_img_gray_b(const TbSlot *slots,
   img_gray_body(code, s.image, step, s.fresh, W, H);
 }
 
-// ---- CLAHE: the staged image (from_fresh: the grey image k_img_gray_b left at level 0) into level 0 of the fresh pyramid
+// ---- the slots' resident remaps (lfvio_track_batch_map / lfvio_track_batch_source).  A slot's maps lie at m.maps +
+// slot * m.maps_stride: [map_x | map_y at maps_y_at | the integer map at maps_index_at] (TbMaps, trackbatch_plan.h, which states the
+// alignment the int4 load and the dword store rest on).
+//   k_remap_gray_b : where k_img_gray_b / k_tb_image stand while the setting is on — the staged SOURCE image gathered through the
+//                    slot's own integer map into grey at level 0 of its fresh pyramid (remap_gray_body, kernels_tracksource.h).
+//                    Grid remap_apply_blocks(W * H) x 1 x slots.  Bounds: every entry of an active slot's integer map was written for
+//                    the staged images' geometry (the host rebuilds them first where it was not), so offset + BPP <= src_height *
+//                    step, the bytes of one staged image; W * H pixels is the size of every active slot's map (the call's check).
+//   k_remap_build_b: k_remap_build for slots first .. first + gridDim.z - 1, the same recipe in each: one launch for slot = -1.
+//                    There are no descriptors on the device outside a frame: the slot is first + blockIdx.z.
+//   k_remap_index_b: the integer maps of ALL mapped slots (map_px != 0 in the descriptor, idle ones too) from their float maps for
+//                    another source geometry, in one launch; grid.x covers the largest map, a lane past its own slot's returns.
+template <int BPP>
+__global__ __launch_bounds__(REMAP_THREADS) void k_remap_gray_b(const TbSlot *slots, TbMem m, TbStage o, int code, size_t pixels) {
+  const TbView s = tb_view(slots, m, o);
+  if (!s.active) return;
+  remap_gray_body<BPP>(code, (const int *)(m.maps + (size_t)blockIdx.z * m.maps_stride + m.maps_index_at), s.image, s.fresh, pixels);
+}
+__global__ __launch_bounds__(REMAP_THREADS) void k_remap_build_b(RemapBuildArgs a, TbMem m, int first) {
+  char *maps = m.maps + ((size_t)first + blockIdx.z) * m.maps_stride;
+  remap_build_body(a, (float *)maps, (float *)(maps + m.maps_y_at), (int *)(maps + m.maps_index_at));
+}
+__global__ __launch_bounds__(REMAP_THREADS) void k_remap_index_b(const TbSlot *slots, TbMem m, RemapGeom g) {
+  const int px = slots[blockIdx.z].map_px;
+  if (!px) return;
+  char *maps = m.maps + (size_t)blockIdx.z * m.maps_stride;
+  remap_index_body(g, (size_t)px, (const float *)maps, (const float *)(maps + m.maps_y_at), (int *)(maps + m.maps_index_at));
+}
+// code: one of image_format.h's table (the host has checked it)
+inline void remap_gray_b_launch(hipStream_t fs, unsigned slots_z, const TbSlot *slots, const TbMem &m, const TbStage &o, int code, size_t pixels) {
+  const dim3 grid(remap_apply_blocks(pixels), 1, slots_z), block(REMAP_THREADS);
+  switch (imgfmt_bpp(code)) {
+    case 1: hipLaunchKernelGGL(k_remap_gray_b<1>, grid, block, 0, fs, slots, m, o, code, pixels); break;
+    case 2: hipLaunchKernelGGL(k_remap_gray_b<2>, grid, block, 0, fs, slots, m, o, code, pixels); break;
+    case 3: hipLaunchKernelGGL(k_remap_gray_b<3>, grid, block, 0, fs, slots, m, o, code, pixels); break;
+    default: hipLaunchKernelGGL(k_remap_gray_b<4>, grid, block, 0, fs, slots, m, o, code, pixels); break;
+  }
+}
+
+// ---- CLAHE: the staged image (from_fresh: the grey image k_img_gray_b or k_remap_gray_b left at level 0) into level 0 of the fresh pyramid
 __global__ __launch_bounds__(CLAHE_THREADS) void k_clahe_hist_b(const TbSlot *slots, TbMem m, TbStage o, int from_fresh, int W, int H, int tiles_x, int tw, int th) {
   const TbView s = tb_view(slots, m, o);
   if (!s.active) return;

@@ -18,9 +18,9 @@
 #include "image_format.h"
 #include "remap_plan.h"
 
+// The body: k_remap_gray below and k_remap_gray_b (kernels_trackbatch.h: a slot of the batched route in blockIdx.z) run it.
 template <int BPP>
-__global__ __launch_bounds__(REMAP_THREADS) void k_remap_gray(int code, const int *__restrict__ imap, const unsigned char *__restrict__ src,
-                                                              unsigned char *__restrict__ level0, size_t pixels) {
+DEV void remap_gray_body(int code, const int *__restrict__ imap, const unsigned char *__restrict__ src, unsigned char *__restrict__ level0, size_t pixels) {
   constexpr int NB = BPP < 3 ? BPP : 3;
   const size_t p0 = ((size_t)blockIdx.x * REMAP_THREADS + threadIdx.x) * REMAP_RUN;
   if (p0 >= pixels) return;
@@ -47,6 +47,11 @@ __global__ __launch_bounds__(REMAP_THREADS) void k_remap_gray(int code, const in
       level0[p] = (unsigned char)imgfmt_gray(code, b[0], b[1], b[2]);
     }
   }
+}
+template <int BPP>
+__global__ __launch_bounds__(REMAP_THREADS) void k_remap_gray(int code, const int *__restrict__ imap, const unsigned char *__restrict__ src,
+                                                              unsigned char *__restrict__ level0, size_t pixels) {
+  remap_gray_body<BPP>(code, imap, src, level0, pixels);
 }
 
 // code: one of image_format.h's table (the host has checked it); imap: written for this source's geometry

@@ -240,6 +240,15 @@ struct lfvio_ctx : CtxQueues {
     bool clahe_on = false, clahe_dirty = false;
     LfvioClaheIn cfg = {};
     ImageFormatState imgfmt;  // lfvio_track_batch_format: the batch's, one for every slot
+    // lfvio_track_batch_map / lfvio_track_batch_source: per slot what its resident remap is, and the maps themselves —
+    // per slot [map_x | map_y | integer map] with the capacities of `mlay`, allocated at the first build, grown for a larger output;
+    // `indexed`: the ONE source geometry every mapped slot's integer map is written for.  None of it is RemapState's above.
+    std::vector<TbMapInfo> map;
+    DevBuf<char> maps;
+    TbMaps mlay = {0};
+    TbIndexed indexed;
+    TrackSourceState source;  // lfvio_track_batch_source: the batch's, one for every slot; survives reserve and reset
+    KbCache map_kb;
   } tbatch;
   std::string err;
   int batch = 0;

@@ -1,11 +1,13 @@
 // trackbatch_plan.h — the host side of the lfvio_track_batch_* calls (include/lfvio.h) that needs no device: the argument check of
 // every batch call (trackframe_check per active entry, then the agreement rule), the bounds the host sizes grids and segments by,
-// the slot's descriptor as the kernels read it, the layout of the staging block as plain functions that return offsets, and the
-// bytes one slot owns at a given image size.  Plain C++ (no HIP): trackbatch.inc uses it, tests/test_track_batch_ref.py compiles it
-// alone with g++ and tests/tools/track_batch_plan_walk.cpp walks it under the CPU sanitizers.
+// the slot's descriptor as the kernels read it, the layout of the staging block as plain functions that return offsets, the bytes
+// one slot owns at a given image size, and the layout of a slot's resident remap (TbMaps; trackbatch_source_plan.h uses it).
+// Plain C++ (no HIP): trackbatch.inc uses it, tests/test_track_batch_ref.py compiles it alone with g++ and
+// tests/tools/track_batch_plan_walk.cpp walks it under the CPU sanitizers.
 #pragma once
 #include <algorithm>
 #include <cstddef>
+#include <initializer_list>
 
 #include "track_stream.h"
 #include "trackframe_plan.h"
@@ -22,6 +24,13 @@ inline const char *trackbatch_reserve_check(int slots) {
 inline const char *trackbatch_slot_check(int slot, int slots) {
   if (slots < 1) return "lfvio_track_batch: no slots reserved";
   if (slot < -1 || slot >= slots) return "lfvio_track_batch: slot outside [-1, slots)";
+  return nullptr;
+}
+
+// lfvio_track_batch_level: one slot (never -1), a resident image in it, a level that some call has built
+inline const char *trackbatch_level_check(int slot, int slots, bool resident, int level, int built) {
+  if (slot < 0 || slot >= slots) return "lfvio_track_batch_level: slot outside [0, slots)";
+  if (!resident || level < 0 || level > built) return "lfvio_track_batch_level: no resident image, or a level that is not built";
   return nullptr;
 }
 
@@ -72,8 +81,9 @@ inline TbBounds trackbatch_bounds(int count, const LfvioTrackFrameIn *in, const 
 }
 
 // ---- the slot as the kernels read it: one entry per slot of the device array at the head of the staging block.  Uniform over a
-// workgroup (blockIdx.z picks it); an entry with active == 0 holds nothing else.  It holds numbers only: WHERE a slot's memory lies
-// follows from the slot's index and TbMem, a kernel argument, so that every pointer a kernel forms starts at a pointer argument.
+// workgroup (blockIdx.z picks it); an entry with active == 0 holds nothing else but map_px.  It holds numbers only: WHERE a slot's
+// memory lies follows from the slot's index and TbMem, a kernel argument, so that every pointer a kernel forms starts at a pointer
+// argument.
 struct TbSlot {
   int active, publish;
   int n0;          // entries of the resident table
@@ -84,7 +94,7 @@ struct TbSlot {
   int pcur, tcur, mcur;  // which of the two pyramid buffers, tables and maps is the resident one; the call writes the other
   int masked;      // a base mask is set
   int image_k, words_k;  // the slot's image among the active slots' and its words among the publishing slots' in the staging block
-  int pad;
+  int map_px;      // pixels of the slot's resident remap (lfvio_track_batch_map), 0: none.  Filled for idle slots too (k_remap_index_b)
   double dt;       // time - the previous call's
   TrackCam cam;
 };
@@ -99,6 +109,8 @@ struct TbMem {  // the bases and strides of the slots' memory
   char *stage, *fixed, *image, *clahe;  // the staging block; per slot: tables and maps | [pyramid | pyramid | mask | work] | CLAHE table and LUTs
   size_t image_stride, pyr, mask_at, work_at, clahe_stride;
   size_t words_at, words_stride, images_at, images_stride;  // in the staging block
+  char *maps;                                                // per slot: [map_x | map_y | integer map] (TbMaps below); nullptr: no slot has a map
+  size_t maps_stride, maps_y_at, maps_index_at;
 };
 
 // ---- the staging block: [descriptors | words of the publishing slots | images of the active slots] goes up; every slot has a segment
@@ -179,3 +191,37 @@ inline TbImage trackbatch_image_grown(const TbImage &have, const TbImage &need) 
   return TbImage{std::max(have.pyr, need.pyr), std::max(have.mask, need.mask), std::max(have.work, need.work)};
 }
 inline size_t trackbatch_slot_bytes(int width, int height, size_t work_bytes) { return TB_FIXED_BYTES + trackbatch_image(width, height, work_bytes).stride(); }
+
+// ---- the slot's resident remap (lfvio_track_batch_map): the two float maps and the integer map of a width x height OUTPUT image, 12
+// bytes per output pixel, [map_x | map_y | integer map] with every plane's capacity `px` pixels — the largest output any slot's map
+// was built for; the planes keep their capacity when a smaller map follows.
+// ALIGNMENT, stated here and checked by trackbatch_maps_aligned / trackbatch_level0_aligned: k_remap_gray_b loads the integer map
+// sixteen bytes at a time and stores level 0 a dword at a time.  Every plane is tb_align'ed and so is the stride, and the block is an
+// allocation of its own (256-aligned), so every slot's integer map starts 256-aligned; level 0 of either pyramid buffer starts at
+// slot * TbImage::stride() + which * pyr, multiples of TB_ALIGN as well.  The source image is read by bytes: its place in the staging
+// block and its step need no alignment.
+struct TbMaps {
+  size_t px;  // capacity of a plane, in pixels
+  size_t plane() const { return tb_align(px * 4); }
+  size_t x_at() const { return 0; }
+  size_t y_at() const { return plane(); }
+  size_t index_at() const { return 2 * plane(); }
+  size_t stride() const { return 3 * plane(); }
+};
+inline TbMaps trackbatch_maps(int width, int height) { return TbMaps{(size_t)width * (size_t)height}; }
+inline bool trackbatch_maps_covers(const TbMaps &have, const TbMaps &need) { return have.px >= need.px; }
+inline TbMaps trackbatch_maps_grown(const TbMaps &have, const TbMaps &need) { return TbMaps{std::max(have.px, need.px)}; }
+// every slot's integer map 256-aligned behind a 256-aligned base, the float maps with it
+inline bool trackbatch_maps_aligned(const TbMaps &m, int slots) {
+  for (int i = 0; i < slots; i++)
+    for (size_t at : {m.x_at(), m.y_at(), m.index_at()})
+      if (((size_t)i * m.stride() + at) % TB_ALIGN) return false;
+  return true;
+}
+// level 0 of either pyramid buffer of every slot 4-aligned behind a 256-aligned base
+inline bool trackbatch_level0_aligned(const TbImage &lay, int slots) {
+  for (int i = 0; i < slots; i++)
+    for (int which = 0; which < 2; which++)
+      if (((size_t)i * lay.stride() + lay.pyr_at(which)) % 4) return false;
+  return true;
+}

@@ -1,8 +1,12 @@
 // tracker_capi.cpp — extern "C" driver of the image route (feature_tracker.h, image_replay.h), beside host_capi.cpp and apart from it:
 // the test suite's CPU build of the host sources (oracle/Makefile) links no tracker, so nothing in the three older sources refers to
 // anything here.  Only host/Makefile compiles this file.
+#include <cstdio>
 #include <cstring>
+#include <string>
+#include <vector>
 
+#include "batch_tracker.h"
 #include "feature_tracker.h"
 #include "image_replay.h"
 #include "window_estimator.h"
@@ -13,6 +17,10 @@ namespace {
 TrackerConfig &trackerConfig() {  // process-wide, like Config
   static TrackerConfig c;
   return c;
+}
+std::string &tracesError() {  // of the last lfvio_host_track_traces
+  static std::string s;
+  return s;
 }
 inline WindowEstimator *E(void *h) { return (WindowEstimator *)h; }
 void give(double *dst, const TrackStats &st) {
@@ -65,6 +73,47 @@ int lfvio_host_track_trace(void *h, const char *in_path, const char *out_path, d
   give(track_stats, st);
   return rc;
 }
+
+// Several recordings through ONE batched tracker call per round (batch_tracker.h): round r takes the r-th raw image of every
+// recording that still has one, recording i is slot i of the estimator's context.  Every out_paths[i] is, byte for byte, what
+// lfvio_host_track_trace writes for in_paths[i] alone under the same lfvio_host_track_config / lfvio_host_track_expand.
+// track_stats[n][7] (or null) as above, per recording (milliseconds: of the rounds the recording took part in).  n in [1, 64].
+// 0; -1 cannot write; -2 a device call failed; -3 unreadable, refused, or n outside [1, 64]; -4 the images of a round that reach the
+// tracker disagree in width, height, step or encoding.  On anything but 0 NO file is written, and lfvio_host_track_traces_error()
+// says why.  Afterwards the estimator's context has no batch reserved and the batch's source, format and CLAHE settings are off.
+int lfvio_host_track_traces(void *h, int n, const char *const *in_paths, const char *const *out_paths, double *track_stats) {
+  std::string &why = tracesError();
+  why.clear();
+  WindowEstimator *e = E(h);
+  if (!e->device()) {
+    why = "no device";
+    return -2;
+  }
+  if (n < 1 || n > LFVIO_TRACK_BATCH_MAX_SLOTS || !in_paths || !out_paths) {
+    why = "lfvio_host_track_traces: n outside [1, 64], or null paths";
+    return -3;
+  }
+  BatchFeatureTracker tracker(trackerConfig(), n, e->gpu);
+  std::vector<TrackStats> st((size_t)n);
+  std::vector<std::vector<char>> bytes;
+  const int rc = trackRecordings(tracker, n, in_paths, &bytes, st.data());
+  if (track_stats) std::memcpy(track_stats, st.data(), (size_t)n * sizeof(TrackStats));
+  if (rc) {
+    why = rc == -3 ? "lfvio_host_track_traces: a recording is unreadable or refused" : tracker.error();
+    return rc;
+  }
+  for (int i = 0; i < n; i++) {
+    std::FILE *f = std::fopen(out_paths[i], "wb");
+    const bool ok = f && std::fwrite(bytes[i].data(), 1, bytes[i].size(), f) == bytes[i].size();
+    if ((f && std::fclose(f) != 0) || !ok) {
+      for (int k = 0; k <= i; k++) std::remove(out_paths[k]);
+      why = "lfvio_host_track_traces: cannot write";
+      return -1;
+    }
+  }
+  return 0;
+}
+const char *lfvio_host_track_traces_error(void) { return tracesError().c_str(); }
 
 // Pixels to poses: the same tracking, then replay() on the result in memory.  stats as lfvio_host_replay, track_stats as above.
 int lfvio_host_replay_images(void *h, const char *path, const char *traj_path, int max_images, int *stats, double *track_stats) {

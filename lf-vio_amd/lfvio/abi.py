@@ -847,6 +847,7 @@ HIP_SYMBOLS = [
     "lfvio_cam_project", "lfvio_remap_build", "lfvio_remap_apply", "lfvio_remap_reset", "lfvio_cloud_fuse",
     "lfvio_track_source_set",
     "lfvio_track_batch_reserve", "lfvio_track_batch_set_mask", "lfvio_track_batch_clahe", "lfvio_track_batch_frame", "lfvio_track_batch_reset",
+    "lfvio_track_batch_map", "lfvio_track_batch_source", "lfvio_track_batch_level",
     "lfvio_group_create", "lfvio_group_unique_id", "lfvio_group_create_rank", "lfvio_group_create_local", "lfvio_group_destroy",
     "lfvio_group_last_error", "lfvio_group_size", "lfvio_group_local", "lfvio_group_rank", "lfvio_group_ctx", "lfvio_group_backend",
     "lfvio_group_solve", "lfvio_group_upload", "lfvio_group_optimize", "lfvio_group_download", "lfvio_group_range",
@@ -961,6 +962,10 @@ def load_hip_library(path=None):
         lib.lfvio_track_batch_clahe.argtypes = [C.c_void_p, C.POINTER(ClaheInC)]
         lib.lfvio_track_batch_frame.argtypes = [C.c_void_p, C.c_int, C.POINTER(TrackFrameInC), C.POINTER(TrackFrameOutC), C.POINTER(TrackMessageC)]
         lib.lfvio_track_batch_reset.argtypes = [C.c_void_p, C.c_int]
+    if hasattr(lib, "lfvio_track_batch_map"):
+        lib.lfvio_track_batch_map.argtypes = [C.c_void_p, C.c_int, C.POINTER(RemapInC)]
+        lib.lfvio_track_batch_source.argtypes = [C.c_void_p, C.POINTER(TrackSourceC)]
+        lib.lfvio_track_batch_level.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_ubyte)]
     lib.lfvio_shard_marg_linearize.argtypes = [C.c_void_p, C.c_int]
     lib.lfvio_shard_marg_finish.argtypes = [C.c_void_p, C.c_int, C.POINTER(Prior)]
     # multi-GPU groups (RCCL inside the library)

@@ -1027,6 +1027,45 @@ class Engine:
             self._check(rc, "lfvio_track_batch_reset")
         return rc
 
+    def track_batch_map(self, slot, cam=None, kind=None, width=0, height=0, M=None, check=True):
+        """lfvio_track_batch_map: remap_build for slot `slot` (-1: every slot, the same recipe in each) — the slot's own resident map
+        of a width x height output through `cam` (projector()).  kind None: a null recipe, the slot's map (every map) is forgotten.
+        Returns the error code."""
+        if kind is None:
+            rc = self.lib.lfvio_track_batch_map(self.ctx, slot, None)
+        else:
+            proj, keep = self.projector(cam)
+            m = np.zeros(9) if M is None else np.ascontiguousarray(M, dtype=np.float64).reshape(9)
+            rin = abi.RemapInC(None if proj is None else C.pointer(proj), kind, width, height, (C.c_double * 9)(*m.tolist()))
+            rc = self.lib.lfvio_track_batch_map(self.ctx, slot, C.byref(rin))
+            del keep
+        if check:
+            self._check(rc, "lfvio_track_batch_map")
+        return rc
+
+    def track_batch_source(self, src_width=None, src_height=None, check=True):
+        """lfvio_track_batch_source: track_source for the batch — every active image of a later track_batch_frame is the SOURCE image
+        (uint8 [src_height, step] in the encoding and step of track_batch_format) and level 0 of slot i is gathered from it through slot
+        i's map (track_batch_map), whose size the call's width and height must name.  track_batch_source(None): off.  Returns the
+        error code."""
+        rc = self.lib.lfvio_track_batch_source(self.ctx, None if src_width is None else C.byref(abi.TrackSourceC(src_width, src_height)))
+        if check:
+            self._check(rc, "lfvio_track_batch_source")
+        return rc
+
+    def track_batch_level(self, slot, level, check=True):
+        """lfvio_track_batch_level: klt_level for slot `slot` — level `level` of its resident pyramid as a [height, width] uint8 array
+        (None, with check=False, where the call is refused)."""
+        w, h = C.c_int(0), C.c_int(0)
+        rc = self.lib.lfvio_track_batch_level(self.ctx, slot, level, C.byref(w), C.byref(h), None)
+        if rc != 0 and not check:
+            return None
+        self._check(rc, "lfvio_track_batch_level")
+        px = np.zeros((h.value, w.value), dtype=np.uint8)
+        self._check(self.lib.lfvio_track_batch_level(self.ctx, slot, level, C.byref(w), C.byref(h), px.ctypes.data_as(C.POINTER(C.c_ubyte))),
+                    "lfvio_track_batch_level")
+        return px
+
     def track_batch_frame(self, frames, message=True, count=None, buffers=None, check=True, **params):
         """lfvio_track_batch_frame: frames is a list with one entry per slot — None (the slot is idle in this call) or a dict with img,
         time, cam and, optionally, publish (True), words [S, 8] uint32 and params (fields of LfvioTrackFrameIn for this entry alone).

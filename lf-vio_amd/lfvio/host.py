@@ -90,6 +90,10 @@ class HostEstimator:
             L.lfvio_host_trace_raw_images.argtypes = [C.c_char_p, C.c_int, _dp, C.c_char_p, C.c_int]
             if hasattr(L, "lfvio_host_trace_raw_encoding"):
                 L.lfvio_host_trace_raw_encoding.argtypes = [C.c_char_p]
+            if hasattr(L, "lfvio_host_track_traces"):
+                L.lfvio_host_track_traces.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), _dp]
+                L.lfvio_host_track_traces_error.argtypes = []
+                L.lfvio_host_track_traces_error.restype = C.c_char_p
         self.L = L
         self.h = L.lfvio_host_create()
 
@@ -256,6 +260,24 @@ class HostEstimator:
         ts = np.zeros(len(self.TRACK_STATS))
         rc = self.L.lfvio_host_track_trace(self.h, str(in_path).encode(), str(out_path).encode(), _p(ts))
         return rc, dict(zip(self.TRACK_STATS, (float(x) for x in ts)))
+
+    def track_traces(self, in_paths, out_paths):
+        """lfvio_host_track_traces: several recordings through one batched tracker call per round — round r takes the r-th raw image of
+        every recording that still has one.  Every out_paths[i] is what track_trace writes for in_paths[i] alone.  -> (rc, [track stats
+        dict per recording]); rc 0 ok, -1 cannot write, -2 a device call failed, -3 unreadable or refused, -4 the images of a round
+        disagree in width, height, step or encoding; on anything but 0 no file is written (track_traces_error() says why)."""
+        self._tracker()
+        n = len(in_paths)
+        assert len(out_paths) == n
+        ins = (C.c_char_p * max(n, 1))(*[str(p).encode() for p in in_paths])
+        outs = (C.c_char_p * max(n, 1))(*[str(p).encode() for p in out_paths])
+        ts = np.zeros((max(n, 1), len(self.TRACK_STATS)))
+        rc = self.L.lfvio_host_track_traces(self.h, n, ins, outs, _p(ts))
+        return rc, [dict(zip(self.TRACK_STATS, (float(x) for x in row))) for row in ts[:n]]
+
+    def track_traces_error(self):
+        """Why the last track_traces failed ("" after one that did not)."""
+        return self.L.lfvio_host_track_traces_error().decode()
 
     def replay_images(self, trace_path, traj_path="", max_images=0):
         """lfvio_host_replay_images: pixels to poses -> (rc, stats dict as replay(), track stats dict)."""
