@@ -4,6 +4,9 @@
 // have published for its images, bit for bit (the batch's contract).  The base mask, the CLAHE setting, the image format and, where
 // asked for, the map of the expanded image in every slot (lfvio_track_batch_map) with lfvio_track_batch_source are set at the first
 // round that reaches the device.  As in FeatureTracker, a restart resets nothing of the slot: the reference's node does not either.
+// The contract holds by construction: the seeding, the mask, the order of the settings, the arguments of every slot with the
+// reference's constants and the results are track_node.h's, for both trackers; the batch's own are the round refused as a whole, the
+// agreement of a round's images, the idle slots and a destructor that turns the batch's settings off.
 // Only host/Makefile builds it.
 #pragma once
 #include <random>
@@ -13,20 +16,10 @@
 #include "../../include/lfvio.h"
 #include "feature_tracker.h"
 #include "image_gate.h"
-#include "image_replay.h"
-#include "replay.h"
+#include "trace_rewrite.h"
+#include "track_node.h"
 
 namespace lfvio {
-
-// One stream's image of a round (present = false: the stream has none), and what became of it
-struct BatchEntry {
-  bool present = false;
-  double stamp = 0;
-  int width = 0, height = 0, step = 0, encoding = LFVIO_IMG_MONO8;
-  const unsigned char *pixels = nullptr;
-  int result = FeatureTracker::DROPPED;  // a FeatureTracker::Result; PUBLISHED: msg is the feature message, stamped `stamp`
-  TraceImage msg;
-};
 
 class BatchFeatureTracker {
  public:
@@ -52,19 +45,12 @@ class BatchFeatureTracker {
   std::vector<ImageGate> gate;
 
  private:
-  int setup(int tw, int th, const LfvioImageFormat &format, const LfvioTrackSource &source);
   TrackerConfig cfg_;
   lfvio_ctx *ctx_ = nullptr;
-  bool own_ = false, ready_ = false, failed_ = false;
+  bool own_ = false, failed_ = false;
   std::vector<std::mt19937> rng_;
-  LfvioImageFormat format_ = {LFVIO_IMG_MONO8, 0};
-  LfvioTrackSource source_ = {0, 0};
-  std::vector<std::vector<unsigned>> words_;
-  struct Arrays {
-    std::vector<float> pts, un_pts, un_pts_3d, velocity_3d, rows;
-    std::vector<int> ids, track_cnt;
-  };
-  std::vector<Arrays> arrays_;
+  NodeSettings settings_;  // of every slot
+  std::vector<FrameBuffers> buffers_;
   std::vector<LfvioTrackFrameIn> in_;
   std::vector<LfvioTrackFrameOut> out_;
   std::vector<LfvioTrackMessage> msg_;

@@ -2,17 +2,15 @@
 // file order, every image replaced by what the node would have published at that place — a feature message (type 2), a restart
 // (type 5, with the stamp) or nothing — and every other record copied byte for byte.  trackTrace() writes that recording ("pre-track
 // a bag"); replayImages() makes it in memory and hands it to the unchanged replay(): pixels and IMU samples in, the trajectory out.
+// The walk over the records, TrackStats and the file writing are trace_rewrite.h's, shared with batch_tracker.h's trackRecordings.
 #pragma once
 #include <vector>
 
 #include "feature_tracker.h"
 #include "replay.h"
+#include "trace_rewrite.h"
 
 namespace lfvio {
-
-struct TrackStats {
-  double raw_images, dropped, restarts, tracked_only /* the skipped first publication included */, published, rows, tracker_ms;
-};
 
 // The recording `in_path` with its raw images tracked, as the bytes of an LFVT file in *out.  0; -3: unreadable or refused by
 // Trace::load; -2: a device call of the tracker failed (tracker.status, tracker.error()).

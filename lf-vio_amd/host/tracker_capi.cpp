@@ -1,4 +1,5 @@
-// tracker_capi.cpp — extern "C" driver of the image route (feature_tracker.h, image_replay.h), beside host_capi.cpp and apart from it:
+// tracker_capi.cpp — extern "C" driver of the image route (feature_tracker.h, batch_tracker.h and image_replay.h, over the recipe of
+// track_node.h and the walk of trace_rewrite.h), beside host_capi.cpp and apart from it:
 // the test suite's CPU build of the host sources (oracle/Makefile) links no tracker, so nothing in the three older sources refers to
 // anything here.  Only host/Makefile compiles this file.
 #include <cstdio>
@@ -103,9 +104,7 @@ int lfvio_host_track_traces(void *h, int n, const char *const *in_paths, const c
     return rc;
   }
   for (int i = 0; i < n; i++) {
-    std::FILE *f = std::fopen(out_paths[i], "wb");
-    const bool ok = f && std::fwrite(bytes[i].data(), 1, bytes[i].size(), f) == bytes[i].size();
-    if ((f && std::fclose(f) != 0) || !ok) {
+    if (writeBytes(out_paths[i], bytes[i])) {
       for (int k = 0; k <= i; k++) std::remove(out_paths[k]);
       why = "lfvio_host_track_traces: cannot write";
       return -1;

@@ -20,7 +20,9 @@ perspective through the pinhole camera behind the shifted M, equirectangular thr
      saw a refused one; reserve drops the maps, reset keeps them; lfvio_track_batch_source(NULL) gives plain batched frames
   6  the host route: lfvio_host_track_traces over three rendered recordings of 12, 12 and 9 frames with `expand` on writes, byte for
      byte, the three files lfvio_host_track_trace writes for each alone; a fourth recording of another image size makes the call
-     fail and write nothing"""
+     fail and write nothing
+  7  the host route with `expand` off: three recordings of 10, 10 and 7 frames at 160 x 120 with the annulus, CLAHE, frames that are
+     tracked only and one restart, against each alone and against tests/node_ref.Gate's counts"""
 import os
 
 import numpy as np
@@ -393,3 +395,86 @@ def test_host_route(tmp_path):
     print("host route:", [w[1] for w in want])
     for (rc, st, body), n in zip(want, (12, 12, 9)):
         assert rc == 0 and st["raw_images"] == n and st["published"] >= n - 4 and st["rows"] >= (n - 4) * 20 and len(body) > 0
+
+
+# ---- 7
+def test_host_route_plain(tmp_path):
+    """What test_host_route leaves out: `expand` off, the annulus as the base mask, CLAHE on, frames that are tracked only, and a restart.
+    Three recordings of 10, 10 and 7 images of 160 x 120 (scale 8; every published message has its 10 rows at this size) at 12.5 Hz, so
+    that the FREQ gate lets some frames be tracked without a publication; recording 1's images from the sixth on are stamped 1.5 s later,
+    so its gate restarts once.  lfvio_host_track_traces gives, byte for byte and count for count, what lfvio_host_track_trace gives for
+    each alone on a fresh estimator; the counts are those of tests/node_ref.Gate over the recording's stamps, which need no device."""
+    import struct
+
+    import node_ref as nr
+    from lfvio import trace
+    from lfvio.host import HostEstimator
+
+    srcs, made, stamps = [], None, []
+    for seed, n in ((0, 10), (1, 10), (2, 7)):
+        p = str(tmp_path / f"raw{seed}.lfvt")
+        made = trace.make_image_stream(p, seed=seed, n_frames=n, scale=8, frame_dt=0.08)
+        assert (made["width"], made["height"]) == (160, 120)
+        body, at, k, st = bytearray(open(p, "rb").read()), 8, 0, []
+        while at < len(body):
+            typ, size = struct.unpack_from("<II", body, at)
+            if typ == 10:
+                t = struct.unpack_from("<d", body, at + 8)[0] + (1.5 if seed == 1 and k >= 5 else 0.0)
+                struct.pack_into("<d", body, at + 8, t)
+                st.append(t)
+                k += 1
+            at += 8 + size
+        assert k == n
+        open(p, "wb").write(body)
+        srcs.append(p)
+        stamps.append(st)
+
+    # what the node does with these stamps
+    counts = []
+    for st in stamps:
+        g, c = nr.Gate(10), dict(raw_images=float(len(st)), dropped=0.0, restarts=0.0, tracked_only=0.0, published=0.0)
+        for t in st:
+            a = g.on_stamp(t)
+            key = {nr.DROP: "dropped", nr.RESTART: "restarts"}.get(a) or ("published" if g.after_frame() == nr.PUBLISHED else "tracked_only")
+            c[key] += 1
+        counts.append(c)
+    assert [c["restarts"] for c in counts] == [0, 1, 0] and all(c["published"] >= 3 for c in counts)
+    assert [c["tracked_only"] for c in counts] == [3, 3, 3] and [c["dropped"] for c in counts] == [1, 2, 1]  # (the skipped first publication and two frames)
+
+    def configured(he):
+        he.clear_state()
+        he.track_config(made["camera"], max_cnt=40, min_dist=8, freq=10, equalize=True, num_samples=100, seed=77, annulus=made["annulus"])
+
+    strip = lambda d: {k: v for k, v in d.items() if k != "tracker_ms"}
+    want = []
+    for k, p in enumerate(srcs):
+        he = HostEstimator()  # a fresh estimator and context for every recording
+        try:
+            configured(he)
+            out = str(tmp_path / f"alone{k}.lfvt")
+            rc, st = he.track_trace(p, out)
+            want.append((rc, strip(st), open(out, "rb").read()))
+        finally:
+            he.close()
+    he = HostEstimator()
+    try:
+        configured(he)
+        outs = [str(tmp_path / f"batch{k}.lfvt") for k in range(3)]
+        rc, stats = he.track_traces(srcs, outs)
+        got = [(rc, strip(st), open(o, "rb").read()) for st, o in zip(stats, outs)]
+    finally:
+        he.close()
+    print("host route, plain:", [w[1] for w in want])
+    assert got == want
+    for (rc, st, body), c in zip(want, counts):
+        assert rc == 0 and {k: st[k] for k in c} == c
+        rows, restarts, at = [], 0, 8  # the file's own records: no comparison of empty messages
+        while at < len(body):
+            typ, size = struct.unpack_from("<II", body, at)
+            assert typ != 10
+            if typ == 2:
+                rows.append(struct.unpack_from("<I", body, at + 16)[0])
+                assert size == 12 + 36 * rows[-1]
+            restarts += typ == 5
+            at += 8 + size
+        assert len(rows) == c["published"] and restarts == c["restarts"] and sum(rows) == st["rows"] and min(rows) >= 10, rows
